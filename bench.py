@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — planning steps/sec of the MI355X CEM-MPC planner (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (one rank per GPU, RCCL).  A "step" is one complete plan = CemMpc.generate_action: I=5 CEM iterations of
 sample -> rollout+score -> select/refit, early stop disabled so exactly I iterations run.
@@ -9,10 +9,18 @@ sample -> rollout+score -> select/refit, early stop disabled so exactly I iterat
 Workload: BASELINE config B2 (obs=60, act=2, K=P=E=5, N=2000, H=30, I=5, k=N/10) at N=1.  At G>1 the candidate
 count is weak-scaled (N = 2000*G, every rank rolls out 2000 candidates x 5 particles) and `value` is in
 B2-equivalent plans/s = candidate-trajectory-steps/s / 300000, so it equals plain plans/s at G=1.  The same line carries the
-unscaled rate (`weak_plans_per_s`) and, as labelled extras, the literal metric strong-scaled (`b2_strong`: N = 2000 in total, 2000/G per
-rank, plain plans/s) and BASELINE config 5 (`b5`: N = 65536 over the G ranks).  A single-GPU run adds `configs`: B1 / B3 / B4 whole plans,
-one rank of B5's eight, and the reference's own policies — SafeCemMpc at the headline shape (`B2_safe`) and the shapes it ships
-(`shipped_safe_cem_mpc`, `shipped_cem_mpc`, each with early stop off and as shipped).
+unscaled rate (`weak_plans_per_s`).
+
+A plain run does only what the headline needs: set-up, W warm-up plans, K timed plans, the outputs (--dump-outputs) and the line.
+`--full` adds everything else, as labelled extras (`value` stays the headline): the roofline of the rollout kernel (HIP-event timed
+plans of their own) and, at G>1, the literal metric strong-scaled (`b2_strong`: N = 2000 in total, 2000/G per rank, plain plans/s),
+BASELINE config 5 (`b5`: N = 65536 over the G ranks) and every rank planning B2 alone; a single-GPU run adds `configs`: B1 / B3 / B4
+whole plans, one rank of B5's eight, and the reference's own policies — SafeCemMpc at the headline shape (`B2_safe`) and the shapes it
+ships (`shipped_safe_cem_mpc`, `shipped_cem_mpc`, each with early stop off and as shipped) — the split-product leg and the CPU baseline.
+With --full the other legs run in front of the headline (see `order`), so its timed plans run at the GPU's sustained clock.
+
+--dump-outputs DIR writes what the last timed plan returned to its caller (action.npy, score.npy, iterations.npy); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -42,6 +50,15 @@ def source_sha16():
                     glob.glob(os.path.join(ROOT, 'include', '*.h'))):
         h.update(os.path.basename(f).encode()); h.update(open(f, 'rb').read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(path, action, score, iterations):
+    """--dump-outputs: what the last timed plan returned to its caller (CemPlanner.plan: the action, the best score, the CEM iterations
+    run), one .npy per array in float32 / float64."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'action.npy'), np.asarray(action, np.float32))
+    np.save(os.path.join(path, 'score.npy'), np.asarray([score], np.float32))
+    np.save(os.path.join(path, 'iterations.npy'), np.asarray([iterations], np.float64))
 
 
 def rollout_kernel_name(pl, obs, act):
@@ -497,7 +514,12 @@ def main():
     ap.add_argument('--chunks', type=int, default=0)
     ap.add_argument('--segments', type=int, default=0, help='rollout work-queue segments: 0 auto, 1 off')
     ap.add_argument('--n-per-gpu', type=int, default=2000)
+    ap.add_argument('--full', action='store_true', help='also run every extra leg (roofline, configs, split leg, CPU baseline, multi-rank extras); '
+                                                        'the --no-* flags above select among them')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed plan returned (action, score, iterations) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     import torch
     from ethz_safe_learning_amd import CemPlanner, PlannerConfig, synthetic
@@ -569,12 +591,12 @@ def main():
             return pl.plan(pb['state'], seed=2026, call=i)
         return drv.plan(pb['state'], seed=2026, call=i)
 
-    # Single-GPU extras FIRST, the headline after them.  A GPU that has been idle ramps its clock over the first ~13 B2 plans (26 ms of work:
-    # 2.07 -> 1.89 ms per plan, profiles/r05_cold_start_steps.txt), which is most of what the driver's `--warmup 5 --steps 20` times; with the
+    # --full: single-GPU extras FIRST, the headline after them.  A GPU that has been idle ramps its clock over the first ~13 B2 plans (26 ms of
+    # work: 2.07 -> 1.89 ms per plan, profiles/r05_cold_start_steps.txt), which is most of what `--warmup 5 --steps 20` times; with the
     # other legs in front, the W warm-up plans and the K timed plans of the headline run at the sustained clock — what "planning steps per
     # second" means for a planner called in a loop.  Exactly W warm-up and K timed steps either way; `ms_per_step_each` lists every timed step.
     pre = {}
-    if G == 1 and not distributed and not args.no_configs:
+    if G == 1 and not distributed and args.full and not args.no_configs:
         # the other single-GPU BASELINE configs (and one rank of B5's eight) on the driver's line: labelled extras, `value` stays B2
         legs = {}
         for name, O_, A_, K_, N_, H_, st_, wu_ in (('B1', 60, 2, 5, 500, 25, 60, 15), ('B3', 60, 2, 16, 8192, 30, 8, 3), ('B4', 100, 12, 8, 4096, 50, 10, 3)):
@@ -588,14 +610,14 @@ def main():
             legs['B5_rank'] = {'error': str(e)[:300]}
         legs.update(policy_legs(torch, dev))          # the reference's default policy and shipped shapes, and the headline shape on SafeCemMpc
         pre['configs'] = legs
-    if G == 1 and not distributed and not args.no_split_leg:
+    if G == 1 and not distributed and args.full and not args.no_split_leg:
         try:
             pre['split_bf16x3'] = split_leg(torch, pb, dev, steps=min(args.steps, 50), warmup=min(max(args.warmup, 3), 10), n_per_gpu=args.n_per_gpu)
         except Exception as e:                             # an extra must never cost the run its headline line
             pre['split_bf16x3'] = {'error': str(e)[:300]}
     if run_guard:
         run_guard.stage = 'per-rank single-GPU leg'
-    if distributed and not args.no_local_leg:
+    if distributed and args.full and not args.no_local_leg:
         # Multi-rank runs: every rank first plans B2 ALONE on its GPU (a single-rank handle, no collective anywhere: nothing to block in) — the
         # per-GPU rate of the node's GPUs side by side (a slow or throttled GPU shows here, not as a mystery in the sharded number), and the
         # same clock conditioning the single-GPU run gets from its extras, so that the N = 1 and N > 1 lines of a scaling sweep compare like
@@ -643,43 +665,53 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert it == I and np.all(np.isfinite(a))
-    if run_guard:
-        run_guard.stage = 'roofline timing'
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, a, s, it)
+    roofline = None
+    if args.full:
+        if run_guard:
+            run_guard.stage = 'roofline timing'
 
-    # roofline of the dominant kernel: HIP events on the handle's stream around every rollout launch (eager launches)
-    pl.set_timing(True)
-    roll_ms, roll_n = 0.0, 0
-    for i in range(5):
-        if not distributed or native:
-            pl.plan(pb['state'], seed=2027, call=i)
-        else:
-            drv.plan(pb['state'], seed=2027, call=i)
-        tm = pl.last_timing()
-        roll_ms += tm['rollout_ms']; roll_n += tm['rollout_launches']
-    pl.set_timing(False)
-    flops_launch = synthetic.flops_per_row_step(obs, act) * K * (N // G) * H
-    avg_ms = roll_ms / max(roll_n, 1)
-    achieved = flops_launch / (avg_ms * 1e-3) / 1e12
-
-    # HBM-side bytes and MFMA-pipe busy cycles per rollout launch come from the committed rocprofv3 PMC passes of this same
-    # workload (counters cannot be collected inside a timed run).  They are only quoted when that profile is of THIS code and THIS
-    # kernel: the summary records the kernel name and a hash of the device sources; anything else is reported as stale, not reused.
-    kname = rollout_kernel_name(pl, obs, act)
-    mfma_util, traffic, profile_note = None, None, None
-    tpath = os.path.join(ROOT, 'profiles', 'traffic_b2.json')
-    if G == 1 and args.n_per_gpu == 2000:
-        if not os.path.exists(tpath):
-            profile_note = 'no PMC profile committed'
-        else:
-            prof = json.load(open(tpath))
-            if prof.get('kernel') != kname:
-                profile_note = 'stale_profile: profiles/traffic_b2.json is of kernel %r, this run launched %r' % (prof.get('kernel'), kname)
-            elif prof.get('source_sha16') != source_sha16():
-                profile_note = 'stale_profile: profiles/traffic_b2.json was collected on device sources %s, this run is %s' % (prof.get('source_sha16'), source_sha16())
+        # roofline of the dominant kernel: HIP events on the handle's stream around every rollout launch (eager launches)
+        pl.set_timing(True)
+        roll_ms, roll_n = 0.0, 0
+        for i in range(5):
+            if not distributed or native:
+                pl.plan(pb['state'], seed=2027, call=i)
             else:
-                traffic = prof['hbm_bytes_per_launch']
-                # MFMA-pipe utilisation: PMC busy cycles per launch over 1024 SIMDs x this run's launch time
-                mfma_util = prof.get('sq_valu_mfma_busy_cycles_per_launch', 0.0) / (1024 * avg_ms * 1e-3 * SHADER_CLOCK_HZ) or None
+                drv.plan(pb['state'], seed=2027, call=i)
+            tm = pl.last_timing()
+            roll_ms += tm['rollout_ms']; roll_n += tm['rollout_launches']
+        pl.set_timing(False)
+        flops_launch = synthetic.flops_per_row_step(obs, act) * K * (N // G) * H
+        avg_ms = roll_ms / max(roll_n, 1)
+        achieved = flops_launch / (avg_ms * 1e-3) / 1e12
+
+        # HBM-side bytes and MFMA-pipe busy cycles per rollout launch come from the committed rocprofv3 PMC passes of this same
+        # workload (counters cannot be collected inside a timed run).  They are only quoted when that profile is of THIS code and THIS
+        # kernel: the summary records the kernel name and a hash of the device sources; anything else is reported as stale, not reused.
+        kname = rollout_kernel_name(pl, obs, act)
+        mfma_util, traffic, profile_note = None, None, None
+        tpath = os.path.join(ROOT, 'profiles', 'traffic_b2.json')
+        if G == 1 and args.n_per_gpu == 2000:
+            if not os.path.exists(tpath):
+                profile_note = 'no PMC profile committed'
+            else:
+                prof = json.load(open(tpath))
+                if prof.get('kernel') != kname:
+                    profile_note = 'stale_profile: profiles/traffic_b2.json is of kernel %r, this run launched %r' % (prof.get('kernel'), kname)
+                elif prof.get('source_sha16') != source_sha16():
+                    profile_note = 'stale_profile: profiles/traffic_b2.json was collected on device sources %s, this run is %s' % (prof.get('source_sha16'), source_sha16())
+                else:
+                    traffic = prof['hbm_bytes_per_launch']
+                    # MFMA-pipe utilisation: PMC busy cycles per launch over 1024 SIMDs x this run's launch time
+                    mfma_util = prof.get('sq_valu_mfma_busy_cycles_per_launch', 0.0) / (1024 * avg_ms * 1e-3 * SHADER_CLOCK_HZ) or None
+
+        roofline = {'bound': 'mfma', 'achieved': achieved, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': achieved / PEAK_FP32_MFMA_TFLOPS, 'traffic': traffic, 'mfma_busy_frac': mfma_util,
+                    'hbm_gbps': (traffic / (avg_ms * 1e-3) / 1e9) if traffic else None, 'hbm_peak_gbps': PEAK_HBM_GBPS,
+                    'kernel': kname, 'profile_note': profile_note, 'avg_launch_ms': avg_ms, 'launches_timed': roll_n,
+                    'algorithmic_flops_per_launch': flops_launch}
 
     if run_guard:
         run_guard.cancel()                             # the headline exists: from here on the extras' own guard keeps it
@@ -703,16 +735,13 @@ def main():
         'candidate_trajectory_steps_per_s': plans_per_s * I * N * H,
         # the same timed interval without the B2-equivalent scaling: whole plans of N = 2000 x G candidates per second
         'weak_plans_per_s': plans_per_s, 'weak_candidates_per_plan': N,
-        'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': achieved / PEAK_FP32_MFMA_TFLOPS, 'traffic': traffic, 'mfma_busy_frac': mfma_util,
-                     'hbm_gbps': (traffic / (avg_ms * 1e-3) / 1e9) if traffic else None, 'hbm_peak_gbps': PEAK_HBM_GBPS,
-                     'kernel': kname, 'profile_note': profile_note, 'avg_launch_ms': avg_ms, 'launches_timed': roll_n,
-                     'algorithmic_flops_per_launch': flops_launch},
     }
-    # BASELINE config 5 (N = 65536 over the node's GPUs) rides along on every multi-GPU run; CEM_BENCH_B5_REHEARSAL=R rehearses one
+    if roofline is not None:
+        out['roofline'] = roofline
+    # --full: BASELINE config 5 (N = 65536 over the node's GPUs) rides along on every multi-GPU run; CEM_BENCH_B5_REHEARSAL=R rehearses one
     # rank of R on a one-GPU box
     rehearse = int(os.environ.get('CEM_BENCH_B5_REHEARSAL', '0'))
-    if (G > 1 or rehearse > 0) and not args.no_b5:
+    if (G > 1 or rehearse > 0) and args.full and not args.no_b5:
         if native:
             pl.comm_destroy()                          # one communicator at a time
         # an extra must never cost the run its headline: failures a rank can have on its own are agreed on before the leg's first
@@ -727,7 +756,7 @@ def main():
                 out['b5_split_bf16x3'] = b5_leg(torch, dist, pb, G, rank, dev, native, steps=min(args.steps, 20), warmup=min(max(args.warmup, 2), 5),
                                                 rehearse_world=rehearse if G == 1 else 0, ctl_dev=ctl_dev, precision='bf16x3')
     out.update(pre)                                    # the single-GPU extras, measured before the headline (see `order`)
-    if rank == 0 and G == 1 and not args.no_cpu_baseline:
+    if rank == 0 and G == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -5,7 +5,7 @@ from collections import defaultdict
 
 out = sys.argv[1]
 workload = sys.argv[2] if len(sys.argv) > 2 else 'B2'
-cmd = sys.argv[3] if len(sys.argv) > 3 else 'bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-split-leg --no-graph'
+cmd = sys.argv[3] if len(sys.argv) > 3 else 'bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-split-leg --no-graph'
 # 1. kernel stats: copy the rocprofv3 summary as is
 for f in glob.glob(os.path.join(out, 'stats', '**', '*kernel_stats.csv'), recursive=True):
     open(os.path.join(out, 'summary_kernel_stats.csv'), 'w').write(open(f).read())

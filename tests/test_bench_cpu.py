@@ -58,3 +58,19 @@ def test_run_guard_says_that_the_headline_never_finished():
     assert 'did not finish' in r.stderr
     r = subprocess.run([sys.executable, '-c', CHILD_RUN % ROOT, '3'], capture_output=True, text=True, timeout=60)
     assert r.returncode == 4 and r.stdout.strip() == '' and 'rank 3' in r.stderr
+
+
+def test_steps_are_checked_and_outputs_dump_as_float_npy(tmp_path):
+    """--steps sets the number of timed plans, so fewer than one is refused before any GPU work; --dump-outputs writes what the last
+    timed plan returned (action, score, iterations) as float32 / float64 .npy files."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and '--steps must be >= 1' in r.stderr
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    d = str(tmp_path / 'out')
+    bench.dump_outputs(d, np.array([0.25, -0.5], np.float32), 1.5, 5)
+    assert sorted(os.listdir(d)) == ['action.npy', 'iterations.npy', 'score.npy']
+    a, s, it = (np.load(os.path.join(d, n + '.npy')) for n in ('action', 'score', 'iterations'))
+    assert a.dtype == np.float32 and a.tolist() == [0.25, -0.5]
+    assert s.dtype == np.float32 and s.tolist() == [1.5] and it.dtype == np.float64 and it.tolist() == [5.0]

@@ -1,18 +1,21 @@
-"""bench.py's contract on the GPU box: the default single-process line, and the multi-rank leg (process group over RCCL,
-stepwise plan with the score all-gather, barrier + max-over-ranks timing) rehearsed with one rank under
-torch.distributed.run — the only rehearsal a one-GPU box allows (CEM_BENCH_FORCE_DIST=1)."""
+"""bench.py's contract on an MI355X: the plain single-process line and its --dump-outputs, the --full line with every extra,
+and the multi-rank leg (process group over RCCL, stepwise plan with the score all-gather, barrier + max-over-ranks timing) rehearsed
+with one rank under torch.distributed.run — the only rehearsal a single GPU allows (CEM_BENCH_FORCE_DIST=1)."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
-        'data', 'config', 'roofline'}
+        'data', 'config'}
+# what only --full measures: a plain run carries none of it
+FULL_ONLY = {'roofline', 'configs', 'split_bf16x3', 'cpu_baseline', 'per_rank_single_gpu_b2_plans_per_s', 'b2_strong', 'b5', 'b5_split_bf16x3'}
 
 
 def _json_line(out):
@@ -21,19 +24,45 @@ def _json_line(out):
     return json.loads(lines[0])
 
 
-def _check(r, steps, warmup):
+def _check(r, steps, warmup, full=True):
     assert KEYS <= set(r)
     assert r['metric'] == 'planning steps/sec (CEM-MPC, N=2000 K=5 H=30)' and r['unit'] == 'plans/s' and r['n_gpus'] == 1
     assert r['steps'] == steps and r['warmup'] == warmup and r['higher_is_better'] is True and r['scaling'] == 'weak'
     assert r['dtype'] == 'f32' and r['vs_baseline'] is None and r['data'] == 'synthetic' and 'workload' in r['config']
     assert abs(r['value'] * r['ms_per_step'] / 1e3 - 1.0) < 1e-6 and r['value'] > 100
+    if not full:
+        assert not FULL_ONLY & set(r), FULL_ONLY & set(r)
+        return
     rf = r['roofline']
     assert rf['bound'] == 'mfma' and rf['unit'] == 'TFLOP/s' and abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-9
     assert 0.3 < rf['frac'] < 1.0
 
 
+def test_plain_bench_line_and_outputs(tmp_path):
+    """A plain run times exactly the steps asked for and nothing else; --dump-outputs writes what the last timed plan returned, and
+    the same arguments give the same outputs bit for bit (seeded inputs, deterministic plan)."""
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ('out%d' % run))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2', '--dump-outputs', d],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = _json_line(out.stdout)
+        _check(r, 7, 2, full=False)
+        assert len(r['ms_per_step_each']) == 7 and abs(sum(r['ms_per_step_each']) / 7 - r['ms_per_step']) < 0.02 * r['ms_per_step']
+        assert r['order'].startswith('headline first') and r['config']['hip_graph'] is True
+        got = {n: np.load(os.path.join(d, n + '.npy')) for n in ('action', 'score', 'iterations')}
+        assert sorted(os.listdir(d)) == ['action.npy', 'iterations.npy', 'score.npy']
+        assert got['action'].dtype == np.float32 and got['action'].shape == (2,) and np.isfinite(got['action']).all()
+        assert got['score'].dtype == np.float32 and got['score'].shape == (1,) and np.isfinite(got['score']).all()
+        assert got['iterations'].dtype == np.float64 and got['iterations'].tolist() == [5.0]
+        dumps.append(got)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n], err_msg=n)
+
+
 def test_default_bench_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '5', '--warmup', '2', '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--full'],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)
@@ -78,7 +107,7 @@ def test_distributed_leg_with_one_rank_over_rccl():
     env = dict(os.environ, CEM_BENCH_FORCE_DIST='1')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
                           '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
-                          '--warmup', '2', '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          '--warmup', '2', '--no-cpu-baseline', '--full'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)
     _check(r, 5, 2)
@@ -91,7 +120,7 @@ def test_distributed_leg_host_stepped_fallback():
     env = dict(os.environ, CEM_BENCH_FORCE_DIST='1', CEM_BENCH_PYTHON_EXCHANGE='1')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
                           '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
-                          '--warmup', '2', '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          '--warmup', '2', '--no-cpu-baseline', '--full'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)
     _check(r, 5, 2)
@@ -106,7 +135,7 @@ def test_b5_leg_rehearsed_as_one_rank_of_eight():
     env = dict(os.environ, CEM_BENCH_FORCE_DIST='1', CEM_BENCH_B5_REHEARSAL='8')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
                           '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
-                          '--warmup', '2', '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          '--warmup', '2', '--no-cpu-baseline', '--full'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)
     _check(r, 5, 2)

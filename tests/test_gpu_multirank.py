@@ -106,7 +106,7 @@ def test_bench_multi_rank_leg_two_ranks_on_one_gpu(fake_rccl):
     """bench.py --gpus 2 as the driver launches it, except that both ranks use cuda:0 (CEM_BENCH_SHARE_GPU=1: gloo carries the
     barrier / max-over-ranks, the fake carries the all-gather).  The line must be the multi-rank one: native exchange, weak
     scaling, the B5 leg present.  (Its numbers mean nothing: two ranks time-share one GPU.)"""
-    r = _launch(2, os.path.join(ROOT, 'bench.py'), ['--gpus', '2', '--steps', '3', '--warmup', '2', '--no-cpu-baseline'],
+    r = _launch(2, os.path.join(ROOT, 'bench.py'), ['--gpus', '2', '--steps', '3', '--warmup', '2', '--no-cpu-baseline', '--full'],
                 {'CEM_RCCL_LIBRARY': fake_rccl, 'CEM_BENCH_SHARE_GPU': '1'}, timeout=600)
     assert r.returncode == 0, r.stdout[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{') and '"metric"' in ln]

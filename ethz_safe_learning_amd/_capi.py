@@ -13,6 +13,7 @@ CEM_ABI_VERSION = 4
 CEM_MAX_ACT = 32
 CEM_MAX_COST_KINDS = 4
 CEM_COMM_ID_BYTES = 128
+CEM_MAX_BATCH = 256
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds
@@ -23,6 +24,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_create', 'cem_planner_destroy', 'cem_planner_layout', 'cem_planner_set_weights',
     'cem_planner_set_normaliser', 'cem_planner_plan', 'cem_plan_begin', 'cem_plan_rollout', 'cem_plan_select',
     'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_launches_per_iteration', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
+    'cem_batch_workspace_bytes', 'cem_batch_planner_create', 'cem_planner_plan_batch', 'cem_planner_batch_capacity',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval',
 ]
@@ -134,6 +136,11 @@ def load():
     lib.cem_planner_set_timing.argtypes = [vp, C.c_int32]
     lib.cem_planner_last_timing.argtypes = [vp, fp, i32p, fp]
     lib.cem_planner_last_timing_detail.argtypes = [vp, fp, fp]
+    lib.cem_batch_workspace_bytes.restype = C.c_size_t
+    lib.cem_batch_workspace_bytes.argtypes = [cfgp, C.c_int32]
+    lib.cem_batch_planner_create.argtypes = [cfgp, C.c_int32, vp, C.c_size_t, vp, C.POINTER(vp)]
+    lib.cem_planner_plan_batch.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    lib.cem_planner_batch_capacity.argtypes = [vp, i32p]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t
@@ -148,7 +155,7 @@ def load():
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)          # raises AttributeError if the symbol is not exported
         if name not in ('cem_status_string', 'cem_weight_blob_floats', 'cem_packed_weight_floats', 'cem_workspace_bytes',
-                        'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
+                        'cem_batch_workspace_bytes', 'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
             fn.restype = C.c_int
     if lib.cem_abi_version() != CEM_ABI_VERSION:
         raise ImportError('ABI mismatch: library %d, binding %d' % (lib.cem_abi_version(), CEM_ABI_VERSION))

@@ -487,21 +487,24 @@ Plan make_plan(const cem_config_t *c, const Dims &d)
     return pl;
 }
 
-Layout make_layout(const cem_config_t *c, const Dims &d, size_t max_tiles)
+// mb > 0: a batch handle of mb problems (cem_batch_planner_create) — every per-problem array becomes [mb] consecutive slices of the
+// single-plan size (the kernels address problem b's slice from that size, cem_device.h RolloutParams::tiles_per_problem)
+Layout make_layout(const cem_config_t *c, const Dims &d, size_t max_tiles, int mb = 0)
 {
     Layout l{}; size_t o = 0;
+    const size_t nb = mb > 0 ? (size_t)mb : 1;
     auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
-    l.ctrl = take(sizeof(CtrlBlock));
-    l.musig = take((size_t)2 * d.H * d.A * 4);
+    l.ctrl = take(nb * sizeof(CtrlBlock));
+    l.musig = take(nb * 2 * d.H * d.A * 4);
     l.act_bounds = take(64 * 4);
-    l.scores_local = take((size_t)d.Nloc * 4);
+    l.scores_local = take(nb * d.Nloc * 4);
     l.scores_global = d.W > 1 ? take((size_t)d.N * 4) : l.scores_local;
-    l.actions = take((size_t)d.N * d.H * d.A * 4);
-    l.act_pad = take((size_t)d.N * d.H * d.act_nq * 16);
-    l.elite = take((size_t)d.k * 4);
-    l.returns = take((size_t)d.Bloc * 4);
-    l.costs = take((size_t)d.H * d.Bloc);
-    l.result = take(64 * 4);
+    l.actions = take(nb * d.N * d.H * d.A * 4);
+    l.act_pad = take(nb * d.N * d.H * d.act_nq * 16);
+    l.elite = take(nb * d.k * 4);
+    l.returns = take(nb * d.Bloc * 4);
+    l.costs = take(nb * d.H * d.Bloc);
+    l.result = take(mb > 0 ? nb * CEM_RESULT_WORDS * 4 : 64 * 4);
     l.wpack = take(d.wide ? (size_t)d.E * (align256(d.nat_member_floats * 4) + wide_image_floats(d) * 4) : (size_t)d.E * d.member_stride_f4 * 16);   // wide: natural blobs, then the packed images
     l.bias_h = take((size_t)d.E * d.L * CEM_U * 4);
     l.bias_mu = take((size_t)d.E * CEM_U * 4);
@@ -512,7 +515,7 @@ Layout make_layout(const cem_config_t *c, const Dims &d, size_t max_tiles)
     l.kind_sel = take(CEM_NKIND * CEM_U * 4);
     l.etab = take((size_t)d.E * etab_rows(d) * CEM_U * 4);
     l.tiles = take(max_tiles * sizeof(TileDesc));
-    l.eps_out = take(CEM_MAX_ACT * 4);
+    l.eps_out = take(nb * CEM_MAX_ACT * 4);
     l.stamps = take(std::max<size_t>(max_tiles * 4 * 8, 128) * sizeof(long long));      // [tiles][4][8] rollout stamps; [64..71] select stamps
     const Plan pl = make_plan(c, d);
     l.seg_queue = take(256);
@@ -529,6 +532,42 @@ Layout make_layout(const cem_config_t *c, const Dims &d, size_t max_tiles)
 }
 
 size_t max_tiles_of(const Dims &d) { std::vector<Tile6> t; build_plan_tiles(d, 1, t); return t.size(); }
+
+// ---- batch handles (cem_batch_planner_create) ----------------------------------------------------------------------------
+// What a batch handle serves (cem_mpc.h, the table at cem_batch_planner_create): one rank, fp32 products on the tuned rollout kernel,
+// the one-workgroup select — every kernel of that path takes the problem from its grid and its own slices from the problem.
+int validate_batch(const cem_config_t *c, int32_t mb)
+{
+    const int st = validate(c); if (st) return st;
+    if (mb < 1 || mb > CEM_MAX_BATCH) return CEM_ERR_INVALID_ARG;
+    if (c->world_size > 1 || c->precision != CEM_PRECISION_FP32) return CEM_ERR_UNSUPPORTED;
+    const Dims d = make_dims(c);
+    if (d.wide) return CEM_ERR_UNSUPPORTED;                                     // units > 128, an activation other than relu
+    if (c->select_mode == 2 || c->select_mode == 3) return CEM_ERR_UNSUPPORTED;
+    if (resolve_select_mode(c->select_mode, d.N, d.k, (long long)d.H * d.A, 140 * 1024, true, nullptr) != 1) return CEM_ERR_UNSUPPORTED;
+    if ((long long)mb * (long long)max_tiles_of(d) > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;   // the rollout grid: problems x tiles
+    return CEM_OK;
+}
+
+// The tile plan of a batch handle: the single plan's tile-size rule priced for ALL mb problems' tiles in one launch (the results do not
+// depend on the tile size), one workgroup per tile for the whole horizon (no floating segments: the work queue is per launch, not per
+// problem; bit-identical either way).
+Plan make_plan_batch(const cem_config_t *c, const Dims &d, int mb)
+{
+    Plan pl{};
+    pl.rc = c->chunks_per_tile;
+    if (!pl.rc) {
+        double bestc = 1e30; pl.rc = 1;
+        for (int rc = 1; rc <= 4; ++rc) {
+            std::vector<Tile6> t; build_plan_tiles(d, rc, t);
+            const double cost = tile_plan_cost(d, rc, (size_t)mb * t.size(), 1);
+            if (cost <= bestc * 1.005) { pl.rc = rc; bestc = std::min(bestc, cost); }     // (auto_chunks' rule)
+        }
+    }
+    std::vector<Tile6> t; build_plan_tiles(d, pl.rc, t);
+    pl.n_tiles = (int)t.size(); pl.n_seg = 1; pl.seg_len = d.H; pl.n_pinned = pl.n_tiles;
+    return pl;
+}
 
 }  // namespace
 
@@ -643,6 +682,8 @@ struct cem_planner {
     // grow-only device scratch of the standalone ops (unfold_sequences tiles + returns, compute_objective returns + costs)
     char *scratch; size_t scratch_bytes;
     std::vector<float> h_etab;               // host copy of RolloutParams::etab ([E][CEM_ET_ROWS + L][128]); re-uploaded whole by create / set_weights / set_normaliser
+    int batch;                               // problems of a batch handle (cem_batch_planner_create); 0: a single-state handle
+    int n_states;                            // problems of the batched plan being enqueued / last run (the rest are staged as done)
 };
 
 extern "C" {
@@ -745,28 +786,33 @@ int cem_rollout_residency(int32_t chunks_per_tile, int32_t input_blocks_per_wave
     return CEM_OK;
 }
 
-int cem_planner_create(const cem_config_t *cfg, void *workspace, size_t workspace_bytes, void *hip_stream, cem_planner_t **out)
+}  // extern "C"
+
+// mb = 0: a single-state handle (cem_planner_create); mb > 0: a batch handle of mb problems (cem_batch_planner_create)
+static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, size_t workspace_bytes, void *hip_stream, cem_planner_t **out)
 {
-    int st = validate(cfg); if (st) return st;
+    int st = mb ? validate_batch(cfg, mb) : validate(cfg); if (st) return st;
     if (!workspace || !out) return CEM_ERR_INVALID_ARG;
     warn_if_two_hip_runtimes();
     cem_planner *h = new (std::nothrow) cem_planner();
     if (!h) return CEM_ERR_INVALID_ARG;
     h->cfg = *cfg; h->d = make_dims(cfg);
-    h->lay = make_layout(cfg, h->d, max_tiles_of(h->d));
+    h->batch = mb; h->n_states = mb ? mb : 1;
+    const size_t nb = mb ? (size_t)mb : 1;
+    h->lay = make_layout(cfg, h->d, max_tiles_of(h->d), mb);
     if (workspace_bytes < h->lay.total || ((uintptr_t)workspace & 255)) { delete h; return CEM_ERR_WORKSPACE; }
     h->ws = (char *)workspace; h->stream = (hipStream_t)hip_stream; h->own_stream = false;
     if (!h->stream) {      // the legacy default stream cannot be captured into a hipGraph: use a stream of our own
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { g_last_hip = (int)hipGetLastError(); delete h; return CEM_ERR_HIP; }
         h->own_stream = true;
     }
-    { const Plan pl = make_plan(cfg, h->d); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
+    { const Plan pl = mb ? make_plan_batch(cfg, h->d, mb) : make_plan(cfg, h->d); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
       // Where the sampler runs (cem_device.h: cem_tile_sample_actions vs cem_sample_kernel).  Inside the rollout launch when ALL its
       // tiles are resident at once (one round of prologues per launch: B1, B2) — one launch and one graph node fewer per iteration for
       // about what the launch cost; as a launch of its own when tiles queue for slots (B3: 8 tiles per CU; every round of tiles would
       // pay the prologue on its critical path, and each candidate is sampled once per particle: K = 16 measured +1.5 % on the launch).
       const int slots = real_cus() * ((h->d.wide || h->d.split) ? 1 : resident_workgroups(h->d.NFW, pl.rc, pl.n_seg > 1));
-      h->sample_in_rollout = pl.n_tiles <= slots;
+      h->sample_in_rollout = (long long)nb * pl.n_tiles <= slots;        // (a batch handle: all its problems' tiles in one launch)
       if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
           h->sample_in_rollout = std::strcmp(e, "kernel") != 0; }
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
@@ -786,10 +832,11 @@ int cem_planner_create(const cem_config_t *cfg, void *workspace, size_t workspac
     };
     // mapped + coherent (fine-grained) host memory, asked for explicitly: the device reads the staged block and writes the result in place,
     // and the host polls that result while the stream is still running
-    if (hipHostMalloc((void **)&h->h_ctrl, sizeof(CtrlBlock), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostMalloc((void **)&h->h_result, 64 * 4, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail(CEM_ERR_HIP);
-    std::memset(h->h_ctrl, 0, sizeof(CtrlBlock));
-    std::memset(h->h_result, 0, 64 * 4);
+    const size_t result_bytes = mb ? nb * CEM_RESULT_WORDS * 4 : 64 * 4;
+    if (hipHostMalloc((void **)&h->h_ctrl, nb * sizeof(CtrlBlock), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostMalloc((void **)&h->h_result, result_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail(CEM_ERR_HIP);
+    std::memset(h->h_ctrl, 0, nb * sizeof(CtrlBlock));
+    std::memset(h->h_result, 0, result_bytes);
     {   // kernels read the staged control block and write the plan's result in place (no copy nodes around a plan)
         void *dc = nullptr, *dr = nullptr;
         if (hipHostGetDevicePointer(&dc, h->h_ctrl, 0) != hipSuccess || hipHostGetDevicePointer(&dr, h->h_result, 0) != hipSuccess) return fail(CEM_ERR_HIP);
@@ -845,7 +892,7 @@ int cem_planner_create(const cem_config_t *cfg, void *workspace, size_t workspac
         !upload(h->lay.tiles, tiles.data(), tiles.size() * sizeof(Tile6)) || !upload(h->lay.omask, om.data(), om.size() * 4) ||
         !upload(h->lay.kind_sel, ks.data(), ks.size() * 4) || !upload(h->lay.nmin, mn.data(), CEM_U * 4) ||
         !upload(h->lay.ndelta, dl.data(), CEM_U * 4) || !upload(h->lay.etab, h->h_etab.data(), h->h_etab.size() * 4) ||
-        hipMemsetAsync(h->ws + h->lay.act_pad, 0, (size_t)d.N * d.H * d.act_nq * 16, h->stream) != hipSuccess ||   // the padding words of the action quads are never written again
+        hipMemsetAsync(h->ws + h->lay.act_pad, 0, nb * d.N * d.H * d.act_nq * 16, h->stream) != hipSuccess ||   // the padding words of the action quads are never written again
         hipStreamSynchronize(h->stream) != hipSuccess)
         return fail(CEM_ERR_HIP);
 
@@ -865,7 +912,44 @@ int cem_planner_create(const cem_config_t *cfg, void *workspace, size_t workspac
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cem_msel_fused_kernel, 1024, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 0; }
         h->fused_resident = per_cu * real_cus();
     }
+    // a batch handle runs the one-workgroup select only: on a device that grants less dynamic LDS than validate_batch() assumed, the
+    // shape may need another form
+    if (mb && resolve_select_mode(cfg->select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, false, nullptr) != 1) {
+        if (h->h_ctrl) hipHostFree(h->h_ctrl);
+        if (h->h_result) hipHostFree(h->h_result);
+        if (h->own_stream) hipStreamDestroy(h->stream);
+        delete h;
+        return CEM_ERR_UNSUPPORTED;
+    }
     *out = h;
+    return CEM_OK;
+}
+
+extern "C" {
+
+int cem_planner_create(const cem_config_t *cfg, void *workspace, size_t workspace_bytes, void *hip_stream, cem_planner_t **out)
+{
+    return planner_create(cfg, 0, workspace, workspace_bytes, hip_stream, out);
+}
+
+size_t cem_batch_workspace_bytes(const cem_config_t *cfg, int32_t max_batch)
+{
+    if (validate_batch(cfg, max_batch) != CEM_OK) return 0;
+    const Dims d = make_dims(cfg);
+    return make_layout(cfg, d, max_tiles_of(d), max_batch).total;
+}
+
+int cem_batch_planner_create(const cem_config_t *cfg, int32_t max_batch, void *workspace, size_t workspace_bytes, void *hip_stream,
+                             cem_planner_t **out)
+{
+    const int st = validate_batch(cfg, max_batch); if (st) return st;      // (max_batch 0 would be planner_create's single-state handle)
+    return planner_create(cfg, max_batch, workspace, workspace_bytes, hip_stream, out);
+}
+
+int cem_planner_batch_capacity(const cem_planner_t *h, int32_t *max_batch_out)
+{
+    if (!h || !max_batch_out) return CEM_ERR_INVALID_ARG;
+    *max_batch_out = h->batch;
     return CEM_OK;
 }
 
@@ -1080,7 +1164,9 @@ int enqueue_begin(cem_planner *h)
     ip.host_ctrl = h->d_h_ctrl;                          // the block stage_ctrl filled, read from pinned host memory by the kernel itself
     for (int a = 0; a < d.A; ++a) { ip.mu0[a] = h->cfg.act_mu0[a]; ip.sigma0[a] = h->cfg.act_sigma0[a]; }
     if (h->n_seg > 1) { ip.seg_queue = (uint32_t *)(h->ws + l.seg_queue); ip.seg_flags = (uint32_t *)(h->ws + l.seg_flags); ip.n_ready = (h->n_tiles - h->n_pinned) * (h->n_seg - 1); }
-    const int n = std::max<int>(ip.HA, (int)(sizeof(CtrlBlock) / 4));
+    ip.n_prob = h->batch;                                // a batch handle: every problem's block and mu / sigma (the done ones included)
+    const int nb = h->batch ? h->batch : 1;
+    const int n = nb * std::max<int>(ip.HA, (int)(sizeof(CtrlBlock) / 4));
     hipLaunchKernelGGL(cem_init_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, ip);
     HIPCHK(hipGetLastError());
     return CEM_OK;
@@ -1103,11 +1189,15 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     rp.musig = (const float *)(ws + l.musig); rp.eps_act = h->eps_act ? h->eps_act + (size_t)it * d.N * d.H * d.A : nullptr;
     rp.act_bounds = (const float *)(ws + l.act_bounds); rp.actions_w = (float *)(ws + l.actions); rp.act_pad_w = (float *)(ws + l.act_pad);
     rp.pad_shift = d.O - 4 * d.act_q0; rp.pad_floats = 4 * d.act_nq; rp.N = d.N; rp.Nloc = d.Nloc; rp.n_off = d.n_off; rp.n_tiles = h->n_tiles;
+    // a batch handle: ONE launch per stage for all its problems, problem b on tiles [b n_tiles, (b + 1) n_tiles) and its own slices
+    const int nb = h->batch ? h->batch : 1;
+    rp.tiles_per_problem = h->batch ? h->n_tiles : 0;
+    rp.eps_act_pstride = (long long)d.I * d.N * d.H * d.A; rp.eps_model_pstride = (long long)d.I * d.H * d.Btot * d.O;
     if (!h->sample_in_rollout) {                          // all N candidates once, in front of the rollout launch (which then samples nothing)
         const int total = d.N * d.H * ((d.A + 3) / 4);
         size_t es = 0;
         if (h->timing) { es = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)es, 3}); hipEventRecord(get_event(h, es), h->stream); }
-        hipLaunchKernelGGL(cem_sample_kernel, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, h->stream, rp);
+        hipLaunchKernelGGL(cem_sample_kernel, dim3(std::min((total + 255) / 256, 2048), nb), dim3(256), 0, h->stream, rp);
         HIPCHK(hipGetLastError());
         if (h->timing) hipEventRecord(get_event(h, es + 1), h->stream);
         rp.musig = nullptr;
@@ -1116,13 +1206,13 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     if (h->timing) { e0 = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)e0, 0}); hipEventRecord(get_event(h, e0), h->stream); }
     if (d.wide) HIPCHK(launch_rollout_wide(h, rp, h->n_tiles, rp.eps_model ? 1 : 0));
     else if (d.split) HIPCHK(launch_rollout_split(h->rc, d.NFW, rp.eps_model ? 1 : 0, rp, h->n_tiles, h->stream));
-    else if (rp.eps_model) HIPCHK(launch_rollout<1>(h->rc, d.NFW, rp, h->n_tiles, h->stream));
+    else if (rp.eps_model) HIPCHK(launch_rollout<1>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
     else if (queued) {
         rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = (uint32_t *)(ws + l.seg_flags); rp.seg_state = (f4 *)(ws + l.seg_state);
         rp.seg_len = h->seg_len; rp.n_seg = h->n_seg; rp.n_pinned = h->n_pinned;
         // one workgroup per pinned tile, then one per (floating tile, segment) item
         HIPCHK(launch_rollout_seg(h->rc, d.NFW, rp, h->n_pinned + h->n_seg * (h->n_tiles - h->n_pinned), h->stream));
-    } else HIPCHK(launch_rollout<0>(h->rc, d.NFW, rp, h->n_tiles, h->stream));
+    } else HIPCHK(launch_rollout<0>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
     if (h->timing) hipEventRecord(get_event(h, e0 + 1), h->stream);
     if (fold_reduce) return CEM_OK;
 
@@ -1132,7 +1222,7 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     qp.zero = (uint32_t *)(ws + l.ms_hist); qp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;     // for this iteration's multi-workgroup select
     size_t er = 0;
     if (h->timing) { er = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)er, 2}); hipEventRecord(get_event(h, er), h->stream); }
-    hipLaunchKernelGGL(cem_reduce_kernel, dim3((d.Nloc + 63) / 64), dim3(CEM_REDUCE_THREADS), 0, h->stream, qp);
+    hipLaunchKernelGGL(cem_reduce_kernel, dim3((d.Nloc + 63) / 64, nb), dim3(CEM_REDUCE_THREADS), 0, h->stream, qp);
     HIPCHK(hipGetLastError());
     if (h->timing) hipEventRecord(get_event(h, er + 1), h->stream);
     return CEM_OK;
@@ -1208,16 +1298,18 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
             hipLaunchKernelGGL(cem_msel_final_kernel, dim3(1), dim3(256), 0, h->stream, m);
         }
     } else {
-        if (fold_final) {
+        if (fold_final && !h->batch) {     // (a batch handle: the final kernel writes every problem's result, then the completion markers)
             p.is_last = it == d.I - 1;
             p.result = h->d_h_result; p.result_dev = (uint32_t *)(ws + l.result); p.eps_out = have_eps_out ? (const float *)(ws + l.eps_out) : nullptr; p.noise_stddev = h->cfg.noise_stddev;
             if (folded) *folded = true;
         }
         if (cache) lds += (size_t)CEM_SEL_KWORDS(d.N) * 4;
         // (SafeCemMpc's scores have a crowd near -100: the instantiation that counts and ranks wave by wave; same results either way)
-        if (cache && h->cfg.variant == CEM_VARIANT_SAFE) hipLaunchKernelGGL((cem_select_kernel<true, true>), dim3(1), dim3(1024), lds, h->stream, p);
-        else if (cache) hipLaunchKernelGGL((cem_select_kernel<true, false>), dim3(1), dim3(1024), lds, h->stream, p);
-        else hipLaunchKernelGGL((cem_select_kernel<false, false>), dim3(1), dim3(1024), lds, h->stream, p);
+        // one workgroup per problem (batch handles: blockIdx.x is the problem)
+        const dim3 grid(h->batch ? h->batch : 1);
+        if (cache && h->cfg.variant == CEM_VARIANT_SAFE) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
+        else if (cache) hipLaunchKernelGGL((cem_select_kernel<true, false>), grid, dim3(1024), lds, h->stream, p);
+        else hipLaunchKernelGGL((cem_select_kernel<false, false>), grid, dim3(1024), lds, h->stream, p);
     }
     HIPCHK(hipGetLastError());
     if (h->timing) hipEventRecord(get_event(h, e0 + 1), h->stream);
@@ -1238,6 +1330,13 @@ int enqueue_exchange(cem_planner *h)
 int enqueue_end(cem_planner *h, bool have_eps_out)
 {
     const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
+    if (h->batch) {
+        FinalBatchParams fb{}; fb.ctrl = (const CtrlBlock *)(ws + l.ctrl); fb.eps_out = have_eps_out ? (const float *)(ws + l.eps_out) : nullptr;
+        fb.result = h->d_h_result; fb.result_dev = (uint32_t *)(ws + l.result); fb.A = d.A; fb.n_prob = h->batch; fb.noise_stddev = h->cfg.noise_stddev;
+        hipLaunchKernelGGL(cem_final_batch_kernel, dim3(1), dim3(256), 0, h->stream, fb);
+        HIPCHK(hipGetLastError());
+        return CEM_OK;
+    }
     FinalParams fp{}; fp.ctrl = (const CtrlBlock *)(ws + l.ctrl); fp.eps_out = have_eps_out ? (const float *)(ws + l.eps_out) : nullptr;
     fp.result = h->d_h_result; fp.result_dev = (uint32_t *)(ws + l.result); fp.A = d.A; fp.noise_stddev = h->cfg.noise_stddev;       // pinned host memory: no copy node behind the kernel
     hipLaunchKernelGGL(cem_final_kernel, dim3(1), dim3(64), 0, h->stream, fp);
@@ -1276,11 +1375,16 @@ void stage_ctrl(cem_planner *h, const float *state, uint64_t seed, uint64_t call
 // through hipStreamSynchronize (an interrupt / yield path that took ~10 us of a 1.9-ms plan).  Bounded: after 100 ms of polling the
 // ordinary synchronisation takes over.
 // the block is complete when it carries this plan's counter AND its checksum holds (device -> host writes arrive in no particular order)
+// (a batch handle: every block of the plan's problems, [n_states][CEM_RESULT_WORDS])
 bool result_landed(const cem_planner *h)
 {
-    const volatile uint32_t *r = reinterpret_cast<const volatile uint32_t *>(h->h_result);
-    if (r[36] != h->plan_seq) return false;
-    return cem_result_checksum(r, h->plan_seq) == r[37];      // position dependent: stale words cannot cancel (cem_device.h)
+    const int nblk = h->batch ? h->n_states : 1;
+    for (int b = 0; b < nblk; ++b) {
+        const volatile uint32_t *r = reinterpret_cast<const volatile uint32_t *>(h->h_result) + (size_t)b * CEM_RESULT_WORDS;
+        if (r[36] != h->plan_seq) return false;
+        if (cem_result_checksum(r, h->plan_seq) != r[37]) return false;     // position dependent: stale words cannot cancel (cem_device.h)
+    }
+    return true;
 }
 
 int wait_result(cem_planner *h)
@@ -1327,13 +1431,100 @@ int read_result(cem_planner *h, float *action_out, float *best_score_out, int32_
     return (fault & (CEM_FAULT_SEGMENT | CEM_FAULT_BARRIER)) ? CEM_ERR_DEVICE : CEM_OK;     // a kernel gave up and nothing made up for it
 }
 
+// a batched plan's control blocks: problem b < n gets states[b] and the Philox key (seed, calls[b]) — exactly what cem_planner_plan
+// stages for that state alone; problems n .. batch - 1 are staged as already stopped (done, no iterations), so every kernel skips them
+void stage_ctrl_batch(cem_planner *h, int32_t n, const float *states, uint64_t seed, const uint64_t *calls)
+{
+    const uint32_t seq = ++h->plan_seq;
+    for (int b = 0; b < h->batch; ++b) {
+        CtrlBlock *c = h->h_ctrl + b;
+        const uint64_t call = b < n ? calls[b] : 0;
+        c->seed_lo = (uint32_t)seed; c->seed_hi = (uint32_t)(seed >> 32); c->call_lo = (uint32_t)call; c->call_hi = (uint32_t)(call >> 32);
+        c->done = b < n ? 0 : 1; c->iters = 0; c->fault = 0; c->best_score = -std::numeric_limits<float>::infinity();
+        for (int f = 0; f < CEM_U; ++f) c->state[f] = (b < n && f < h->d.O) ? states[(size_t)b * h->d.O + f] : 0.f;
+        for (int a = 0; a < 32; ++a) c->best[a] = 0.f;
+        c->seq = seq; c->inject = 0;
+    }
+    h->n_states = n;
+}
+
+int read_batch_results(cem_planner *h, int32_t n, float *actions_out, float *scores_out, int32_t *iters_out)
+{
+    for (int spin = 0; spin < 2000000 && !result_landed(h); ++spin) { }
+    if (!result_landed(h)) return CEM_ERR_DEVICE;
+    int fault = 0;
+    for (int b = 0; b < n; ++b) {
+        const float *r = h->h_result + (size_t)b * CEM_RESULT_WORDS;
+        if (actions_out) std::memcpy(actions_out + (size_t)b * h->d.A, r, h->d.A * 4);
+        if (scores_out) scores_out[b] = r[32];
+        if (iters_out) iters_out[b] = reinterpret_cast<const int32_t *>(r)[33];
+        fault |= reinterpret_cast<const int32_t *>(r)[35];
+    }
+    return (fault & (CEM_FAULT_SEGMENT | CEM_FAULT_BARRIER)) ? CEM_ERR_DEVICE : CEM_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
+                           const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
+                           float *best_scores_out, int32_t *iters_out)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (!h->batch) return CEM_ERR_STATE;                 // a single-state handle: cem_planner_plan
+    if (!states || !calls || n_states < 1 || n_states > h->batch) return CEM_ERR_INVALID_ARG;
+    if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
+    if ((eps_act_dev == nullptr) != (eps_model_dev == nullptr) && h->cfg.sampling_propagation) return CEM_ERR_INVALID_ARG;
+    const bool fold = folds_reduce(h);
+    // One hipGraph per handle, captured for all `batch` problems: n_states only changes what is staged (the rest are done), never the graph
+    if (h->cfg.use_graph && !eps_act_dev && !eps_model_dev && !eps_out_host && !h->timing) {
+        stage_ctrl_batch(h, n_states, states, seed, calls);
+        if (!h->graph_ready) {
+            h->eps_act = h->eps_model = nullptr;
+            HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+            int st = enqueue_begin(h);
+            for (int it = 0; it < h->d.I && !st; ++it) {
+                st = enqueue_rollout(h, it, fold);
+                if (!st) st = enqueue_select(h, it, fold);
+            }
+            if (!st) st = enqueue_end(h, false);
+            hipError_t ce = hipStreamEndCapture(h->stream, &h->graph);
+            if (!st && ce == hipSuccess) ce = hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0);
+            if (st || ce != hipSuccess) {
+                if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
+                h->gexec = nullptr;
+                if (st) return st;
+                HIPCHK(ce);
+            }
+            h->graph_ready = true;
+        }
+        HIPCHK(hipGraphLaunch(h->gexec, h->stream));
+        { const int ws_ = wait_result(h); if (ws_) return ws_; }
+        return read_batch_results(h, n_states, actions_out, best_scores_out, iters_out);
+    }
+    stage_ctrl_batch(h, n_states, states, seed, calls);
+    h->eps_act = eps_act_dev; h->eps_model = eps_model_dev;
+    h->ev_kind.clear();
+    int st = enqueue_begin(h);
+    if (!st && eps_out_host)
+        HIPCHK(hipMemcpyAsync(h->ws + h->lay.eps_out, eps_out_host, (size_t)n_states * h->d.A * 4, hipMemcpyHostToDevice, h->stream));
+    for (int it = 0; it < h->d.I && !st; ++it) {
+        st = enqueue_rollout(h, it, fold);
+        if (!st) st = enqueue_select(h, it, fold);
+    }
+    if (!st) st = enqueue_end(h, eps_out_host != nullptr);
+    h->eps_act = h->eps_model = nullptr;
+    if (st) return st;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->timing) collect_timing(h);
+    return read_batch_results(h, n_states, actions_out, best_scores_out, iters_out);
+}
+
 int cem_plan_begin(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
 {
     if (!h || !state) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;                  // a batch handle plans through cem_planner_plan_batch only
     if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
     if ((eps_act_dev == nullptr) != (eps_model_dev == nullptr) && h->cfg.sampling_propagation) return CEM_ERR_INVALID_ARG;
     stage_ctrl(h, state, seed, call);
@@ -1375,6 +1566,7 @@ int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64
                      const float *eps_model_dev, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
 {
     if (!h || !state) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;                  // a batch handle plans through cem_planner_plan_batch only
     if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
     if (h->d.W != 1 && !h->comm) return CEM_ERR_STATE;   // sharded ranks without cem_planner_comm_init use the stepwise calls around their own collective
     // With a communicator the first plan runs eagerly: RCCL finishes its lazy set-up (buffers, kernels) outside any capture.
@@ -1443,6 +1635,7 @@ int cem_comm_unique_id(void *id_out)
 int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int32_t rank)
 {
     if (!h || !id) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;                                        // batch handles are single-rank
     if (n_ranks != h->d.W || rank != h->d.R) return CEM_ERR_INVALID_ARG;       // the communicator IS the candidate sharding of this handle
     if (h->in_plan) return CEM_ERR_STATE;
     Rccl *r = rccl(); if (!r) return CEM_ERR_COMM;
@@ -1535,6 +1728,7 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
                          const float *eps_model_dev, uint64_t seed, uint64_t call, float *traj_out_dev, float *mu_out_dev, float *sd_out_dev)
 {
     if (!h || !s0_dev || !actions_dev || n_rows < 1 || horizon < 1 || horizon > 65535) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;                  // the model ops run on single-state handles
     if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
     if (h->in_plan) return CEM_ERR_STATE;
     const Dims &d = h->d;
@@ -1570,6 +1764,7 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
 int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_rows, int32_t horizon, float *scores_out_dev)
 {
     if (!h || !traj_dev || !scores_out_dev || n_rows < 1 || horizon < 1 || horizon > 65535) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;
     const Dims &d = h->d;
     if (n_rows % d.P != 0) return CEM_ERR_INVALID_ARG;                 // reshape(cum, (particles, -1)) would raise (mpc_policy.py:38)
     if ((long long)n_rows * horizon > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;
@@ -1602,12 +1797,14 @@ int cem_scorer_reward(cem_planner_t *h, const float *obs_dev, const float *next_
                       uint8_t *goal_achieved_out_dev)
 {
     if (!h || !obs_dev || !next_obs_dev || !reward_out_dev || n < 1) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;
     return scorer_op(h, obs_dev, next_obs_dev, n, reward_out_dev, goal_achieved_out_dev, 0);
 }
 
 int cem_scorer_cost(cem_planner_t *h, const float *obs_dev, int32_t n, float *cost_out_dev)
 {
     if (!h || !obs_dev || !cost_out_dev || n < 1) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;
     return scorer_op(h, obs_dev, nullptr, n, cost_out_dev, nullptr, 1);
 }
 

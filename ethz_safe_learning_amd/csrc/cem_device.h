@@ -134,6 +134,12 @@ struct RolloutParams {
     uint32_t *seg_flags;         // [n_float * (n_seg - 1)] FIFO of ready floating items ((tile << 8 | segment) + 1; 0 = not written yet)
     f4 *seg_state;               // [n_float][2*NFW*RC*256 + 64] state a floating tile carries across a segment boundary
     int32_t seg_len, n_seg, n_tiles, n_pinned;
+    // batched plans (cem_planner_plan_batch): problem b owns tiles [b * tiles_per_problem, (b + 1) * tiles_per_problem) of the launch, all
+    // of them described by the SAME descriptors tiles[0 .. tiles_per_problem) (problem-relative rows, candidates and Philox rows), and its
+    // own slice of ctrl (one CtrlBlock), musig (2 H A), actions (N H A), act_pad (N H act_nq quads), ret (Bloc), costs (H Bloc) and of the
+    // explicit noise tensors (the strides below, in floats).  0: one problem (every single-state plan and standalone op).
+    int32_t tiles_per_problem;
+    long long eps_act_pstride, eps_model_pstride;
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -475,23 +481,26 @@ __device__ __forceinline__ void cem_scorer_terms(const f4 sn, const float D, con
 // select still runs over ALL N candidates, so the tiles also share out the sequences of the OTHER ranks' candidates (`actions` only):
 // tile b of n_tiles takes the b-th slice of those (N - Nloc) * H * ceil(A / 4) draws.  With this the sampler costs no launch of its own
 // (it was 4.8 us + a graph-node gap per iteration at B2).  The caller waits (vmcnt(0)) and barriers before the first action load.
+// b: the problem of a batched plan (RolloutParams::tiles_per_problem): its own mu / sigma, noise and action arrays; n stays problem-relative
 __device__ __forceinline__ void cem_sample_store(const RolloutParams &p, const int n, const int t, const int z, const PhiloxKey key, const bool pad,
-                                                 const bool natural = true)
+                                                 const bool natural = true, const int b = 0)
 {
     const int A = p.A, HA = p.H * A;
+    const float *musig = p.musig + (size_t)b * 2 * HA;
     f4 e;
     if (p.eps_act) {
+        const float *eps_act = p.eps_act + b * p.eps_act_pstride;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int a = 4 * z + r; e[r] = p.eps_act[((size_t)n * p.H + t) * A + (a < A ? a : A - 1)]; }
+        for (int r = 0; r < 4; ++r) { const int a = 4 * z + r; e[r] = eps_act[((size_t)n * p.H + t) * A + (a < A ? a : A - 1)]; }
     } else e = cem_normal4((uint32_t)n, (uint32_t)t, (uint32_t)p.it, (uint32_t)z, CEM_STREAM_ACT, key);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int a = 4 * z + r;
         if (a < A) {
-            float v = e[r] * p.musig[HA + t * A + a] + p.musig[t * A + a];             // tf.random.normal(mean, stddev)
+            float v = e[r] * musig[HA + t * A + a] + musig[t * A + a];                 // tf.random.normal(mean, stddev)
             v = fminf(fmaxf(v, p.act_bounds[a]), p.act_bounds[32 + a]);                // tf.clip_by_value
-            if (natural) p.actions_w[((size_t)n * p.H + t) * A + a] = v;
-            if (pad) p.act_pad_w[((size_t)n * p.H + t) * p.pad_floats + p.pad_shift + a] = v;   // padding words stay 0 (zeroed at create)
+            if (natural) p.actions_w[((size_t)b * p.N + n) * HA + (size_t)t * A + a] = v;
+            if (pad) p.act_pad_w[((size_t)b * p.N * p.H + (size_t)n * p.H + t) * p.pad_floats + p.pad_shift + a] = v;   // padding words stay 0 (zeroed at create)
         }
     }
 }
@@ -504,19 +513,20 @@ __device__ __forceinline__ void cem_tile_sample_join()
 // WAIT false: the stores are only issued; the caller joins (cem_tile_sample_join) once the rest of its tile set-up is issued too
 // natural_all: every tile also stores its candidates in the [N][H][A] layout (the explicit-tensor rollout forms read that one back);
 // otherwise only the tiles of particle 0 do — the select is its only reader then, and P - 1 of P copies were 2 MB of stores a launch
+// b: the problem of a batched plan; tile_idx is then the tile's index within its problem
 template <bool WAIT = true>
 __device__ __forceinline__ void cem_tile_sample_actions(const RolloutParams &p, const int tile_idx, const int t0, const int t1, const bool foreign,
-                                                        const bool natural_all = true)
+                                                        const bool natural_all = true, const int b = 0)
 {
     if (!p.musig) return;                                    // wave-uniform (a kernel argument)
     const TileDesc td = p.tiles[tile_idx];
     const bool natural = natural_all || td.row_base < p.Nloc;
     const int AZ = (p.A + 3) >> 2, nst = t1 - t0;
-    const PhiloxKey key = cem_key(p.ctrl);
+    const PhiloxKey key = cem_key(p.ctrl + b);
     const int own = td.cnt * nst * AZ;
     for (int idx = (int)threadIdx.x; idx < own; idx += 256) {
         const int z = idx % AZ, tt = (idx / AZ) % nst, r_ = idx / (AZ * nst);
-        cem_sample_store(p, td.act_base + r_, t0 + tt, z, key, true, natural);
+        cem_sample_store(p, td.act_base + r_, t0 + tt, z, key, true, natural, b);
     }
     if (foreign && p.Nloc < p.N) {                           // the other ranks' candidates, shared out over this rank's tiles
         const long long total = (long long)(p.N - p.Nloc) * p.H * AZ;
@@ -536,15 +546,17 @@ __device__ __forceinline__ void cem_tile_sample_actions(const RolloutParams &p, 
 // tiles on the critical path: measured +1.5 % on B3's launch, K = 16, against 0.2 % for this kernel; at B1 / B2 — every tile resident
 // at once, five particles — the prologue costs what this launch plus its graph node cost, and saves the node).  Host rule: cem_capi.hip
 // sample_in_rollout().
+// Batched plans: blockIdx.y is the problem (each problem skips on its own early stop).
 __global__ __launch_bounds__(256) void cem_sample_kernel(const RolloutParams p)
 {
-    if (p.check_done && p.ctrl->done) return;
+    const int b = (int)blockIdx.y;
+    if (p.check_done && p.ctrl[b].done) return;
     const int AZ = (p.A + 3) >> 2;
     const int total = p.N * p.H * AZ;
-    const PhiloxKey key = cem_key(p.ctrl);
+    const PhiloxKey key = cem_key(p.ctrl + b);
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int z = idx % AZ, t = (idx / AZ) % p.H, n = idx / (AZ * p.H);
-        cem_sample_store(p, n, t, z, key, true);
+        cem_sample_store(p, n, t, z, key, true, true, b);
     }
 }
 
@@ -552,8 +564,10 @@ __global__ __launch_bounds__(256) void cem_sample_kernel(const RolloutParams p)
 // segment of it; what a tile carries across a segment boundary (state registers, its next layer-0 input blocks, the bookkeeping
 // wave's reward / done state) goes through p.seg_state, so any workgroup on any CU can run the tile's next segment and the
 // result is bit-identical to the unsegmented run.
+// b: the problem of a batched plan (tile_idx is then the tile's index within the problem): state, key, actions, noise, returns and costs
+// come from / go to that problem's slices (RolloutParams::tiles_per_problem)
 template <int RC, int NFW, int MODE, bool SEG>
-__device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *smem, const int tile_idx, const int t_begin, const int t_end)
+__device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *smem, const int tile_idx, const int t_begin, const int t_end, const int b = 0)
 {
     // The four waves' ROLES (which input / output feature blocks a wave owns, hence its weight stream; who keeps the books) rotate
     // with the tile: hardware wave v plays logical wave w = (v + tile rotation) mod 4.  The roles are not equally heavy — the
@@ -576,7 +590,8 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
     constexpr int LA = CEM_LDS_AHEAD_OF(RC, NFW);
     float *part = reinterpret_cast<float *>(smem + 2 * XB);
     int xw = 0;                                          // LDS buffer the current stage's outputs go to
-    const PhiloxKey key = cem_key(p.ctrl);
+    const CtrlBlock *const ctrl = p.ctrl + b;
+    const PhiloxKey key = cem_key(ctrl);
     const float rscale = p.sampling ? CEM_BM_RSCALE : 0.0f;     // sampling_propagation False: the model noise is exactly 0
 
     // descriptor inputs made provably wave-uniform (the tile descriptor load and the wave id are uniform in fact)
@@ -622,7 +637,7 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
             for (int r = 0; r < 4; ++r) {
                 const int f = f0 + r;
                 float v = 0.f;
-                if (f < O) v = td.s0_base < 0 ? p.ctrl->state[f] : p.s0[(size_t)(td.s0_base + slotc[c]) * O + f];
+                if (f < O) v = td.s0_base < 0 ? ctrl->state[f] : p.s0[(size_t)(td.s0_base + slotc[c]) * O + f];
                 s[i][c][r] = v;
             }
         }
@@ -630,12 +645,13 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
 
     // this lane's actions.  MODE 0: the padded quad layout (one 16-byte buffer load per unit and step, the step in the scalar
     // offset); MODE 1 (caller-supplied action tensors): the natural [n][H][A] layout, element by element.
-    const __amdgpu_buffer_rsrc_t act_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4 *>(p.act_pad), 0, MODE == 0 ? p.act_pad_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t act_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4 *>(p.act_pad + (size_t)b * p.N * H * p.act_nq), 0,
+                                                                            MODE == 0 ? p.act_pad_bytes : 0u, 0x00020000);
     int actv[NFW][RC];
     const float *actrow[RC];
 #pragma unroll
     for (int c = 0; c < RC; ++c) {
-        actrow[c] = p.actions + (size_t)(td.act_base + slotc[c]) * H * A;
+        actrow[c] = p.actions + ((size_t)b * p.N + td.act_base + slotc[c]) * H * A;
 #pragma unroll
         for (int i = 0; i < NFW; ++i) {
             int qi = 4 * (w + 4 * i) + q - p.act_q0;
@@ -655,7 +671,7 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
     const int nk = 1 + p.sc.n_cost;
     const float csz[4] = {p.sc.cost_size[0], p.sc.cost_size[1], p.sc.cost_size[2], p.sc.cost_size[3]};
     const float ind_cap = p.sc.indicator ? 1.0f : __builtin_inff(), clipv = p.sc.reward_clip > 0.f ? p.sc.reward_clip : __builtin_inff();
-    const __amdgpu_buffer_rsrc_t cost_rs = __builtin_amdgcn_make_buffer_rsrc(p.costs, 0, p.costs ? (uint32_t)(H * p.Bloc) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t cost_rs = __builtin_amdgcn_make_buffer_rsrc(p.costs ? p.costs + (size_t)b * H * p.Bloc : p.costs, 0, p.costs ? (uint32_t)(H * p.Bloc) : 0u, 0x00020000);
 
     // reward / cost / done bookkeeping of step T_ from the scorer terms in `part` (rows of the tile on the bookkeeping wave's
     // lanes); T_ = -1 only initialises d_prev / c_prev from s_0
@@ -878,7 +894,7 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int fc = (f0 + r < O) ? f0 + r : O - 1;
-                        eps4[c][r] = p.eps_model[((size_t)t * p.Btot + td.noise_row_base + slotc[c]) * O + fc];
+                        eps4[c][r] = p.eps_model[b * p.eps_model_pstride + ((size_t)t * p.Btot + td.noise_row_base + slotc[c]) * O + fc];
                     }
                     eps4[c] = eps4[c] * (p.sampling ? 1.0f : 0.0f);
                 } else {
@@ -934,7 +950,7 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
     __syncthreads();
     CEM_BOOKKEEP(t_end - 1);
     if (!SEG || t_end == H) {
-        if (w == wbk && lane < td.cnt) p.ret[td.row_base + lane] = cum;
+        if (w == wbk && lane < td.cnt) p.ret[(size_t)b * p.Bloc + td.row_base + lane] = cum;
     } else {
 #pragma unroll
         for (int i = 0; i < NFW; ++i)
@@ -956,13 +972,16 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
 // CEM_BOOKKEEP, CEM_PART_MIN4, CEM_PAIR_MIN_STORE and CEM_RARE_KINDS_AND_STORE stay defined: cem_rollout_wide.h uses them with the
 // same local names (RC = 1) and undefines them.
 
+// Batched plans: workgroup g runs tile g % tiles_per_problem of problem g / tiles_per_problem, and leaves at once when THAT problem has stopped.
 template <int RC, int NFW, int MODE>
 __global__ __launch_bounds__(256) void cem_rollout_kernel(const RolloutParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (p.check_done && p.ctrl->done) return;
-    cem_tile_sample_actions<false>(p, (int)blockIdx.x, 0, p.H, true, MODE == 1);
-    cem_rollout_tile<RC, NFW, MODE, false>(p, smem, (int)blockIdx.x, 0, p.H);
+    const int tpp = p.tiles_per_problem;
+    const int b = tpp ? (int)blockIdx.x / tpp : 0, tile = (int)blockIdx.x - b * tpp;
+    if (p.check_done && p.ctrl[b].done) return;
+    cem_tile_sample_actions<false>(p, tile, 0, p.H, true, MODE == 1, b);
+    cem_rollout_tile<RC, NFW, MODE, false>(p, smem, tile, 0, p.H, b);
 }
 
 // Pinned tiles + floating segments.  A tile is 16*RC rows for the WHOLE horizon, so a launch whose tile count is not a multiple
@@ -1044,20 +1063,25 @@ __global__ __launch_bounds__(256) void cem_rollout_seg_kernel(const RolloutParam
 // ---------------------------------------------------------------------------------------------------------
 // small kernels of the optimiser loop
 // ---------------------------------------------------------------------------------------------------------
-struct InitParams { CtrlBlock *ctrl; const CtrlBlock *host_ctrl; float *musig; int32_t HA, A; float mu0[32], sigma0[32]; uint32_t *seg_queue, *seg_flags; int32_t n_ready; };
+struct InitParams { CtrlBlock *ctrl; const CtrlBlock *host_ctrl; float *musig; int32_t HA, A; float mu0[32], sigma0[32]; uint32_t *seg_queue, *seg_flags; int32_t n_ready;
+                    int32_t n_prob;   /* problems of a batched plan: ctrl / host_ctrl are [n_prob] blocks, musig [n_prob][2][HA] (0 = one) */ };
 
 __global__ void cem_init_kernel(const InitParams p)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     // the plan's control block (Philox key, observation, cleared best-so-far / flags) as the host staged it in PINNED memory: read
     // from there directly — a copy node of its own in front of every plan cost a 3.6 us blit kernel plus its gap
-    if (p.host_ctrl && i < (int)(sizeof(CtrlBlock) / 4)) reinterpret_cast<uint32_t *>(p.ctrl)[i] = reinterpret_cast<const uint32_t *>(p.host_ctrl)[i];
+    const int np = p.n_prob > 1 ? p.n_prob : 1;
+    if (p.host_ctrl && i < np * (int)(sizeof(CtrlBlock) / 4)) reinterpret_cast<uint32_t *>(p.ctrl)[i] = reinterpret_cast<const uint32_t *>(p.host_ctrl)[i];
     // the rollout launches' work queue starts every plan empty (a launch resets it itself; this covers a plan that ended in a fault)
     if (p.seg_queue) {
         if (i < 3) p.seg_queue[i] = 0u;
         for (int e = i; e < p.n_ready; e += gridDim.x * blockDim.x) p.seg_flags[e] = 0u;
     }
-    if (i < p.HA) { p.musig[i] = p.mu0[i % p.A]; p.musig[p.HA + i] = p.sigma0[i % p.A]; }   // cem_mpc.py:39-40
+    if (i < np * p.HA) {                                                                         // cem_mpc.py:39-40
+        const int b = i / p.HA, j = i - b * p.HA;
+        p.musig[(size_t)b * 2 * p.HA + j] = p.mu0[j % p.A]; p.musig[(size_t)b * 2 * p.HA + p.HA + j] = p.sigma0[j % p.A];
+    }
     if (!p.host_ctrl) {                                       // (staged by the host along with the rest of the block otherwise: stage_ctrl)
         if (i < 32) p.ctrl->best[i] = 0.f;                                                     // cem_mpc.py:41
         if (i == 0) { p.ctrl->best_score = -__builtin_inff(); p.ctrl->done = 0; p.ctrl->iters = 0; p.ctrl->fault = 0; }
@@ -1069,6 +1093,8 @@ struct ReduceParams {
     int32_t Nloc, P, H, variant, check_done;
     float alpha, beta, thr;
     uint32_t *zero; int32_t zero_n;        // words block 0 clears for the multi-workgroup select that follows (digit histograms + barrier counter), or null
+    // batched plans: blockIdx.y is the problem; its ret / costs / scores are the next [P][Nloc] / [H][P][Nloc] / [Nloc] slices, its
+    // control block ctrl[blockIdx.y]
 };
 
 // One block = 64 candidates (one per lane) x 16 waves.  The kernel is a latency chain — a few hundred bytes per candidate, one dependent
@@ -1084,8 +1110,11 @@ __global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const Re
 {
     __shared__ int32_t unsafe_w[16][64];
     __shared__ uint32_t cnt_s[16][64];
-    if (p.check_done && p.ctrl->done) return;
-    if (p.zero && blockIdx.x == 0) for (int i = threadIdx.x; i < p.zero_n; i += CEM_REDUCE_THREADS) p.zero[i] = 0u;
+    const int b = (int)blockIdx.y;
+    if (p.check_done && p.ctrl[b].done) return;
+    if (p.zero && blockIdx.x == 0 && b == 0) for (int i = threadIdx.x; i < p.zero_n; i += CEM_REDUCE_THREADS) p.zero[i] = 0u;
+    const float *const ret = p.ret + (size_t)b * p.P * p.Nloc;
+    const uint8_t *const costs = p.costs ? p.costs + (size_t)b * p.H * p.P * p.Nloc : p.costs;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int n = blockIdx.x * 64 + lane;
     const bool live = n < p.Nloc;
@@ -1095,7 +1124,7 @@ __global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const Re
     float r0[16];
     if (w == 0) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j) r0[j] = p.ret[(size_t)(j < P ? j : 0) * p.Nloc + nn];
+        for (int j = 0; j < 16; ++j) r0[j] = ret[(size_t)(j < P ? j : 0) * p.Nloc + nn];
     }
     int32_t unsafe = 0;
     if (p.variant == 1) {                                              // safe_cem_mpc.py:90-96,110-120
@@ -1104,7 +1133,7 @@ __global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const Re
         if (H >= 16) {
             for (int t = w; t < H; t += 32) {
                 const int t2 = t + 16 < H ? t + 16 : t;               // (clamped: the loads are unconditional, the second count is dropped)
-                const uint8_t *ca = p.costs + (size_t)t * Bloc + nn, *cb = p.costs + (size_t)t2 * Bloc + nn;
+                const uint8_t *ca = costs + (size_t)t * Bloc + nn, *cb = costs + (size_t)t2 * Bloc + nn;
                 uint32_t cnta = 0, cntb = 0;
                 for (int q = 0; q < P; q += 8) {
                     uint32_t va[8], vb[8];
@@ -1122,7 +1151,7 @@ __global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const Re
             __syncthreads();
             if (w < H * wpt) {
                 const int t = w / wpt, part = w % wpt;
-                const uint8_t *c = p.costs + (size_t)t * Bloc + nn;
+                const uint8_t *c = costs + (size_t)t * Bloc + nn;
                 uint32_t cnt = 0;
                 for (int q = part; q < P; q += 16 * wpt) {
                     uint32_t v[16];
@@ -1145,7 +1174,7 @@ __global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const Re
         for (int q = 16; q < P; q += 16) {
             float v[16];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = p.ret[(size_t)(q + j < P ? q + j : q) * p.Nloc + nn];
+            for (int j = 0; j < 16; ++j) v[j] = ret[(size_t)(q + j < P ? q + j : q) * p.Nloc + nn];
 #pragma unroll
             for (int j = 0; j < 16; ++j) if (q + j < P) sum = sum + v[j];
         }
@@ -1159,7 +1188,7 @@ __global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const Re
         for (int i = 0; i < 16; ++i) u |= unsafe_w[i][lane];
         score = score - (u ? 1.0f : 0.0f) * 100.0f;
     }
-    p.scores[n] = score;
+    p.scores[(size_t)b * p.Nloc + n] = score;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1413,7 +1442,16 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
     __shared__ __attribute__((aligned(16))) float red[4096];   // per-thread partial sums (float4 in the wide moments path)
     __shared__ float bsc[16];
     __shared__ int bpos[16];
-    if (p.check_done && p.ctrl->done) return;
+    // batched plans: one workgroup per problem (grid = problems), each on its own slices; blockIdx.x = 0 for a single plan
+    const int prob = (int)blockIdx.x;
+    CtrlBlock *const ctrl = p.ctrl + prob;
+    if (p.check_done && ctrl->done) return;
+    const float *const scores_b = p.scores + (size_t)prob * p.N;
+    const float *const actions_b = p.actions + (size_t)prob * p.N * p.HA;
+    float *const musig_b = p.musig + (size_t)prob * 2 * p.HA;
+    int32_t *const elite_b = p.elite_idx + (size_t)prob * p.k;
+    const float *const ret_b = p.ret ? p.ret + (size_t)prob * p.P * p.N : p.ret;
+    float *const scores_wb = p.scores_w ? p.scores_w + (size_t)prob * p.N : p.scores_w;
 
     const int tid = threadIdx.x;
     const int N = p.N, k = p.k, HA = p.HA;
@@ -1428,7 +1466,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
 
     // old mu / sigma of the columns this thread will finish (first column block): requested now, needed at the very end
     float old_mu = 0.f, old_sg = 0.f;
-    if (tid < HA) { old_mu = p.musig[tid]; old_sg = p.musig[HA + tid]; }
+    if (tid < HA) { old_mu = musig_b[tid]; old_sg = musig_b[HA + tid]; }
 
     // stage the keys; their block-wide min / max tell which leading bytes every key shares (scores of one iteration
     // usually share sign and exponent): those radix passes have nothing to count
@@ -1436,7 +1474,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
     if (CACHE) {
         for (int i0 = 0; i0 < N; i0 += 4096) {
             float v[4];
-            if (p.ret) {
+            if (ret_b) {
                 // cem_reduce_kernel's sum for this thread's four candidates: particles in ascending order, eight (clamped, hence
                 // unconditional) loads per candidate in flight; reduce_mean = sum / P
                 float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1447,7 +1485,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
                         if (i0 + j * 1024 < N) {                              // (block-uniform: a slice of 1024 candidates that exists)
                             const int i = i0 + j * 1024 + tid, ic = i < N ? i : N - 1;
 #pragma unroll
-                            for (int u = 0; u < 8; ++u) r[u][j] = p.ret[(size_t)(q0 + u < p.P ? q0 + u : p.P - 1) * N + ic];
+                            for (int u = 0; u < 8; ++u) r[u][j] = ret_b[(size_t)(q0 + u < p.P ? q0 + u : p.P - 1) * N + ic];
                         }
 #pragma unroll
                     for (int u = 0; u < 8; ++u)
@@ -1457,10 +1495,10 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
                         }
                 }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { const int i = i0 + j * 1024 + tid; v[j] = acc[j] / (float)p.P; if (i < N) p.scores_w[i] = v[j]; }
+                for (int j = 0; j < 4; ++j) { const int i = i0 + j * 1024 + tid; v[j] = acc[j] / (float)p.P; if (i < N) scores_wb[i] = v[j]; }
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { const int i = i0 + j * 1024 + tid; if (i < N) v[j] = p.scores[i]; }
+                for (int j = 0; j < 4; ++j) { const int i = i0 + j * 1024 + tid; if (i < N) v[j] = scores_b[i]; }
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -1475,7 +1513,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
         }
         if ((tid & 63) == 0) { wsum[0][tid >> 6] = kmin; wsum[1][tid >> 6] = kmax; }
     }
-    auto K = [&](const int i) { return CACHE ? ckey[CEM_SEL_KIDX(i)] : cem_f2key(p.scores[i]); };
+    auto K = [&](const int i) { return CACHE ? ckey[CEM_SEL_KIDX(i)] : cem_f2key(scores_b[i]); };
     if (tid < 256) hist[1][tid] = 0;                  // pass 3 counts into hist[3 & 1]
     __syncthreads();
     uint32_t kdiff = 0xFFFFFFFFu;
@@ -1662,12 +1700,12 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
         uint32_t pos = pre_gt + (pre_eq < need ? pre_eq : need);
         float bs = -__builtin_inff(); int bp = 0x7fffffff;               // bp: CANDIDATE index of this thread's best elite
         for (int i = beg; i < end; ++i) {
-            const float scv = CACHE ? 0.f : p.scores[i];
+            const float scv = CACHE ? 0.f : scores_b[i];
             const uint32_t key = CACHE ? ckey[CEM_SEL_KIDX(i)] : cem_f2key(scv);
             bool take = key > T;
             if (key == T) { take = eqr < need; ++eqr; }
             if (take) {
-                elite[pos] = i; p.elite_idx[pos] = i; ++pos;
+                elite[pos] = i; elite_b[pos] = i; ++pos;
                 const float sc = CACHE ? cem_key2f(key) : scv;
                 if (bp == 0x7fffffff || sc > bs) { bs = sc; bp = i; }
             }
@@ -1698,7 +1736,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
             const int part = tid / ncol4, c4 = tid % ncol4;
             const bool act = part < tpc;
             f4 *red4 = reinterpret_cast<f4 *>(red);
-            const f4 *act4 = reinterpret_cast<const f4 *>(p.actions);
+            const f4 *act4 = reinterpret_cast<const f4 *>(actions_b);
             const f4 zero4 = (f4){0.f, 0.f, 0.f, 0.f};
             f4 av[8];
 #pragma unroll
@@ -1736,9 +1774,9 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
                         for (int r = 0; r < 4; ++r) {
                             const float sd = sqrtf(tot[r] / fk);
                             const int ci = 4 * c4 + r;
-                            const float nsg = sm * p.musig[HA + ci] + osm * sd;                // cem_mpc.py:65
-                            p.musig[ci] = sm * p.musig[ci] + osm * colmean[ci];                // cem_mpc.py:64
-                            p.musig[HA + ci] = nsg;
+                            const float nsg = sm * musig_b[HA + ci] + osm * sd;                // cem_mpc.py:65
+                            musig_b[ci] = sm * musig_b[ci] + osm * colmean[ci];                // cem_mpc.py:64
+                            musig_b[HA + ci] = nsg;
                             newsig[ci] = nsg;
                         }
                     }
@@ -1760,7 +1798,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int e = part + j * tpc;
-            av[j] = (act && e < k) ? p.actions[(size_t)elite[e] * HA + cb + col] : 0.f;
+            av[j] = (act && e < k) ? actions_b[(size_t)elite[e] * HA + cb + col] : 0.f;
         }
         for (int phase = 0; phase < 2; ++phase) {
             float acc = 0.f;
@@ -1774,7 +1812,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
                 for (int e0 = part + 16 * tpc; e0 < k; e0 += 8 * tpc) {      // large k: 8 gathers in flight, same summation order
                     float b[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { const int e = e0 + j * tpc; b[j] = e < k ? p.actions[(size_t)elite[e] * HA + cb + col] : 0.f; }
+                    for (int j = 0; j < 8; ++j) { const int e = e0 + j * tpc; b[j] = e < k ? actions_b[(size_t)elite[e] * HA + cb + col] : 0.f; }
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
                         if (e0 + j * tpc < k) { const float a = b[j]; acc = phase ? acc + (a - m) * (a - m) : acc + a; }
@@ -1790,10 +1828,10 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
                 else {
                     const float sd = sqrtf(tot / fk);
                     const int ci = cb + col;
-                    const float omu = cb == 0 ? old_mu : p.musig[ci], osg = cb == 0 ? old_sg : p.musig[HA + ci];
+                    const float omu = cb == 0 ? old_mu : musig_b[ci], osg = cb == 0 ? old_sg : musig_b[HA + ci];
                     const float nsg = sm * osg + osm * sd;                             // cem_mpc.py:65
-                    p.musig[ci] = sm * omu + osm * colmean[ci];                        // cem_mpc.py:64
-                    p.musig[HA + ci] = nsg;
+                    musig_b[ci] = sm * omu + osm * colmean[ci];                        // cem_mpc.py:64
+                    musig_b[HA + ci] = nsg;
                     newsig[ci] = nsg;
                 }
             }
@@ -1809,12 +1847,12 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
         float ssum = 0.f;
         for (int i = 0; i < HA; ++i) ssum = ssum + newsig[i];
         const float mean_sigma = ssum / (float)HA;
-        const int iters = p.ctrl->iters + 1;
+        const int iters = ctrl->iters + 1;
         const bool stop = mean_sigma <= p.threshold;                                          // cem_mpc.py:66-67
-        p.ctrl->iters = iters;
-        if (stop) p.ctrl->done = 1;
+        ctrl->iters = iters;
+        if (stop) ctrl->done = 1;
         if (p.result) {             // (the select that ends the plan — its last iteration or the early stop — hands the result to the host)
-            res_l[33] = (uint32_t)iters; res_l[34] = stop ? 1u : (uint32_t)p.ctrl->done; res_l[35] = (uint32_t)p.ctrl->fault;
+            res_l[33] = (uint32_t)iters; res_l[34] = stop ? 1u : (uint32_t)ctrl->done; res_l[35] = (uint32_t)ctrl->fault;
             res_l[36] = (stop || p.is_last != 0) ? 1u : 0u;
         }
         CEM_SEL_STAMP(6);
@@ -1825,27 +1863,27 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
             const float os = bsc[i]; const int op = bpos[i];
             if (op != 0x7fffffff && (bp == 0x7fffffff || os > bs || (os == bs && op < bp))) { bs = os; bp = op; }
         }
-        const bool better = bs > p.ctrl->best_score;                         // strict (cem_mpc.py:58)
+        const bool better = bs > ctrl->best_score;                         // strict (cem_mpc.py:58)
         const int idx = bp;                                                  // (candidate index: the compaction walk recorded it)
         for (int a0 = 0; a0 < p.A; a0 += 4) {
             f4 e = (f4){0.f, 0.f, 0.f, 0.f};                                                    // the output noise of these four actions: one draw
-            if (p.result && !p.eps_out) e = cem_normal4((uint32_t)(a0 >> 2), 0u, 0u, 0u, CEM_STREAM_OUT, cem_key(p.ctrl));
+            if (p.result && !p.eps_out) e = cem_normal4((uint32_t)(a0 >> 2), 0u, 0u, 0u, CEM_STREAM_OUT, cem_key(ctrl));
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int a = a0 + r;
                 if (a < p.A) {
-                    const float b = better ? p.actions[(size_t)idx * HA + a] : p.ctrl->best[a];     // first step's action
-                    if (better) p.ctrl->best[a] = b;
+                    const float b = better ? actions_b[(size_t)idx * HA + a] : ctrl->best[a];     // first step's action
+                    if (better) ctrl->best[a] = b;
                     if (p.result) res_l[a] = __float_as_uint(b + (p.eps_out ? p.eps_out[a] : e[r]) * p.noise_stddev);   // cem_mpc.py:68
                 }
             }
         }
-        if (better) p.ctrl->best_score = bs;
-        if (p.result) res_l[32] = __float_as_uint(better ? bs : p.ctrl->best_score);
+        if (better) ctrl->best_score = bs;
+        if (p.result) res_l[32] = __float_as_uint(better ? bs : ctrl->best_score);
     }
     if (p.result) {
         __syncthreads();
-        if (tid < 64 && res_l[36]) cem_emit_result(p.result, p.result_dev, res_l, p.ctrl->seq, tid);
+        if (tid < 64 && res_l[36]) cem_emit_result(p.result, p.result_dev, res_l, ctrl->seq, tid);
     }
 }
 
@@ -2353,6 +2391,44 @@ __global__ void cem_final_kernel(const FinalParams p)
     }
     __syncthreads();
     if (a < 64) cem_emit_result(p.result, p.result_dev, res_l, p.ctrl->seq, a);
+}
+
+// The final kernel of a batched plan (cem_planner_plan_batch): problem b's result as block result[b][0 .. 37], word for word what
+// cem_final_kernel writes for one plan.  One wave per problem at a time; a lane holds one word and the checksum is formed from the
+// wave's words in order.  Every problem's data and checksum go out first; then, behind every wave's store acknowledgements and a
+// barrier, the plan counters (word 36 of each block): the completion markers follow every problem's result.  The host still accepts a
+// block only when its counter AND its checksum match (writes to host memory arrive in no particular order).
+struct FinalBatchParams { const CtrlBlock *ctrl; const float *eps_out /* [n_prob][A] or null */; float *result; uint32_t *result_dev; int32_t A, n_prob; float noise_stddev; };
+
+__global__ __launch_bounds__(256) void cem_final_batch_kernel(const FinalBatchParams p)
+{
+    const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+    uint32_t *const res_h = reinterpret_cast<uint32_t *>(p.result);
+    for (int b = wv; b < p.n_prob; b += 4) {
+        const CtrlBlock *const c = p.ctrl + b;
+        uint32_t w = 0u;
+        if (lane < p.A) w = __float_as_uint(c->best[lane] + cem_out_noise(c, p.eps_out ? p.eps_out + (size_t)b * p.A : nullptr, lane) * p.noise_stddev);   // cem_mpc.py:68
+        else if (lane == 32) w = __float_as_uint(c->best_score);
+        else if (lane == 33) w = (uint32_t)c->iters;
+        else if (lane == 34) w = (uint32_t)c->done;
+        else if (lane == 35) w = (uint32_t)c->fault;
+        uint32_t x = CEM_RESULT_MAGIC ^ c->seq;                 // cem_result_checksum over the wave's words 0 .. 35
+        for (int i = 0; i < 36; ++i) x = (x ^ (uint32_t)__builtin_amdgcn_readlane((int)w, i)) * 0x01000193u;
+        x = x ^ (x >> 15);
+        const size_t o = (size_t)b * CEM_RESULT_WORDS;
+        if (lane < 36 || lane == 37) {
+            const uint32_t v = lane < 36 ? w : x;
+            if (p.result_dev) p.result_dev[o + lane] = v;
+            __hip_atomic_store(res_h + o + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0): this wave's result stores are acknowledged
+    __syncthreads();
+    for (int b = (int)threadIdx.x; b < p.n_prob; b += 256) {
+        const uint32_t seq = p.ctrl[b].seq;
+        if (p.result_dev) p.result_dev[(size_t)b * CEM_RESULT_WORDS + 36] = seq;
+        __hip_atomic_store(res_h + (size_t)b * CEM_RESULT_WORDS + 36, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 // the raw Philox4x32-7 words of n counters (idx0 + i, t | it << 16, sub | stream << 16, call_lo) — what cem_normal4 turns into four

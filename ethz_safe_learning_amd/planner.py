@@ -507,6 +507,111 @@ class CemPlanner:
             pass
 
 
+class BatchCemPlanner(CemPlanner):
+    """One batch handle (cem_batch_planner_create): up to ``max_batch`` observations per plan call, all problems side by side in one
+    launch per stage.  Problem b of ``plan_batch`` returns bit for bit what ``CemPlanner.plan(states[b], seed, calls[b])`` returns on a
+    single-state handle of the same configuration.  Weights, normaliser, timing and the workspace views are CemPlanner's (the per-problem
+    arrays of the layout are [max_batch] consecutive slices); the single-state and stepwise calls raise (CEM_ERR_STATE)."""
+
+    def __init__(self, cfg: PlannerConfig, max_batch: int, device='cuda:0'):
+        import torch
+        self._torch = torch
+        self.lib = _capi.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError('BatchCemPlanner needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path')
+        self.cfg = cfg
+        self.max_batch = int(max_batch)
+        self.ccfg = to_c_config(cfg)
+        self.device = torch.device(device)
+        nbytes = self.lib.cem_batch_workspace_bytes(C.byref(self.ccfg), self.max_batch)
+        if nbytes == 0:
+            nbytes = 256                                # let create() report the precise status
+        with torch.cuda.device(self.device):
+            self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
+            off = (-self.workspace.data_ptr()) % 256
+            self._ws_view = self.workspace[off:off + nbytes]
+            self.stream = torch.cuda.Stream(device=self.device)
+            torch.cuda.synchronize(self.device)
+            h = C.c_void_p()
+            _capi.check(self.lib.cem_batch_planner_create(C.byref(self.ccfg), self.max_batch, _ptr(self._ws_view), nbytes,
+                                                          C.c_void_p(self.stream.cuda_stream), C.byref(h)), 'cem_batch_planner_create')
+        self.h = h
+        lay = _capi.CemLayout()
+        _capi.check(self.lib.cem_planner_layout(self.h, C.byref(lay)), 'cem_planner_layout')
+        self.layout = lay
+        self._call = 0
+        self.has_comm = False
+        # staging for the hot path, made once (as CemPlanner.plan's)
+        mb, O, A = self.max_batch, cfg.obs_dim, cfg.act_dim
+        self._states_buf = np.zeros((mb, O), np.float32)
+        self._calls_buf = np.zeros(mb, np.uint64)
+        self._acts_buf = np.zeros((mb, A), np.float32)
+        self._scores_buf = np.zeros(mb, np.float32)
+        self._iters_buf = np.zeros(mb, np.int32)
+        self._b_ptrs = tuple(_np_ptr(a) for a in (self._states_buf, self._calls_buf, self._acts_buf, self._scores_buf, self._iters_buf))
+        # (CemPlanner.plan's staging too: a single-state call reaches the library, which refuses it with CEM_ERR_STATE)
+        self._st_buf, self._act_buf = np.zeros(O, np.float32), np.zeros(A, np.float32)
+        self._st_ptr, self._act_ptr = _np_ptr(self._st_buf), _np_ptr(self._act_buf)
+        self._score, self._iters = C.c_float(), C.c_int32()
+        self._score_ref, self._iters_ref = C.byref(self._score), C.byref(self._iters)
+
+    def batch_capacity(self):
+        n = C.c_int32()
+        _capi.check(self.lib.cem_planner_batch_capacity(self.h, C.byref(n)), 'cem_planner_batch_capacity')
+        return n.value
+
+    def _batch_noise_args(self, n, eps_act, eps_model):
+        c = self.cfg
+        t = self._torch
+        if eps_act is None and eps_model is None:
+            return None, None
+        if eps_act is None or eps_model is None:
+            raise ValueError('eps_act and eps_model must be given together')
+        ea = t.as_tensor(eps_act, dtype=t.float32, device=self.device).contiguous()
+        em = t.as_tensor(eps_model, dtype=t.float32, device=self.device).contiguous()
+        if tuple(ea.shape) != (n, c.iterations, c.n_samples, c.horizon, c.act_dim):
+            raise ValueError('eps_act must be [B,I,N,H,A]')
+        if tuple(em.shape) != (n, c.iterations, c.horizon, c.particles * c.n_samples, c.obs_dim):
+            raise ValueError('eps_model must be [B,I,H,P*N,O]')
+        return ea, em
+
+    def plan_batch(self, states, seed=0, calls=None, eps_act=None, eps_model=None, eps_out=None):
+        """CemMpc.generate_action for every row of states[B, O] in ONE plan call -> (actions[B, A], scores[B], iters[B]).
+        calls=None draws B consecutive call numbers from the handle's counter."""
+        st = np.asarray(states)
+        if st.ndim != 2 or st.shape[1] != self.cfg.obs_dim:
+            raise ValueError('states must have shape [B, %d]' % self.cfg.obs_dim)
+        n = st.shape[0]
+        sp, cp, ap, scp, ip = self._b_ptrs
+        if n < 1 or n > self.max_batch:                 # the library's own check (CEM_ERR_INVALID_ARG); nothing is staged
+            _capi.check(self.lib.cem_planner_plan_batch(self.h, n, sp, seed, cp, None, None, None, ap, scp, ip), 'cem_planner_plan_batch')
+        self._states_buf[:n] = st
+        if calls is None:
+            self._calls_buf[:n] = np.arange(self._call, self._call + n, dtype=np.uint64)
+            self._call += n
+        else:
+            cl = np.asarray(calls, np.uint64).reshape(-1)
+            if cl.shape != (n,):
+                raise ValueError('calls must have shape [B]')
+            self._calls_buf[:n] = cl
+        if eps_act is None and eps_model is None and eps_out is None:
+            st_ = self.lib.cem_planner_plan_batch(self.h, n, sp, seed, cp, None, None, None, ap, scp, ip)
+            if st_:
+                _capi.check(st_, 'cem_planner_plan_batch')
+        else:
+            ea, em = self._batch_noise_args(n, eps_act, eps_model)
+            eo = None
+            if eps_out is not None:
+                eo = np.ascontiguousarray(np.asarray(eps_out, np.float32))
+                if eo.shape != (n, self.cfg.act_dim):
+                    raise ValueError('eps_out must be [B,A]')
+            if ea is not None:
+                self._wait_inputs()
+            _capi.check(self.lib.cem_planner_plan_batch(self.h, n, sp, seed, cp, _ptr(ea), _ptr(em), _np_ptr(eo), ap, scp, ip),
+                        'cem_planner_plan_batch')
+        return self._acts_buf[:n].copy(), self._scores_buf[:n].copy(), self._iters_buf[:n].copy()
+
+
 def plan_tiles(cfg: PlannerConfig):
     lib = _capi.load()
     cc = to_c_config(cfg)
@@ -569,6 +674,19 @@ def cached_planner(cfg: PlannerConfig, device='cuda:0') -> CemPlanner:
             # (CemPlanner.__del__ destroys it with its last reference)
             _PLANNER_CACHE.pop(next(iter(_PLANNER_CACHE)))
     _PLANNER_CACHE[key] = pl                     # most recently used last
+    return pl
+
+
+def cached_batch_planner(cfg: PlannerConfig, max_batch: int, device='cuda:0') -> BatchCemPlanner:
+    """cached_planner for batch handles: the same key plus max_batch (its own LRU entries in the same cache)."""
+    key = config_key(cfg, device) + (('max_batch', int(max_batch)),)
+    pl = _PLANNER_CACHE.pop(key, None)
+    if pl is None:
+        pl = BatchCemPlanner(cfg, int(max_batch), device=device)
+        pl.staged = None
+        while len(_PLANNER_CACHE) >= _PLANNER_CACHE_MAX:
+            _PLANNER_CACHE.pop(next(iter(_PLANNER_CACHE)))
+    _PLANNER_CACHE[key] = pl
     return pl
 
 

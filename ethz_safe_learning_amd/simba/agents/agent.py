@@ -87,3 +87,65 @@ class BaseAgent(object):
             rec['info'].append(info)
         assert np.shape(rec['a'][0]) == environment.action_space.shape, "Policy produces wrong actions shape."
         return rb.path_summary(rec['o'], rec['a'], rec['r'], rec['o2'], rec['d'], rec['info']), steps
+
+    def sample_trajectories_lockstep(self, environments, policy, batch_size, max_trajectory_length):
+        """sample_trajectories over several environments stepped side by side: ONE ``policy.generate_actions(observations[B, O])``
+        per decision for all environments still running (a policy without it: ``generate_action`` per environment), each
+        environment holding its action for ``action_repeat`` steps exactly as sample_trajectory does.  Every environment starts an
+        episode; one whose episode ends starts another only while fewer than ``batch_size`` simulator steps (all environments
+        together) have been taken, else it drops out of the batch.  Returns (trajectories, steps) as sample_trajectories does,
+        the records ordered by environment, then episode — with one environment, exactly sample_trajectories' records."""
+        envs = list(environments)
+        batched = getattr(policy, 'generate_actions', None)
+        recs = [None] * len(envs)
+        obs = [None] * len(envs)
+        ep_steps = [0] * len(envs)
+        done_paths = []                                   # (environment, episode, path)
+        episode = [0] * len(envs)
+        steps = 0
+
+        def start(i):
+            obs[i] = envs[i].reset()
+            recs[i] = dict(o=[], a=[], r=[], o2=[], d=[], info=[])
+            ep_steps[i] = 0
+
+        active = list(range(len(envs)))
+        for i in active:
+            start(i)
+        while active:
+            batch_obs = [obs[i] for i in active]
+            if batched is not None:
+                actions = batched(np.stack(batch_obs))
+            else:
+                actions = [policy.generate_action(o) for o in batch_obs]
+            still = []
+            for i, action in zip(active, actions):
+                env, rec = envs[i], recs[i]
+                rec['o'].append(obs[i])
+                rec['a'].append(action)
+                held_reward, held_cost, info, over = 0.0, 0.0, {}, False
+                for _ in range(self.action_repeat):
+                    obs[i], reward, done, info = env.step(action)
+                    ep_steps[i] += 1
+                    steps += 1
+                    held_reward += reward
+                    held_cost += info.get('cost', 0.0)
+                    over = done or ep_steps[i] == max_trajectory_length
+                    if over or info.get('goal_met', False):
+                        break
+                rec['o2'].append(obs[i])
+                rec['r'].append(held_reward)
+                rec['d'].append(over)
+                rec['info'].append(dict(info, cost=held_cost))
+                if not over:
+                    still.append(i)
+                    continue
+                assert np.shape(rec['a'][0]) == env.action_space.shape, "Policy produces wrong actions shape."
+                done_paths.append((i, episode[i], rb.path_summary(rec['o'], rec['a'], rec['r'], rec['o2'], rec['d'], rec['info'])))
+                episode[i] += 1
+                if steps < batch_size:
+                    start(i)
+                    still.append(i)
+            active = still
+        done_paths.sort(key=lambda x: (x[0], x[1]))
+        return [p for _, _, p in done_paths], steps

@@ -7,7 +7,7 @@ policy object, as in scripts/tune_cem_policy.py:109-115).  Weights / normaliser 
 ``version`` changed (after ``fit``: mbrl_agent.py:53)."""
 import numpy as np
 
-from ...planner import PlannerConfig, cached_planner
+from ...planner import PlannerConfig, cached_batch_planner, cached_planner
 from .mpc_policy import MpcPolicy
 
 
@@ -27,8 +27,10 @@ class CemMpc(MpcPolicy):
         self.use_graph = use_graph
         self.precision = precision                     # 'fp32' | 'bf16x3' (PlannerConfig.precision; beyond the reference's kwargs)
         self._planner = None
+        self._batch_planners = {}                      # capacity (a power of two) -> batch handle (generate_actions)
         self.last_score = None
         self.last_iterations = None
+        self.last_scores = None
 
     # ---- planner plumbing -------------------------------------------------------------------------------------
     def _extra_config(self):
@@ -59,12 +61,23 @@ class CemMpc(MpcPolicy):
             self._planner = cached_planner(self.planner_config(), device=self.device)
         self._sync_model()
 
-    def _sync_model(self):
+    def _sync_model(self, planner=None):
+        planner = self._planner if planner is None else planner
         tag = (self.model.uid, self.model.version)            # uid, not id(): ids are reused after garbage collection
-        if self._planner.staged != tag:
-            self._planner.set_weights(self.model.model.get_weights())
-            self._planner.set_normaliser(self.model.inputs_min, self.model.inputs_max)
-            self._planner.staged = tag
+        if planner.staged != tag:
+            planner.set_weights(self.model.model.get_weights())
+            planner.set_normaliser(self.model.inputs_min, self.model.inputs_max)
+            planner.staged = tag
+
+    def build_batch(self, n):
+        """The batch handle for n observations: capacity n rounded up to a power of two (one cached handle, hence one captured
+        graph, per capacity), with the current model version's weights / normaliser staged."""
+        cap = 1 << max(int(n) - 1, 0).bit_length()
+        pl = self._batch_planners.get(cap)
+        if pl is None or pl.h is None:
+            pl = self._batch_planners[cap] = cached_batch_planner(self.planner_config(), cap, device=self.device)
+        self._sync_model(pl)
+        return pl
 
     # ---- the plugin boundary ------------------------------------------------------------------------------------
     def generate_action(self, state):
@@ -72,6 +85,17 @@ class CemMpc(MpcPolicy):
         action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed)
         self.last_score, self.last_iterations = score, iters
         return action
+
+    def generate_actions(self, states):
+        """generate_action for every row of states[B, O] in ONE batched plan -> np.float32[B, A]: row b is what generate_action
+        returns for states[b] with the same call number (BatchCemPlanner.plan_batch).  Sets last_scores / last_iterations (arrays)."""
+        st = np.asarray(states, np.float32)
+        if st.ndim != 2:
+            raise ValueError('states must be [B, obs_dim]')
+        pl = self.build_batch(st.shape[0])
+        actions, scores, iters = pl.plan_batch(st, seed=self.seed)
+        self.last_scores, self.last_iterations = scores, iters
+        return actions
 
     def do_generate_action(self, state, eps_act=None, eps_model=None, eps_out=None):
         """(action, best_score) like cem_mpc.py:35-68; explicit noise tensors replace TF's stateful RNG."""

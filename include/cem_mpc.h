@@ -16,7 +16,8 @@
  * by the caller (torch-ROCm tensors or hipMalloc), the HIP stream is the
  * caller's.  Every function returns an int status (CEM_OK == 0); nothing
  * throws across the boundary.  A handle is not thread-safe; one plan in flight
- * per handle (the reference has one synchronous caller, simba/agents/agent.py:120).
+ * per handle (the reference has one synchronous caller, simba/agents/agent.py:120);
+ * a batch handle plans many observations in that one call (cem_planner_plan_batch).
  * A shape change (scripts/tune_cem_policy.py:109-115) = a new handle.
  *
  * Environment variables the library reads (none changes a result; all are diagnostics or deployment overrides):
@@ -44,6 +45,7 @@ extern "C" {
 #define CEM_ABI_VERSION 4
 #define CEM_MAX_ACT 32
 #define CEM_MAX_COST_KINDS 4
+#define CEM_MAX_BATCH 256         /* problems of one batch handle (cem_batch_planner_create) */
 
 enum cem_status {
     CEM_OK = 0,
@@ -295,6 +297,48 @@ int cem_planner_last_timing(cem_planner_t *h, float *rollout_ms_total, int32_t *
 /* the same plan's other launches: the particle-mean / Beta-filter kernel (where it is a launch of its own) and the sampler launch (where the
  * sampler is not the rollout tiles' prologue); 0 where the plan has no such launch */
 int cem_planner_last_timing_detail(cem_planner_t *h, float *reduce_ms_total, float *sampler_ms_total);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Batched planning: ONE plan call for up to max_batch observations (vectorised environments, evaluation episodes run side by side).
+ * A batch handle runs B copies of the single-state plan side by side in one launch per stage — the rollout launch holds every problem's
+ * tiles (problem b on its own contiguous block of workgroups), the select one 1024-thread workgroup per problem — and captures them as
+ * ONE hipGraph (use_graph) for max_batch problems: any 1 <= n_states <= max_batch is valid on every call, problems n_states .. max_batch - 1
+ * are staged as already stopped (no iterations), so varying n_states never re-captures (cem_planner_graph_status stays 1).
+ * Problem b returns exactly — bit for bit: action, best score, iterations — what cem_planner_plan(h1, states[b], seed, calls[b], ...)
+ * returns on a single-state handle h1 of the same configuration: same Philox counters (keyed (seed, calls[b]); rows and candidates
+ * problem-relative), same arithmetic, its own early stop (a problem that has stopped is skipped by every later kernel).  Explicit noise:
+ * problem b reads slice b of eps_act[n][I][N][H][A], eps_model[n][I][H][P*N][obs] (device) and eps_out[n][A] (host), each slice laid out
+ * as the single-plan tensor.  All problems share the handle's weights, normaliser and scorer.
+ *
+ * Scope — cem_batch_workspace_bytes returns 0 and cem_batch_planner_create returns the status when:
+ *   world_size > 1                                                                CEM_ERR_UNSUPPORTED
+ *   precision other than CEM_PRECISION_FP32                                       CEM_ERR_UNSUPPORTED
+ *   a shape for the generic rollout kernel (units > 128, activation other than relu, or CEM_FORCE_GENERIC_ROLLOUT set)   CEM_ERR_UNSUPPORTED
+ *   select_mode 2 or 3                                                            CEM_ERR_UNSUPPORTED
+ *   select_mode 0 that would not resolve to the one-workgroup select (N >= 24 000, or its LDS limit)                    CEM_ERR_UNSUPPORTED
+ *   max_batch x (tiles of one problem) beyond the int32 range of a launch grid    CEM_ERR_UNSUPPORTED
+ *   max_batch outside 1 .. CEM_MAX_BATCH                                          CEM_ERR_INVALID_ARG
+ *   ... and every configuration cem_workspace_bytes rejects, with the same status.
+ * Rollout segments: a batch handle runs one workgroup per tile for the whole horizon (rollout_segments is ignored; bit-identical).
+ * Its tile size is priced for all max_batch problems' tiles in one launch (chunks_per_tile 0), which need not be the single plan's.
+ *
+ * Calls that work on a batch handle: set_weights, set_normaliser, layout (per-problem arrays are [max_batch] consecutive slices of the
+ * single-plan sizes; result is [max_batch][38]), destroy, graph_status, launches_per_iteration (at most 4, independent of n_states),
+ * set_timing / last_timing / last_timing_detail (I rollout launches per batched plan whatever n_states is), select_mode, fill_noise,
+ * philox_words.  cem_planner_plan, the stepwise cem_plan_* calls, cem_planner_comm_init and the model ops (unfold_sequences,
+ * compute_objective, scorer_reward / scorer_cost) return CEM_ERR_STATE on a batch handle; cem_planner_plan_batch returns
+ * CEM_ERR_STATE on a single-state handle.
+ * Result: the final kernel writes every problem's block ([b][0 .. 37] as cem_layout_t::result describes one) to pinned host memory, the
+ * plan counters last; cem_planner_plan_batch waits for all n_states blocks as cem_planner_plan waits for its one. */
+size_t cem_batch_workspace_bytes(const cem_config_t *cfg, int32_t max_batch);            /* 0 if cfg or max_batch is out of scope */
+int cem_batch_planner_create(const cem_config_t *cfg, int32_t max_batch, void *workspace, size_t workspace_bytes, void *hip_stream,
+                             cem_planner_t **out);
+/* states[n_states][obs], calls[n_states] (host); actions_out[n_states][act], best_scores_out[n_states], iters_out[n_states] (host).
+ * CEM_ERR_INVALID_ARG for n_states < 1 or > max_batch (the handle stays usable). */
+int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
+                           const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
+                           float *best_scores_out, int32_t *iters_out);
+int cem_planner_batch_capacity(const cem_planner_t *h, int32_t *max_batch_out);          /* max_batch; 0 for a single-state handle */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step

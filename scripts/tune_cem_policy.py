@@ -6,6 +6,10 @@ by shape.  Results go to <log_dir>/grid_search.json (and scores.svg / costs.svg 
 
   python scripts/tune_cem_policy.py --config_dir ethz_safe_learning_amd/config --config_basename smoke.yaml \
          --eval_steps 300 --eval_episode_length 300
+
+--parallel_episodes K (K > 1) evaluates each configuration on K PointGoal environments of distinct seeds stepped in lockstep
+(BaseAgent.sample_trajectories_lockstep): one batched plan (CemMpc.generate_actions) per decision for all of them.  The default, 1,
+is the serial evaluation above.
 """
 import argparse
 import json
@@ -32,8 +36,24 @@ def make_new_policy(model, environment, horizon, iterations, n_samples, elite_ra
                   smoothing=policy_kwargs['smoothing'], seed=policy_kwargs.get('seed', 0))
 
 
+def make_parallel_environments(params, k, seed):
+    """K environments of the experiment's task with distinct seeds, for the lockstep evaluation."""
+    from ethz_safe_learning_amd.simba.environment_utils.environment_factory import make_environment
+    return [make_environment(params, seed=seed + 1 + i) for i in range(k)]
+
+
+def evaluate_lockstep(trainer, environments, eval_steps, eval_episode_length):
+    """trainer.evaluate_agent's metrics over episodes of several environments stepped side by side."""
+    from ethz_safe_learning_amd.simba.infrastructure.trainer import _returns_and_costs
+    agent = trainer.agent
+    trajectories, _ = agent.sample_trajectories_lockstep(environments, agent.policy, eval_steps, eval_episode_length)
+    returns, costs = _returns_and_costs(trajectories)
+    return dict(training_rl_objective=returns.mean(), sum_rewards_stddev=returns.std(), sum_costs_mean=costs.mean(),
+                sum_costs_stddev=costs.std())
+
+
 def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=HORIZONS,
-                proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS):
+                proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS, parallel_envs=None):
     from ethz_safe_learning_amd.simba.infrastructure.logging_utils import logger
     agent = trainer.agent
     results = []
@@ -42,7 +62,10 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
             for ratio in elite_ratios:
                 agent.policy = make_new_policy(agent.model, env, horizon, iterations, n_samples, ratio, params['policies']['cem_mpc'])
                 t0 = time.perf_counter()
-                m = trainer.evaluate_agent(eval_steps, eval_episode_length)
+                if parallel_envs:
+                    m = evaluate_lockstep(trainer, parallel_envs, eval_steps, eval_episode_length)
+                else:
+                    m = trainer.evaluate_agent(eval_steps, eval_episode_length)
                 rec = dict(horizon=horizon, n_samples=n_samples, iterations=iterations, elite_ratio=ratio,
                            n_elite=agent.policy.elite, score_mean=float(m['training_rl_objective']),
                            score_std=float(m['sum_rewards_stddev']), cost_mean=float(m['sum_costs_mean']),
@@ -66,13 +89,19 @@ def main(argv=None):
     ap.add_argument('--eval_steps', type=int, default=7000)                 # tune_cem_policy.py:116
     ap.add_argument('--eval_episode_length', type=int, default=1000)
     ap.add_argument('--quick', action='store_true', help='2 x 2 x 2 corner of the grid (tests)')
+    ap.add_argument('--parallel_episodes', type=int, default=1,
+                    help='K > 1: evaluate on K environments of distinct seeds in lockstep, one batched plan per decision')
     args = ap.parse_args(argv)
+    if args.parallel_episodes < 1:
+        ap.error('--parallel_episodes must be at least 1')
     from ethz_safe_learning_amd.config.config import load_config_or_die
     params = load_config_or_die(args.config_dir, args.config_basename)
     trainer = train_script.main(['--config_dir', args.config_dir, '--config_basename', args.config_basename, '--log_dir', args.log_dir,
                                  '--name', args.name, '--seed', str(args.seed), '--log_level', args.log_level,
                                  '--cuda_device', args.cuda_device])
     grid = dict(horizons=HORIZONS[:2], proposals_with_iterations=PROPOSALS_WITH_ITERATIONS[1:], elite_ratios=ELITE_RATIOS[:2]) if args.quick else {}
+    if args.parallel_episodes > 1:
+        grid['parallel_envs'] = make_parallel_environments(params, args.parallel_episodes, args.seed)
     results = grid_search(trainer, trainer.environment, params, args.eval_steps, args.eval_episode_length, **grid)
     out_dir = trainer.training_logger.log_dir or args.log_dir
     with open(os.path.join(out_dir, 'grid_search.json'), 'w') as fh:

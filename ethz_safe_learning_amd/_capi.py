@@ -14,6 +14,7 @@ CEM_MAX_ACT = 32
 CEM_MAX_COST_KINDS = 4
 CEM_COMM_ID_BYTES = 128
 CEM_MAX_BATCH = 256
+CEM_TRAIN_MAX_BATCH = 4096
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds

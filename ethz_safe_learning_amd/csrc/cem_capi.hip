@@ -1893,6 +1893,8 @@ struct cem_trainer {
     float *eval_part; size_t eval_part_floats;     // per-chunk loss partials of a one-launch validation pass (grown on demand, kept)
 };
 
+static_assert(CEM_TBMAX == CEM_TRAIN_MAX_BATCH, "cem_train.h and cem_mpc.h agree on the largest minibatch");
+
 namespace {
 int validate_train(const cem_train_config_t *c)
 {
@@ -1900,7 +1902,7 @@ int validate_train(const cem_train_config_t *c)
     if (c->inputs_dim < 1 || c->outputs_dim < 1 || c->n_layers < 1 || c->ensemble_size < 1 || c->batch_size < 1) return CEM_ERR_INVALID_ARG;
     if (c->units < 1 || c->activation < CEM_ACT_RELU || c->activation > CEM_ACT_GELU) return CEM_ERR_INVALID_ARG;
     if (!(c->dropout_rate >= 0.f && c->dropout_rate < 1.f)) return CEM_ERR_INVALID_ARG;
-    if (c->units > CEM_TWIDE || c->inputs_dim > CEM_U || c->outputs_dim > CEM_U || c->batch_size > CEM_TB) return CEM_ERR_UNSUPPORTED;
+    if (c->units > CEM_TWIDE || c->inputs_dim > CEM_U || c->outputs_dim > CEM_U || c->batch_size > CEM_TBMAX) return CEM_ERR_UNSUPPORTED;
     return CEM_OK;
 }
 size_t train_nat(const cem_train_config_t *c)
@@ -1908,9 +1910,17 @@ size_t train_nat(const cem_train_config_t *c)
     return (size_t)c->inputs_dim * c->units + c->units + (size_t)(c->n_layers - 1) * ((size_t)c->units * c->units + c->units) +
            2 * ((size_t)c->units * c->outputs_dim + c->outputs_dim);
 }
+// row parts of a step of bt rows per member (TrainParams::nparts): one per 16 rows up to CEM_TPMAX; beyond, several passes per part
+int train_parts(int bt) { return std::min((bt + CEM_TROWS - 1) / CEM_TROWS, CEM_TPMAX); }
+// the partial-gradient, scratch and loss-partial slots the workspace holds: the most parts a step of at most batch_size rows takes,
+// and never fewer than the four of a <= 64-row minibatch (the layout of every such configuration is the one it always had)
+int train_parts_alloc(const cem_train_config_t &c) { return std::max(CEM_TPARTS, train_parts(c.batch_size)); }
+// validation_step walks the set in chunks of batch_size rows, 64 for a larger batch_size: the validation loss does not depend on it
+int eval_chunk_rows(const cem_train_config_t &c) { return std::min(c.batch_size, CEM_TB); }
 void train_layout(cem_trainer *t)
 {
     const cem_train_config_t &c = t->cfg;
+    const int P = train_parts_alloc(c);
     t->nat = train_nat(&c);
     // per (member, row part) workgroup: the input, L hidden outputs, seven head / loss / gradient matrices — and, for swish / gelu, the L kept
     // pre-activations the backward gate of a non-monotone activation needs (cem_train.h: GemmEpi::outz)
@@ -1918,8 +1928,8 @@ void train_layout(cem_trainer *t)
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align256(o + bytes); return r; };
     t->oW = take(t->nat * c.ensemble_size * 4); t->oM = take(t->nat * c.ensemble_size * 4); t->oV = take(t->nat * c.ensemble_size * 4);
-    t->oG = take(((t->nat * c.ensemble_size + 3) & ~(size_t)3) * CEM_TPARTS * 4); t->oS = take(t->scratch_pm * c.ensemble_size * CEM_TPARTS * 4);
-    t->oL = take((size_t)c.ensemble_size * 4); t->oP = take((size_t)c.ensemble_size * CEM_TPARTS * 2 * 4);
+    t->oG = take(((t->nat * c.ensemble_size + 3) & ~(size_t)3) * P * 4); t->oS = take(t->scratch_pm * c.ensemble_size * P * 4);
+    t->oL = take((size_t)c.ensemble_size * 4); t->oP = take((size_t)c.ensemble_size * P * 2 * 4);
     t->oT = take(32 * sizeof(long long));            // phase stamps of -DCEM_STAMPS diagnostic builds: the LAST 256 B of the workspace
     t->total = o;
 }
@@ -1928,16 +1938,24 @@ void train_layout(cem_trainer *t)
 template <int L>
 hipError_t tile_kernel_lds(size_t lds)
 {
-    return lds > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void *>(&cem_train_tile_kernel<L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    if (lds <= 48 * 1024) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&cem_train_tile_kernel<L, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(&cem_train_tile_kernel<L, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
 void launch_train_step(const cem_trainer *t, const TrainParams &p)
 {
     const size_t lds = (size_t)(t->cfg.n_layers + 5) * CEM_TT_NB * CEM_TT_BLK;
-    const dim3 grid(t->cfg.ensemble_size * CEM_TPARTS, t->tile_kernel ? (p.Bt + p.chunk - 1) / p.chunk : 1);
-    if (!t->tile_kernel) { hipLaunchKernelGGL(cem_train_step_kernel, grid, dim3(CEM_TNT), 0, t->stream, p); return; }
+    const dim3 grid(t->cfg.ensemble_size * p.nparts, t->tile_kernel ? (p.Bt + p.chunk - 1) / p.chunk : 1);
+    const bool multi = p.chunk > CEM_TROWS * p.nparts;       // some part takes more than one 16-row pass
+    if (!t->tile_kernel) {
+        if (multi) hipLaunchKernelGGL(cem_train_step_kernel<true>, grid, dim3(CEM_TNT), 0, t->stream, p);
+        else hipLaunchKernelGGL(cem_train_step_kernel<false>, grid, dim3(CEM_TNT), 0, t->stream, p);
+        return;
+    }
     switch (t->cfg.n_layers) {
-#define CEM_CASE(LL) case LL: hipLaunchKernelGGL(cem_train_tile_kernel<LL>, grid, dim3(64 * CEM_TT_WAVES), lds, t->stream, p); break;
+#define CEM_CASE(LL) case LL: if (multi) hipLaunchKernelGGL((cem_train_tile_kernel<LL, true>), grid, dim3(64 * CEM_TT_WAVES), lds, t->stream, p); \
+                              else hipLaunchKernelGGL((cem_train_tile_kernel<LL, false>), grid, dim3(64 * CEM_TT_WAVES), lds, t->stream, p); break;
     CEM_CASE(1) CEM_CASE(2) CEM_CASE(3) CEM_CASE(4) CEM_CASE(5) CEM_CASE(6)
 #undef CEM_CASE
     }
@@ -2044,6 +2062,7 @@ int cem_trainer_step(cem_trainer_t *t, const float *x_dev, const float *y_dev, c
     if (perm_dev && offset + bt > nperm) return CEM_ERR_INVALID_ARG;
     TrainParams p; fill_train_params(t, p);
     p.x = x_dev; p.y = y_dev; p.perm = perm_dev; p.nperm = nperm; p.offset = offset; p.Bt = bt; p.chunk = bt; p.lr_t = lr_t; p.loss_out = loss_dev; p.train = 1;
+    p.nparts = train_parts(bt);
     launch_train_step(t, p);
     t->steps_done += 1;
     const size_t n4 = (size_t)p.E * p.nat / 4;
@@ -2072,14 +2091,15 @@ int cem_trainer_eval(cem_trainer_t *t, const float *x_dev, const float *y_dev, i
     std::fill(sums.begin(), sums.end(), 0.f);
     TrainParams p; fill_train_params(t, p);
     p.x = x_dev; p.y = y_dev; p.perm = nullptr; p.loss_out = (float *)(t->ws + t->oL); p.train = 0;
-    const int B = t->cfg.batch_size, nchunks = (n + B - 1) / B;
-    const size_t per_chunk = (size_t)E * CEM_TPARTS * 2;
+    const int B = eval_chunk_rows(t->cfg), nchunks = (n + B - 1) / B;
+    const int P = train_parts(B);                   // <= 4: a chunk of at most 64 rows, one 16-row pass per part
+    const size_t per_chunk = (size_t)E * P * 2;
     std::vector<float> part(per_chunk * (t->tile_kernel ? nchunks : 1));
     // the sums are added on the host in the same order either way: chunk by chunk, member by member, part by part
     auto add_chunk = [&](const float *pc, int rows) {
         const int nparts = (rows + CEM_TROWS - 1) / CEM_TROWS;
         for (int m = 0; m < E; ++m)
-            for (int q = 0; q < nparts; ++q) { sums[2 * m] += pc[((size_t)m * CEM_TPARTS + q) * 2]; sums[2 * m + 1] += pc[((size_t)m * CEM_TPARTS + q) * 2 + 1]; }
+            for (int q = 0; q < nparts; ++q) { sums[2 * m] += pc[((size_t)m * P + q) * 2]; sums[2 * m + 1] += pc[((size_t)m * P + q) * 2 + 1]; }
     };
     if (t->tile_kernel) {
         // ONE launch for the whole set: grid.y walks the 64-row chunks, each writing its own loss partials
@@ -2087,7 +2107,7 @@ int cem_trainer_eval(cem_trainer_t *t, const float *x_dev, const float *y_dev, i
             if (t->eval_part) { HIPCHK(hipStreamSynchronize(t->stream)); HIPCHK(hipFree(t->eval_part)); t->eval_part = nullptr; t->eval_part_floats = 0; }
             HIPCHK(hipMalloc((void **)&t->eval_part, part.size() * 4)); t->eval_part_floats = part.size();
         }
-        p.chunk = B;
+        p.chunk = B; p.nparts = P;
         const int kMaxChunks = 32768;                   // grid.y is limited to 65535: very large sets go in several launches
         for (int c0 = 0; c0 < nchunks; c0 += kMaxChunks) {
             const int nc = std::min(kMaxChunks, nchunks - c0);
@@ -2100,7 +2120,7 @@ int cem_trainer_eval(cem_trainer_t *t, const float *x_dev, const float *y_dev, i
         for (int ch = 0; ch < nchunks; ++ch) add_chunk(part.data() + (size_t)ch * per_chunk, std::min(B, n - ch * B));
     } else {
         for (int off = 0; off < n; off += B) {
-            p.offset = off; p.Bt = std::min(B, n - off); p.chunk = p.Bt;
+            p.offset = off; p.Bt = std::min(B, n - off); p.chunk = p.Bt; p.nparts = P;
             launch_train_step(t, p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(part.data(), t->ws + t->oP, part.size() * 4, hipMemcpyDeviceToHost, t->stream));

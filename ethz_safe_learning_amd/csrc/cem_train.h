@@ -4,34 +4,54 @@
 // simba/models/mlp_ensemble.py:134-155, with negative_log_likelihood (:64-67) and
 // tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).
 //
-// A training step is ~28 MFLOP per member in 14 small dependent GEMMs (batch <= 64): latency-bound by construction.  The
+// A training step is ~28 MFLOP per member in 14 small dependent GEMMs (batch 64): latency-bound by construction.  The
 // members are independent (their own minibatch, weights and Adam moments), and so are the ROWS of a member's minibatch in
-// everything except the weight gradients, which sum over rows.  So a member's step runs on CEM_TPARTS workgroups, each
-// taking CEM_TROWS = 16 of the rows through the forward pass, the loss, and the backward pass; each writes its PARTIAL weight
-// gradients, and the Adam kernel adds the partials in a fixed order before the update (deterministic: no atomics).  15
-// members x 4 parts = 60 workgroups instead of 15, and each GEMM's row dimension is one MFMA block.
+// everything except the weight gradients, which sum over rows.  So a member's step of Bt rows runs on P = min(ceil(Bt / 16),
+// CEM_TPMAX) workgroups (row parts, TrainParams::nparts), each taking a contiguous range of the rows through the forward pass,
+// the loss, and the backward pass in passes of CEM_TROWS = 16 rows; each writes its PARTIAL weight gradients (the first pass
+// stores, every later pass adds its own to what the same thread stored: one writer per word, a fixed order), and the Adam
+// kernel adds the partials in part order before the update (deterministic: no atomics).  Up to 64 rows every part is one
+// 16-row pass (15 members x 4 parts = 60 workgroups at the shipped shape); each GEMM's row dimension is one MFMA block.
+// Minibatches up to CEM_TBMAX rows per member; the workspace holds max(CEM_TPARTS, min(ceil(batch_size / 16), CEM_TPMAX)) partials.
 // The GEMM is LDS-tiled on v_mfma_f32_16x16x4_f32, everything L2 resident; the workgroup is 512 threads (two waves per SIMD:
 // the partner hides LDS / L2 latency).  Weights stay in the Keras layout ([in][out]) the planner's set_weights() consumes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define CEM_TB 64            // max minibatch rows per member (config/models.yaml:4 batch_size: 64)
-#define CEM_TROWS 16         // minibatch rows per workgroup
+#define CEM_TB 64            // minibatch rows per member that every part takes in ONE pass (config/models.yaml:4 batch_size: 64)
+#define CEM_TBMAX 4096       // max minibatch rows per member (cem_train_config_t::batch_size)
+#define CEM_TROWS 16         // minibatch rows per workgroup pass
+#ifndef CEM_TPMAX
+#define CEM_TPMAX 32         // max row parts (workgroups) per member: beyond 16 x CEM_TPMAX rows a part makes several passes
+                             // (measured against 8 and 16: profiles/train_pmax_ab.jsonl)
+#endif
 #define CEM_TS 128           // row stride of every activation matrix in the scratch for units <= 128 (TrainParams::ts: 256 above)
 #define CEM_TWIDE 256         // widest hidden layer the GEMM-by-GEMM kernel is laid out for (inputs_dim, outputs_dim <= 128)
-#define CEM_TPARTS (CEM_TB / CEM_TROWS)
+#define CEM_TPARTS (CEM_TB / CEM_TROWS)     // row parts of a <= 64-row minibatch (the least the workspace holds)
+static_assert(CEM_TPMAX >= CEM_TPARTS, "a <= 64-row minibatch takes one pass per part");
+
+// rows [r0, r1) of a minibatch (or validation chunk) of Bt rows that part `part` of P takes: 16-row blocks [part nb / P,
+// (part + 1) nb / P) of the nb = ceil(Bt / 16), so with P = nb part q takes rows [16 q, 16 q + 16)
+__host__ __device__ __forceinline__ void cem_part_rows(const int Bt, const int P, const int part, int &r0, int &r1)
+{
+    const int nb = (Bt + CEM_TROWS - 1) / CEM_TROWS;
+    r0 = part * nb / P * CEM_TROWS;
+    r1 = (part + 1) * nb / P * CEM_TROWS;
+    if (r1 > Bt) r1 = Bt;
+}
 
 struct TrainParams {
     float *W, *Mo, *Vo;          // [E][nat] weights, Adam first / second moments (natural blob layout of cem_mpc.h)
-    float *grad;                 // [CEM_TPARTS][gpart] partial gradients of the row parts, each [E][nat] (gpart = E * nat rounded up to
+    float *grad;                 // [nparts][gpart] partial gradients of the row parts, each [E][nat] (gpart = E * nat rounded up to
                                  // a multiple of 4 floats: the Adam kernel reads every part with 16-byte loads)
-    float *loss_part;            // [E][CEM_TPARTS][2] partial sums of the loss (log term, squared term)
-    float *scratch;              // [E * CEM_TPARTS][scratch_per_member]
+    float *loss_part;            // [E][nparts][2] partial sums of the loss (log term, squared term); per chunk in a validation launch
+    float *scratch;              // [E * nparts][scratch_per_member]
     const float *x, *y;          // [n][D] scaled inputs, [n][O] targets (next_obs - obs)
     const int32_t *perm;         // [E][nperm] bootstrap shuffles (mlp_ensemble.py:172-173) or nullptr (rows offset.. directly)
     int32_t nperm, offset, Bt;   // Bt rows from `offset` on; the tile kernel takes them in chunks of `chunk` rows along blockIdx.y (training: one
     int32_t chunk;               // chunk = the minibatch; validation: every 64-row slice of the set in ONE launch, loss_part per chunk)
+    int32_t nparts;              // P: row parts (workgroups along blockIdx.x) per member and chunk, min(ceil(chunk / 16), CEM_TPMAX)
     int32_t D, O, U, L, E;
     uint32_t nat, scratch_per_member, gpart;
     int32_t ts;                  // row stride of the GEMM kernel's activation matrices in the scratch: CEM_TS, or CEM_TWIDE for units > 128
@@ -96,6 +116,9 @@ struct GemmEpi {
     // optional (forward GEMMs of swish / gelu layers): the pre-activation z of every output element, same indexing as `out` — what the
     // backward gate of a non-monotone activation needs; an element Dropout drops is stored as CEM_Z_DROPPED (a NaN bit pattern, compared as bits)
     gptr outz;
+    // the weight-gradient GEMMs of a row part's second and later 16-row passes: out / colsum += this pass's values instead of =
+    // (every word is loaded back by the thread that stored it in the pass before)
+    int accum;
 };
 
 __device__ __forceinline__ float cem_dropout_fwd(const GemmEpi &e, const int row, const int n, const float v)
@@ -211,7 +234,8 @@ __device__ __attribute__((noinline)) void wg_gemm_t(const int M, const int N, co
 #pragma unroll 8
                 for (int k = 0; k < CEM_TK; ++k) t = t + Bs[0][k][tid];
                 const int n = n0 + tid;
-                (n < sp.nsplit ? e.colsum : e.colsum1)[n < sp.nsplit ? n : n - sp.nsplit] = t;
+                const gptr cs = &(n < sp.nsplit ? e.colsum : e.colsum1)[n < sp.nsplit ? n : n - sp.nsplit];
+                *cs = e.accum ? *cs + t : t;
             }
             // epilogue operands, requested now (batched, clamped indices) so that their latency hides behind the k loop
             float bia[NCB], gat[NRB][4][NCB];
@@ -271,7 +295,10 @@ __device__ __attribute__((noinline)) void wg_gemm_t(const int M, const int N, co
                             if (e.drop_thresh) { const float kept = cem_dropout_fwd(e, mI, n, 1.0f); dropped = kept == 0.f; v = dropped ? 0.f : v * e.drop_scale; }
                             if (e.outz && mI < M && n < N) e.outz[mI * e.ldo + n] = dropped ? __uint_as_float(CEM_Z_DROPPED) : zpre;
                         }
-                        if (mI < M && n < N) (n < sp.nsplit ? e.out : e.out1)[(mI < M ? mI : M - 1) * e.ldo + (n < sp.nsplit ? n : n - sp.nsplit)] = v;
+                        if (mI < M && n < N) {
+                            const gptr o = &(n < sp.nsplit ? e.out : e.out1)[(mI < M ? mI : M - 1) * e.ldo + (n < sp.nsplit ? n : n - sp.nsplit)];
+                            *o = e.accum ? *o + v : v;
+                        }
                     }
 #ifdef CEM_STAMPS
             if (e.st && blockIdx.x == 0 && tid == 0) { const long long t3_ = (long long)__builtin_amdgcn_s_memtime(); e.st[8] += t1_ - t0_; e.st[9] += t2_ - t1_; e.st[10] += t3_ - t2_; e.st[11] += 1; }
@@ -377,7 +404,8 @@ __device__ __attribute__((noinline)) void wg_gemm_r16_deep(const int M, const in
     if (e.colsum && tid < N) {                             // bias gradient next to a weight gradient with few rows (inputs_dim <= 16)
         float t = 0.f;
         for (int k = 0; k < K; ++k) t = t + Bs[k][tid];
-        (tid < sp.nsplit ? e.colsum : e.colsum1)[tid < sp.nsplit ? tid : tid - sp.nsplit] = t;
+        const gptr cs = &(tid < sp.nsplit ? e.colsum : e.colsum1)[tid < sp.nsplit ? tid : tid - sp.nsplit];
+        *cs = e.accum ? *cs + t : t;
     }
     f4v acc = (f4v){0.f, 0.f, 0.f, 0.f};
     const int nP = (K + 3) / 4;
@@ -400,7 +428,10 @@ __device__ __attribute__((noinline)) void wg_gemm_r16_deep(const int M, const in
             if (e.drop_thresh) { const float kept = cem_dropout_fwd(e, mI, n, 1.0f); dropped = kept == 0.f; v = dropped ? 0.f : v * e.drop_scale; }
             if (e.outz && mI < M && n < N) e.outz[mI * e.ldo + n] = dropped ? __uint_as_float(CEM_Z_DROPPED) : zpre;
         }
-        if (mI < M && n < N) (n < sp.nsplit ? e.out : e.out1)[mI * e.ldo + (n < sp.nsplit ? n : n - sp.nsplit)] = v;
+        if (mI < M && n < N) {
+            const gptr o = &(n < sp.nsplit ? e.out : e.out1)[mI * e.ldo + (n < sp.nsplit ? n : n - sp.nsplit)];
+            *o = e.accum ? *o + v : v;
+        }
     }
 #ifdef CEM_STAMPS
     if (e.st && blockIdx.x == 0 && tid == 0) { const long long t3_ = (long long)__builtin_amdgcn_s_memtime(); e.st[8] += t1_ - t0_; e.st[9] += t2_ - t1_; e.st[10] += t3_ - t2_; e.st[11] += 1; }
@@ -456,16 +487,18 @@ __device__ __forceinline__ float block_sum(float v, float *red)
     return t;
 }
 
+// MULTI: some part has more than 16 rows (p.Bt > 16 x p.nparts); without it the pass loop runs once and folds away
+template <bool MULTI>
 __global__ __launch_bounds__(CEM_TNT) void cem_train_step_kernel(const TrainParams p)
 {
     float *lds = g_train_lds;
     __shared__ float red[CEM_TNT / 64];
-    // workgroup = (member m, row part): rows [part * CEM_TROWS, +Bt) of the member's minibatch of p.Bt rows
-    const int m = blockIdx.x / CEM_TPARTS, part = blockIdx.x % CEM_TPARTS, tid = threadIdx.x;
+    // workgroup = (member m, row part): rows [r0, r1) of the member's minibatch of p.Bt rows, in 16-row passes
+    const int m = blockIdx.x / p.nparts, part = blockIdx.x % p.nparts, tid = threadIdx.x;
     const int D = p.D, O = p.O, U = p.U, L = p.L;
-    const int row0 = part * CEM_TROWS;
-    const int Bt = p.Bt - row0 < CEM_TROWS ? p.Bt - row0 : CEM_TROWS;
-    if (Bt <= 0) return;                          // a short minibatch: the Adam kernel only adds the parts that exist
+    int r0 = part * CEM_TROWS, r1 = p.Bt - r0 < CEM_TROWS ? p.Bt : r0 + CEM_TROWS;  // one pass: part q takes rows [16 q, +16)
+    if (MULTI) cem_part_rows(p.Bt, p.nparts, part, r0, r1);                       // (p.nparts < ceil(Bt / 16): training steps only)
+    if (r1 <= r0) return;                         // a short minibatch: the Adam kernel only adds the parts that exist
     float *W = p.W + (size_t)m * p.nat, *G = p.grad + (size_t)part * p.gpart + (size_t)m * p.nat;
     float *sc = p.scratch + (size_t)blockIdx.x * p.scratch_per_member;
     // scratch carve: every activation matrix has row stride S (128: D, O, U <= 128, narrower units leave columns unused; 256 for wider units)
@@ -490,92 +523,103 @@ __global__ __launch_bounds__(CEM_TNT) void cem_train_step_kernel(const TrainPara
 #ifdef CEM_STAMPS
     if (blockIdx.x == 0 && threadIdx.x == 0) { p.stamps[8] = p.stamps[9] = p.stamps[10] = p.stamps[11] = 0; }
 #endif
-    // ---- gather this part's rows of the minibatch ---------------------------------------------------------------
-    {
-        int32_t *rows = reinterpret_cast<int32_t *>(lds);
-        if (tid < Bt) rows[tid] = p.perm ? p.perm[(size_t)m * p.nperm + p.offset + row0 + tid] : p.offset + row0 + tid;
+    float tot_log = 0.f, tot_sq = 0.f;           // the part's loss sums over its passes (every thread holds them; thread 0 stores them)
+    for (int row0 = r0; row0 < (MULTI ? r1 : r0 + 1); row0 += CEM_TROWS) {
+        const int Bt = r1 - row0 < CEM_TROWS ? r1 - row0 : CEM_TROWS;
+        const int accum = MULTI && row0 != r0;    // a later pass adds its weight gradients to the part's partial
+        if (accum) __syncthreads();               // the pass before is done with the scratch and the LDS
+        // ---- gather this part's rows of the minibatch ---------------------------------------------------------------
+        {
+            int32_t *rows = reinterpret_cast<int32_t *>(lds);
+            if (tid < Bt) rows[tid] = p.perm ? p.perm[(size_t)m * p.nperm + p.offset + row0 + tid] : p.offset + row0 + tid;
+            __syncthreads();
+            wg_map<float2>(Bt * S,
+                [&](int e) { const int r = e / S, c = e % S; const int row = rows[r];
+                             return make_float2(c < D ? p.x[(size_t)row * D + c] : 0.f, c < O ? p.y[(size_t)row * O + c] : 0.f); },
+                [&](int e, float2 v) { xs[e] = v.x; ys[e] = v.y; });
+        }
         __syncthreads();
-        wg_map<float2>(Bt * S,
-            [&](int e) { const int r = e / S, c = e % S; const int row = rows[r];
-                         return make_float2(c < D ? p.x[(size_t)row * D + c] : 0.f, c < O ? p.y[(size_t)row * O + c] : 0.f); },
-            [&](int e, float2 v) { xs[e] = v.x; ys[e] = v.y; });
-    }
-    __syncthreads();
 
-    CEM_TR_STAMP(1);
-    // ---- forward (mlp_ensemble.py:18-22,33-34,59-61) -----------------------------------------------------------
-    for (int l = 0; l < L; ++l) {
-        const float *hin = l == 0 ? xs : hs + (size_t)(l - 1) * CEM_TROWS * S;
-        float *hout = hs + (size_t)l * CEM_TROWS * S;
-        const float *Wl = W + offW(l), *bl = W + offb(l);
-        GemmEpi fe{(gptr)hout, S, (gcptr)bl, nullptr, 0, 1 + p.act, nullptr, nullptr, p.stamps, nullptr, nullptr};      // f(h W + b), f = relu unless configured otherwise
-        if (p.train && p.drop_thresh) {                                       // Dropout(training=True), mlp_ensemble.py:21,138
-            fe.drop_thresh = p.drop_thresh; fe.drop_scale = p.drop_scale; fe.drop_keep = p.drop_keep; fe.drop_step = p.drop_step;
-            fe.drop_c2 = ((uint32_t)l << 8) | (3u << 16); fe.drop_member = (uint32_t)m; fe.drop_k0 = p.drop_k0; fe.drop_k1 = p.drop_k1; fe.drop_row0 = row0;
-        }
-        if (zs && p.train) fe.outz = (gptr)(zs + (size_t)l * CEM_TROWS * S);
-        wg_gemm(Bt, U, l == 0 ? D : U, (gcptr)hin, S, 1, (gcptr)Wl, U, 1, fe, CEM_NOSPLIT);
-    }
-    CEM_TR_STAMP(2);
-    const float *hL = hs + (size_t)(L - 1) * CEM_TROWS * S;
-    // both heads as ONE GEMM: columns [0, O) = mu head, [O, 2O) = variance head (2O <= 128 fills the tile two N = O GEMMs half use)
-    wg_gemm(Bt, 2 * O, U, (gcptr)hL, S, 1, (gcptr)(W + oWmu), O, 1,
-            GemmEpi{(gptr)mu, S, (gcptr)(W + obmu), nullptr, 0, 0, (gptr)vp, (gcptr)(W + obv), p.stamps, nullptr, nullptr}, GemmSplit{nullptr, (gcptr)(W + oWv), 0x7fffffff, O});
-    CEM_TR_STAMP(3);
-    // ---- negative_log_likelihood (:64-67) and its gradient w.r.t. mu and the pre-softplus variance -----------------
-    float s_log = 0.f, s_sq = 0.f;
-    const float ninv = 1.0f / ((float)p.Bt * (float)O * (float)p.E);          // the mean runs over the WHOLE minibatch (mlp_ensemble.py:64-67)
-    wg_map<float3>(Bt * O,
-        [&](int e) { const int r = e / O, c = e % O; return make_float3(vp[r * S + c], mu[r * S + c], ys[r * S + c]); },
-        [&](int e, float3 in) {
-            const int r = e / O, c = e % O;
-            const float v = in.x, var = train_softplus(v) + 1e-4f;
-            const float diff = in.y - in.z;
-            s_log += logf(6.283185307179586f * var);
-            s_sq += diff * diff / var;
-            if (p.train) {
-                dmu[r * S + c] = diff / var * ninv;
-                const float dvar = (0.5f / var - 0.5f * diff * diff / (var * var)) * ninv;
-                dv[r * S + c] = dvar / (1.0f + expf(-v));               // d softplus(v)/dv = sigmoid(v)
+        CEM_TR_STAMP(1);
+        // ---- forward (mlp_ensemble.py:18-22,33-34,59-61) -----------------------------------------------------------
+        for (int l = 0; l < L; ++l) {
+            const float *hin = l == 0 ? xs : hs + (size_t)(l - 1) * CEM_TROWS * S;
+            float *hout = hs + (size_t)l * CEM_TROWS * S;
+            const float *Wl = W + offW(l), *bl = W + offb(l);
+            GemmEpi fe{(gptr)hout, S, (gcptr)bl, nullptr, 0, 1 + p.act, nullptr, nullptr, p.stamps, nullptr, nullptr};      // f(h W + b), f = relu unless configured otherwise
+            if (p.train && p.drop_thresh) {                                       // Dropout(training=True), mlp_ensemble.py:21,138
+                fe.drop_thresh = p.drop_thresh; fe.drop_scale = p.drop_scale; fe.drop_keep = p.drop_keep; fe.drop_step = p.drop_step;
+                fe.drop_c2 = ((uint32_t)l << 8) | (3u << 16); fe.drop_member = (uint32_t)m; fe.drop_k0 = p.drop_k0; fe.drop_k1 = p.drop_k1; fe.drop_row0 = row0;
             }
-        });
-    s_log = block_sum(s_log, red);
-    s_sq = block_sum(s_sq, red);
-    CEM_TR_STAMP(4);
-    // this part's share of the two sums of the loss; the Adam kernel (training) or the host (validation) adds the parts in order
-    if (tid == 0) { p.loss_part[((size_t)m * CEM_TPARTS + part) * 2] = s_log; p.loss_part[((size_t)m * CEM_TPARTS + part) * 2 + 1] = s_sq; }
-    if (!p.train) return;
-    __syncthreads();
-
-    CEM_TR_STAMP(5);
-    // ---- backward ------------------------------------------------------------------------------------------------
-    // [dW_mu | dW_var] = h_L^T [dmu | dv] as one GEMM
-    wg_gemm(U, 2 * O, Bt, (gcptr)hL, 1, S, (gcptr)dmu, S, 1,
-            GemmEpi{(gptr)(G + oWmu), O, nullptr, nullptr, 0, 0, (gptr)(G + oWv), nullptr, p.stamps, (gptr)(G + obmu), (gptr)(G + obv)},
-            GemmSplit{nullptr, (gcptr)dv, 0x7fffffff, O});                    // + [db_mu | db_var] = column sums of [dmu | dv]
-    // dh_L = (dmu Wmu^T + dv Wvar^T) * relu'(h_L): the relu mask rides in the epilogue of the GEMM that completes dh
-    // dh_L = ([dmu | dv] [W_mu | W_var]^T) * relu'(h_L): one GEMM over K = 2O; the relu mask rides in its epilogue
-    wg_gemm(Bt, U, 2 * O, (gcptr)dmu, S, 1, (gcptr)(W + oWmu), 1, O,
-            GemmEpi{(gptr)dha, S, nullptr, (gcptr)(zs ? zs + (size_t)(L - 1) * CEM_TROWS * S : hL), S, 1 + p.act, nullptr, nullptr, p.stamps, nullptr, nullptr, p.drop_thresh, p.drop_scale, p.drop_keep}, GemmSplit{(gcptr)dv, (gcptr)(W + oWv), O, 0x7fffffff});
-    CEM_TR_STAMP(6);
-    float *dcur = dha, *dnext = dhb;
-    for (int l = L - 1; l >= 0; --l) {
-        const float *hin = l == 0 ? xs : hs + (size_t)(l - 1) * CEM_TROWS * S;
-        const int in = l == 0 ? D : U;
-        wg_gemm(in, U, Bt, (gcptr)hin, 1, S, (gcptr)dcur, S, 1, GemmEpi{(gptr)(G + offW(l)), U, nullptr, nullptr, 0, 0, nullptr, nullptr, p.stamps, (gptr)(G + offb(l)), nullptr}, CEM_NOSPLIT);   // dW_l = h_{l-1}^T dh_l, db_l = column sums of dh_l
-        if (l > 0) {
-            wg_gemm(Bt, U, U, (gcptr)dcur, S, 1, (gcptr)(W + offW(l)), 1, U, GemmEpi{(gptr)dnext, S, nullptr, (gcptr)(zs ? zs + (size_t)(l - 1) * CEM_TROWS * S : hin), S, 1 + p.act, nullptr, nullptr, p.stamps, nullptr, nullptr, p.drop_thresh, p.drop_scale, p.drop_keep}, CEM_NOSPLIT);   // dh_{l-1} = (dh_l W_l^T) f'(z_{l-1})
-            float *t = dcur; dcur = dnext; dnext = t;
+            if (zs && p.train) fe.outz = (gptr)(zs + (size_t)l * CEM_TROWS * S);
+            wg_gemm(Bt, U, l == 0 ? D : U, (gcptr)hin, S, 1, (gcptr)Wl, U, 1, fe, CEM_NOSPLIT);
         }
+        CEM_TR_STAMP(2);
+        const float *hL = hs + (size_t)(L - 1) * CEM_TROWS * S;
+        // both heads as ONE GEMM: columns [0, O) = mu head, [O, 2O) = variance head (2O <= 128 fills the tile two N = O GEMMs half use)
+        wg_gemm(Bt, 2 * O, U, (gcptr)hL, S, 1, (gcptr)(W + oWmu), O, 1,
+                GemmEpi{(gptr)mu, S, (gcptr)(W + obmu), nullptr, 0, 0, (gptr)vp, (gcptr)(W + obv), p.stamps, nullptr, nullptr}, GemmSplit{nullptr, (gcptr)(W + oWv), 0x7fffffff, O});
+        CEM_TR_STAMP(3);
+        // ---- negative_log_likelihood (:64-67) and its gradient w.r.t. mu and the pre-softplus variance -----------------
+        float s_log = 0.f, s_sq = 0.f;
+        const float ninv = 1.0f / ((float)p.Bt * (float)O * (float)p.E);          // the mean runs over the WHOLE minibatch (mlp_ensemble.py:64-67)
+        wg_map<float3>(Bt * O,
+            [&](int e) { const int r = e / O, c = e % O; return make_float3(vp[r * S + c], mu[r * S + c], ys[r * S + c]); },
+            [&](int e, float3 in) {
+                const int r = e / O, c = e % O;
+                const float v = in.x, var = train_softplus(v) + 1e-4f;
+                const float diff = in.y - in.z;
+                s_log += logf(6.283185307179586f * var);
+                s_sq += diff * diff / var;
+                if (p.train) {
+                    dmu[r * S + c] = diff / var * ninv;
+                    const float dvar = (0.5f / var - 0.5f * diff * diff / (var * var)) * ninv;
+                    dv[r * S + c] = dvar / (1.0f + expf(-v));               // d softplus(v)/dv = sigmoid(v)
+                }
+            });
+        s_log = block_sum(s_log, red);
+        s_sq = block_sum(s_sq, red);
+        CEM_TR_STAMP(4);
+        // this part's share of the two sums of the loss (its passes added in order); the Adam kernel (training) or the host
+        // (validation) adds the parts in order
+        tot_log = accum ? tot_log + s_log : s_log;
+        tot_sq = accum ? tot_sq + s_sq : s_sq;
+        if (tid == 0) { p.loss_part[((size_t)m * p.nparts + part) * 2] = tot_log; p.loss_part[((size_t)m * p.nparts + part) * 2 + 1] = tot_sq; }
+        if (!p.train) continue;
+        __syncthreads();
+
+        CEM_TR_STAMP(5);
+        // ---- backward ------------------------------------------------------------------------------------------------
+        // [dW_mu | dW_var] = h_L^T [dmu | dv] as one GEMM
+        GemmEpi ghead{(gptr)(G + oWmu), O, nullptr, nullptr, 0, 0, (gptr)(G + oWv), nullptr, p.stamps, (gptr)(G + obmu), (gptr)(G + obv)};
+        ghead.accum = accum;
+        wg_gemm(U, 2 * O, Bt, (gcptr)hL, 1, S, (gcptr)dmu, S, 1, ghead, GemmSplit{nullptr, (gcptr)dv, 0x7fffffff, O});   // + [db_mu | db_var] = column sums of [dmu | dv]
+        // dh_L = (dmu Wmu^T + dv Wvar^T) * relu'(h_L): the relu mask rides in the epilogue of the GEMM that completes dh
+        // dh_L = ([dmu | dv] [W_mu | W_var]^T) * relu'(h_L): one GEMM over K = 2O; the relu mask rides in its epilogue
+        wg_gemm(Bt, U, 2 * O, (gcptr)dmu, S, 1, (gcptr)(W + oWmu), 1, O,
+                GemmEpi{(gptr)dha, S, nullptr, (gcptr)(zs ? zs + (size_t)(L - 1) * CEM_TROWS * S : hL), S, 1 + p.act, nullptr, nullptr, p.stamps, nullptr, nullptr, p.drop_thresh, p.drop_scale, p.drop_keep}, GemmSplit{(gcptr)dv, (gcptr)(W + oWv), O, 0x7fffffff});
+        CEM_TR_STAMP(6);
+        float *dcur = dha, *dnext = dhb;
+        for (int l = L - 1; l >= 0; --l) {
+            const float *hin = l == 0 ? xs : hs + (size_t)(l - 1) * CEM_TROWS * S;
+            const int in = l == 0 ? D : U;
+            GemmEpi gl{(gptr)(G + offW(l)), U, nullptr, nullptr, 0, 0, nullptr, nullptr, p.stamps, (gptr)(G + offb(l)), nullptr};
+            gl.accum = accum;
+            wg_gemm(in, U, Bt, (gcptr)hin, 1, S, (gcptr)dcur, S, 1, gl, CEM_NOSPLIT);   // dW_l = h_{l-1}^T dh_l, db_l = column sums of dh_l
+            if (l > 0) {
+                wg_gemm(Bt, U, U, (gcptr)dcur, S, 1, (gcptr)(W + offW(l)), 1, U, GemmEpi{(gptr)dnext, S, nullptr, (gcptr)(zs ? zs + (size_t)(l - 1) * CEM_TROWS * S : hin), S, 1 + p.act, nullptr, nullptr, p.stamps, nullptr, nullptr, p.drop_thresh, p.drop_scale, p.drop_keep}, CEM_NOSPLIT);   // dh_{l-1} = (dh_l W_l^T) f'(z_{l-1})
+                float *t = dcur; dcur = dnext; dnext = t;
+            }
+        }
+        CEM_TR_STAMP(7);
     }
-    CEM_TR_STAMP(7);
 }
 
 // ---- Adam with clipvalue (mlp_ensemble.py:113-117,143-144), every member's parameters in one grid ---------------------
 __global__ __launch_bounds__(256) void cem_adam_kernel(const TrainParams p)
 {
     const size_t n = (size_t)p.E * p.nat, n4 = n / 4;
-    const int nparts = (p.Bt + CEM_TROWS - 1) / CEM_TROWS;          // row parts that ran this step (a short last minibatch has fewer)
+    const int nparts = p.nparts;                                    // row parts that ran this step (a short minibatch has fewer)
     const float ob1 = 1.0f - p.beta1, ob2 = 1.0f - p.beta2;
     auto upd = [&](float g, float &mo, float &vo, float &w) {
         g = fminf(fmaxf(g, -p.clip), p.clip);
@@ -593,6 +637,13 @@ __global__ __launch_bounds__(256) void cem_adam_kernel(const TrainParams p)
 #pragma unroll
         for (int q = 1; q < CEM_TPARTS; ++q)
             if (q < nparts) { g.x = g.x + gp[q].x; g.y = g.y + gp[q].y; g.z = g.z + gp[q].z; g.w = g.w + gp[q].w; }
+        for (int q0 = CEM_TPARTS; q0 < nparts; q0 += CEM_TPARTS) {     // more than 64 rows: the further parts, four loads in flight at a time
+#pragma unroll
+            for (int q = 0; q < CEM_TPARTS; ++q) gp[q] = G4[(q0 + q < nparts ? (size_t)(q0 + q) : 0) * (p.gpart / 4) + e];
+#pragma unroll
+            for (int q = 0; q < CEM_TPARTS; ++q)
+                if (q0 + q < nparts) { g.x = g.x + gp[q].x; g.y = g.y + gp[q].y; g.z = g.z + gp[q].z; g.w = g.w + gp[q].w; }
+        }
         float4 mo = M4[e], vo = V4[e], w = W4[e];
         upd(g.x, mo.x, vo.x, w.x); upd(g.y, mo.y, vo.y, w.y); upd(g.z, mo.z, vo.z, w.z); upd(g.w, mo.w, vo.w, w.w);
         M4[e] = mo; V4[e] = vo; W4[e] = w;
@@ -606,7 +657,7 @@ __global__ __launch_bounds__(256) void cem_adam_kernel(const TrainParams p)
     // training_step's return value, per member: negative_log_likelihood / ensemble_size (mlp_ensemble.py:64-67,139-141)
     if (blockIdx.x == 0) for (int m = threadIdx.x; m < p.E; m += blockDim.x) {       // any ensemble size (the reference takes any)
         float s_log = 0.f, s_sq = 0.f;
-        for (int q = 0; q < nparts; ++q) { s_log = s_log + p.loss_part[((size_t)m * CEM_TPARTS + q) * 2]; s_sq = s_sq + p.loss_part[((size_t)m * CEM_TPARTS + q) * 2 + 1]; }
+        for (int q = 0; q < nparts; ++q) { s_log = s_log + p.loss_part[((size_t)m * nparts + q) * 2]; s_sq = s_sq + p.loss_part[((size_t)m * nparts + q) * 2 + 1]; }
         const float cnt = (float)p.Bt * (float)p.O;
         p.loss_out[m] = (0.5f * s_log / cnt + 0.5f * s_sq / cnt) / (float)p.E;
     }

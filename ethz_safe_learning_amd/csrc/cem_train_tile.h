@@ -13,7 +13,9 @@
 //   backward  dh_{l-1}^T         = (W_l dh_l^T) * relu'(h_{l-1})      A = W_l[in][k], B = dh_l block
 //   weights   dW_l [in x out]    = h_{l-1}^T dh_l                     A, B gathered from LDS with the row as the k index
 //   biases    db_l               = sum over rows of dh_l               16-lane reductions of the accumulators
-// Each workgroup writes PARTIAL gradients (its 16 rows); the Adam kernel adds a member's parts in a fixed order.
+// Each workgroup writes PARTIAL gradients (its rows); the Adam kernel adds a member's parts in a fixed order.  A part of more
+// than 16 rows (minibatches beyond 16 x CEM_TPMAX rows) runs the whole step once per 16-row pass; later passes add their
+// gradients to what the same lanes stored before.
 //
 // Weight traffic.  A stage (one layer for one wave: 1 output block x 8 k blocks; 2 for the heads) needs 32 words per lane and 32
 // MFMAs that take 1 K cycles — less than one L2 round trip with nothing else in flight.  The weights do not depend on the activations, so every
@@ -31,7 +33,12 @@
 #define CEM_TT_WAVES 8                       // waves per workgroup: wave w owns 16-feature block w of every activation matrix
 #define CEM_TT_MAXL 6                        // layer counts with their own instantiation (the reference ships 4)
 
-struct TtCtx { int lane, q, j, w, cnt; };
+struct TtCtx { int lane, q, j, w, cnt, acc; };       // acc: a later pass of the part (gradients are added, not stored)
+
+__device__ __forceinline__ void tt_put(float *g, const float v, const TtCtx &c)     // a gradient word: stored, or added in a later pass
+{
+    *g = c.acc ? *g + v : v;
+}
 
 __device__ __forceinline__ float tt_row_sum(float v)          // sum over the 16 rows (lanes j) of a feature: four DPP row rotations
 {                                                             // (fixed order; every lane of the row ends with the sum; no LDS traffic)
@@ -147,7 +154,7 @@ __device__ __forceinline__ void tt_dw_n(const char *hsrc, const char *dsrc, cons
 #ifdef CEM_TT_DBG_NOSTORE
                 if (mI < inDim && n < outDim && acc[F][r] == 123.456f) Gw[(size_t)mI * ldw + n] = acc[F][r];
 #else
-                if (mI < inDim && n < outDim) Gw[(size_t)mI * ldw + n] = acc[F][r];
+                if (mI < inDim && n < outDim) tt_put(&Gw[(size_t)mI * ldw + n], acc[F][r], c);
 #endif
             }
         }
@@ -161,22 +168,18 @@ __device__ __forceinline__ void tt_dw(const char *hsrc, const char *dsrc, const 
     else tt_dw_n<8>(hsrc, dsrc, nIn, inDim, outDim, Gw, ldw, c);
 }
 
+// One pass of a workgroup: rows [row0, row0 + cnt) of member m's minibatch (chunk), cnt <= 16, through the forward pass, the loss
+// and the backward pass.  `later`: not the part's first pass — the gradients are added to what the same lanes stored before, and the
+// loss sums to the part's running ones (tot_log / tot_sq, thread 0).
 template <int L>
-__global__ __launch_bounds__(64 * CEM_TT_WAVES) void cem_train_tile_kernel(const TrainParams p)
+__device__ __forceinline__ void tt_pass(const TrainParams &p, const int m, const int part, const int chunk0, const int Bt, const int row0,
+                                        const int cnt, const bool later, float &tot_log, float &tot_sq)
 {
     extern __shared__ __attribute__((aligned(16))) char tsm[];
     __shared__ float red[2][CEM_TT_WAVES];
     __shared__ int32_t rows_s[CEM_TROWS];
-    const int m = blockIdx.x / CEM_TPARTS, part = blockIdx.x % CEM_TPARTS, tid = threadIdx.x;
-    const int D = p.D, O = p.O, U = p.U;
-    // rows of this workgroup: chunk blockIdx.y of the launch (training launches have one chunk = the minibatch), part `part` of it
-    const int chunk0 = (int)blockIdx.y * p.chunk;
-    const int Bt = p.Bt - chunk0 < p.chunk ? p.Bt - chunk0 : p.chunk;
-    const int row0 = part * CEM_TROWS;
-    const int cnt = Bt - row0 < CEM_TROWS ? Bt - row0 : CEM_TROWS;
-    if (cnt <= 0) return;                          // a short minibatch: the Adam kernel only adds the parts that exist
-    CEM_TR_STAMP(0);
-    TtCtx c; c.lane = tid & 63; c.q = c.lane >> 4; c.j = c.lane & 15; c.w = __builtin_amdgcn_readfirstlane(tid >> 6); c.cnt = cnt;
+    const int tid = threadIdx.x, D = p.D, O = p.O, U = p.U;
+    TtCtx c; c.lane = tid & 63; c.q = c.lane >> 4; c.j = c.lane & 15; c.w = __builtin_amdgcn_readfirstlane(tid >> 6); c.cnt = cnt; c.acc = later;
     const gcptr W = (gcptr)(p.W + (size_t)m * p.nat);
     float *G = p.grad + (size_t)part * p.gpart + (size_t)m * p.nat;
     // natural-blob offsets (cem_mpc.h): W_0,b_0,...,W_mu,b_mu,W_var,b_var
@@ -294,7 +297,7 @@ __global__ __launch_bounds__(64 * CEM_TT_WAVES) void cem_train_tile_kernel(const
             for (int r = 0; r < 4; ++r) {
                 const int o = mb + 4 * c.q + r;
                 const float a = tt_row_sum(dmu[r]), b = tt_row_sum(dv[r]);
-                if (c.j == 0 && o < O) { G[obmu + o] = a; G[obv + o] = b; }
+                if (c.j == 0 && o < O) { tt_put(&G[obmu + o], a, c); tt_put(&G[obv + o], b, c); }
             }
         }
     }
@@ -307,8 +310,10 @@ __global__ __launch_bounds__(64 * CEM_TT_WAVES) void cem_train_tile_kernel(const
         float a = red[0][0], b = red[1][0];
 #pragma unroll
         for (int w = 1; w < CEM_TT_WAVES; ++w) { a += red[0][w]; b += red[1][w]; }
-        float *lp = p.loss_part + (((size_t)blockIdx.y * p.E + m) * CEM_TPARTS + part) * 2;
-        lp[0] = a; lp[1] = b;
+        tot_log = c.acc ? tot_log + a : a;
+        tot_sq = c.acc ? tot_sq + b : b;
+        float *lp = p.loss_part + (((size_t)blockIdx.y * p.E + m) * p.nparts + part) * 2;
+        lp[0] = tot_log; lp[1] = tot_sq;
     }
     CEM_TR_STAMP(2 + L);
     if (!p.train) return;
@@ -331,7 +336,7 @@ __global__ __launch_bounds__(64 * CEM_TT_WAVES) void cem_train_tile_kernel(const
         for (int r = 0; r < 4; ++r) {
             const int o = mb + 4 * c.q + r;
             const float sum = tt_row_sum(d[r]);
-            if (c.j == 0 && o < U) G[offb(L - 1) + o] = sum;
+            if (c.j == 0 && o < U) tt_put(&G[offb(L - 1) + o], sum, c);
         }
     }
     // [dW_mu | dW_var] = h_L^T [dmu | dv]: off the dh chain's critical path (the other wave of the SIMD runs ahead meanwhile)
@@ -361,11 +366,32 @@ __global__ __launch_bounds__(64 * CEM_TT_WAVES) void cem_train_tile_kernel(const
             for (int r = 0; r < 4; ++r) {
                 const int o = mb + 4 * c.q + r;
                 const float sum = tt_row_sum(d[r]);
-                if (c.j == 0 && o < U) G[offb(l - 1) + o] = sum;
+                if (c.j == 0 && o < U) tt_put(&G[offb(l - 1) + o], sum, c);
             }
         }
         tt_dw(hin, dcur, nIn, in, U, G + offW(l), U, c);                    // dW_l = h_{l-1}^T dh_l
         if (l > 0) __syncthreads();
         CEM_TR_STAMP(4 + L + (L - 1 - l));
+    }
+}
+
+// MULTI: some part has more than 16 rows (p.Bt > 16 x p.nparts), i.e. several passes; without it the kernel is the one pass of a
+// minibatch of up to 16 x CEM_TPMAX rows, as compiled before there were passes.
+template <int L, bool MULTI>
+__global__ __launch_bounds__(64 * CEM_TT_WAVES) void cem_train_tile_kernel(const TrainParams p)
+{
+    const int m = blockIdx.x / p.nparts, part = blockIdx.x % p.nparts;
+    // rows of this workgroup: chunk blockIdx.y of the launch (training launches have one chunk = the minibatch), part `part` of it
+    const int chunk0 = (int)blockIdx.y * p.chunk;
+    const int Bt = p.Bt - chunk0 < p.chunk ? p.Bt - chunk0 : p.chunk;
+    int r0 = part * CEM_TROWS, r1 = Bt - r0 < CEM_TROWS ? Bt : r0 + CEM_TROWS;     // one pass: part q takes rows [16 q, +16)
+    if (MULTI) cem_part_rows(Bt, p.nparts, part, r0, r1);                         // (p.nparts < ceil(Bt / 16): training steps only)
+    if (r1 <= r0) return;                          // a short minibatch: the Adam kernel only adds the parts that exist
+    CEM_TR_STAMP(0);
+    float tot_log = 0.f, tot_sq = 0.f;
+    if (!MULTI) { tt_pass<L>(p, m, part, chunk0, Bt, r0, r1 - r0, false, tot_log, tot_sq); return; }
+    for (int row0 = r0; row0 < r1; row0 += CEM_TROWS) {
+        if (row0 != r0) __syncthreads();           // the pass before is done with the LDS
+        tt_pass<L>(p, m, part, chunk0, Bt, row0, r1 - row0 < CEM_TROWS ? r1 - row0 : CEM_TROWS, row0 != r0, tot_log, tot_sq);
     }
 }

@@ -39,6 +39,9 @@ class CemTrainer:
         import torch
         self._torch = torch
         self.lib = _capi.load()
+        if not 1 <= batch_size <= _capi.CEM_TRAIN_MAX_BATCH:
+            raise ValueError('batch_size %r: the device trainer takes 1 to %d rows per member per step (CEM_TRAIN_MAX_BATCH)'
+                             % (batch_size, _capi.CEM_TRAIN_MAX_BATCH))
         if not torch.cuda.is_available():
             raise RuntimeError('CemTrainer needs a ROCm GPU; there is no CPU path')
         self.dims = (inputs_dim, outputs_dim, units, n_layers, ensemble_size)

@@ -345,11 +345,16 @@ int cem_planner_batch_capacity(const cem_planner_t *h, int32_t *max_batch_out); 
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate
  * schedule loop of fit() (:163-187, :70-88) is host logic above this ABI.  Weights use the natural blob layout above,
- * so the result of training feeds cem_planner_set_weights() unchanged. */
+ * so the result of training feeds cem_planner_set_weights() unchanged.
+ * A step takes 1 .. batch_size <= CEM_TRAIN_MAX_BATCH rows per member; a larger batch_size is CEM_ERR_UNSUPPORTED (and a workspace
+ * size of 0).  Each member's rows are split into at most 32 row parts (one workgroup each), which take their rows in passes of 16
+ * and leave partial gradients that the Adam step adds in part order: no atomics, repeated steps give identical bits.  Up to 64 rows
+ * every part is one pass of 16 rows.  validation_step walks the set in chunks of min(batch_size, 64) rows. */
+#define CEM_TRAIN_MAX_BATCH 4096
 typedef struct cem_train_config {
     int32_t abi_version;
     int32_t inputs_dim, outputs_dim, units, n_layers, ensemble_size;
-    int32_t batch_size;           /* rows per member per step, <= 64 (config/models.yaml:4) */
+    int32_t batch_size;           /* rows per member per step, 1 .. CEM_TRAIN_MAX_BATCH (config/models.yaml:4 ships 64) */
     int32_t activation;           /* enum cem_activation */
     float dropout_rate;           /* mlp_params['dropout_rate'] (config/models.yaml:13; the shipped value is 0): Dropout after every hidden layer in
                                    * training_step only (mlp_ensemble.py:15,21,138); 0 <= rate < 1.  The keep mask of training step s (0-based,

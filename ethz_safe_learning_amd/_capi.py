@@ -15,6 +15,7 @@ CEM_MAX_COST_KINDS = 4
 CEM_COMM_ID_BYTES = 128
 CEM_MAX_BATCH = 256
 CEM_TRAIN_MAX_BATCH = 4096
+CEM_INIT_COLD, CEM_INIT_EXPLICIT, CEM_INIT_SHIFT = 0, 1, 2      # enum cem_init_mode
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds
@@ -26,6 +27,8 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_normaliser', 'cem_planner_plan', 'cem_plan_begin', 'cem_plan_rollout', 'cem_plan_select',
     'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_launches_per_iteration', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
     'cem_batch_workspace_bytes', 'cem_batch_planner_create', 'cem_planner_plan_batch', 'cem_planner_batch_capacity',
+    'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
+    'cem_planner_get_carry', 'cem_planner_set_carry_slots',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval',
 ]
@@ -64,6 +67,10 @@ class CemTrainConfig(C.Structure):
                 ('n_layers', C.c_int32), ('ensemble_size', C.c_int32), ('batch_size', C.c_int32), ('activation', C.c_int32),
                 ('dropout_rate', C.c_float), ('dropout_seed_lo', C.c_uint32), ('dropout_seed_hi', C.c_uint32),
                 ('beta1', C.c_float), ('beta2', C.c_float), ('epsilon', C.c_float), ('clipvalue', C.c_float)]
+
+
+class CemWarmStart(C.Structure):
+    _fields_ = [('shift', C.c_int32), ('tail', C.c_int32), ('sigma_rule', C.c_int32), ('sigma_floor', C.c_float * CEM_MAX_ACT)]
 
 
 class CemLayout(C.Structure):
@@ -142,6 +149,12 @@ def load():
     lib.cem_batch_planner_create.argtypes = [cfgp, C.c_int32, vp, C.c_size_t, vp, C.POINTER(vp)]
     lib.cem_planner_plan_batch.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     lib.cem_planner_batch_capacity.argtypes = [vp, i32p]
+    lib.cem_planner_set_warm_start.argtypes = [vp, C.POINTER(CemWarmStart)]
+    lib.cem_planner_set_initial_distribution.argtypes = [vp, C.c_int32, vp, vp]
+    lib.cem_planner_set_init_mode.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.cem_planner_reset_carry.argtypes = [vp, C.c_int32]
+    lib.cem_planner_get_carry.argtypes = [vp, C.c_int32, vp, vp, i32p]
+    lib.cem_planner_set_carry_slots.argtypes = [vp, C.c_int32, vp]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

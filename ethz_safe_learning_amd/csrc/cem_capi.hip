@@ -465,7 +465,7 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct Layout {
     size_t ctrl, musig, act_bounds, scores_local, scores_global, actions, act_pad, elite, returns, costs, result, wpack, bias_h, bias_mu, bias_var,
         nmin, ndelta, omask, kind_sel, etab, tiles, eps_out, stamps, seg_queue, seg_flags, seg_state,
-        ms_hist, ms_sel, ms_counts, ms_best_sc, ms_best_ix, ms_part, ms_colmean, total;
+        ms_hist, ms_sel, ms_counts, ms_best_sc, ms_best_ix, ms_part, ms_colmean, carry, expl, total;
 };
 
 struct Plan { int rc, n_tiles, n_seg, seg_len, n_pinned; };
@@ -527,6 +527,9 @@ Layout make_layout(const cem_config_t *c, const Dims &d, size_t max_tiles, int m
     l.ms_hist = take(3 * CEM_MS_BINS * 4); l.ms_sel = take(256);
     l.ms_counts = take(msG * 2 * 4); l.ms_best_sc = take(msG * 4); l.ms_best_ix = take(msG * 4);
     l.ms_part = take(2 * msG2 * (size_t)d.H * d.A * 4); l.ms_colmean = take((size_t)d.H * d.A * 4);
+    // warm start, behind everything else so that no earlier offset moves: per slot the carry (mu, sigma [H][A] of its last completed plan)
+    // and the explicit initial distribution (cem_planner_set_initial_distribution)
+    l.carry = take(nb * 2 * d.H * d.A * 4); l.expl = take(nb * 2 * d.H * d.A * 4);
     l.total = o;
     return l;
 }
@@ -662,6 +665,7 @@ struct cem_planner {
     // pinned host staging
     CtrlBlock *h_ctrl;
     float *h_result;
+    WarmCtl *h_warm; const WarmCtl *d_h_warm;  // warm-start control of the next plan (stage_warm), read by cem_init_kernel alone
     uint32_t plan_seq;                       // plans staged on this handle (CtrlBlock::seq)
     const CtrlBlock *d_h_ctrl; float *d_h_result;     // the same two blocks as the DEVICE addresses them (hipHostGetDevicePointer)
     // timing
@@ -678,12 +682,22 @@ struct cem_planner {
     int fused_resident;                      // workgroups of cem_msel_fused_kernel the device keeps resident at once (occupancy x CUs)
     bool sel_zeroed;                         // the multi-workgroup select's histograms / barrier counter were cleared by this iteration's reduce kernel
     bool fuse_banned;                        // a grid barrier of the fused select expired on this handle once (recovered in-stream): select_mode 2 from then on
+    bool inject_capture_fail;                // cem_planner_inject_fault kind 2: treat the next graph capture of cem_planner_plan as refused by the runtime
     uint32_t inject_next;                    // cem_planner_inject_fault: CtrlBlock::inject of the next plan
     // grow-only device scratch of the standalone ops (unfold_sequences tiles + returns, compute_objective returns + costs)
     char *scratch; size_t scratch_bytes;
     std::vector<float> h_etab;               // host copy of RolloutParams::etab ([E][CEM_ET_ROWS + L][128]); re-uploaded whole by create / set_weights / set_normaliser
     int batch;                               // problems of a batch handle (cem_batch_planner_create); 0: a single-state handle
     int n_states;                            // problems of the batched plan being enqueued / last run (the rest are staged as done)
+    // warm start (cem_mpc.h): per carry slot [max(batch, 1)]
+    cem_warm_start_t warm;                   // parameters of CEM_INIT_SHIFT
+    std::vector<int32_t> slot_mode;          // cem_init_mode, sticky
+    std::vector<uint8_t> carry_valid, have_expl;
+    std::vector<int32_t> carry_at;           // problem index whose mu / sigma slice still holds the slot's carry (the next plan's first kernel saves it), or -1: it is in Layout::carry
+    std::vector<int32_t> slot_of;            // problem b -> carry slot (cem_planner_set_carry_slots), a permutation of 0 .. batch - 1
+    bool warm_save_skipped;                  // the staged plan overwrites the one slot's carry without a copy (stage_warm)
+    int warm_staged;                       // problems of the plan whose warm control is staged and whose outcome finish_warm has not seen yet
+    std::vector<float> h_expl;               // host copy of the explicit uploads [slots][2][HA]: the source of their stream-ordered copies
 };
 
 extern "C" {
@@ -819,13 +833,18 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false;
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
-    h->h_ctrl = nullptr; h->h_result = nullptr;
-    h->scratch = nullptr; h->scratch_bytes = 0; h->sel_zeroed = false; h->plan_seq = 0; h->fuse_banned = false; h->inject_next = 0;
+    h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr;
+    h->warm = cem_warm_start_t{}; h->warm.shift = 1; h->warm_staged = 0; h->warm_save_skipped = false;
+    h->slot_mode.assign(nb, CEM_INIT_COLD); h->carry_valid.assign(nb, 0); h->have_expl.assign(nb, 0); h->carry_at.assign(nb, -1);
+    h->slot_of.resize(nb); for (size_t b = 0; b < nb; ++b) h->slot_of[b] = (int32_t)b;
+    h->h_expl.assign(nb * 2 * h->d.H * h->d.A, 0.f);
+    h->scratch = nullptr; h->scratch_bytes = 0; h->sel_zeroed = false; h->plan_seq = 0; h->fuse_banned = false; h->inject_next = 0; h->inject_capture_fail = false;
     // every failure from here on frees what was acquired and reports the HIP code
     auto fail = [&](int status) {
         g_last_hip = (int)hipGetLastError();
         if (h->h_ctrl) hipHostFree(h->h_ctrl);
         if (h->h_result) hipHostFree(h->h_result);
+        if (h->h_warm) hipHostFree(h->h_warm);
         if (h->own_stream) hipStreamDestroy(h->stream);
         delete h;
         return status;
@@ -834,13 +853,16 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     // and the host polls that result while the stream is still running
     const size_t result_bytes = mb ? nb * CEM_RESULT_WORDS * 4 : 64 * 4;
     if (hipHostMalloc((void **)&h->h_ctrl, nb * sizeof(CtrlBlock), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostMalloc((void **)&h->h_result, result_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail(CEM_ERR_HIP);
+        hipHostMalloc((void **)&h->h_result, result_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostMalloc((void **)&h->h_warm, sizeof(WarmCtl) + nb * sizeof(WarmProb), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail(CEM_ERR_HIP);
+    std::memset(h->h_warm, 0, sizeof(WarmCtl) + nb * sizeof(WarmProb));
     std::memset(h->h_ctrl, 0, nb * sizeof(CtrlBlock));
     std::memset(h->h_result, 0, result_bytes);
     {   // kernels read the staged control block and write the plan's result in place (no copy nodes around a plan)
-        void *dc = nullptr, *dr = nullptr;
-        if (hipHostGetDevicePointer(&dc, h->h_ctrl, 0) != hipSuccess || hipHostGetDevicePointer(&dr, h->h_result, 0) != hipSuccess) return fail(CEM_ERR_HIP);
-        h->d_h_ctrl = (const CtrlBlock *)dc; h->d_h_result = (float *)dr;
+        void *dc = nullptr, *dr = nullptr, *dw = nullptr;
+        if (hipHostGetDevicePointer(&dc, h->h_ctrl, 0) != hipSuccess || hipHostGetDevicePointer(&dr, h->h_result, 0) != hipSuccess ||
+            hipHostGetDevicePointer(&dw, h->h_warm, 0) != hipSuccess) return fail(CEM_ERR_HIP);
+        h->d_h_ctrl = (const CtrlBlock *)dc; h->d_h_result = (float *)dr; h->d_h_warm = (const WarmCtl *)dw;
     }
     auto upload = [&](size_t off, const void *src, size_t bytes) {
         return hipMemcpyAsync(h->ws + off, src, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess;
@@ -917,6 +939,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     if (mb && resolve_select_mode(cfg->select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, false, nullptr) != 1) {
         if (h->h_ctrl) hipHostFree(h->h_ctrl);
         if (h->h_result) hipHostFree(h->h_result);
+        if (h->h_warm) hipHostFree(h->h_warm);
         if (h->own_stream) hipStreamDestroy(h->stream);
         delete h;
         return CEM_ERR_UNSUPPORTED;
@@ -966,6 +989,7 @@ int cem_planner_destroy(cem_planner_t *h)
     for (auto e : h->ev) hipEventDestroy(e);
     if (h->h_ctrl) hipHostFree(h->h_ctrl);
     if (h->h_result) hipHostFree(h->h_result);
+    if (h->h_warm) hipHostFree(h->h_warm);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
     return CEM_OK;
@@ -1157,6 +1181,8 @@ hipEvent_t get_event(cem_planner *h, size_t i)
     return h->ev[i];
 }
 
+void warm_handed_over(cem_planner *h);
+
 int enqueue_begin(cem_planner *h)
 {
     const Dims &d = h->d; const Layout &l = h->lay;
@@ -1165,10 +1191,16 @@ int enqueue_begin(cem_planner *h)
     for (int a = 0; a < d.A; ++a) { ip.mu0[a] = h->cfg.act_mu0[a]; ip.sigma0[a] = h->cfg.act_sigma0[a]; }
     if (h->n_seg > 1) { ip.seg_queue = (uint32_t *)(h->ws + l.seg_queue); ip.seg_flags = (uint32_t *)(h->ws + l.seg_flags); ip.n_ready = (h->n_tiles - h->n_pinned) * (h->n_seg - 1); }
     ip.n_prob = h->batch;                                // a batch handle: every problem's block and mu / sigma (the done ones included)
+    ip.warm = h->d_h_warm; ip.carry = (float *)(h->ws + l.carry); ip.expl = (const float *)(h->ws + l.expl);
     const int nb = h->batch ? h->batch : 1;
     const int n = nb * std::max<int>(ip.HA, (int)(sizeof(CtrlBlock) / 4));
     hipLaunchKernelGGL(cem_init_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, ip);
     HIPCHK(hipGetLastError());
+    {   // launched for real (not recorded into a graph): the pending carries are on their way to Layout::carry (stage_warm's invariant)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+        if (cs == hipStreamCaptureStatusNone) warm_handed_over(h);
+    }
     return CEM_OK;
 }
 
@@ -1359,8 +1391,75 @@ void collect_timing(cem_planner *h)
     h->ev_kind.clear();
 }
 
+// ---- warm start (cem_mpc.h: cem_init_mode) ---------------------------------------------------------------
+// The host owns the bookkeeping (which slot's carry is valid, where it currently lives), the first kernel of a plan does the copies.
+// A plan's last mu / sigma stay where the select left them — slice b of Layout::musig — until the NEXT plan's first kernel, which is
+// about to restart every slice, moves them to the slot's carry first (WarmProb::save_slot).  Nothing else touches Layout::musig between
+// two plans, and that kernel is ordered behind the whole previous plan by the stream, early stop or not.
+int warm_slots(const cem_planner *h) { return h->batch ? h->batch : 1; }
+// (by the bits: the library is built with -fno-honor-nans, under which the compiler may drop a floating-point NaN test)
+bool finite_bits(float x) { uint32_t u; std::memcpy(&u, &x, 4); return (u & 0x7f800000u) != 0x7f800000u; }
+
+// what has to hold before anything of a plan of n problems is staged
+int check_warm(const cem_planner *h, int n)
+{
+    for (int b = 0; b < n; ++b) {
+        const int s = h->slot_of[b];
+        if (h->slot_mode[s] == CEM_INIT_EXPLICIT && !h->have_expl[s]) return CEM_ERR_STATE;
+    }
+    return CEM_OK;
+}
+
+// INVARIANT: the hand-over of a pending carry (carry_at[s] -> WarmProb::save_slot) is consumed by exactly one EXECUTED first kernel.
+// stage_warm only describes it and may run any number of times before a launch (a plan staged for a capture that then fails is staged
+// again for the eager launches; a HIP call may fail between staging and launch): it rebuilds save_slot from carry_at and changes
+// nothing.  warm_handed_over, called where the first kernel is really put on the stream (an eager launch outside a capture, a graph
+// launch), is what clears carry_at — from then on the carries are in Layout::carry, in stream order, and a later staging (a second
+// cem_plan_begin without an end, say) must not save the slices again, which hold the new plan's distribution by then.
+void warm_handed_over(cem_planner *h)
+{
+    for (auto &c : h->carry_at) c = -1;
+    if (h->warm_save_skipped) { h->carry_valid[0] = 0; h->warm_save_skipped = false; }   // (stage_warm: the launched plan overwrites a carry nobody copied)
+}
+
+void stage_warm(cem_planner *h, int n)
+{
+    WarmCtl *w = h->h_warm;
+    const int nb = warm_slots(h);
+    w->shift = h->warm.shift; w->tail = h->warm.tail; w->sigma_rule = h->warm.sigma_rule;
+    for (int a = 0; a < 32; ++a) w->sigma_floor[a] = h->warm.sigma_floor[a];
+    for (int b = 0; b < nb; ++b) { w->prob[b].mode = CEM_INIT_COLD; w->prob[b].slot = h->slot_of[b]; w->prob[b].save_slot = -1; w->prob[b].pad = 0; }
+    for (int s = 0; s < nb; ++s)                                   // carries still in a mu / sigma slice: all of them move now, also
+        if (h->carry_at[s] >= 0) w->prob[h->carry_at[s]].save_slot = s;                            // those of slots that sit this plan out
+    w->two_phase = 0;
+    for (int b = 0; b < n; ++b) {
+        const int s = h->slot_of[b];
+        int m = h->slot_mode[s];
+        if (m == CEM_INIT_SHIFT && !h->carry_valid[s]) m = CEM_INIT_COLD;
+        w->prob[b].mode = m;
+        if (m == CEM_INIT_SHIFT) w->two_phase = 1;            // some problem reads a carry: the first kernel takes its two-phase form
+    }
+    // A single-state handle whose plan does not read the carry needs no copy of it either: the plan overwrites the one slice there is, and
+    // until its own result becomes the carry nothing can read the old one (cem_planner_get_carry is refused inside a stepwise plan; the
+    // launch drops the old carry's validity, see warm_handed_over).  This keeps a cold plan's first kernel free of loads.
+    h->warm_save_skipped = !h->batch && !w->two_phase && w->prob[0].save_slot >= 0;
+    if (h->warm_save_skipped) w->prob[0].save_slot = -1;
+    h->warm_staged = n;
+}
+
+// the plan staged last has returned `status`: its slots' carries are what it left (CEM_OK) or invalid
+void finish_warm(cem_planner *h, int status)
+{
+    for (int b = 0; b < h->warm_staged; ++b) {
+        const int s = h->slot_of[b];
+        h->carry_valid[s] = status == CEM_OK; h->carry_at[s] = status == CEM_OK ? b : -1;
+    }
+    h->warm_staged = 0;
+}
+
 void stage_ctrl(cem_planner *h, const float *state, uint64_t seed, uint64_t call)
 {
+    stage_warm(h, 1);
     CtrlBlock *c = h->h_ctrl;
     c->seed_lo = (uint32_t)seed; c->seed_hi = (uint32_t)(seed >> 32); c->call_lo = (uint32_t)call; c->call_hi = (uint32_t)(call >> 32);
     c->done = 0; c->iters = 0; c->fault = 0; c->best_score = -std::numeric_limits<float>::infinity();
@@ -1435,6 +1534,7 @@ int read_result(cem_planner *h, float *action_out, float *best_score_out, int32_
 // stages for that state alone; problems n .. batch - 1 are staged as already stopped (done, no iterations), so every kernel skips them
 void stage_ctrl_batch(cem_planner *h, int32_t n, const float *states, uint64_t seed, const uint64_t *calls)
 {
+    stage_warm(h, n);
     const uint32_t seq = ++h->plan_seq;
     for (int b = 0; b < h->batch; ++b) {
         CtrlBlock *c = h->h_ctrl + b;
@@ -1467,7 +1567,7 @@ int read_batch_results(cem_planner *h, int32_t n, float *actions_out, float *sco
 
 extern "C" {
 
-int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
+static int plan_batch_impl(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
                            const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
                            float *best_scores_out, int32_t *iters_out)
 {
@@ -1476,6 +1576,7 @@ int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *stat
     if (!states || !calls || n_states < 1 || n_states > h->batch) return CEM_ERR_INVALID_ARG;
     if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
     if ((eps_act_dev == nullptr) != (eps_model_dev == nullptr) && h->cfg.sampling_propagation) return CEM_ERR_INVALID_ARG;
+    { const int wst = check_warm(h, n_states); if (wst) return wst; }
     const bool fold = folds_reduce(h);
     // One hipGraph per handle, captured for all `batch` problems: n_states only changes what is staged (the rest are done), never the graph
     if (h->cfg.use_graph && !eps_act_dev && !eps_model_dev && !eps_out_host && !h->timing) {
@@ -1500,6 +1601,7 @@ int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *stat
             h->graph_ready = true;
         }
         HIPCHK(hipGraphLaunch(h->gexec, h->stream));
+        warm_handed_over(h);
         { const int ws_ = wait_result(h); if (ws_) return ws_; }
         return read_batch_results(h, n_states, actions_out, best_scores_out, iters_out);
     }
@@ -1521,12 +1623,13 @@ int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *stat
     return read_batch_results(h, n_states, actions_out, best_scores_out, iters_out);
 }
 
-int cem_plan_begin(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
+static int plan_begin_impl(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
 {
     if (!h || !state) return CEM_ERR_INVALID_ARG;
     if (h->batch) return CEM_ERR_STATE;                  // a batch handle plans through cem_planner_plan_batch only
     if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
     if ((eps_act_dev == nullptr) != (eps_model_dev == nullptr) && h->cfg.sampling_propagation) return CEM_ERR_INVALID_ARG;
+    { const int wst = check_warm(h, 1); if (wst) return wst; }
     stage_ctrl(h, state, seed, call);
     h->eps_act = eps_act_dev; h->eps_model = eps_model_dev;
     h->ev_kind.clear();
@@ -1550,7 +1653,7 @@ int cem_plan_select(cem_planner_t *h, int32_t it)
     return enqueue_select(h, it, false);
 }
 
-int cem_plan_end(cem_planner_t *h, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
+static int plan_end_impl(cem_planner_t *h, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
 {
     if (!h) return CEM_ERR_INVALID_ARG;
     if (!h->in_plan) return CEM_ERR_STATE;
@@ -1562,7 +1665,7 @@ int cem_plan_end(cem_planner_t *h, const float *eps_out_host, float *action_out,
     return read_result(h, action_out, best_score_out, iters_out);
 }
 
-int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev,
+static int plan_impl(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev,
                      const float *eps_model_dev, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
 {
     if (!h || !state) return CEM_ERR_INVALID_ARG;
@@ -1573,6 +1676,7 @@ int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64
     const bool graphable = h->cfg.use_graph && !eps_act_dev && !eps_model_dev && !eps_out_host && !h->timing && !h->graph_failed &&
                            (!h->comm || h->plans_since_comm > 0);
     if (h->comm) h->plans_since_comm++;
+    { const int wst = check_warm(h, 1); if (wst) return wst; }
     if (graphable) {
         stage_ctrl(h, state, seed, call);
         if (!h->graph_ready) {
@@ -1590,8 +1694,10 @@ int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64
             if (!st && !final_folded) st = enqueue_end(h, false);
             hipError_t ce = hipStreamEndCapture(h->stream, &h->graph);
             if (!st && ce == hipSuccess) ce = hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0);
-            if (st || ce != hipSuccess) {
-                if (!h->comm) { if (st) return st; HIPCHK(ce); }
+            const bool refuse = h->inject_capture_fail; h->inject_capture_fail = false;      // (test hook, cem_planner_inject_fault kind 2)
+            if (refuse && !st && ce == hipSuccess) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+            if (st || ce != hipSuccess || refuse) {
+                if (!h->comm && !refuse) { if (st) return st; HIPCHK(ce); }
                 // a captured collective is not something every RCCL / runtime pair supports: fall back to eager launches for good
                 (void)hipGetLastError();
                 if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
@@ -1602,11 +1708,12 @@ int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64
         }
         if (h->graph_ready) {
             HIPCHK(hipGraphLaunch(h->gexec, h->stream));
+            warm_handed_over(h);
             { const int ws_ = wait_result(h); if (ws_) return ws_; }
             return read_result(h, action_out, best_score_out, iters_out);
         }
     }
-    int st = cem_plan_begin(h, state, seed, call, eps_act_dev, eps_model_dev); if (st) return st;
+    int st = plan_begin_impl(h, state, seed, call, eps_act_dev, eps_model_dev); if (st) return st;
     const bool fold = folds_reduce(h);                  // the same launches as the captured form
     if (eps_out_host) HIPCHK(hipMemcpyAsync(h->ws + h->lay.eps_out, eps_out_host, h->d.A * 4, hipMemcpyHostToDevice, h->stream));
     bool final_folded = false;
@@ -1620,6 +1727,115 @@ int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->timing) collect_timing(h);
     return read_result(h, action_out, best_score_out, iters_out);
+}
+
+// The public plan calls: the work above, then the carry bookkeeping — whatever a plan whose control data was staged returns decides
+// whether its slots' carries are valid (finish_warm); a call refused before staging leaves them alone.
+int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
+                           const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
+                           float *best_scores_out, int32_t *iters_out)
+{
+    const int st = plan_batch_impl(h, n_states, states, seed, calls, eps_act_dev, eps_model_dev, eps_out_host, actions_out, best_scores_out, iters_out);
+    if (h && h->warm_staged) finish_warm(h, st);
+    return st;
+}
+
+int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev,
+                     const float *eps_model_dev, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
+{
+    const int st = plan_impl(h, state, seed, call, eps_act_dev, eps_model_dev, eps_out_host, action_out, best_score_out, iters_out);
+    if (h && h->warm_staged) finish_warm(h, st);
+    return st;
+}
+
+int cem_plan_begin(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
+{
+    const int st = plan_begin_impl(h, state, seed, call, eps_act_dev, eps_model_dev);
+    if (st && h && h->warm_staged) finish_warm(h, st);           // (a plan that began is settled by its end call)
+    return st;
+}
+
+int cem_plan_end(cem_planner_t *h, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
+{
+    const int st = plan_end_impl(h, eps_out_host, action_out, best_score_out, iters_out);
+    if (h && h->warm_staged && !h->in_plan) finish_warm(h, st);
+    return st;
+}
+
+int cem_planner_set_warm_start(cem_planner_t *h, const cem_warm_start_t *ws)
+{
+    if (!h || !ws) return CEM_ERR_INVALID_ARG;
+    if (ws->shift < 1 || ws->shift >= h->d.H || (ws->tail != 0 && ws->tail != 1) || (ws->sigma_rule != 0 && ws->sigma_rule != 1)) return CEM_ERR_INVALID_ARG;
+    for (int a = 0; a < h->d.A; ++a) if (!finite_bits(ws->sigma_floor[a]) || ws->sigma_floor[a] < 0.f) return CEM_ERR_INVALID_ARG;
+    h->warm = *ws;
+    for (int a = h->d.A; a < CEM_MAX_ACT; ++a) h->warm.sigma_floor[a] = 0.f;
+    return CEM_OK;
+}
+
+int cem_planner_set_initial_distribution(cem_planner_t *h, int32_t slot, const float *mu, const float *sigma)
+{
+    if (!h || !mu || !sigma || slot < 0 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    const size_t HA = (size_t)h->d.H * h->d.A;
+    for (size_t i = 0; i < HA; ++i) if (!finite_bits(mu[i]) || !finite_bits(sigma[i]) || sigma[i] < 0.f) return CEM_ERR_INVALID_ARG;
+    // through a copy the handle owns: a previous plan may still be draining behind its polled result, and the caller's arrays need
+    // not outlive this call
+    float *dst = h->h_expl.data() + (size_t)slot * 2 * HA;
+    std::memcpy(dst, mu, HA * 4); std::memcpy(dst + HA, sigma, HA * 4);
+    HIPCHK(hipMemcpyAsync(h->ws + h->lay.expl + (size_t)slot * 2 * HA * 4, dst, 2 * HA * 4, hipMemcpyHostToDevice, h->stream));
+    h->have_expl[slot] = 1;
+    return CEM_OK;
+}
+
+int cem_planner_set_init_mode(cem_planner_t *h, int32_t slot, int32_t mode)
+{
+    if (!h || slot < -1 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
+    if (mode != CEM_INIT_COLD && mode != CEM_INIT_EXPLICIT && mode != CEM_INIT_SHIFT) return CEM_ERR_INVALID_ARG;
+    for (int s = 0; s < warm_slots(h); ++s) if (slot < 0 || s == slot) h->slot_mode[s] = mode;
+    return CEM_OK;
+}
+
+int cem_planner_reset_carry(cem_planner_t *h, int32_t slot)
+{
+    if (!h || slot < -1 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
+    for (int s = 0; s < warm_slots(h); ++s) if (slot < 0 || s == slot) { h->carry_valid[s] = 0; h->carry_at[s] = -1; }
+    return CEM_OK;
+}
+
+int cem_planner_get_carry(cem_planner_t *h, int32_t slot, float *mu, float *sigma, int32_t *valid)
+{
+    if (!h || slot < 0 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
+    const size_t HA = (size_t)h->d.H * h->d.A;
+    if (h->in_plan) return CEM_ERR_STATE;               // a stepwise plan is open: the slot's slice holds that plan's distribution
+    const bool ok = h->carry_valid[slot] != 0;
+    if (valid) *valid = ok ? 1 : 0;
+    if (!ok) {
+        if (mu) std::memset(mu, 0, HA * 4);
+        if (sigma) std::memset(sigma, 0, HA * 4);
+        return CEM_OK;
+    }
+    // where the carry is right now: still in the mu / sigma slice of the problem that ran it, or already moved to the slot's buffer
+    const char *src = h->carry_at[slot] >= 0 ? h->ws + h->lay.musig + (size_t)h->carry_at[slot] * 2 * HA * 4 : h->ws + h->lay.carry + (size_t)slot * 2 * HA * 4;
+    if (mu) HIPCHK(hipMemcpyAsync(mu, src, HA * 4, hipMemcpyDeviceToHost, h->stream));
+    if (sigma) HIPCHK(hipMemcpyAsync(sigma, src + HA * 4, HA * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CEM_OK;
+}
+
+int cem_planner_set_carry_slots(cem_planner_t *h, int32_t n, const int32_t *slots)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (!h->batch) return CEM_ERR_STATE;
+    if (n < 1 || n > h->batch) return CEM_ERR_INVALID_ARG;
+    std::vector<int32_t> map(h->batch); std::vector<uint8_t> used(h->batch, 0);
+    for (int b = 0; b < n; ++b) {
+        const int32_t s = slots ? slots[b] : b;
+        if (s < 0 || s >= h->batch || used[s]) return CEM_ERR_INVALID_ARG;
+        used[s] = 1; map[b] = s;
+    }
+    for (int b = n, s = 0; b < h->batch; ++b) { while (used[s]) ++s; used[s] = 1; map[b] = s; }   // the rest, ascending: always a permutation
+    h->slot_of.swap(map);
+    return CEM_OK;
 }
 
 int cem_comm_unique_id(void *id_out)
@@ -1848,8 +2064,9 @@ int cem_planner_select_mode(const cem_planner_t *h, int32_t *mode_out)
 
 int cem_planner_inject_fault(cem_planner_t *h, int32_t kind)
 {
-    if (!h || kind != 1) return CEM_ERR_INVALID_ARG;
+    if (!h || (kind != 1 && kind != 2)) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
+    if (kind == 2) { h->inject_capture_fail = true; return CEM_OK; }      // the next capture counts as refused: eager launches for good
     h->inject_next = 1u;            // staged with the next plan's control block (stage_ctrl) and consumed by it
     return CEM_OK;
 }

@@ -1063,8 +1063,23 @@ __global__ __launch_bounds__(256) void cem_rollout_seg_kernel(const RolloutParam
 // ---------------------------------------------------------------------------------------------------------
 // small kernels of the optimiser loop
 // ---------------------------------------------------------------------------------------------------------
+// Warm start (cem_mpc.h: cem_init_mode).  What a plan's first kernel needs to know per problem, staged by the host in pinned memory next
+// to the control blocks (stage_warm) and read by cem_init_kernel alone — so modes, slot maps and parameters change without touching a
+// captured graph.  `mode` is already resolved (SHIFT on an invalid carry arrives as COLD).
+struct WarmProb {
+    int32_t mode;            // cem_init_mode of THIS plan's problem b
+    int32_t slot;            // its carry slot (EXPLICIT: its slice of the explicit buffer)
+    int32_t save_slot;       // the slot whose completed plan still sits in mu / sigma slice b (the PREVIOUS plan's problem b), or -1
+    int32_t pad;
+};
+struct WarmCtl { int32_t shift, tail, sigma_rule, two_phase /* some problem of this plan is in SHIFT mode, i.e. reads a carry */; float sigma_floor[32]; WarmProb prob[1]; /* [max(batch, 1)] */ };
+#define CEM_WARM_LDS_PROBS 256      /* CEM_MAX_BATCH */
+
 struct InitParams { CtrlBlock *ctrl; const CtrlBlock *host_ctrl; float *musig; int32_t HA, A; float mu0[32], sigma0[32]; uint32_t *seg_queue, *seg_flags; int32_t n_ready;
-                    int32_t n_prob;   /* problems of a batched plan: ctrl / host_ctrl are [n_prob] blocks, musig [n_prob][2][HA] (0 = one) */ };
+                    int32_t n_prob;   /* problems of a batched plan: ctrl / host_ctrl are [n_prob] blocks, musig [n_prob][2][HA] (0 = one) */
+                    const WarmCtl *warm;   /* pinned host memory (never null) */
+                    float *carry;          /* [slots][2][HA] */
+                    const float *expl;     /* [slots][2][HA] cem_planner_set_initial_distribution */ };
 
 __global__ void cem_init_kernel(const InitParams p)
 {
@@ -1072,19 +1087,76 @@ __global__ void cem_init_kernel(const InitParams p)
     // the plan's control block (Philox key, observation, cleared best-so-far / flags) as the host staged it in PINNED memory: read
     // from there directly — a copy node of its own in front of every plan cost a 3.6 us blit kernel plus its gap
     const int np = p.n_prob > 1 ? p.n_prob : 1;
+    // (block 0 asks for its warm-start control words FIRST: both reads go to pinned host memory, and issued back to back they cost one
+    // trip over the bus, not two)
+    WarmProb wp0{}; float fl0 = 0.f; int32_t hd0 = 0;
+    if (blockIdx.x == 0) {
+        if ((int)threadIdx.x < np) wp0 = p.warm->prob[threadIdx.x];
+        if (threadIdx.x < 32) fl0 = p.warm->sigma_floor[threadIdx.x];
+        if (threadIdx.x < 4) hd0 = reinterpret_cast<const int32_t *>(p.warm)[threadIdx.x];          // shift, tail, sigma_rule, two_phase
+    }
     if (p.host_ctrl && i < np * (int)(sizeof(CtrlBlock) / 4)) reinterpret_cast<uint32_t *>(p.ctrl)[i] = reinterpret_cast<const uint32_t *>(p.host_ctrl)[i];
     // the rollout launches' work queue starts every plan empty (a launch resets it itself; this covers a plan that ended in a fault)
     if (p.seg_queue) {
         if (i < 3) p.seg_queue[i] = 0u;
         for (int e = i; e < p.n_ready; e += gridDim.x * blockDim.x) p.seg_flags[e] = 0u;
     }
-    if (i < np * p.HA) {                                                                         // cem_mpc.py:39-40
-        const int b = i / p.HA, j = i - b * p.HA;
-        p.musig[(size_t)b * 2 * p.HA + j] = p.mu0[j % p.A]; p.musig[(size_t)b * 2 * p.HA + p.HA + j] = p.sigma0[j % p.A];
-    }
     if (!p.host_ctrl) {                                       // (staged by the host along with the rest of the block otherwise: stage_ctrl)
         if (i < 32) p.ctrl->best[i] = 0.f;                                                     // cem_mpc.py:41
         if (i == 0) { p.ctrl->best_score = -__builtin_inff(); p.ctrl->done = 0; p.ctrl->iters = 0; p.ctrl->fault = 0; }
+    }
+    // The initial distribution of every problem (cem_mpc.py:39-40, or a warm start).  ONE workgroup does it for all problems, in two
+    // phases around a barrier, because the slot map may permute problems between two plans of a batch handle: phase 1 moves what the
+    // previous plan left in mu / sigma slice b to the carry of the slot that ran there (also of slots that sit this plan out, whose slice
+    // is about to be restarted); phase 2 builds slice b from the carry of the slot that runs there NOW.  With one workgroup per problem
+    // the second would read what another workgroup is writing.  The work is np x 2 x H x A copies (120 floats at the shipped shapes).
+    if (blockIdx.x != 0) return;
+    __shared__ WarmProb wp_s[CEM_WARM_LDS_PROBS];
+    __shared__ float floor_s[32];
+    __shared__ int32_t hdr_s[4];
+    if ((int)threadIdx.x < np) wp_s[threadIdx.x] = wp0;                                     // (np <= CEM_WARM_LDS_PROBS = blockDim.x)
+    if (threadIdx.x < 32) floor_s[threadIdx.x] = fl0;
+    if (threadIdx.x < 4) hdr_s[threadIdx.x] = hd0;
+    __syncthreads();
+    const int HA2 = 2 * p.HA, n = np * HA2;
+    if (!hdr_s[3]) {
+        // no problem reads a carry (the usual cold plan): element e's old value goes to its carry and its new one replaces it in the
+        // same thread, in program order — no barrier and no wait for the stores in the middle of the kernel
+        for (int e = threadIdx.x; e < n; e += blockDim.x) {
+            const int b = e / HA2, r = e - b * HA2, sg = r >= p.HA, j = r - sg * p.HA, a = j % p.A, sv = wp_s[b].save_slot;
+            if (sv >= 0) p.carry[(size_t)sv * HA2 + r] = p.musig[e];
+            p.musig[e] = wp_s[b].mode == 1 ? p.expl[(size_t)wp_s[b].slot * HA2 + r] : (sg ? p.sigma0[a] : p.mu0[a]);
+        }
+        return;
+    }
+    for (int e = threadIdx.x; e < n; e += blockDim.x) {
+        const int b = e / HA2, r = e - b * HA2, sv = wp_s[b].save_slot;
+        if (sv >= 0) __hip_atomic_store(p.carry + (size_t)sv * HA2 + r, p.musig[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // phase 2 reads carry words other waves of this workgroup stored: the stores are acknowledged (vmcnt(0); s_barrier alone does not
+    // drain them on gfx940+) before the barrier, and both sides go to the agent-coherent level, past the CU's vector cache
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+    const int s = hdr_s[0], tail = hdr_s[1], rule = hdr_s[2], H = p.HA / p.A;
+    for (int e = threadIdx.x; e < n; e += blockDim.x) {
+        const int b = e / HA2, r = e - b * HA2, sg = r >= p.HA, j = r - sg * p.HA, t = j / p.A, a = j - t * p.A;
+        const int mode = wp_s[b].mode;
+        float v = sg ? p.sigma0[a] : p.mu0[a];                                                   // CEM_INIT_COLD, and every tail but `repeat`
+        if (mode == 1) {
+            v = p.expl[(size_t)wp_s[b].slot * HA2 + r];
+        } else if (mode == 2) {
+            // copies and one max: nothing is rounded.  No clip either: the carried mu is a convex blend of clipped samples (cem_mpc.py:48,64),
+            // so it lies inside the action box already
+            const float *c = p.carry + (size_t)wp_s[b].slot * HA2;
+            if (!sg) {
+                if (t < H - s) v = __hip_atomic_load(c + j + s * p.A, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else if (tail) v = __hip_atomic_load(c + (H - 1) * p.A + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (rule == 1 && t < H - s) {
+                const float cs = __hip_atomic_load(c + p.HA + j + s * p.A, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), fl = floor_s[a];
+                v = cs > fl ? cs : fl;
+            }
+        }
+        p.musig[e] = v;
     }
 }
 

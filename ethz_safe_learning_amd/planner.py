@@ -333,6 +333,53 @@ class CemPlanner:
         """Test hook (cem_planner_inject_fault): the next plan's first fused select sees one of its grid barriers expire."""
         _capi.check(self.lib.cem_planner_inject_fault(self.h, kind), 'cem_planner_inject_fault')
 
+    # ------------------------------------------------------------------ warm start (cem_mpc.h: cem_init_mode; DESIGN.md 4.6)
+    # The handle keeps, per slot, the mu / sigma its last completed plan ended with (the carry).  A slot's next plan starts from the
+    # action box ('cold': the reference's behaviour and the default), from arrays the caller uploaded ('explicit') or from the carry
+    # shifted towards the present ('shift'; cold while the carry is invalid).  A single-state handle has one slot, 0.
+    # The carry lives on the HANDLE: two users of one handle (cached_planner) would continue each other's plans, so anything that
+    # warm-starts must own its handle (owner= of cached_planner / cached_batch_planner).
+    INIT_MODES = {'cold': _capi.CEM_INIT_COLD, 'explicit': _capi.CEM_INIT_EXPLICIT, 'shift': _capi.CEM_INIT_SHIFT}
+
+    def n_slots(self):
+        return getattr(self, 'max_batch', 1)
+
+    def set_warm_start(self, shift=1, tail='box', sigma='reset', floor_frac=0.0):
+        """Parameters of the 'shift' mode: mu moves `shift` steps; the freed tail takes the box centre ('box') or repeats the last step
+        ('repeat'); sigma restarts from the box ('reset', PETS) or is kept, floored at fl32(floor_frac * sigma0) per dimension ('keep')."""
+        tails, rules = {'box': 0, 'repeat': 1}, {'reset': 0, 'keep': 1}
+        if tail not in tails or sigma not in rules:
+            raise ValueError("tail is 'box' or 'repeat', sigma is 'reset' or 'keep'")
+        ws = _capi.CemWarmStart(shift=int(shift), tail=tails[tail], sigma_rule=rules[sigma])
+        ws.sigma_floor[:self.cfg.act_dim] = warm_sigma_floor(self.cfg, floor_frac).tolist()
+        _capi.check(self.lib.cem_planner_set_warm_start(self.h, C.byref(ws)), 'cem_planner_set_warm_start')
+
+    def set_initial_distribution(self, mu, sigma, slot=0):
+        """mu[H, A], sigma[H, A] of the 'explicit' mode for `slot` (the mode itself is set by set_init_mode)."""
+        c = self.cfg
+        m = np.ascontiguousarray(np.asarray(mu, np.float32))
+        s = np.ascontiguousarray(np.asarray(sigma, np.float32))
+        if m.shape != (c.horizon, c.act_dim) or s.shape != (c.horizon, c.act_dim):
+            raise ValueError('mu and sigma must have shape [%d, %d]' % (c.horizon, c.act_dim))
+        _capi.check(self.lib.cem_planner_set_initial_distribution(self.h, int(slot), _np_ptr(m), _np_ptr(s)), 'cem_planner_set_initial_distribution')
+
+    def set_init_mode(self, mode, slot=0):
+        """'cold' | 'explicit' | 'shift' (or the enum value) for `slot` (None: every slot); sticky until changed."""
+        m = self.INIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        _capi.check(self.lib.cem_planner_set_init_mode(self.h, -1 if slot is None else int(slot), m), 'cem_planner_set_init_mode')
+
+    def reset_carry(self, slot=None):
+        """Forget the carry of `slot` (None: of every slot): its next 'shift' plan starts cold."""
+        _capi.check(self.lib.cem_planner_reset_carry(self.h, -1 if slot is None else int(slot)), 'cem_planner_reset_carry')
+
+    def carry(self, slot=0):
+        """(mu[H, A], sigma[H, A], valid) of the slot's last completed plan; zeros while invalid.  Waits for the planner's stream."""
+        c = self.cfg
+        m, s = np.zeros((c.horizon, c.act_dim), np.float32), np.zeros((c.horizon, c.act_dim), np.float32)
+        v = C.c_int32()
+        _capi.check(self.lib.cem_planner_get_carry(self.h, int(slot), _np_ptr(m), _np_ptr(s), C.byref(v)), 'cem_planner_get_carry')
+        return m, s, bool(v.value)
+
     # ------------------------------------------------------------------ planning
     def _noise_args(self, eps_act, eps_model):
         c = self.cfg
@@ -575,9 +622,23 @@ class BatchCemPlanner(CemPlanner):
             raise ValueError('eps_model must be [B,I,H,P*N,O]')
         return ea, em
 
-    def plan_batch(self, states, seed=0, calls=None, eps_act=None, eps_model=None, eps_out=None):
+    def set_carry_slots(self, slots=None):
+        """Problem b of the following plan_batch calls reads and writes carry slot slots[b] (distinct, in [0, max_batch)); None: b."""
+        if slots is None:
+            _capi.check(self.lib.cem_planner_set_carry_slots(self.h, self.max_batch, None), 'cem_planner_set_carry_slots')
+            return
+        sl = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        _capi.check(self.lib.cem_planner_set_carry_slots(self.h, sl.size, _np_ptr(sl)), 'cem_planner_set_carry_slots')
+
+    def plan_batch(self, states, seed=0, calls=None, eps_act=None, eps_model=None, eps_out=None, slots=None):
         """CemMpc.generate_action for every row of states[B, O] in ONE plan call -> (actions[B, A], scores[B], iters[B]).
-        calls=None draws B consecutive call numbers from the handle's counter."""
+        calls=None draws B consecutive call numbers from the handle's counter.  slots[B] (warm start): the carry slot of every row,
+        e.g. its environment's index when the rows are a compacted subset; the map stays for later calls; None leaves it as it is
+        (initially row b -> slot b)."""
+        if slots is not None:
+            if np.size(slots) != np.shape(states)[0]:
+                raise ValueError('slots must have one entry per row of states')
+            self.set_carry_slots(slots)
         st = np.asarray(states)
         if st.ndim != 2 or st.shape[1] != self.cfg.obs_dim:
             raise ValueError('states must have shape [B, %d]' % self.cfg.obs_dim)
@@ -610,6 +671,28 @@ class BatchCemPlanner(CemPlanner):
             _capi.check(self.lib.cem_planner_plan_batch(self.h, n, sp, seed, cp, _ptr(ea), _ptr(em), _np_ptr(eo), ap, scp, ip),
                         'cem_planner_plan_batch')
         return self._acts_buf[:n].copy(), self._scores_buf[:n].copy(), self._iters_buf[:n].copy()
+
+
+def warm_sigma_floor(cfg: PlannerConfig, floor_frac) -> np.ndarray:
+    """sigma_floor[A] of cem_warm_start_t: fl32(fl32(floor_frac) * sigma0), sigma0 as the handle's configuration carries it."""
+    sigma0 = sampling_params(cfg.act_low, cfg.act_high)[3]
+    return (np.float32(floor_frac) * np.asarray(sigma0, np.float32)).astype(np.float32)
+
+
+def shift_distribution(mu, sigma, mu0, sigma0, shift=1, tail=0, sigma_rule=0, sigma_floor=None):
+    """Host restatement of CEM_INIT_SHIFT (cem_mpc.h) — copies and one max, so it is exact: (mu_init, sigma_init) [H, A] from a carry."""
+    mu, sigma = np.asarray(mu, np.float32), np.asarray(sigma, np.float32)
+    H = mu.shape[0]
+    if not 1 <= shift < H:
+        raise ValueError('shift must lie in 1 .. H - 1')
+    m = np.broadcast_to(np.asarray(mu0, np.float32), mu.shape).copy()
+    s = np.broadcast_to(np.asarray(sigma0, np.float32), mu.shape).copy()
+    m[:H - shift] = mu[shift:]
+    if tail:
+        m[H - shift:] = mu[H - 1]
+    if sigma_rule:
+        s[:H - shift] = np.maximum(sigma[shift:], np.asarray(sigma_floor, np.float32))
+    return m, s
 
 
 def plan_tiles(cfg: PlannerConfig):
@@ -663,8 +746,10 @@ def config_key(cfg: PlannerConfig, device='cuda:0'):
     return (str(device),) + _freeze(cfg)
 
 
-def cached_planner(cfg: PlannerConfig, device='cuda:0') -> CemPlanner:
-    key = config_key(cfg, device)
+def cached_planner(cfg: PlannerConfig, device='cuda:0', owner=None) -> CemPlanner:
+    """owner: an object that warm-starts its plans gets a handle of its OWN (the carry lives on the handle, and two users of one handle
+    would continue each other's plans): its id joins the key.  None: the handle is shared by everything of this shape."""
+    key = config_key(cfg, device) + ((('owner', id(owner)),) if owner is not None else ())
     pl = _PLANNER_CACHE.pop(key, None)
     if pl is None:
         pl = CemPlanner(cfg, device=device)
@@ -677,9 +762,9 @@ def cached_planner(cfg: PlannerConfig, device='cuda:0') -> CemPlanner:
     return pl
 
 
-def cached_batch_planner(cfg: PlannerConfig, max_batch: int, device='cuda:0') -> BatchCemPlanner:
+def cached_batch_planner(cfg: PlannerConfig, max_batch: int, device='cuda:0', owner=None) -> BatchCemPlanner:
     """cached_planner for batch handles: the same key plus max_batch (its own LRU entries in the same cache)."""
-    key = config_key(cfg, device) + (('max_batch', int(max_batch)),)
+    key = config_key(cfg, device) + (('max_batch', int(max_batch)),) + ((('owner', id(owner)),) if owner is not None else ())
     pl = _PLANNER_CACHE.pop(key, None)
     if pl is None:
         pl = BatchCemPlanner(cfg, int(max_batch), device=device)

@@ -65,6 +65,8 @@ class BaseAgent(object):
         steps are summed into one transition; the hold is cut short when the goal is met or the episode ends
         (agent.py:119-143)."""
         observation = environment.reset()
+        if callable(getattr(policy, 'reset', None)):
+            policy.reset()                               # a policy that carries state between decisions (warm-started CEM) starts over
         rec = dict(o=[], a=[], r=[], o2=[], d=[], info=[])
         steps, over = 0, False
         while not over:
@@ -97,6 +99,10 @@ class BaseAgent(object):
         the records ordered by environment, then episode — with one environment, exactly sample_trajectories' records."""
         envs = list(environments)
         batched = getattr(policy, 'generate_actions', None)
+        # a policy that carries state per environment (warm-started CEM) is told which environment every row belongs to — the rows are
+        # compacted as episodes end — and which rows begin an episode.  Policies without that interface are called as before.
+        with_slots = batched is not None and getattr(policy, 'accepts_slots', False)
+        fresh = [False] * len(envs)
         recs = [None] * len(envs)
         obs = [None] * len(envs)
         ep_steps = [0] * len(envs)
@@ -108,16 +114,21 @@ class BaseAgent(object):
             obs[i] = envs[i].reset()
             recs[i] = dict(o=[], a=[], r=[], o2=[], d=[], info=[])
             ep_steps[i] = 0
+            fresh[i] = True
 
         active = list(range(len(envs)))
         for i in active:
             start(i)
         while active:
             batch_obs = [obs[i] for i in active]
-            if batched is not None:
+            if with_slots:
+                actions = batched(np.stack(batch_obs), slots=np.array(active, np.int32), reset=np.array([fresh[i] for i in active], bool))
+            elif batched is not None:
                 actions = batched(np.stack(batch_obs))
             else:
                 actions = [policy.generate_action(o) for o in batch_obs]
+            for i in active:
+                fresh[i] = False
             still = []
             for i, action in zip(active, actions):
                 env, rec = envs[i], recs[i]

@@ -4,7 +4,17 @@ Same constructor kwargs (cem_mpc.py:7-17), same ``generate_action(state) -> np.f
 (cem_mpc.py:31-33; caller simba/agents/agent.py:120).  One ``CemPlanner`` handle corresponds to the reference's one
 traced ``@tf.function`` graph; it is built lazily on the first call and rebuilt never (a shape change is a new
 policy object, as in scripts/tune_cem_policy.py:109-115).  Weights / normaliser are re-staged whenever the model's
-``version`` changed (after ``fit``: mbrl_agent.py:53)."""
+``version`` changed (after ``fit``: mbrl_agent.py:53).
+
+Warm start (beyond the reference, off by default): with ``warm_start=True`` every plan starts from the previous plan's distribution
+shifted ``warm_shift`` steps (planner.CemPlanner.set_warm_start) instead of the action box; ``reset()`` — called by the agent at every
+episode start — makes the next plan a cold one again.  The carry lives on the planner handle, and handles are shared between policy
+objects of one shape; a warm-started policy therefore gets handles of its OWN (``owner=`` of cached_planner / cached_batch_planner),
+so two policies of one shape never continue each other's plans.
+A warm-started policy also numbers its plans per ENVIRONMENT: the Philox call number of environment e's d-th decision is
+``e * 2**32 + d``, whether the decision is planned alone (``generate_action``, environment ``self.slot``, 0 by default) or as a row of
+``generate_actions(..., slots=)`` — so an environment sees the same plans however it is batched with others."""
+import logging
 import numpy as np
 
 from ...planner import PlannerConfig, cached_batch_planner, cached_planner
@@ -15,7 +25,8 @@ class CemMpc(MpcPolicy):
     variant = 'cem'
 
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
-                 stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32'):
+                 stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
+                 warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -26,6 +37,12 @@ class CemMpc(MpcPolicy):
         self.device = device
         self.use_graph = use_graph
         self.precision = precision                     # 'fp32' | 'bf16x3' (PlannerConfig.precision; beyond the reference's kwargs)
+        # warm start (beyond the reference's kwargs, like precision): see the module docstring
+        self.warm_start, self.warm_shift, self.warm_tail, self.warm_sigma, self.warm_sigma_floor = bool(warm_start), warm_shift, warm_tail, warm_sigma, warm_sigma_floor
+        self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
+        self._warm_cap = 1                             # slots the warm-started batch handle must hold
+        self.slot = 0                                  # the environment generate_action plans for (warm start: its call numbers)
+        self._decisions = {}                           # environment -> decisions planned so far (warm start: call numbering)
         self._planner = None
         self._batch_planners = {}                      # capacity (a power of two) -> batch handle (generate_actions)
         self.last_score = None
@@ -58,7 +75,7 @@ class CemMpc(MpcPolicy):
     def build(self):
         if self._planner is None or self._planner.h is None:      # never built, or closed by its owner
             # one handle per distinct shape, shared by every policy object of that shape (tune_cem_policy.py:109-115)
-            self._planner = cached_planner(self.planner_config(), device=self.device)
+            self._planner = self._own(cached_planner(self.planner_config(), device=self.device, owner=self if self.warm_start else None))
         self._sync_model()
 
     def _sync_model(self, planner=None):
@@ -69,29 +86,81 @@ class CemMpc(MpcPolicy):
             planner.set_normaliser(self.model.inputs_min, self.model.inputs_max)
             planner.staged = tag
 
+    def _own(self, planner):
+        """A handle fresh from the cache: with warm start on, make it this policy's (shift mode on every slot, no carry)."""
+        if self.warm_start and getattr(planner, 'warm_owner', None) is not self._warm_token:
+            planner.set_warm_start(shift=self.warm_shift, tail=self.warm_tail, sigma=self.warm_sigma, floor_frac=self.warm_sigma_floor)
+            planner.set_init_mode('shift', slot=None)
+            planner.reset_carry()
+            planner.warm_owner = self._warm_token
+        return planner
+
+    def reset(self):
+        """An episode begins: the next plan of every slot starts cold (no effect without warm start)."""
+        if not self.warm_start:
+            return
+        for pl in [self._planner] + list(self._batch_planners.values()):
+            if pl is not None and pl.h is not None:
+                pl.reset_carry()
+
     def build_batch(self, n):
         """The batch handle for n observations: capacity n rounded up to a power of two (one cached handle, hence one captured
         graph, per capacity), with the current model version's weights / normaliser staged."""
+        if self.warm_start:
+            # ONE handle holds every environment's carry: its capacity never shrinks with the number of rows (a larger one starts cold)
+            n = self._warm_cap = max(int(n), self._warm_cap)
+            grown = [c for c in self._batch_planners if c < (1 << max(n - 1, 0).bit_length())]
+            for c in grown:                            # more environments than the handle in use holds: a larger one takes over, cold
+                logging.getLogger(__name__).warning('warm start: %d environments exceed the batch handle of %d slots; a larger handle '
+                                                    'takes over and every environment\'s next plan starts cold', n, c)
+                del self._batch_planners[c]
         cap = 1 << max(int(n) - 1, 0).bit_length()
         pl = self._batch_planners.get(cap)
         if pl is None or pl.h is None:
-            pl = self._batch_planners[cap] = cached_batch_planner(self.planner_config(), cap, device=self.device)
+            pl = self._batch_planners[cap] = self._own(cached_batch_planner(self.planner_config(), cap, device=self.device,
+                                                                            owner=self if self.warm_start else None))
         self._sync_model(pl)
         return pl
 
     # ---- the plugin boundary ------------------------------------------------------------------------------------
     def generate_action(self, state):
         self.build()                                   # cached handle + weights of the current model version
-        action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed)
+        action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed,
+                                                  call=self._next_calls([self.slot])[0] if self.warm_start else None)
         self.last_score, self.last_iterations = score, iters
         return action
 
-    def generate_actions(self, states):
+    def _next_calls(self, slots):
+        """Call numbers of the next decision of every environment in `slots` (module docstring), counted."""
+        out = []
+        for e in slots:
+            d = self._decisions.get(int(e), 0)
+            self._decisions[int(e)] = d + 1
+            out.append((int(e) << 32) + d)
+        return out
+
+    accepts_slots = True                               # generate_actions takes slots / reset (BaseAgent.sample_trajectories_lockstep)
+
+    def generate_actions(self, states, slots=None, reset=None):
         """generate_action for every row of states[B, O] in ONE batched plan -> np.float32[B, A]: row b is what generate_action
-        returns for states[b] with the same call number (BatchCemPlanner.plan_batch).  Sets last_scores / last_iterations (arrays)."""
+        returns for states[b] with the same call number (BatchCemPlanner.plan_batch).  Sets last_scores / last_iterations (arrays).
+        Warm start: slots[B] is the environment index of every row (distinct; default: the row index) — row b continues the plans of
+        ITS environment whichever rows the call holds — and reset[B] marks rows whose environment begins an episode (they plan cold).
+        Both are ignored without warm start."""
         st = np.asarray(states, np.float32)
         if st.ndim != 2:
             raise ValueError('states must be [B, obs_dim]')
+        if self.warm_start:
+            sl = np.arange(st.shape[0], dtype=np.int32) if slots is None else np.asarray(slots, np.int32).reshape(-1)
+            if sl.shape != (st.shape[0],):
+                raise ValueError('slots must have one entry per row of states')
+            pl = self.build_batch(max(st.shape[0], int(sl.max()) + 1))
+            if reset is not None:
+                for s in sl[np.asarray(reset, bool).reshape(-1)]:
+                    pl.reset_carry(int(s))
+            actions, scores, iters = pl.plan_batch(st, seed=self.seed, slots=sl, calls=np.array(self._next_calls(sl), np.uint64))
+            self.last_scores, self.last_iterations = scores, iters
+            return actions
         pl = self.build_batch(st.shape[0])
         actions, scores, iters = pl.plan_batch(st, seed=self.seed)
         self.last_scores, self.last_iterations = scores, iters

@@ -244,7 +244,9 @@ int cem_plan_exchange(cem_planner_t *h);
 int cem_planner_select_mode(const cem_planner_t *h, int32_t *mode_out);
 /* Test hook.  kind 1: in the NEXT plan's first iteration, the last workgroup of the fused select treats its first grid barrier as
  * expired (as if its peers were not resident) — the recovery path then runs without having to load the GPU.  No effect on plans
- * whose select is not fused. */
+ * whose select is not fused.
+ * kind 2: the next hipGraph capture cem_planner_plan attempts on this handle counts as refused by the runtime — the path a communicator
+ * takes on a stack without captured collectives: that plan and all later ones launch kernel by kernel (graph_status 2), same results. */
 int cem_planner_inject_fault(cem_planner_t *h, int32_t kind);
 /* 0: cem_planner_plan launches kernel by kernel; 1: it replays a captured hipGraph; 2: capturing was tried and is not supported
  * with this communicator / runtime (the plan then stays kernel by kernel — same results) */
@@ -339,6 +341,51 @@ int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *stat
                            const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
                            float *best_scores_out, int32_t *iters_out);
 int cem_planner_batch_capacity(const cem_planner_t *h, int32_t *max_batch_out);          /* max_batch; 0 for a single-state handle */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Warm start: where a plan's initial mu / sigma [H][A] come from.  Additive: a handle on which none of
+ * these is called plans bit for bit as before (CEM_INIT_COLD, the reference's behaviour: cem_mpc.py:39-40).
+ *
+ * Every handle keeps a CARRY per slot: mu and sigma [H][A] as the slot's last completed plan left them (after the refit of
+ * the last iteration it ran, early stop included) and a valid flag.  A single-state handle has one slot, 0; a batch handle
+ * has max_batch slots.  A plan that returns anything but CEM_OK, and cem_planner_reset_carry, make the carry invalid;
+ * set_weights / set_normaliser keep it.  The carry becomes valid when the plan call returns CEM_OK (stepwise: at the end call).
+ * The model ops (unfold_sequences, compute_objective, the scorer ops) neither read nor change it.
+ *
+ * The next plan of a slot starts from (mode is sticky per slot until changed):
+ *   CEM_INIT_COLD      act_mu0[a], act_sigma0[a] at every step
+ *   CEM_INIT_EXPLICIT  the [H][A] arrays uploaded for the slot (none uploaded: CEM_ERR_STATE from the plan call)
+ *   CEM_INIT_SHIFT     the carry moved `shift` = s steps towards the present; exactly COLD while the carry is invalid
+ *       mu[t]    = carry_mu[t + s]                               t <  H - s
+ *                = act_mu0 (tail 0)  or  carry_mu[H - 1] (tail 1) t >= H - s
+ *       sigma[t] = act_sigma0                                     sigma_rule 0 (reset), every t
+ *                = max(carry_sigma[t + s], sigma_floor[a])        sigma_rule 1 (keep), t <  H - s;  act_sigma0 for t >= H - s
+ * Every operation is a copy or a max of two fp32 values: nothing is rounded, a host restatement is exact.
+ * All of it happens in the plan's first kernel, from control data staged in pinned memory: changing a mode, the slot map,
+ * n_states or the warm-start parameters never re-captures the handle's graph. */
+enum cem_init_mode { CEM_INIT_COLD = 0, CEM_INIT_EXPLICIT = 1, CEM_INIT_SHIFT = 2 };
+typedef struct cem_warm_start {
+    int32_t shift;                   /* 1 .. horizon - 1 */
+    int32_t tail;                    /* 0: the box's act_mu0; 1: repeat the carry's last step */
+    int32_t sigma_rule;              /* 0: reset to act_sigma0; 1: keep, floored */
+    float sigma_floor[CEM_MAX_ACT];  /* per action dimension, >= 0 and finite (read by sigma_rule 1 only) */
+} cem_warm_start_t;
+/* parameters of CEM_INIT_SHIFT (default: shift 1, tail 0, sigma_rule 0).  CEM_ERR_INVALID_ARG for a shift outside 1 .. H - 1, a tail or
+ * sigma_rule other than 0 / 1, a negative or non-finite floor; the handle keeps its previous parameters and stays usable. */
+int cem_planner_set_warm_start(cem_planner_t *h, const cem_warm_start_t *ws);
+/* mu[H][A], sigma[H][A] (host) of CEM_INIT_EXPLICIT for `slot`: a stream-ordered copy in front of the next plan.  CEM_ERR_INVALID_ARG
+ * for a slot out of range, a non-finite value or a negative sigma (nothing is uploaded then).  Does not change the slot's mode. */
+int cem_planner_set_initial_distribution(cem_planner_t *h, int32_t slot, const float *mu, const float *sigma);
+int cem_planner_set_init_mode(cem_planner_t *h, int32_t slot, int32_t mode);             /* slot -1: every slot */
+int cem_planner_reset_carry(cem_planner_t *h, int32_t slot);                             /* slot -1: every slot */
+/* the slot's carry to host mu[H][A], sigma[H][A] (either may be NULL) and its valid flag (arrays are zero filled while invalid);
+ * waits for the handle's stream; CEM_ERR_STATE between the begin and end calls of a stepwise plan */
+int cem_planner_get_carry(cem_planner_t *h, int32_t slot, float *mu, float *sigma, int32_t *valid);
+/* Batch handles only (CEM_ERR_STATE otherwise): in the following cem_planner_plan_batch calls problem b reads and writes carry slot slots[b]
+ * (default, and slots NULL: b); problems n .. max_batch - 1 take the remaining slots in ascending order.  n is 1 .. max_batch; slots must be
+ * distinct and in 0 .. max_batch - 1, else CEM_ERR_INVALID_ARG (the previous map stays).  A slot that takes no part in a call (its problem
+ * index is >= that call's n_states) keeps its carry and its mode. */
+int cem_planner_set_carry_slots(cem_planner_t *h, int32_t n, const int32_t *slots);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step

@@ -28,12 +28,16 @@ PROPOSALS_WITH_ITERATIONS = [(100, 15), (150, 10), (300, 5)]
 ELITE_RATIOS = [0.05, 0.1, 0.2]
 
 
+WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor')
+
+
 def make_new_policy(model, environment, horizon, iterations, n_samples, elite_ratio, policy_kwargs):
     from ethz_safe_learning_amd.simba.policies import CemMpc
     return CemMpc(model=model, environment=environment, horizon=horizon, iterations=iterations, n_samples=n_samples,
                   n_elite=round(elite_ratio * n_samples), particles=policy_kwargs['particles'],
                   stddev_threshold=policy_kwargs['stddev_threshold'], noise_stddev=policy_kwargs['noise_stddev'],
-                  smoothing=policy_kwargs['smoothing'], seed=policy_kwargs.get('seed', 0))
+                  smoothing=policy_kwargs['smoothing'], seed=policy_kwargs.get('seed', 0),
+                  **{k: policy_kwargs[k] for k in WARM_KWARGS if k in policy_kwargs})      # (--warm_start, or the user's own config)
 
 
 def make_parallel_environments(params, k, seed):
@@ -91,6 +95,8 @@ def main(argv=None):
     ap.add_argument('--quick', action='store_true', help='2 x 2 x 2 corner of the grid (tests)')
     ap.add_argument('--parallel_episodes', type=int, default=1,
                     help='K > 1: evaluate on K environments of distinct seeds in lockstep, one batched plan per decision')
+    ap.add_argument('--warm_start', action='store_true',
+                    help="every grid point's policy warm-starts its plans (CemMpc(warm_start=True, warm_sigma='keep')): run the search both ways")
     args = ap.parse_args(argv)
     if args.parallel_episodes < 1:
         ap.error('--parallel_episodes must be at least 1')
@@ -99,6 +105,8 @@ def main(argv=None):
     trainer = train_script.main(['--config_dir', args.config_dir, '--config_basename', args.config_basename, '--log_dir', args.log_dir,
                                  '--name', args.name, '--seed', str(args.seed), '--log_level', args.log_level,
                                  '--cuda_device', args.cuda_device])
+    if args.warm_start:
+        params['policies']['cem_mpc'] = dict(params['policies']['cem_mpc'], warm_start=True, warm_sigma='keep')
     grid = dict(horizons=HORIZONS[:2], proposals_with_iterations=PROPOSALS_WITH_ITERATIONS[1:], elite_ratios=ELITE_RATIOS[:2]) if args.quick else {}
     if args.parallel_episodes > 1:
         grid['parallel_envs'] = make_parallel_environments(params, args.parallel_episodes, args.seed)

@@ -21,6 +21,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 static thread_local int g_last_hip = 0;
@@ -113,7 +114,7 @@ Dims make_dims(const cem_config_t *c)
     d.Nloc = d.N / d.W; d.n_off = d.R * d.Nloc; d.Bloc = d.P * d.Nloc; d.Btot = d.P * d.N;
     d.KB_in = (d.Din + 15) / 16; d.KB_obs = (d.O + 15) / 16; d.NFW = (d.KB_in + 3) / 4; d.KF0 = 4 * d.NFW;
     d.act_q0 = d.O / 4; d.act_nq = (d.Din + 3) / 4 - d.act_q0;
-    d.wide = d.U > CEM_U || c->activation != CEM_ACT_RELU || std::getenv("CEM_FORCE_GENERIC_ROLLOUT") != nullptr;   // (the variable: a diagnostic, scripts/sweep_configs.py)   // the tuned kernels: units <= 128 and relu; everything else takes the generic rollout kernel
+    d.wide = d.U > CEM_U || c->activation != CEM_ACT_RELU || std::getenv("CEM_FORCE_GENERIC_ROLLOUT") != nullptr;   // (the variable: a diagnostic, scripts/sweep_configs.py)
     d.split = !d.wide && c->precision == CEM_PRECISION_SPLIT_BF16X3;
     uint32_t off = 0;
     for (int w = 0; w < 4; ++w) {
@@ -315,6 +316,18 @@ void build_plan_tiles(const Dims &d, int rc, std::vector<Tile6> &out)
 // prologue: 153/161/189/222, 167/219/243/293 and 157/163/190/223, 172/222/255/294), [form][nfw - 1][rc - 1]
 static const int kResidentStatic[2][2][4] = {{{4, 3, 2, 2}, {3, 2, 2, 1}}, {{3, 3, 2, 2}, {3, 2, 2, 1}}};
 
+// The tuned rollout kernels exist for <chunks per tile 1 .. 4, input blocks per wave 1 .. 2>.  The one place a run-time (rc, nfw) picks
+// the instantiation: fn(std::integral_constant<int, rc>, std::integral_constant<int, nfw>), or `none` for a pair outside the table.
+template <class Ret, class Fn>
+Ret with_tile_shape(int rc, int nfw, Ret none, Fn fn)
+{
+#define CEM_CASE(R, F) if (rc == R && nfw == F) return fn(std::integral_constant<int, R>{}, std::integral_constant<int, F>{});
+    CEM_CASE(1, 1) CEM_CASE(2, 1) CEM_CASE(3, 1) CEM_CASE(4, 1)
+    CEM_CASE(1, 2) CEM_CASE(2, 2) CEM_CASE(3, 2) CEM_CASE(4, 2)
+#undef CEM_CASE
+    return none;
+}
+
 template <int RC, int NFW>
 int query_resident(bool seg)
 {
@@ -342,13 +355,7 @@ const DeviceFacts &device_facts()
         for (int seg = 0; seg < 2; ++seg)
             for (int nfw = 1; nfw <= 2; ++nfw)
                 for (int rc = 1; rc <= 4; ++rc) {
-                    int n = 0;
-                    if (have) {
-#define CEM_CASE(R, F) if (rc == R && nfw == F) n = query_resident<R, F>(seg != 0);
-                        CEM_CASE(1, 1) CEM_CASE(2, 1) CEM_CASE(3, 1) CEM_CASE(4, 1)
-                        CEM_CASE(1, 2) CEM_CASE(2, 2) CEM_CASE(3, 2) CEM_CASE(4, 2)
-#undef CEM_CASE
-                    }
+                    const int n = have ? with_tile_shape(rc, nfw, 0, [&](auto R, auto F) { return query_resident<R(), F()>(seg != 0); }) : 0;
                     f.resident[seg][nfw - 1][rc - 1] = n > 0 ? n : kResidentStatic[seg][nfw - 1][rc - 1];
                 }
         f.cus = 256;                                // MI355X; a partitioned or different device reports its own count
@@ -426,12 +433,13 @@ double tile_plan_cost(const Dims &d, int rc, size_t n_tiles, int requested_segme
     return cu_cost(d.NFW, rc, per_cu, resident_workgroups(d.NFW, rc, false), per_cu > 0 ? L / (double)per_cu : 1.0);
 }
 
-int auto_chunks(const Dims &d, int requested_segments)
+// problems > 1: a batch handle's launch carries that many problems' tiles, and is priced for all of them
+int auto_chunks(const Dims &d, int requested_segments, int problems = 1)
 {
     int best = 1; double bestc = 1e30;
     for (int rc = 1; rc <= 4; ++rc) {
         std::vector<Tile6> t; build_plan_tiles(d, rc, t);
-        const double cost = tile_plan_cost(d, rc, t.size(), requested_segments);
+        const double cost = tile_plan_cost(d, rc, (size_t)problems * t.size(), requested_segments);
         // rc ascends: a cost within 0.5 % of the best so far goes to the larger tile (fewer workgroups, less weight traffic)
         if (cost <= bestc * 1.005) { best = rc; bestc = std::min(bestc, cost); }
     }
@@ -470,15 +478,19 @@ struct Layout {
 
 struct Plan { int rc, n_tiles, n_seg, seg_len, n_pinned; };
 
-// tile size, tile count and horizon segments of a configuration: one function, so workspace_bytes / create / the host helpers agree
-Plan make_plan(const cem_config_t *c, const Dims &d)
+// tile size, tile count and horizon segments of a configuration: one function, so workspace_bytes / create / the host helpers agree.
+// mb > 0: the plan of a batch handle of mb problems (validate_batch: fp32 products on the tuned kernel) — the same tile-size rule priced
+// for ALL mb problems' tiles in one launch (the results do not depend on the tile size), one workgroup per tile for the whole horizon (no
+// floating segments: the work queue is per launch, not per problem; bit-identical either way).  n_tiles stays the count of ONE problem.
+Plan make_plan(const cem_config_t *c, const Dims &d, int mb = 0)
 {
     Plan pl{};
-    pl.rc = d.wide ? 1 : (c->chunks_per_tile ? c->chunks_per_tile : auto_chunks(d, c->rollout_segments));   // the wide kernel: 16-row tiles
+    const int seg_req = mb > 0 ? 1 : c->rollout_segments;
+    pl.rc = d.wide ? 1 : (c->chunks_per_tile ? c->chunks_per_tile : auto_chunks(d, seg_req, std::max(mb, 1)));   // the wide kernel: 16-row tiles
     if (d.split && !c->chunks_per_tile) pl.rc = auto_chunks_split(d);
     std::vector<Tile6> t; build_plan_tiles(d, pl.rc, t);
     pl.n_tiles = (int)t.size();
-    pl.n_seg = (d.wide || d.split) ? 1 : segments_for(d, pl.rc, t.size(), c->rollout_segments);
+    pl.n_seg = (d.wide || d.split) ? 1 : segments_for(d, pl.rc, t.size(), seg_req);
     pl.seg_len = (d.H + pl.n_seg - 1) / pl.n_seg;
     pl.n_seg = (d.H + pl.seg_len - 1) / pl.seg_len;
     // tiles every CU gets the same number of stay whole ("pinned"); only the remainder floats in segments
@@ -517,6 +529,8 @@ Layout make_layout(const cem_config_t *c, const Dims &d, size_t max_tiles, int m
     l.tiles = take(max_tiles * sizeof(TileDesc));
     l.eps_out = take(nb * CEM_MAX_ACT * 4);
     l.stamps = take(std::max<size_t>(max_tiles * 4 * 8, 128) * sizeof(long long));      // [tiles][4][8] rollout stamps; [64..71] select stamps
+    // the SINGLE plan, for a batch handle too (which never floats a tile and would get the two minimum sizes): the size of these two
+    // arrays decides every later offset, and batch workspaces keep the offsets they were introduced with
     const Plan pl = make_plan(c, d);
     l.seg_queue = take(256);
     const size_t n_float = (size_t)(pl.n_tiles - pl.n_pinned);
@@ -550,26 +564,6 @@ int validate_batch(const cem_config_t *c, int32_t mb)
     if (resolve_select_mode(c->select_mode, d.N, d.k, (long long)d.H * d.A, 140 * 1024, true, nullptr) != 1) return CEM_ERR_UNSUPPORTED;
     if ((long long)mb * (long long)max_tiles_of(d) > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;   // the rollout grid: problems x tiles
     return CEM_OK;
-}
-
-// The tile plan of a batch handle: the single plan's tile-size rule priced for ALL mb problems' tiles in one launch (the results do not
-// depend on the tile size), one workgroup per tile for the whole horizon (no floating segments: the work queue is per launch, not per
-// problem; bit-identical either way).
-Plan make_plan_batch(const cem_config_t *c, const Dims &d, int mb)
-{
-    Plan pl{};
-    pl.rc = c->chunks_per_tile;
-    if (!pl.rc) {
-        double bestc = 1e30; pl.rc = 1;
-        for (int rc = 1; rc <= 4; ++rc) {
-            std::vector<Tile6> t; build_plan_tiles(d, rc, t);
-            const double cost = tile_plan_cost(d, rc, (size_t)mb * t.size(), 1);
-            if (cost <= bestc * 1.005) { pl.rc = rc; bestc = std::min(bestc, cost); }     // (auto_chunks' rule)
-        }
-    }
-    std::vector<Tile6> t; build_plan_tiles(d, pl.rc, t);
-    pl.n_tiles = (int)t.size(); pl.n_seg = 1; pl.seg_len = d.H; pl.n_pinned = pl.n_tiles;
-    return pl;
 }
 
 }  // namespace
@@ -700,6 +694,40 @@ struct cem_planner {
     std::vector<float> h_expl;               // host copy of the explicit uploads [slots][2][HA]: the source of their stream-ordered copies
 };
 
+namespace {
+
+// problems side by side on the handle = its carry slots: a single-state handle is a handle of ONE problem
+int warm_slots(const cem_planner *h) { return h->batch ? h->batch : 1; }
+
+// The select form the handle's next iteration takes (resolve_select_mode): the fused form only while the device keeps all its
+// ceil(N / 4096) workgroups resident at once and none of its grid barriers has expired on this handle.
+int select_mode_now(const cem_planner *h, bool *cache = nullptr)
+{
+    const Dims &d = h->d;
+    const bool can_fuse = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS <= h->fused_resident && !h->fuse_banned;
+    return resolve_select_mode(h->cfg.select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, can_fuse, cache);
+}
+
+// the captured plan no longer describes what the handle would launch (or never came to be): the next graphable plan captures anew
+void drop_graph(cem_planner *h)
+{
+    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+    if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
+    h->graph_ready = false;
+}
+
+// what every handle owns from create on: the three pinned blocks, its stream if it made one, itself
+void release_handle(cem_planner *h)
+{
+    if (h->h_ctrl) hipHostFree(h->h_ctrl);
+    if (h->h_result) hipHostFree(h->h_result);
+    if (h->h_warm) hipHostFree(h->h_warm);
+    if (h->own_stream) hipStreamDestroy(h->stream);
+    delete h;
+}
+
+}  // namespace
+
 extern "C" {
 
 int cem_abi_version(void) { return CEM_ABI_VERSION; }
@@ -788,14 +816,8 @@ int cem_rollout_residency(int32_t chunks_per_tile, int32_t input_blocks_per_wave
     if (chunks_per_tile < 1 || chunks_per_tile > 4 || input_blocks_per_wave < 1 || input_blocks_per_wave > 2) return CEM_ERR_INVALID_ARG;
     for (int seg = 0; seg < 2; ++seg) {
         if (table_out) table_out[seg] = kResidentStatic[seg][input_blocks_per_wave - 1][chunks_per_tile - 1];
-        if (runtime_out) {
-            int n = 0;
-#define CEM_CASE(R, F) if (chunks_per_tile == R && input_blocks_per_wave == F) n = query_resident<R, F>(seg != 0);
-            CEM_CASE(1, 1) CEM_CASE(2, 1) CEM_CASE(3, 1) CEM_CASE(4, 1)
-            CEM_CASE(1, 2) CEM_CASE(2, 2) CEM_CASE(3, 2) CEM_CASE(4, 2)
-#undef CEM_CASE
-            runtime_out[seg] = n;
-        }
+        if (runtime_out)
+            runtime_out[seg] = with_tile_shape(chunks_per_tile, input_blocks_per_wave, 0, [&](auto R, auto F) { return query_resident<R(), F()>(seg != 0); });
     }
     return CEM_OK;
 }
@@ -811,8 +833,8 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     cem_planner *h = new (std::nothrow) cem_planner();
     if (!h) return CEM_ERR_INVALID_ARG;
     h->cfg = *cfg; h->d = make_dims(cfg);
-    h->batch = mb; h->n_states = mb ? mb : 1;
-    const size_t nb = mb ? (size_t)mb : 1;
+    h->batch = mb; h->n_states = warm_slots(h);
+    const size_t nb = (size_t)warm_slots(h);
     h->lay = make_layout(cfg, h->d, max_tiles_of(h->d), mb);
     if (workspace_bytes < h->lay.total || ((uintptr_t)workspace & 255)) { delete h; return CEM_ERR_WORKSPACE; }
     h->ws = (char *)workspace; h->stream = (hipStream_t)hip_stream; h->own_stream = false;
@@ -820,7 +842,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { g_last_hip = (int)hipGetLastError(); delete h; return CEM_ERR_HIP; }
         h->own_stream = true;
     }
-    { const Plan pl = mb ? make_plan_batch(cfg, h->d, mb) : make_plan(cfg, h->d); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
+    { const Plan pl = make_plan(cfg, h->d, mb); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
       // Where the sampler runs (cem_device.h: cem_tile_sample_actions vs cem_sample_kernel).  Inside the rollout launch when ALL its
       // tiles are resident at once (one round of prologues per launch: B1, B2) — one launch and one graph node fewer per iteration for
       // about what the launch cost; as a launch of its own when tiles queue for slots (B3: 8 tiles per CU; every round of tiles would
@@ -840,15 +862,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->h_expl.assign(nb * 2 * h->d.H * h->d.A, 0.f);
     h->scratch = nullptr; h->scratch_bytes = 0; h->sel_zeroed = false; h->plan_seq = 0; h->fuse_banned = false; h->inject_next = 0; h->inject_capture_fail = false;
     // every failure from here on frees what was acquired and reports the HIP code
-    auto fail = [&](int status) {
-        g_last_hip = (int)hipGetLastError();
-        if (h->h_ctrl) hipHostFree(h->h_ctrl);
-        if (h->h_result) hipHostFree(h->h_result);
-        if (h->h_warm) hipHostFree(h->h_warm);
-        if (h->own_stream) hipStreamDestroy(h->stream);
-        delete h;
-        return status;
-    };
+    auto fail = [&](int status) { g_last_hip = (int)hipGetLastError(); release_handle(h); return status; };
     // mapped + coherent (fine-grained) host memory, asked for explicitly: the device reads the staged block and writes the result in place,
     // and the host polls that result while the stream is still running
     const size_t result_bytes = mb ? nb * CEM_RESULT_WORDS * 4 : 64 * 4;
@@ -936,14 +950,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     }
     // a batch handle runs the one-workgroup select only: on a device that grants less dynamic LDS than validate_batch() assumed, the
     // shape may need another form
-    if (mb && resolve_select_mode(cfg->select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, false, nullptr) != 1) {
-        if (h->h_ctrl) hipHostFree(h->h_ctrl);
-        if (h->h_result) hipHostFree(h->h_result);
-        if (h->h_warm) hipHostFree(h->h_warm);
-        if (h->own_stream) hipStreamDestroy(h->stream);
-        delete h;
-        return CEM_ERR_UNSUPPORTED;
-    }
+    if (mb && select_mode_now(h) != 1) { release_handle(h); return CEM_ERR_UNSUPPORTED; }
     *out = h;
     return CEM_OK;
 }
@@ -984,14 +991,9 @@ int cem_planner_destroy(cem_planner_t *h)
     if (hipStreamSynchronize(h->stream) != hipSuccess) (void)hipGetLastError();
     if (h->scratch) hipFree(h->scratch);
     if (h->comm) { if (Rccl *r = rccl()) r->CommDestroy(h->comm); h->comm = nullptr; }
-    if (h->gexec) hipGraphExecDestroy(h->gexec);
-    if (h->graph) hipGraphDestroy(h->graph);
+    drop_graph(h);
     for (auto e : h->ev) hipEventDestroy(e);
-    if (h->h_ctrl) hipHostFree(h->h_ctrl);
-    if (h->h_result) hipHostFree(h->h_result);
-    if (h->h_warm) hipHostFree(h->h_warm);
-    if (h->own_stream) hipStreamDestroy(h->stream);
-    delete h;
+    release_handle(h);
     return CEM_OK;
 }
 
@@ -1113,21 +1115,13 @@ hipError_t launch_rollout_seg_t(const RolloutParams &p, int grid, hipStream_t st
 
 hipError_t launch_rollout_seg(int rc, int nfw, const RolloutParams &p, int grid, hipStream_t st)
 {
-#define CEM_CASE(R, F) if (rc == R && nfw == F) return launch_rollout_seg_t<R, F>(p, grid, st);
-    CEM_CASE(1, 1) CEM_CASE(2, 1) CEM_CASE(3, 1) CEM_CASE(4, 1)
-    CEM_CASE(1, 2) CEM_CASE(2, 2) CEM_CASE(3, 2) CEM_CASE(4, 2)
-#undef CEM_CASE
-    return hipErrorInvalidValue;
+    return with_tile_shape(rc, nfw, hipErrorInvalidValue, [&](auto R, auto F) { return launch_rollout_seg_t<R(), F()>(p, grid, st); });
 }
 
 template <int MODE>
 hipError_t launch_rollout(int rc, int nfw, const RolloutParams &p, int n_tiles, hipStream_t st)
 {
-#define CEM_CASE(R, F) if (rc == R && nfw == F) return launch_rollout_t<R, F, MODE>(p, n_tiles, st);
-    CEM_CASE(1, 1) CEM_CASE(2, 1) CEM_CASE(3, 1) CEM_CASE(4, 1)
-    CEM_CASE(1, 2) CEM_CASE(2, 2) CEM_CASE(3, 2) CEM_CASE(4, 2)
-#undef CEM_CASE
-    return hipErrorInvalidValue;
+    return with_tile_shape(rc, nfw, hipErrorInvalidValue, [&](auto R, auto F) { return launch_rollout_t<R(), F(), MODE>(p, n_tiles, st); });
 }
 
 // the split-product rollout (cem_rollout_split.h): rc 1 / 2, whole-horizon tiles; mode 1 = caller-supplied noise tensors
@@ -1140,11 +1134,10 @@ hipError_t launch_rollout_split_t(const RolloutParams &p, int n_tiles, hipStream
 }
 hipError_t launch_rollout_split(int rc, int nfw, int mode, const RolloutParams &p, int n_tiles, hipStream_t st)
 {
-#define CEM_CASE(R, F, M) if (rc == R && nfw == F && mode == M) return launch_rollout_split_t<R, F, M>(p, n_tiles, st);
-    CEM_CASE(1, 1, 0) CEM_CASE(2, 1, 0) CEM_CASE(1, 2, 0) CEM_CASE(2, 2, 0) CEM_CASE(3, 1, 0) CEM_CASE(4, 1, 0) CEM_CASE(3, 2, 0) CEM_CASE(4, 2, 0)
-    CEM_CASE(1, 1, 1) CEM_CASE(2, 1, 1) CEM_CASE(1, 2, 1) CEM_CASE(2, 2, 1) CEM_CASE(3, 1, 1) CEM_CASE(4, 1, 1) CEM_CASE(3, 2, 1) CEM_CASE(4, 2, 1)
-#undef CEM_CASE
-    return hipErrorInvalidValue;
+    if (mode != 0 && mode != 1) return hipErrorInvalidValue;
+    return with_tile_shape(rc, nfw, hipErrorInvalidValue, [&](auto R, auto F) {
+        return mode ? launch_rollout_split_t<R(), F(), 1>(p, n_tiles, st) : launch_rollout_split_t<R(), F(), 0>(p, n_tiles, st);
+    });
 }
 
 // mode 0: planning; mode 1: caller-supplied action / noise tensors, trajectory and head-moment outputs
@@ -1181,6 +1174,19 @@ hipEvent_t get_event(cem_planner *h, size_t i)
     return h->ev[i];
 }
 
+// Times what is launched within its scope as `kind` (0 rollout / 1 select / 2 reduce / 3 sampler launch) when timing is on: the start
+// event and the ev_kind entry now, the stop event at stop() or at the end of the scope.  Nothing when timing is off.
+struct TimedLaunch {
+    cem_planner *h; size_t e0;
+    TimedLaunch(cem_planner *h_, int kind) : h(h_->timing ? h_ : nullptr), e0(0)
+    {
+        if (!h) return;
+        e0 = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)e0, kind}); hipEventRecord(get_event(h, e0), h->stream);
+    }
+    void stop() { if (h) hipEventRecord(get_event(h, e0 + 1), h->stream); h = nullptr; }
+    ~TimedLaunch() { stop(); }
+};
+
 void warm_handed_over(cem_planner *h);
 
 int enqueue_begin(cem_planner *h)
@@ -1192,8 +1198,7 @@ int enqueue_begin(cem_planner *h)
     if (h->n_seg > 1) { ip.seg_queue = (uint32_t *)(h->ws + l.seg_queue); ip.seg_flags = (uint32_t *)(h->ws + l.seg_flags); ip.n_ready = (h->n_tiles - h->n_pinned) * (h->n_seg - 1); }
     ip.n_prob = h->batch;                                // a batch handle: every problem's block and mu / sigma (the done ones included)
     ip.warm = h->d_h_warm; ip.carry = (float *)(h->ws + l.carry); ip.expl = (const float *)(h->ws + l.expl);
-    const int nb = h->batch ? h->batch : 1;
-    const int n = nb * std::max<int>(ip.HA, (int)(sizeof(CtrlBlock) / 4));
+    const int n = warm_slots(h) * std::max<int>(ip.HA, (int)(sizeof(CtrlBlock) / 4));
     hipLaunchKernelGGL(cem_init_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, ip);
     HIPCHK(hipGetLastError());
     {   // launched for real (not recorded into a graph): the pending carries are on their way to Layout::carry (stage_warm's invariant)
@@ -1222,20 +1227,17 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     rp.act_bounds = (const float *)(ws + l.act_bounds); rp.actions_w = (float *)(ws + l.actions); rp.act_pad_w = (float *)(ws + l.act_pad);
     rp.pad_shift = d.O - 4 * d.act_q0; rp.pad_floats = 4 * d.act_nq; rp.N = d.N; rp.Nloc = d.Nloc; rp.n_off = d.n_off; rp.n_tiles = h->n_tiles;
     // a batch handle: ONE launch per stage for all its problems, problem b on tiles [b n_tiles, (b + 1) n_tiles) and its own slices
-    const int nb = h->batch ? h->batch : 1;
+    const int nb = warm_slots(h);
     rp.tiles_per_problem = h->batch ? h->n_tiles : 0;
     rp.eps_act_pstride = (long long)d.I * d.N * d.H * d.A; rp.eps_model_pstride = (long long)d.I * d.H * d.Btot * d.O;
     if (!h->sample_in_rollout) {                          // all N candidates once, in front of the rollout launch (which then samples nothing)
         const int total = d.N * d.H * ((d.A + 3) / 4);
-        size_t es = 0;
-        if (h->timing) { es = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)es, 3}); hipEventRecord(get_event(h, es), h->stream); }
+        TimedLaunch timed(h, 3);
         hipLaunchKernelGGL(cem_sample_kernel, dim3(std::min((total + 255) / 256, 2048), nb), dim3(256), 0, h->stream, rp);
         HIPCHK(hipGetLastError());
-        if (h->timing) hipEventRecord(get_event(h, es + 1), h->stream);
         rp.musig = nullptr;
     }
-    size_t e0 = 0;
-    if (h->timing) { e0 = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)e0, 0}); hipEventRecord(get_event(h, e0), h->stream); }
+    TimedLaunch timed(h, 0);
     if (d.wide) HIPCHK(launch_rollout_wide(h, rp, h->n_tiles, rp.eps_model ? 1 : 0));
     else if (d.split) HIPCHK(launch_rollout_split(h->rc, d.NFW, rp.eps_model ? 1 : 0, rp, h->n_tiles, h->stream));
     else if (rp.eps_model) HIPCHK(launch_rollout<1>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
@@ -1245,18 +1247,16 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         // one workgroup per pinned tile, then one per (floating tile, segment) item
         HIPCHK(launch_rollout_seg(h->rc, d.NFW, rp, h->n_pinned + h->n_seg * (h->n_tiles - h->n_pinned), h->stream));
     } else HIPCHK(launch_rollout<0>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
-    if (h->timing) hipEventRecord(get_event(h, e0 + 1), h->stream);
+    timed.stop();
     if (fold_reduce) return CEM_OK;
 
     ReduceParams qp{}; qp.ret = rp.ret; qp.costs = rp.costs; qp.scores = (float *)(ws + l.scores_local); qp.ctrl = rp.ctrl;
     qp.Nloc = d.Nloc; qp.P = d.P; qp.H = d.H; qp.variant = h->cfg.variant; qp.check_done = 1;
     qp.alpha = h->alpha; qp.beta = h->beta; qp.thr = h->cfg.posterior_mean_threashold;
     qp.zero = (uint32_t *)(ws + l.ms_hist); qp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;     // for this iteration's multi-workgroup select
-    size_t er = 0;
-    if (h->timing) { er = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)er, 2}); hipEventRecord(get_event(h, er), h->stream); }
+    TimedLaunch timed_reduce(h, 2);
     hipLaunchKernelGGL(cem_reduce_kernel, dim3((d.Nloc + 63) / 64, nb), dim3(CEM_REDUCE_THREADS), 0, h->stream, qp);
     HIPCHK(hipGetLastError());
-    if (h->timing) hipEventRecord(get_event(h, er + 1), h->stream);
     return CEM_OK;
 }
 
@@ -1267,7 +1267,7 @@ bool folds_reduce(const cem_planner *h)
     const Dims &d = h->d;
     if (d.W != 1 || h->comm || h->cfg.variant != CEM_VARIANT_CEM) return false;
     bool cache = false;
-    return resolve_select_mode(h->cfg.select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, false, &cache) == 1 && cache;
+    return select_mode_now(h, &cache) == 1 && cache;
 }
 
 // fold_final: the select writes the plan's result itself (whole plans only: eps_out is known before the loop) — returns through
@@ -1294,15 +1294,14 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     // The fused form's grid barriers need all G workgroups resident at once: G is held against what the RUNTIME says the device keeps
     // resident of this kernel (asked once at create: workgroups per CU x CUs), not against the CU count alone.  What it cannot see is
     // other work on the device — another stream, handle or process, a CU-masked queue: the form assumes a GPU that is otherwise idle
-    // for the few microseconds of the launch; under contention a barrier times out (bounded polls) and the plan fails with
-    // CEM_ERR_DEVICE rather than hanging.  select_mode 2 has no such assumption.
+    // for the few microseconds of the launch; under contention a barrier times out (bounded polls), cem_msel_solo_kernel redoes that
+    // iteration's select in stream order (the plan stays valid, with select_mode 2's bits) and the handle stops fusing: read_results,
+    // select_mode_now.  select_mode 2 has no such assumption.
     const int G = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS;
-    const bool can_fuse = G <= h->fused_resident && !h->fuse_banned;
     bool cache = false;
-    const int mode = resolve_select_mode(h->cfg.select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, can_fuse, &cache);
+    const int mode = select_mode_now(h, &cache);
     if (mode == 0) return CEM_ERR_UNSUPPORTED;          // (an explicit select_mode 1 on a device that grants less dynamic LDS than validate() assumed)
-    size_t e0 = 0;
-    if (h->timing) { e0 = h->ev_kind.size() * 2; h->ev_kind.push_back({(int)e0, 1}); hipEventRecord(get_event(h, e0), h->stream); }
+    TimedLaunch timed(h, 1);
     if (mode >= 2) {
         MSelParams m{}; m.scores = p.scores; m.actions = p.actions; m.musig = p.musig; m.ctrl = p.ctrl; m.elite_idx = p.elite_idx;
         m.hist = (uint32_t *)(ws + l.ms_hist); m.sel = (uint32_t *)(ws + l.ms_sel); m.wg_counts = (uint32_t *)(ws + l.ms_counts);
@@ -1338,13 +1337,12 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
         if (cache) lds += (size_t)CEM_SEL_KWORDS(d.N) * 4;
         // (SafeCemMpc's scores have a crowd near -100: the instantiation that counts and ranks wave by wave; same results either way)
         // one workgroup per problem (batch handles: blockIdx.x is the problem)
-        const dim3 grid(h->batch ? h->batch : 1);
+        const dim3 grid(warm_slots(h));
         if (cache && h->cfg.variant == CEM_VARIANT_SAFE) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
         else if (cache) hipLaunchKernelGGL((cem_select_kernel<true, false>), grid, dim3(1024), lds, h->stream, p);
         else hipLaunchKernelGGL((cem_select_kernel<false, false>), grid, dim3(1024), lds, h->stream, p);
     }
     HIPCHK(hipGetLastError());
-    if (h->timing) hipEventRecord(get_event(h, e0 + 1), h->stream);
     return CEM_OK;
 }
 
@@ -1396,7 +1394,6 @@ void collect_timing(cem_planner *h)
 // A plan's last mu / sigma stay where the select left them — slice b of Layout::musig — until the NEXT plan's first kernel, which is
 // about to restart every slice, moves them to the slot's carry first (WarmProb::save_slot).  Nothing else touches Layout::musig between
 // two plans, and that kernel is ordered behind the whole previous plan by the stream, early stop or not.
-int warm_slots(const cem_planner *h) { return h->batch ? h->batch : 1; }
 // (by the bits: the library is built with -fno-honor-nans, under which the compiler may drop a floating-point NaN test)
 bool finite_bits(float x) { uint32_t u; std::memcpy(&u, &x, 4); return (u & 0x7f800000u) != 0x7f800000u; }
 
@@ -1411,10 +1408,10 @@ int check_warm(const cem_planner *h, int n)
 }
 
 // INVARIANT: the hand-over of a pending carry (carry_at[s] -> WarmProb::save_slot) is consumed by exactly one EXECUTED first kernel.
-// stage_warm only describes it and may run any number of times before a launch (a plan staged for a capture that then fails is staged
-// again for the eager launches; a HIP call may fail between staging and launch): it rebuilds save_slot from carry_at and changes
-// nothing.  warm_handed_over, called where the first kernel is really put on the stream (an eager launch outside a capture, a graph
-// launch), is what clears carry_at — from then on the carries are in Layout::carry, in stream order, and a later staging (a second
+// stage_warm only describes it and may run any number of times before a launch (a plan whose capture fails is staged once, but between
+// staging and launch a HIP call may fail, and the next plan is staged over it): it rebuilds save_slot from carry_at and changes
+// nothing.  warm_handed_over, called at the two places the first kernel is really put on the stream (enqueue_begin outside a capture,
+// run_plan's graph launch), is what clears carry_at — from then on the carries are in Layout::carry, in stream order, and a later staging (a second
 // cem_plan_begin without an end, say) must not save the slices again, which hold the new plan's distribution by then.
 void warm_handed_over(cem_planner *h)
 {
@@ -1457,16 +1454,39 @@ void finish_warm(cem_planner *h, int status)
     h->warm_staged = 0;
 }
 
-void stage_ctrl(cem_planner *h, const float *state, uint64_t seed, uint64_t call)
+// One plan call as every entry point describes it: n problems side by side (cem_planner_plan, cem_plan_begin: one), problem b with state
+// states[b][O], Philox key (seed, calls[b]) and row b of the outputs.  eps_act / eps_model: device tensors or null; eps_out: host or null.
+struct PlanCall {
+    int n; const float *states; uint64_t seed; const uint64_t *calls;
+    const float *eps_act, *eps_model, *eps_out;
+    float *actions, *scores; int32_t *iters;
+};
+
+// explicit noise comes as both tensors or neither (the sampler of the propagation draws from both)
+bool noise_pair_ok(const cem_planner *h, const PlanCall &pc)
 {
-    stage_warm(h, 1);
-    CtrlBlock *c = h->h_ctrl;
-    c->seed_lo = (uint32_t)seed; c->seed_hi = (uint32_t)(seed >> 32); c->call_lo = (uint32_t)call; c->call_hi = (uint32_t)(call >> 32);
-    c->done = 0; c->iters = 0; c->fault = 0; c->best_score = -std::numeric_limits<float>::infinity();
-    for (int f = 0; f < CEM_U; ++f) c->state[f] = f < h->d.O ? state[f] : 0.f;
-    for (int a = 0; a < 32; ++a) c->best[a] = 0.f;
-    c->seq = ++h->plan_seq;                             // echoed into result[36] by the kernel that completes the plan
-    c->inject = h->inject_next; h->inject_next = 0;     // (test hook, cem_planner_inject_fault)
+    return (pc.eps_act == nullptr) == (pc.eps_model == nullptr) || !h->cfg.sampling_propagation;
+}
+
+// The plan's control blocks, one per problem of the handle: problem b < n gets states[b] and the key (seed, calls[b]) — what a
+// single-state handle stages for that state alone; problems n .. batch - 1 are staged as already stopped (done, no iterations), so every
+// kernel skips them.  Runs once per plan a caller sees: the plan counter advances by one.
+void stage_ctrl(cem_planner *h, const PlanCall &pc)
+{
+    stage_warm(h, pc.n);
+    const uint32_t seq = ++h->plan_seq;                  // echoed into result[36] by the kernel that completes the plan
+    for (int b = 0; b < warm_slots(h); ++b) {
+        CtrlBlock *c = h->h_ctrl + b;
+        const bool live = b < pc.n;
+        const uint64_t call = live ? pc.calls[b] : 0;
+        c->seed_lo = (uint32_t)pc.seed; c->seed_hi = (uint32_t)(pc.seed >> 32); c->call_lo = (uint32_t)call; c->call_hi = (uint32_t)(call >> 32);
+        c->done = live ? 0 : 1; c->iters = 0; c->fault = 0; c->best_score = -std::numeric_limits<float>::infinity();
+        for (int f = 0; f < CEM_U; ++f) c->state[f] = (live && f < h->d.O) ? pc.states[(size_t)b * h->d.O + f] : 0.f;
+        for (int a = 0; a < 32; ++a) c->best[a] = 0.f;
+        c->seq = seq; c->inject = h->batch ? 0 : h->inject_next;     // (test hook, cem_planner_inject_fault: single-state handles consume it)
+    }
+    if (!h->batch) h->inject_next = 0;
+    h->n_states = pc.n;
 }
 
 // The plan is queued: wait for its result.  The kernel that completes it stores the plan counter into pinned host memory after
@@ -1474,11 +1494,10 @@ void stage_ctrl(cem_planner *h, const float *state, uint64_t seed, uint64_t call
 // through hipStreamSynchronize (an interrupt / yield path that took ~10 us of a 1.9-ms plan).  Bounded: after 100 ms of polling the
 // ordinary synchronisation takes over.
 // the block is complete when it carries this plan's counter AND its checksum holds (device -> host writes arrive in no particular order)
-// (a batch handle: every block of the plan's problems, [n_states][CEM_RESULT_WORDS])
+// (every block of the plan's problems, [n_states][CEM_RESULT_WORDS]; a single-state handle has the one)
 bool result_landed(const cem_planner *h)
 {
-    const int nblk = h->batch ? h->n_states : 1;
-    for (int b = 0; b < nblk; ++b) {
+    for (int b = 0; b < h->n_states; ++b) {
         const volatile uint32_t *r = reinterpret_cast<const volatile uint32_t *>(h->h_result) + (size_t)b * CEM_RESULT_WORDS;
         if (r[36] != h->plan_seq) return false;
         if (cem_result_checksum(r, h->plan_seq) != r[37]) return false;     // position dependent: stale words cannot cancel (cem_device.h)
@@ -1504,16 +1523,21 @@ int wait_result(cem_planner *h)
     return CEM_OK;
 }
 
-int read_result(cem_planner *h, float *action_out, float *best_score_out, int32_t *iters_out)
+// the results of the plan's n problems: row b of the outputs from block b
+int read_results(cem_planner *h, const PlanCall &pc)
 {
-    // (after a stream synchronisation the block has landed; the check costs nothing and a short wait covers a write still in flight)
+    // (after a stream synchronisation the blocks have landed; the check costs nothing and a short wait covers a write still in flight)
     for (int spin = 0; spin < 2000000 && !result_landed(h); ++spin) { }
     if (!result_landed(h)) return CEM_ERR_DEVICE;
-    if (action_out) std::memcpy(action_out, h->h_result, h->d.A * 4);
-    if (best_score_out) *best_score_out = h->h_result[32];
-    if (iters_out) *iters_out = reinterpret_cast<int32_t *>(h->h_result)[33];
-    const int32_t fault = reinterpret_cast<int32_t *>(h->h_result)[35];                 // CtrlBlock::fault
-    if (fault & CEM_FAULT_RECOVERED) {
+    int32_t fault = 0;
+    for (int b = 0; b < pc.n; ++b) {
+        const float *r = h->h_result + (size_t)b * CEM_RESULT_WORDS;
+        if (pc.actions) std::memcpy(pc.actions + (size_t)b * h->d.A, r, h->d.A * 4);
+        if (pc.scores) pc.scores[b] = r[32];
+        if (pc.iters) pc.iters[b] = reinterpret_cast<const int32_t *>(r)[33];
+        fault |= reinterpret_cast<const int32_t *>(r)[35];                                  // CtrlBlock::fault
+    }
+    if (fault & CEM_FAULT_RECOVERED) {                  // (the fused select only: never on a batch handle, which runs the one-workgroup select)
         // A grid barrier of the fused select expired (its workgroups were not all resident: another stream, handle or process held
         // CUs) and cem_msel_solo_kernel redid that iteration's select in stream order: the plan is valid, with select_mode 2's bits.
         // This handle stops fusing: the next plan re-captures its graph on the eight-launch chain, which has no residency assumption.
@@ -1522,120 +1546,145 @@ int read_result(cem_planner *h, float *action_out, float *best_score_out, int32_
                                  "by the recovery kernel and this handle uses the multi-launch select (select_mode 2) from now on\n");
             h->fuse_banned = true;
             if (hipStreamSynchronize(h->stream) != hipSuccess) (void)hipGetLastError();      // the graph may still be draining behind the polled result
-            if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-            if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-            h->graph_ready = false;
+            drop_graph(h);
         }
     }
     return (fault & (CEM_FAULT_SEGMENT | CEM_FAULT_BARRIER)) ? CEM_ERR_DEVICE : CEM_OK;     // a kernel gave up and nothing made up for it
 }
 
-// a batched plan's control blocks: problem b < n gets states[b] and the Philox key (seed, calls[b]) — exactly what cem_planner_plan
-// stages for that state alone; problems n .. batch - 1 are staged as already stopped (done, no iterations), so every kernel skips them
-void stage_ctrl_batch(cem_planner *h, int32_t n, const float *states, uint64_t seed, const uint64_t *calls)
+// A whole plan recorded on the stream — under capture and eagerly alike; the one place the iteration loop exists.  The first kernel,
+// then per iteration rollout, exchange (a no-op without a communicator) and select, then the final kernel unless the last select wrote
+// the result itself (single-state handles on the one-workgroup select: enqueue_select).
+int enqueue_plan(cem_planner *h, bool have_eps_out)
 {
-    stage_warm(h, n);
-    const uint32_t seq = ++h->plan_seq;
-    for (int b = 0; b < h->batch; ++b) {
-        CtrlBlock *c = h->h_ctrl + b;
-        const uint64_t call = b < n ? calls[b] : 0;
-        c->seed_lo = (uint32_t)seed; c->seed_hi = (uint32_t)(seed >> 32); c->call_lo = (uint32_t)call; c->call_hi = (uint32_t)(call >> 32);
-        c->done = b < n ? 0 : 1; c->iters = 0; c->fault = 0; c->best_score = -std::numeric_limits<float>::infinity();
-        for (int f = 0; f < CEM_U; ++f) c->state[f] = (b < n && f < h->d.O) ? states[(size_t)b * h->d.O + f] : 0.f;
-        for (int a = 0; a < 32; ++a) c->best[a] = 0.f;
-        c->seq = seq; c->inject = 0;
+    const bool fold = folds_reduce(h);
+    bool final_folded = false;
+    int st = enqueue_begin(h);
+    for (int it = 0; it < h->d.I && !st; ++it) {
+        st = enqueue_rollout(h, it, fold);
+        if (!st) st = enqueue_exchange(h);
+        if (!st) st = enqueue_select(h, it, fold, true, have_eps_out, &final_folded);
     }
-    h->n_states = n;
+    if (!st && !final_folded) st = enqueue_end(h, have_eps_out);
+    return st;
 }
 
-int read_batch_results(cem_planner *h, int32_t n, float *actions_out, float *scores_out, int32_t *iters_out)
+// The handle's hipGraph: the staged plan captured once (for all `batch` problems of a batch handle: n_states only changes what is staged,
+// never the graph) and kept until something drops it.  Leaves graph_ready set, or — CEM_OK all the same — graph_failed: a captured
+// collective is not something every RCCL / runtime pair supports, so a handle with a communicator whose capture does not work launches
+// eagerly for good, as does one told so by cem_planner_inject_fault(h, 2).  Without either the failure is the caller's; batch handles
+// never fall back.
+int ensure_graph(cem_planner *h)
 {
-    for (int spin = 0; spin < 2000000 && !result_landed(h); ++spin) { }
-    if (!result_landed(h)) return CEM_ERR_DEVICE;
-    int fault = 0;
-    for (int b = 0; b < n; ++b) {
-        const float *r = h->h_result + (size_t)b * CEM_RESULT_WORDS;
-        if (actions_out) std::memcpy(actions_out + (size_t)b * h->d.A, r, h->d.A * 4);
-        if (scores_out) scores_out[b] = r[32];
-        if (iters_out) iters_out[b] = reinterpret_cast<const int32_t *>(r)[33];
-        fault |= reinterpret_cast<const int32_t *>(r)[35];
+    if (h->graph_ready) return CEM_OK;
+    h->eps_act = h->eps_model = nullptr;
+    // relaxed mode: RCCL may touch the runtime from its proxy thread while this thread captures
+    HIPCHK(hipStreamBeginCapture(h->stream, h->comm ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
+    const int st = enqueue_plan(h, false);
+    hipError_t ce = hipStreamEndCapture(h->stream, &h->graph);
+    if (!st && ce == hipSuccess) ce = hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0);
+    const bool refuse = !h->batch && h->inject_capture_fail;       // (test hook, cem_planner_inject_fault kind 2)
+    if (!h->batch) h->inject_capture_fail = false;
+    if (!st && ce == hipSuccess && !refuse) { h->graph_ready = true; return CEM_OK; }
+    if (st || ce != hipSuccess) h->gexec = nullptr;                // (nothing was instantiated)
+    drop_graph(h);
+    if (!h->comm && !refuse) { if (st) return st; HIPCHK(ce); }
+    (void)hipGetLastError();
+    h->graph_failed = true;
+    return CEM_OK;
+}
+
+// The one plan driver, behind cem_planner_plan (one problem) and cem_planner_plan_batch alike; the entry points have checked their
+// arguments.  Stage, then replay the graph or launch the same kernels eagerly, wait, read the n results.
+int run_plan(cem_planner *h, const PlanCall &pc)
+{
+    // With a communicator the first plan runs eagerly: RCCL finishes its lazy set-up (buffers, kernels) outside any capture.
+    bool graph = h->cfg.use_graph && !pc.eps_act && !pc.eps_model && !pc.eps_out && !h->timing && !h->graph_failed &&
+                 (!h->comm || h->plans_since_comm > 0);
+    if (h->comm) h->plans_since_comm++;
+    { const int wst = check_warm(h, pc.n); if (wst) return wst; }
+    if (!noise_pair_ok(h, pc)) return CEM_ERR_INVALID_ARG;
+    stage_ctrl(h, pc);
+    if (graph) { const int st = ensure_graph(h); if (st) return st; graph = h->graph_ready; }
+    if (graph) {
+        HIPCHK(hipGraphLaunch(h->gexec, h->stream));
+        warm_handed_over(h);                            // the graph's first kernel is on the stream (the eager one: enqueue_begin)
+        const int st = wait_result(h); if (st) return st;
+    } else {
+        if (pc.eps_out) HIPCHK(hipMemcpyAsync(h->ws + h->lay.eps_out, pc.eps_out, (size_t)pc.n * h->d.A * 4, hipMemcpyHostToDevice, h->stream));
+        h->eps_act = pc.eps_act; h->eps_model = pc.eps_model;
+        h->ev_kind.clear();
+        const int st = enqueue_plan(h, pc.eps_out != nullptr);
+        h->eps_act = h->eps_model = nullptr;
+        if (st) return st;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->timing) collect_timing(h);
     }
-    return (fault & (CEM_FAULT_SEGMENT | CEM_FAULT_BARRIER)) ? CEM_ERR_DEVICE : CEM_OK;
+    return read_results(h, pc);
+}
+
+// Whatever a plan whose control data was staged returns decides whether its slots' carries are valid (finish_warm); a call refused
+// before staging leaves them alone.
+int settle_warm(cem_planner *h, int status)
+{
+    if (h && h->warm_staged) finish_warm(h, status);
+    return status;
 }
 
 }  // namespace
 
 extern "C" {
 
-static int plan_batch_impl(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
+// The public plan calls.  Each makes its own checks, in its own order (which status a bad call gets is part of the contract), and hands the
+// rest to run_plan; whatever comes back settles the carries (settle_warm).
+int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
                            const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
                            float *best_scores_out, int32_t *iters_out)
 {
-    if (!h) return CEM_ERR_INVALID_ARG;
-    if (!h->batch) return CEM_ERR_STATE;                 // a single-state handle: cem_planner_plan
-    if (!states || !calls || n_states < 1 || n_states > h->batch) return CEM_ERR_INVALID_ARG;
-    if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
-    if ((eps_act_dev == nullptr) != (eps_model_dev == nullptr) && h->cfg.sampling_propagation) return CEM_ERR_INVALID_ARG;
-    { const int wst = check_warm(h, n_states); if (wst) return wst; }
-    const bool fold = folds_reduce(h);
-    // One hipGraph per handle, captured for all `batch` problems: n_states only changes what is staged (the rest are done), never the graph
-    if (h->cfg.use_graph && !eps_act_dev && !eps_model_dev && !eps_out_host && !h->timing) {
-        stage_ctrl_batch(h, n_states, states, seed, calls);
-        if (!h->graph_ready) {
-            h->eps_act = h->eps_model = nullptr;
-            HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            int st = enqueue_begin(h);
-            for (int it = 0; it < h->d.I && !st; ++it) {
-                st = enqueue_rollout(h, it, fold);
-                if (!st) st = enqueue_select(h, it, fold);
-            }
-            if (!st) st = enqueue_end(h, false);
-            hipError_t ce = hipStreamEndCapture(h->stream, &h->graph);
-            if (!st && ce == hipSuccess) ce = hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0);
-            if (st || ce != hipSuccess) {
-                if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-                h->gexec = nullptr;
-                if (st) return st;
-                HIPCHK(ce);
-            }
-            h->graph_ready = true;
-        }
-        HIPCHK(hipGraphLaunch(h->gexec, h->stream));
-        warm_handed_over(h);
-        { const int ws_ = wait_result(h); if (ws_) return ws_; }
-        return read_batch_results(h, n_states, actions_out, best_scores_out, iters_out);
-    }
-    stage_ctrl_batch(h, n_states, states, seed, calls);
-    h->eps_act = eps_act_dev; h->eps_model = eps_model_dev;
-    h->ev_kind.clear();
-    int st = enqueue_begin(h);
-    if (!st && eps_out_host)
-        HIPCHK(hipMemcpyAsync(h->ws + h->lay.eps_out, eps_out_host, (size_t)n_states * h->d.A * 4, hipMemcpyHostToDevice, h->stream));
-    for (int it = 0; it < h->d.I && !st; ++it) {
-        st = enqueue_rollout(h, it, fold);
-        if (!st) st = enqueue_select(h, it, fold);
-    }
-    if (!st) st = enqueue_end(h, eps_out_host != nullptr);
-    h->eps_act = h->eps_model = nullptr;
-    if (st) return st;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->timing) collect_timing(h);
-    return read_batch_results(h, n_states, actions_out, best_scores_out, iters_out);
+    const PlanCall pc{n_states, states, seed, calls, eps_act_dev, eps_model_dev, eps_out_host, actions_out, best_scores_out, iters_out};
+    const int st = !h ? CEM_ERR_INVALID_ARG
+                 : !h->batch ? CEM_ERR_STATE                                 // a single-state handle: cem_planner_plan
+                 : (!states || !calls || n_states < 1 || n_states > h->batch) ? CEM_ERR_INVALID_ARG
+                 : !h->have_weights ? CEM_ERR_NO_WEIGHTS
+                 : !noise_pair_ok(h, pc) ? CEM_ERR_INVALID_ARG               // (this entry: ahead of the warm-start check)
+                 : run_plan(h, pc);
+    return settle_warm(h, st);
 }
 
+int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev,
+                     const float *eps_model_dev, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
+{
+    const PlanCall pc{1, state, seed, &call, eps_act_dev, eps_model_dev, eps_out_host, action_out, best_score_out, iters_out};
+    const int st = (!h || !state) ? CEM_ERR_INVALID_ARG
+                 : h->batch ? CEM_ERR_STATE                                  // a batch handle plans through cem_planner_plan_batch only
+                 : !h->have_weights ? CEM_ERR_NO_WEIGHTS
+                 : (h->d.W != 1 && !h->comm) ? CEM_ERR_STATE                 // sharded ranks without cem_planner_comm_init use the stepwise calls around their own collective
+                 : run_plan(h, pc);
+    return settle_warm(h, st);
+}
+
+// The stepwise form of a single-state plan: the same launches, one call each, the scores left in scores_local between rollout and select
+// (the caller may exchange them).
 static int plan_begin_impl(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
 {
     if (!h || !state) return CEM_ERR_INVALID_ARG;
     if (h->batch) return CEM_ERR_STATE;                  // a batch handle plans through cem_planner_plan_batch only
     if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
-    if ((eps_act_dev == nullptr) != (eps_model_dev == nullptr) && h->cfg.sampling_propagation) return CEM_ERR_INVALID_ARG;
+    const PlanCall pc{1, state, seed, &call, eps_act_dev, eps_model_dev, nullptr, nullptr, nullptr, nullptr};
+    if (!noise_pair_ok(h, pc)) return CEM_ERR_INVALID_ARG;
     { const int wst = check_warm(h, 1); if (wst) return wst; }
-    stage_ctrl(h, state, seed, call);
+    stage_ctrl(h, pc);
     h->eps_act = eps_act_dev; h->eps_model = eps_model_dev;
     h->ev_kind.clear();
     int st = enqueue_begin(h); if (st) return st;
     h->in_plan = true;
     return CEM_OK;
+}
+
+int cem_plan_begin(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
+{
+    const int st = plan_begin_impl(h, state, seed, call, eps_act_dev, eps_model_dev);
+    return st ? settle_warm(h, st) : st;                 // (a plan that began is settled by its end call)
 }
 
 int cem_plan_rollout(cem_planner_t *h, int32_t it)
@@ -1662,104 +1711,14 @@ static int plan_end_impl(cem_planner_t *h, const float *eps_out_host, float *act
     int st = enqueue_end(h, eps_out_host != nullptr); if (st) return st;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->timing) collect_timing(h);
-    return read_result(h, action_out, best_score_out, iters_out);
-}
-
-static int plan_impl(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev,
-                     const float *eps_model_dev, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
-{
-    if (!h || !state) return CEM_ERR_INVALID_ARG;
-    if (h->batch) return CEM_ERR_STATE;                  // a batch handle plans through cem_planner_plan_batch only
-    if (!h->have_weights) return CEM_ERR_NO_WEIGHTS;
-    if (h->d.W != 1 && !h->comm) return CEM_ERR_STATE;   // sharded ranks without cem_planner_comm_init use the stepwise calls around their own collective
-    // With a communicator the first plan runs eagerly: RCCL finishes its lazy set-up (buffers, kernels) outside any capture.
-    const bool graphable = h->cfg.use_graph && !eps_act_dev && !eps_model_dev && !eps_out_host && !h->timing && !h->graph_failed &&
-                           (!h->comm || h->plans_since_comm > 0);
-    if (h->comm) h->plans_since_comm++;
-    { const int wst = check_warm(h, 1); if (wst) return wst; }
-    if (graphable) {
-        stage_ctrl(h, state, seed, call);
-        if (!h->graph_ready) {
-            h->eps_act = h->eps_model = nullptr;
-            // relaxed mode: RCCL may touch the runtime from its proxy thread while this thread captures
-            HIPCHK(hipStreamBeginCapture(h->stream, h->comm ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
-            int st = enqueue_begin(h);
-            const bool fold = folds_reduce(h);
-            bool final_folded = false;
-            for (int it = 0; it < h->d.I && !st; ++it) {
-                st = enqueue_rollout(h, it, fold);
-                if (!st) st = enqueue_exchange(h);
-                if (!st) st = enqueue_select(h, it, fold, true, false, &final_folded);
-            }
-            if (!st && !final_folded) st = enqueue_end(h, false);
-            hipError_t ce = hipStreamEndCapture(h->stream, &h->graph);
-            if (!st && ce == hipSuccess) ce = hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0);
-            const bool refuse = h->inject_capture_fail; h->inject_capture_fail = false;      // (test hook, cem_planner_inject_fault kind 2)
-            if (refuse && !st && ce == hipSuccess) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-            if (st || ce != hipSuccess || refuse) {
-                if (!h->comm && !refuse) { if (st) return st; HIPCHK(ce); }
-                // a captured collective is not something every RCCL / runtime pair supports: fall back to eager launches for good
-                (void)hipGetLastError();
-                if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-                h->gexec = nullptr; h->graph_failed = true;
-            } else {
-                h->graph_ready = true;
-            }
-        }
-        if (h->graph_ready) {
-            HIPCHK(hipGraphLaunch(h->gexec, h->stream));
-            warm_handed_over(h);
-            { const int ws_ = wait_result(h); if (ws_) return ws_; }
-            return read_result(h, action_out, best_score_out, iters_out);
-        }
-    }
-    int st = plan_begin_impl(h, state, seed, call, eps_act_dev, eps_model_dev); if (st) return st;
-    const bool fold = folds_reduce(h);                  // the same launches as the captured form
-    if (eps_out_host) HIPCHK(hipMemcpyAsync(h->ws + h->lay.eps_out, eps_out_host, h->d.A * 4, hipMemcpyHostToDevice, h->stream));
-    bool final_folded = false;
-    for (int it = 0; it < h->d.I; ++it) {
-        st = enqueue_rollout(h, it, fold); if (st) { h->in_plan = false; return st; }
-        st = enqueue_exchange(h); if (st) { h->in_plan = false; return st; }
-        st = enqueue_select(h, it, fold, true, eps_out_host != nullptr, &final_folded); if (st) { h->in_plan = false; return st; }
-    }
-    h->in_plan = false;
-    if (!final_folded) { st = enqueue_end(h, eps_out_host != nullptr); if (st) return st; }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->timing) collect_timing(h);
-    return read_result(h, action_out, best_score_out, iters_out);
-}
-
-// The public plan calls: the work above, then the carry bookkeeping — whatever a plan whose control data was staged returns decides
-// whether its slots' carries are valid (finish_warm); a call refused before staging leaves them alone.
-int cem_planner_plan_batch(cem_planner_t *h, int32_t n_states, const float *states, uint64_t seed, const uint64_t *calls,
-                           const float *eps_act_dev, const float *eps_model_dev, const float *eps_out_host, float *actions_out,
-                           float *best_scores_out, int32_t *iters_out)
-{
-    const int st = plan_batch_impl(h, n_states, states, seed, calls, eps_act_dev, eps_model_dev, eps_out_host, actions_out, best_scores_out, iters_out);
-    if (h && h->warm_staged) finish_warm(h, st);
-    return st;
-}
-
-int cem_planner_plan(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev,
-                     const float *eps_model_dev, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
-{
-    const int st = plan_impl(h, state, seed, call, eps_act_dev, eps_model_dev, eps_out_host, action_out, best_score_out, iters_out);
-    if (h && h->warm_staged) finish_warm(h, st);
-    return st;
-}
-
-int cem_plan_begin(cem_planner_t *h, const float *state, uint64_t seed, uint64_t call, const float *eps_act_dev, const float *eps_model_dev)
-{
-    const int st = plan_begin_impl(h, state, seed, call, eps_act_dev, eps_model_dev);
-    if (st && h && h->warm_staged) finish_warm(h, st);           // (a plan that began is settled by its end call)
-    return st;
+    const PlanCall pc{1, nullptr, 0, nullptr, nullptr, nullptr, eps_out_host, action_out, best_score_out, iters_out};
+    return read_results(h, pc);
 }
 
 int cem_plan_end(cem_planner_t *h, const float *eps_out_host, float *action_out, float *best_score_out, int32_t *iters_out)
 {
     const int st = plan_end_impl(h, eps_out_host, action_out, best_score_out, iters_out);
-    if (h && h->warm_staged && !h->in_plan) finish_warm(h, st);
-    return st;
+    return (h && !h->in_plan) ? settle_warm(h, st) : st;
 }
 
 int cem_planner_set_warm_start(cem_planner_t *h, const cem_warm_start_t *ws)
@@ -1861,9 +1820,7 @@ int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int
     NCCLCHK(r->CommInitRank(&comm, n_ranks, nid, rank));
     h->comm = comm; h->plans_since_comm = 0;
     // a graph captured without the collective (world 1) no longer describes the plan
-    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-    h->graph_ready = false; h->graph_failed = false;
+    drop_graph(h); h->graph_failed = false;
     return CEM_OK;
 }
 
@@ -1887,9 +1844,7 @@ int cem_planner_comm_destroy(cem_planner_t *h)
         HIPCHK(hipStreamSynchronize(h->stream));
         if (Rccl *r = rccl()) r->CommDestroy(h->comm);
         h->comm = nullptr;
-        if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-        if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-        h->graph_ready = false;
+        drop_graph(h);
     }
     return CEM_OK;
 }
@@ -1904,9 +1859,7 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out)
 int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches_out)
 {
     if (!h || !launches_out) return CEM_ERR_INVALID_ARG;
-    const Dims &d = h->d;
-    const int G = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS;
-    const int mode = resolve_select_mode(h->cfg.select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, G <= h->fused_resident && !h->fuse_banned, nullptr);
+    const int mode = select_mode_now(h);
     *launches_out = 1 + (h->sample_in_rollout ? 0 : 1) + (folds_reduce(h) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1));
     return CEM_OK;
 }
@@ -2056,9 +2009,7 @@ int cem_philox_words(cem_planner_t *h, uint64_t seed, uint64_t call, uint32_t st
 int cem_planner_select_mode(const cem_planner_t *h, int32_t *mode_out)
 {
     if (!h || !mode_out) return CEM_ERR_INVALID_ARG;
-    const Dims &d = h->d;
-    const int G = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS;
-    *mode_out = resolve_select_mode(h->cfg.select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, G <= h->fused_resident && !h->fuse_banned, nullptr);
+    *mode_out = select_mode_now(h);
     return CEM_OK;
 }
 

@@ -158,16 +158,18 @@ def _np_ptr(a):
 class CemPlanner:
     """One planner handle (fixed shapes) on one GPU."""
 
+    max_batch = 1                                     # problems (= carry slots) of the handle; BatchCemPlanner sets its own
+
     def __init__(self, cfg: PlannerConfig, device='cuda:0'):
         import torch
         self._torch = torch
         self.lib = _capi.load()                       # raises if the HIP extension is missing
         if not torch.cuda.is_available():
-            raise RuntimeError('CemPlanner needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path')
+            raise RuntimeError('%s needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path' % type(self).__name__)
         self.cfg = cfg
         self.ccfg = to_c_config(cfg)
         self.device = torch.device(device)
-        nbytes = self.lib.cem_workspace_bytes(C.byref(self.ccfg))
+        nbytes = self._workspace_bytes()
         if nbytes == 0:
             # let create() report the precise status
             nbytes = 256
@@ -179,8 +181,7 @@ class CemPlanner:
             self.stream = torch.cuda.Stream(device=self.device)
             torch.cuda.synchronize(self.device)         # workspace zero-fill (default stream) before the library uses it
             h = C.c_void_p()
-            _capi.check(self.lib.cem_planner_create(C.byref(self.ccfg), _ptr(self._ws_view), nbytes,
-                                                    C.c_void_p(self.stream.cuda_stream), C.byref(h)), 'cem_planner_create')
+            self._create(_ptr(self._ws_view), nbytes, C.c_void_p(self.stream.cuda_stream), C.byref(h))
         self.h = h
         lay = _capi.CemLayout()
         _capi.check(self.lib.cem_planner_layout(self.h, C.byref(lay)), 'cem_planner_layout')
@@ -194,6 +195,13 @@ class CemPlanner:
         self._st_ptr, self._act_ptr = _np_ptr(self._st_buf), _np_ptr(self._act_buf)
         self._score, self._iters = C.c_float(), C.c_int32()
         self._score_ref, self._iters_ref = C.byref(self._score), C.byref(self._iters)
+
+    # the two library calls a batch handle makes differently (BatchCemPlanner)
+    def _workspace_bytes(self):
+        return self.lib.cem_workspace_bytes(C.byref(self.ccfg))
+
+    def _create(self, ws_ptr, nbytes, stream, out):
+        _capi.check(self.lib.cem_planner_create(C.byref(self.ccfg), ws_ptr, nbytes, stream, out), 'cem_planner_create')
 
     # ------------------------------------------------------------------ stream plumbing
     def _wait_inputs(self):
@@ -342,7 +350,7 @@ class CemPlanner:
     INIT_MODES = {'cold': _capi.CEM_INIT_COLD, 'explicit': _capi.CEM_INIT_EXPLICIT, 'shift': _capi.CEM_INIT_SHIFT}
 
     def n_slots(self):
-        return getattr(self, 'max_batch', 1)
+        return self.max_batch
 
     def set_warm_start(self, shift=1, tail='box', sigma='reset', floor_frac=0.0):
         """Parameters of the 'shift' mode: mu moves `shift` steps; the freed tail takes the box centre ('box') or repeats the last step
@@ -381,20 +389,21 @@ class CemPlanner:
         return m, s, bool(v.value)
 
     # ------------------------------------------------------------------ planning
-    def _noise_args(self, eps_act, eps_model):
+    def _noise_args(self, eps_act, eps_model, lead=()):
+        """The explicit noise tensors on the device, shapes checked; lead = (B,) for the rows of a batched plan."""
         c = self.cfg
         t = self._torch
         if eps_act is None and eps_model is None:
             return None, None
         if eps_act is None or eps_model is None:
             raise ValueError('eps_act and eps_model must be given together')
-        B = c.particles * c.n_samples
         ea = t.as_tensor(eps_act, dtype=t.float32, device=self.device).contiguous()
         em = t.as_tensor(eps_model, dtype=t.float32, device=self.device).contiguous()
-        if tuple(ea.shape) != (c.iterations, c.n_samples, c.horizon, c.act_dim):
-            raise ValueError('eps_act must be [I,N,H,A]')
-        if tuple(em.shape) != (c.iterations, c.horizon, B, c.obs_dim):
-            raise ValueError('eps_model must be [I,H,P*N,O]')
+        b = 'B,' if lead else ''
+        if tuple(ea.shape) != tuple(lead) + (c.iterations, c.n_samples, c.horizon, c.act_dim):
+            raise ValueError('eps_act must be [%sI,N,H,A]' % b)
+        if tuple(em.shape) != tuple(lead) + (c.iterations, c.horizon, c.particles * c.n_samples, c.obs_dim):
+            raise ValueError('eps_model must be [%sI,H,P*N,O]' % b)
         return ea, em
 
     def plan(self, state, seed=0, call=None, eps_act=None, eps_model=None, eps_out=None):
@@ -561,33 +570,8 @@ class BatchCemPlanner(CemPlanner):
     arrays of the layout are [max_batch] consecutive slices); the single-state and stepwise calls raise (CEM_ERR_STATE)."""
 
     def __init__(self, cfg: PlannerConfig, max_batch: int, device='cuda:0'):
-        import torch
-        self._torch = torch
-        self.lib = _capi.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError('BatchCemPlanner needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path')
-        self.cfg = cfg
         self.max_batch = int(max_batch)
-        self.ccfg = to_c_config(cfg)
-        self.device = torch.device(device)
-        nbytes = self.lib.cem_batch_workspace_bytes(C.byref(self.ccfg), self.max_batch)
-        if nbytes == 0:
-            nbytes = 256                                # let create() report the precise status
-        with torch.cuda.device(self.device):
-            self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-            off = (-self.workspace.data_ptr()) % 256
-            self._ws_view = self.workspace[off:off + nbytes]
-            self.stream = torch.cuda.Stream(device=self.device)
-            torch.cuda.synchronize(self.device)
-            h = C.c_void_p()
-            _capi.check(self.lib.cem_batch_planner_create(C.byref(self.ccfg), self.max_batch, _ptr(self._ws_view), nbytes,
-                                                          C.c_void_p(self.stream.cuda_stream), C.byref(h)), 'cem_batch_planner_create')
-        self.h = h
-        lay = _capi.CemLayout()
-        _capi.check(self.lib.cem_planner_layout(self.h, C.byref(lay)), 'cem_planner_layout')
-        self.layout = lay
-        self._call = 0
-        self.has_comm = False
+        super().__init__(cfg, device=device)          # (CemPlanner.plan's staging too: the library refuses a single-state call, CEM_ERR_STATE)
         # staging for the hot path, made once (as CemPlanner.plan's)
         mb, O, A = self.max_batch, cfg.obs_dim, cfg.act_dim
         self._states_buf = np.zeros((mb, O), np.float32)
@@ -596,31 +580,17 @@ class BatchCemPlanner(CemPlanner):
         self._scores_buf = np.zeros(mb, np.float32)
         self._iters_buf = np.zeros(mb, np.int32)
         self._b_ptrs = tuple(_np_ptr(a) for a in (self._states_buf, self._calls_buf, self._acts_buf, self._scores_buf, self._iters_buf))
-        # (CemPlanner.plan's staging too: a single-state call reaches the library, which refuses it with CEM_ERR_STATE)
-        self._st_buf, self._act_buf = np.zeros(O, np.float32), np.zeros(A, np.float32)
-        self._st_ptr, self._act_ptr = _np_ptr(self._st_buf), _np_ptr(self._act_buf)
-        self._score, self._iters = C.c_float(), C.c_int32()
-        self._score_ref, self._iters_ref = C.byref(self._score), C.byref(self._iters)
+
+    def _workspace_bytes(self):
+        return self.lib.cem_batch_workspace_bytes(C.byref(self.ccfg), self.max_batch)
+
+    def _create(self, ws_ptr, nbytes, stream, out):
+        _capi.check(self.lib.cem_batch_planner_create(C.byref(self.ccfg), self.max_batch, ws_ptr, nbytes, stream, out), 'cem_batch_planner_create')
 
     def batch_capacity(self):
         n = C.c_int32()
         _capi.check(self.lib.cem_planner_batch_capacity(self.h, C.byref(n)), 'cem_planner_batch_capacity')
         return n.value
-
-    def _batch_noise_args(self, n, eps_act, eps_model):
-        c = self.cfg
-        t = self._torch
-        if eps_act is None and eps_model is None:
-            return None, None
-        if eps_act is None or eps_model is None:
-            raise ValueError('eps_act and eps_model must be given together')
-        ea = t.as_tensor(eps_act, dtype=t.float32, device=self.device).contiguous()
-        em = t.as_tensor(eps_model, dtype=t.float32, device=self.device).contiguous()
-        if tuple(ea.shape) != (n, c.iterations, c.n_samples, c.horizon, c.act_dim):
-            raise ValueError('eps_act must be [B,I,N,H,A]')
-        if tuple(em.shape) != (n, c.iterations, c.horizon, c.particles * c.n_samples, c.obs_dim):
-            raise ValueError('eps_model must be [B,I,H,P*N,O]')
-        return ea, em
 
     def set_carry_slots(self, slots=None):
         """Problem b of the following plan_batch calls reads and writes carry slot slots[b] (distinct, in [0, max_batch)); None: b."""
@@ -660,7 +630,7 @@ class BatchCemPlanner(CemPlanner):
             if st_:
                 _capi.check(st_, 'cem_planner_plan_batch')
         else:
-            ea, em = self._batch_noise_args(n, eps_act, eps_model)
+            ea, em = self._noise_args(eps_act, eps_model, lead=(n,))
             eo = None
             if eps_out is not None:
                 eo = np.ascontiguousarray(np.asarray(eps_out, np.float32))
@@ -746,13 +716,15 @@ def config_key(cfg: PlannerConfig, device='cuda:0'):
     return (str(device),) + _freeze(cfg)
 
 
-def cached_planner(cfg: PlannerConfig, device='cuda:0', owner=None) -> CemPlanner:
+def cached_planner(cfg: PlannerConfig, device='cuda:0', owner=None, max_batch=None) -> CemPlanner:
     """owner: an object that warm-starts its plans gets a handle of its OWN (the carry lives on the handle, and two users of one handle
-    would continue each other's plans): its id joins the key.  None: the handle is shared by everything of this shape."""
-    key = config_key(cfg, device) + ((('owner', id(owner)),) if owner is not None else ())
+    would continue each other's plans): its id joins the key.  None: the handle is shared by everything of this shape.
+    max_batch: a batch handle of that capacity (BatchCemPlanner), its own LRU entries in the same cache; None: a single-state handle."""
+    key = config_key(cfg, device) + ((('max_batch', int(max_batch)),) if max_batch is not None else ()) + \
+        ((('owner', id(owner)),) if owner is not None else ())
     pl = _PLANNER_CACHE.pop(key, None)
     if pl is None:
-        pl = CemPlanner(cfg, device=device)
+        pl = CemPlanner(cfg, device=device) if max_batch is None else BatchCemPlanner(cfg, int(max_batch), device=device)
         pl.staged = None                         # (model.uid, model.version) whose weights/normaliser are on the device
         while len(_PLANNER_CACHE) >= _PLANNER_CACHE_MAX:
             # least recently used entry: only the cache's reference goes; a policy still holding the handle keeps it alive
@@ -763,16 +735,8 @@ def cached_planner(cfg: PlannerConfig, device='cuda:0', owner=None) -> CemPlanne
 
 
 def cached_batch_planner(cfg: PlannerConfig, max_batch: int, device='cuda:0', owner=None) -> BatchCemPlanner:
-    """cached_planner for batch handles: the same key plus max_batch (its own LRU entries in the same cache)."""
-    key = config_key(cfg, device) + (('max_batch', int(max_batch)),) + ((('owner', id(owner)),) if owner is not None else ())
-    pl = _PLANNER_CACHE.pop(key, None)
-    if pl is None:
-        pl = BatchCemPlanner(cfg, int(max_batch), device=device)
-        pl.staged = None
-        while len(_PLANNER_CACHE) >= _PLANNER_CACHE_MAX:
-            _PLANNER_CACHE.pop(next(iter(_PLANNER_CACHE)))
-    _PLANNER_CACHE[key] = pl
-    return pl
+    """cached_planner for batch handles."""
+    return cached_planner(cfg, device=device, owner=owner, max_batch=max_batch)
 
 
 def planner_cache_info():

@@ -150,6 +150,7 @@ class CemMpc(MpcPolicy):
         st = np.asarray(states, np.float32)
         if st.ndim != 2:
             raise ValueError('states must be [B, obs_dim]')
+        warm = {}                                      # plan_batch's extra arguments with warm start: the rows' slots and call numbers
         if self.warm_start:
             sl = np.arange(st.shape[0], dtype=np.int32) if slots is None else np.asarray(slots, np.int32).reshape(-1)
             if sl.shape != (st.shape[0],):
@@ -158,11 +159,10 @@ class CemMpc(MpcPolicy):
             if reset is not None:
                 for s in sl[np.asarray(reset, bool).reshape(-1)]:
                     pl.reset_carry(int(s))
-            actions, scores, iters = pl.plan_batch(st, seed=self.seed, slots=sl, calls=np.array(self._next_calls(sl), np.uint64))
-            self.last_scores, self.last_iterations = scores, iters
-            return actions
-        pl = self.build_batch(st.shape[0])
-        actions, scores, iters = pl.plan_batch(st, seed=self.seed)
+            warm = dict(slots=sl, calls=np.array(self._next_calls(sl), np.uint64))
+        else:
+            pl = self.build_batch(st.shape[0])
+        actions, scores, iters = pl.plan_batch(st, seed=self.seed, **warm)
         self.last_scores, self.last_iterations = scores, iters
         return actions
 

@@ -1,11 +1,40 @@
 """Shared builders for the parity tests: one synthetic problem -> (oracle config, planner config)."""
+import hashlib
 import os
+import re
+import subprocess
 
 import numpy as np
+import pytest
 
 from oracle import cem_oracle as o
 
 from ethz_safe_learning_amd import PlannerConfig, ScorerConfig
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'ethz_safe_learning_amd', 'csrc')
+
+
+def device_assembly():
+    """The device ISA of csrc/cem_capi.hip as text, compiled with the Makefile's own flags (hipcc -S --cuda-device-only; cached under
+    /tmp on the hash of the device sources).  Skips the calling test where there is no hipcc."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    if not os.path.exists(hipcc):
+        pytest.skip('no hipcc')
+    mk = open(os.path.join(CSRC, 'Makefile')).read()
+    flags = [f for f in re.search(r'^FLAGS\s*:=\s*(.*)$', mk, re.M).group(1).replace('$(ARCH)', 'gfx950').split() if f not in ('-fPIC', '-shared')]
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(('.h', '.hip')) or f == 'Makefile':
+            h.update(open(os.path.join(CSRC, f), 'rb').read())
+    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
+    out = '/tmp/cem_isa_%s.s' % h.hexdigest()[:16]
+    if not os.path.exists(out):
+        r = subprocess.run([hipcc] + flags + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(CSRC, 'cem_capi.hip')],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        os.replace(out + '.tmp', out)
+    return open(out).read()
 
 
 def make_problem(obs_dim=60, act_dim=2, E=5, n_layers=4, seed=1234, bias_noise=0.05, units=128, **kw):

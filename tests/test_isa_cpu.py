@@ -1,40 +1,16 @@
 """Build-time checks on the device ISA (no GPU): properties of the generated code that the memory model of the hand-over paths
 depends on and that the compiler is free to break silently.  The kernels are compiled to assembly with the Makefile's own
 flags (hipcc -S --cuda-device-only, ~25 s; cached under /tmp on the hash of the device sources)."""
-import hashlib
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'ethz_safe_learning_amd', 'csrc')
-
-
-def _makefile_flags():
-    mk = open(os.path.join(CSRC, 'Makefile')).read()
-    flags = re.search(r'^FLAGS\s*:=\s*(.*)$', mk, re.M).group(1).replace('$(ARCH)', 'gfx950').split()
-    return [f for f in flags if f not in ('-fPIC', '-shared')]
+from tests import helpers as hp
 
 
 @pytest.fixture(scope='module')
 def isa():
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    if not os.path.exists(hipcc):
-        pytest.skip('no hipcc')
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(CSRC)):
-        if f.endswith(('.h', '.hip')) or f == 'Makefile':
-            h.update(open(os.path.join(CSRC, f), 'rb').read())
-    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
-    out = '/tmp/cem_isa_%s.s' % h.hexdigest()[:16]
-    if not os.path.exists(out):
-        r = subprocess.run([hipcc] + _makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(CSRC, 'cem_capi.hip')],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(out + '.tmp', out)
-    return open(out).read()
+    return hp.device_assembly()
 
 
 def _kernel_bodies(isa, pattern):

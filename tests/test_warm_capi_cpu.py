@@ -10,6 +10,7 @@ import pytest
 
 from ethz_safe_learning_amd import _capi
 from ethz_safe_learning_amd.planner import PlannerConfig, ScorerConfig, shift_distribution, to_c_config, warm_sigma_floor
+from tests import helpers as hp
 from tests import warm_cases as wc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -124,29 +125,10 @@ def test_sigma_floor_is_the_fp32_product():
 
 
 # ---- nothing else moved: the planning kernels' register budgets are what they were before warm start -----------------------------
-CSRC = os.path.join(ROOT, 'ethz_safe_learning_amd', 'csrc')
-
-
 @pytest.fixture(scope='module')
 def isa():
-    """The device assembly, compiled with the Makefile's own flags (tests/test_isa_cpu.py's recipe and cache file)."""
-    import hashlib
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    if not os.path.exists(hipcc):
-        pytest.skip('no hipcc')
-    mk = open(os.path.join(CSRC, 'Makefile')).read()
-    flags = [f for f in re.search(r'^FLAGS\s*:=\s*(.*)$', mk, re.M).group(1).replace('$(ARCH)', 'gfx950').split() if f not in ('-fPIC', '-shared')]
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(CSRC)):
-        if f.endswith(('.h', '.hip')) or f == 'Makefile':
-            h.update(open(os.path.join(CSRC, f), 'rb').read())
-    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
-    out = '/tmp/cem_isa_%s.s' % h.hexdigest()[:16]
-    if not os.path.exists(out):
-        r = subprocess.run([hipcc] + flags + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(CSRC, 'cem_capi.hip')], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(out + '.tmp', out)
-    return open(out).read()
+    """The device assembly, compiled with the Makefile's own flags (the recipe and cache file tests/test_isa_cpu.py uses)."""
+    return hp.device_assembly()
 
 
 def _kernel_meta(isa, pattern):

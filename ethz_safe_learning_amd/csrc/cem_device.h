@@ -560,6 +560,12 @@ __global__ __launch_bounds__(256) void cem_sample_kernel(const RolloutParams p)
     }
 }
 
+#include "cem_rollout_common.h"
+
+// a quad of one of the eight per-feature rows cem_rollout_tile keeps in LDS (TABL_): row ROW_, byte TV_ of the row
+#define CEM_TAB(TABL_, ROW_, TV_) (*reinterpret_cast<const f4 *>((TABL_) + (ROW_) * 512 + (TV_)))
+#define CEM_SEL0_LDS(TABL_, TV_) CEM_TAB(TABL_, CEM_ET_SEL0, TV_)      /* the SEL0_ROW_ of CEM_RARE_KINDS_AND_STORE here: the row comes out of LDS */
+
 // One tile for steps [t_begin, t_end) of the horizon.  SEG false: the whole horizon (t_begin = 0, t_end = H).  SEG true: one
 // segment of it; what a tile carries across a segment boundary (state registers, its next layer-0 input blocks, the bookkeeping
 // wave's reward / done state) goes through p.seg_state, so any workgroup on any CU can run the tile's next segment and the
@@ -615,8 +621,6 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
         const int ht = (int)threadIdx.x;                 // (hardware thread id: any one-to-one assignment of the 256 pieces)
         *reinterpret_cast<f4 *>(const_cast<char *>(tabl) + ht * 16) = cem_ld_tab(et_rs, (ht & 31) * 16, (ht >> 5) * 512);
     }
-#define CEM_TAB(ROW_, TV_) (*reinterpret_cast<const f4 *>(tabl + (ROW_) * 512 + (TV_)))
-#define CEM_SEL0_ROW(TV_) CEM_TAB(CEM_ET_SEL0, TV_)       /* (what CEM_RARE_KINDS_AND_STORE reads; the other kernels that use that macro fetch it from memory) */
     // one barrier publishes the table rows AND (with the sampler in this launch: the kernel entry issued its stores without waiting)
     // the tile's own action samples; a resumed segment without a sampler has stage barriers in front of its first table read
     if (p.musig) cem_tile_sample_join();
@@ -659,11 +663,6 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
             actv[i][c] = ((td.act_base + slotc[c]) * H * p.act_nq + qi) * 16;
         }
     }
-#define CEM_LOAD_ACT(DST, I_, C_, TN_) do { \
-        if (MODE == 0) DST = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(act_rs, actv[I_][C_], (TN_) * p.act_nq * 16, 0)); \
-        else { _Pragma("unroll") for (int r = 0; r < 4; ++r) { \
-            int af = 16 * (w + 4 * (I_)) + 4 * q + r - O; af = af < 0 ? 0 : (af >= A ? A - 1 : af); \
-            DST[r] = actrow[C_][(TN_) * A + af]; } } } while (0)
 
     // score owner (wave wbk, lane == row slot)
     float d_prev = 0.f, c_prev = 0.f, cum = 0.f;
@@ -672,68 +671,6 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
     const float csz[4] = {p.sc.cost_size[0], p.sc.cost_size[1], p.sc.cost_size[2], p.sc.cost_size[3]};
     const float ind_cap = p.sc.indicator ? 1.0f : __builtin_inff(), clipv = p.sc.reward_clip > 0.f ? p.sc.reward_clip : __builtin_inff();
     const __amdgpu_buffer_rsrc_t cost_rs = __builtin_amdgcn_make_buffer_rsrc(p.costs ? p.costs + (size_t)b * H * p.Bloc : p.costs, 0, p.costs ? (uint32_t)(H * p.Bloc) : 0u, 0x00020000);
-
-    // reward / cost / done bookkeeping of step T_ from the scorer terms in `part` (rows of the tile on the bookkeeping wave's
-    // lanes); T_ = -1 only initialises d_prev / c_prev from s_0
-#define CEM_PART_MIN4(K_) fminf(fminf(part[((K_) * 4 + 0) * 64 + lane], part[((K_) * 4 + 1) * 64 + lane]), \
-                                fminf(part[((K_) * 4 + 2) * 64 + lane], part[((K_) * 4 + 3) * 64 + lane]))
-#define CEM_BOOKKEEP(T_) do { if (w == wbk) { \
-        const float dn = CEM_PART_MIN4(0); \
-        float cn = 0.f; \
-        _Pragma("unroll") for (int k = 1; k < CEM_NKIND; ++k) \
-            if (k < nk) { const float dk = CEM_PART_MIN4(k); cn = cn + ((dk <= csz[k - 1]) ? 1.0f : 0.0f); } \
-        cn = fminf(cn, ind_cap);                                   /* constrain_indicator: cost > 0 -> 1 (cn is a count) */ \
-        if ((T_) >= 0) { \
-            const bool ga = d_prev <= p.sc.goal_thresh;                                   /* safety_gym.py:116 */ \
-            float r = (d_prev - dn) * p.sc.reward_distance + (ga ? 1.0f : 0.0f) * p.sc.reward_goal; \
-            r = fminf(fmaxf(r, -clipv), clipv);                        /* reward_clip (safety_gym.py:141); +inf: none */ \
-            if (p.variant == 1) {                                                         /* safe_cem_mpc.py:86-93 */ \
-                done = done || ga; \
-                const float nd = done ? 0.0f : 1.0f; \
-                const float cst = c_prev * nd; \
-                if (p.costs && lane < td.cnt) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)cst, cost_rs, td.row_base + lane, __builtin_amdgcn_readfirstlane((T_) * p.Bloc), 0); \
-                cum = cum + r * nd; \
-            } else {                                                                      /* mpc_policy.py:34-37 */ \
-                const float nd = done ? 0.0f : 1.0f; \
-                cum = cum + r * nd; \
-                done = done || ga; \
-            } } \
-        d_prev = dn; c_prev = cn; } } while (0)
-
-    // min over the 4 lane rows that hold different features of the same batch row, for TWO scorer kinds at once: one row swap
-    // puts kind KA's partial minima into the even lane rows and kind KA+1's into the odd ones, one half swap finishes both (two
-    // VALU swaps + two v_min for a pair of kinds, no LDS).  Lane rows 0 / 2 then hold kind KA, rows 1 / 3 kind KA + 1 (PAIRED)
-    // and every row stores its kind's value for its batch row (rows q and q + 2 store the same word).
-#define CEM_PAIR_MIN_STORE(KA, VA, VB, PAIRED, C_) do { \
-        const auto r16_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(VA), __float_as_uint(VB), false, false); \
-        const uint32_t m16_ = __float_as_uint(fminf(__uint_as_float(r16_[0]), __uint_as_float(r16_[1]))); \
-        const auto r32_ = __builtin_amdgcn_permlane32_swap(m16_, m16_, false, false); \
-        part[(((KA) + ((PAIRED) ? (q & 1) : 0)) * 4 + w) * 64 + 16 * (C_) + j] = fminf(__uint_as_float(r32_[0]), __uint_as_float(r32_[1])); \
-    } while (0)
-
-    // scorer kinds beyond (goal, first cost kind) and the observe_goal_dist form of the goal kind: rare, kept out of the hot block
-#define CEM_RARE_KINDS_AND_STORE() do { \
-        if (p.sc.goal_mode) {                                 /* squeeze(relu(goal_dist)), safety_gym.py:172-174 */ \
-            _Pragma("unroll") for (int c = 0; c < RC; ++c) pm[0][c] = __builtin_inff(); \
-            _Pragma("unroll") for (int i = 0; i < NFW; ++i) { \
-                const f4 selg = CEM_SEL0_ROW(tab_v + 256 * i); \
-                _Pragma("unroll") for (int c = 0; c < RC; ++c) \
-                    _Pragma("unroll") for (int r = 0; r < 4; ++r) pm[0][c] = fminf(pm[0][c], fmaxf(fmaxf(s[i][c][r], 0.f), selg[r])); } } \
-        _Pragma("unroll") for (int c = 0; c < RC; ++c) CEM_PAIR_MIN_STORE(0, pm[0][c], pm[1][c], true, c); \
-        if (nk > 2) {                                         /* vases + hazards + pillars + gremlins all constrained */ \
-            float pk[3][RC]; \
-            _Pragma("unroll") for (int k = 0; k < 3; ++k) _Pragma("unroll") for (int c = 0; c < RC; ++c) pk[k][c] = __builtin_inff(); \
-            _Pragma("unroll") for (int i = 0; i < NFW; ++i) { \
-                const int f0 = 16 * (w + 4 * i) + 4 * q; \
-                _Pragma("unroll") for (int k = 2; k < CEM_NKIND; ++k) if (k < nk) { \
-                    const f4 selk = *reinterpret_cast<const f4 *>(p.kind_sel + k * CEM_U + f0); \
-                    _Pragma("unroll") for (int c = 0; c < RC; ++c) \
-                        _Pragma("unroll") for (int r = 0; r < 4; ++r) { \
-                            const float lid = fminf(fmaxf(p.sc.D - p.sc.D * (1.0f - s[i][c][r]), 0.f), p.sc.D); \
-                            pk[k - 2][c] = fminf(pk[k - 2][c], fmaxf(lid, selk[r])); } } } \
-            _Pragma("unroll") for (int c = 0; c < RC; ++c) { \
-                CEM_PAIR_MIN_STORE(2, pk[0][c], pk[1][c], true, c); \
-                if (nk > 4) CEM_PAIR_MIN_STORE(4, pk[2][c], pk[2][c], false, c); } } } while (0)
 
     f4 hB[CEM_NG][RC];
     if (resumed) {
@@ -761,12 +698,12 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
 #pragma unroll
         for (int i = 0; i < NFW; ++i) {
             const int tv = tab_v + 256 * i;
-            const f4 mn4 = CEM_TAB(CEM_ET_NMIN, tv), rd4 = CEM_TAB(CEM_ET_RDELTA, tv);
-            const f4 isact4 = CEM_TAB(CEM_ET_ACT, tv);
-            const f4 sel0 = CEM_TAB(CEM_ET_SEL0, tv), sel1 = CEM_TAB(CEM_ET_SEL1, tv);
+            const f4 mn4 = CEM_TAB(tabl, CEM_ET_NMIN, tv), rd4 = CEM_TAB(tabl, CEM_ET_RDELTA, tv);
+            const f4 isact4 = CEM_TAB(tabl, CEM_ET_ACT, tv);
+            const f4 sel0 = CEM_TAB(tabl, CEM_ET_SEL0, tv), sel1 = CEM_TAB(tabl, CEM_ET_SEL1, tv);
 #pragma unroll
             for (int c = 0; c < RC; ++c) {
-                f4 act4; CEM_LOAD_ACT(act4, i, c, 0);
+                f4 act4; CEM_LOAD_ACT(act4, MODE, p, act_rs, actv, actrow, w, q, O, A, i, c, 0);
                 const f4 sn = s[i][c];
                 if (MODE == 1) {
                     const int slot = 16 * c + j, f0 = 16 * (w + 4 * i) + 4 * q;
@@ -782,7 +719,7 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
                 hB[i][c] = x;
             }
         }
-        CEM_RARE_KINDS_AND_STORE();
+        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_LDS, tabl);
         xw = XB;
     }
     f4 nb0 = cem_ld_tab(et_rs, bias_v, CEM_ET_ROWS * 512);                              // layer-0 bias, own blocks 2w, 2w+1
@@ -834,7 +771,7 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
             CEM_NEXT_BIAS(p.L > 1 ? 1 : 0);
             // stage input = previous stage's output buffer = xw ^ XB (the previous stage toggled xw after writing)
             cem_mfma_stage<RC, 4 * NFW, NFW, true, CEM_X_EXCHANGE, LA>(acc0, acc1, hB, wq, smem, xw ^ XB, lane, w);
-            if (!(resumed && t == t_begin)) CEM_BOOKKEEP(t - 1);   // the barrier inside the stage published step t-1's scorer terms (a resumed segment took them from seg_state)
+            if (!(resumed && t == t_begin)) CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, t - 1);   // the barrier inside the stage published step t-1's scorer terms (a resumed segment took them from seg_state)
             CEM_RELU_PUBLISH();
             CEM_STAMP(0);
         }
@@ -871,10 +808,10 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
             // them, so they fill the matrix pipe's drain instead of standing in front of it
             f4 act4[RC], eps4[RC];
 #pragma unroll
-            for (int c = 0; c < RC; ++c) CEM_LOAD_ACT(act4[c], i, c, tn);
+            for (int c = 0; c < RC; ++c) CEM_LOAD_ACT(act4[c], MODE, p, act_rs, actv, actrow, w, q, O, A, i, c, tn);
             f4 accm[RC], accv[RC];
             {
-                const f4 bm = CEM_TAB(CEM_ET_BMU, tv), bv = CEM_TAB(CEM_ET_BVAR, tv);
+                const f4 bm = CEM_TAB(tabl, CEM_ET_BMU, tv), bv = CEM_TAB(tabl, CEM_ET_BVAR, tv);
 #pragma unroll
                 for (int c = 0; c < RC; ++c) { accm[c] = bm; accv[c] = bv; }
             }
@@ -889,22 +826,11 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
             CEM_STAMP(3);
 #pragma unroll
             for (int c = 0; c < RC; ++c) {
-                if (MODE == 1 && p.eps_model) {
-                    const int f0 = 16 * Fo + 4 * q;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int fc = (f0 + r < O) ? f0 + r : O - 1;
-                        eps4[c][r] = p.eps_model[b * p.eps_model_pstride + ((size_t)t * p.Btot + td.noise_row_base + slotc[c]) * O + fc];
-                    }
-                    eps4[c] = eps4[c] * (p.sampling ? 1.0f : 0.0f);
-                } else {
-                    eps4[c] = cem_normal4((uint32_t)(td.noise_row_base + slotc[c]), (uint32_t)t, (uint32_t)p.it,
-                                          (uint32_t)(4 * Fo + q), CEM_STREAM_MODEL, key, rscale);
-                }
+                CEM_MODEL_NOISE4(eps4[c], MODE, p, td, b, O, t, t, slotc[c], Fo, q, key, rscale);
             }
-            const f4 mn4 = CEM_TAB(CEM_ET_NMIN, tv), rd4 = CEM_TAB(CEM_ET_RDELTA, tv);
-            const f4 om4 = CEM_TAB(CEM_ET_OBS, tv), isact4 = CEM_TAB(CEM_ET_ACT, tv);
-            const f4 sel0 = CEM_TAB(CEM_ET_SEL0, tv), sel1 = CEM_TAB(CEM_ET_SEL1, tv);
+            const f4 mn4 = CEM_TAB(tabl, CEM_ET_NMIN, tv), rd4 = CEM_TAB(tabl, CEM_ET_RDELTA, tv);
+            const f4 om4 = CEM_TAB(tabl, CEM_ET_OBS, tv), isact4 = CEM_TAB(tabl, CEM_ET_ACT, tv);
+            const f4 sel0 = CEM_TAB(tabl, CEM_ET_SEL0, tv), sel1 = CEM_TAB(tabl, CEM_ET_SEL1, tv);
 
 #pragma unroll
             for (int c = 0; c < RC; ++c) {
@@ -942,13 +868,13 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
         for (int i = 0; i < NFW; ++i)
 #pragma unroll
             for (int c = 0; c < RC; ++c) hB[i][c] = xown[i][c];
-        CEM_RARE_KINDS_AND_STORE();
+        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_LDS, tabl);
         xw ^= XB;
         CEM_STAMP(4);
     }
     // the last step's scorer terms: publish, then its bookkeeping
     __syncthreads();
-    CEM_BOOKKEEP(t_end - 1);
+    CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, t_end - 1);
     if (!SEG || t_end == H) {
         if (w == wbk && lane < td.cnt) p.ret[(size_t)b * p.Bloc + td.row_base + lane] = cum;
     } else {
@@ -965,12 +891,6 @@ __device__ __forceinline__ void cem_rollout_tile(const RolloutParams &p, char *s
     if (p.stamps && lane == 0) for (int i = 0; i < 8; ++i) p.stamps[((size_t)tile_idx * 4 + w) * 8 + i] = st_[i];
 #endif
 }
-#undef CEM_LOAD_ACT
-#undef CEM_TAB
-#undef CEM_SEL0_ROW
-#define CEM_SEL0_ROW(TV_) cem_ld_tab(et_rs, (TV_), CEM_ET_SEL0 * 512)
-// CEM_BOOKKEEP, CEM_PART_MIN4, CEM_PAIR_MIN_STORE and CEM_RARE_KINDS_AND_STORE stay defined: cem_rollout_wide.h uses them with the
-// same local names (RC = 1) and undefines them.
 
 // Batched plans: workgroup g runs tile g % tiles_per_problem of problem g / tiles_per_problem, and leaves at once when THAT problem has stopped.
 template <int RC, int NFW, int MODE>

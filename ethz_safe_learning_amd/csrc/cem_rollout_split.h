@@ -14,7 +14,7 @@
 // Structure: cem_rollout_tile's — 4 waves per tile of 16 RC rows of one member for the whole horizon, wave w computes output blocks
 // 2w, 2w + 1 of a hidden layer and keeps them, SPLIT, as its own K = 32 input chunk of the next stage; the other chunks travel through
 // LDS as three bf16 planes; weights stream from a per-wave image of 6 KB groups (chunk x {a, b} output block x 3 planes) in visiting
-// order.  The epilogue, scorer terms and bookkeeping are cem_rollout_tile's own macros.  Whole-horizon tiles only (no floating
+// order.  Action loads, model noise, rare scorer kinds and bookkeeping are cem_rollout_common.h's, arguments explicit.  Whole-horizon tiles only (no floating
 // segments); MODE 1 also serves cem_unfold_sequences (trajectory / head-moment outputs).
 #pragma once
 #include "cem_device.h"
@@ -220,11 +220,6 @@ __device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, c
             actv[i][c] = ((td.act_base + slotc[c]) * H * p.act_nq + qi) * 16;
         }
     }
-#define CEM_LOAD_ACT(DST, I_, C_, TN_) do { \
-        if (MODE == 0) DST = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(act_rs, actv[I_][C_], (TN_) * p.act_nq * 16, 0)); \
-        else { _Pragma("unroll") for (int r = 0; r < 4; ++r) { \
-            int af = 16 * (w + 4 * (I_)) + 4 * q + r - O; af = af < 0 ? 0 : (af >= A ? A - 1 : af); \
-            DST[r] = actrow[C_][(TN_) * A + af]; } } } while (0)
     // the scaled input block Fo of chunk c_rc goes to LDS as three planes of 4 bf16 per lane (its half of the lane's 16 bytes)
 #define CEM_PUBLISH_X(X_, FO_, C_) do { cem_u2 px_[3]; cem_split4((X_), px_); \
         _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_) \
@@ -250,7 +245,7 @@ __device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, c
             const f4 sel0 = cem_ld_tab(et_rs, tv, CEM_ET_SEL0 * 512), sel1 = cem_ld_tab(et_rs, tv, CEM_ET_SEL1 * 512);
 #pragma unroll
             for (int c = 0; c < RC; ++c) {
-                f4 act4; CEM_LOAD_ACT(act4, i, c, 0);
+                f4 act4; CEM_LOAD_ACT(act4, MODE, p, act_rs, actv, actrow, w, q, O, A, i, c, 0);
                 const f4 sn = s[i][c];
                 if (MODE == 1) {
                     const int slot = 16 * c + j, f0 = 16 * (w + 4 * i) + 4 * q;
@@ -265,7 +260,7 @@ __device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, c
                 CEM_PUBLISH_X(x, w + 4 * i, c);
             }
         }
-        CEM_RARE_KINDS_AND_STORE();
+        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_MEM, et_rs);
         xw = XB;
     }
     f4 nb0 = cem_ld_tab(et_rs, bias_v, CEM_ET_ROWS * 512);
@@ -310,7 +305,7 @@ __device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, c
             // hidden stages ahead (requested next to their use they cost the heads stage an L2 round trip: 2.26 K vs 1.8 K cycles)
             bm0 = cem_ld_tab(et_rs, tab_v, CEM_ET_BMU * 512); bv0 = cem_ld_tab(et_rs, tab_v, CEM_ET_BVAR * 512);
             CEM_STAMP(0);
-            CEM_BOOKKEEP(t - 1);
+            CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, t - 1);
             CEM_STAMP(6);
             CEM_SPLIT_PUBLISH();
             CEM_STAMP(5);
@@ -357,19 +352,8 @@ __device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, c
             f4 act4[RC], eps4[RC];
 #pragma unroll
             for (int c = 0; c < RC; ++c) {
-                CEM_LOAD_ACT(act4[c], i, c, tn);
-                if (MODE == 1 && p.eps_model) {
-                    const int f0 = 16 * Fo + 4 * q;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int fc = (f0 + r < O) ? f0 + r : O - 1;
-                        eps4[c][r] = p.eps_model[((size_t)t * p.Btot + td.noise_row_base + slotc[c]) * O + fc];
-                    }
-                    eps4[c] = eps4[c] * (p.sampling ? 1.0f : 0.0f);
-                } else {
-                    eps4[c] = cem_normal4((uint32_t)(td.noise_row_base + slotc[c]), (uint32_t)t, (uint32_t)p.it,
-                                          (uint32_t)(4 * Fo + q), CEM_STREAM_MODEL, key, rscale);
-                }
+                CEM_LOAD_ACT(act4[c], MODE, p, act_rs, actv, actrow, w, q, O, A, i, c, tn);
+                CEM_MODEL_NOISE4(eps4[c], MODE, p, td, 0, O, t, t, slotc[c], Fo, q, key, rscale);
             }
 #pragma unroll
             for (int c = 0; c < RC; ++c) {
@@ -399,17 +383,16 @@ __device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, c
                 CEM_PUBLISH_X(x, Fo, c);
             }
         }
-        CEM_RARE_KINDS_AND_STORE();
+        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_MEM, et_rs);
         xw ^= XB;
         CEM_STAMP(4);
     }
     __syncthreads();
-    CEM_BOOKKEEP(H - 1);
+    CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, H - 1);
     if (w == wbk && lane < td.cnt) p.ret[td.row_base + lane] = cum;
 #ifdef CEM_STAMPS
     if (p.stamps && lane == 0) for (int i = 0; i < 8; ++i) p.stamps[((size_t)tile_idx * 4 + w) * 8 + i] = st_[i];
 #endif
-#undef CEM_LOAD_ACT
 #undef CEM_PUBLISH_X
 }
 

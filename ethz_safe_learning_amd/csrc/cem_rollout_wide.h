@@ -4,7 +4,7 @@
 // The reference takes any `units` and any activation from config/models.yaml:11-12 (128 / relu ship).  cem_rollout_tile keeps a
 // layer's 8 feature blocks in registers and streams pre-packed weights through a ring sized for exactly that; this kernel trades
 // some of that speed for generality: the same tile (16 rows of one member for the whole horizon, 4 waves), the same arithmetic per
-// element, the same Philox keys, the same epilogue / scorer terms / bookkeeping (cem_rollout_tile's own macros on the same
+// element, the same Philox keys, the same epilogue / scorer terms / bookkeeping (cem_rollout_common.h's pieces on the same
 // per-member feature table) — but runtime loops over 16-feature blocks, activations exchanged through LDS at every stage, and
 // weights streamed from a per-member image packed in A-operand order: one 1 KB group per (k block, output block), so a lane's four
 // MFMA steps of a group are ONE 16-byte load.  A layer's products are summed over k blocks in ascending order (the fast kernel
@@ -99,7 +99,7 @@ __device__ __forceinline__ void cem_wide_kloop(f4 (&acc)[CEM_WIDE_OB], WideRing 
 
 // MODE 0: planning (actions from the padded quad layout the tile's own prologue writes, cem_tile_sample_actions; Philox noise).  MODE 1: caller-supplied action /
 // noise tensors and the trajectory / head-moment outputs of cem_unfold_sequences.  The epilogue, the scorer terms and the
-// bookkeeping are cem_rollout_tile's (its macros, with RC = 1), on the same per-member feature table; the hidden layers' biases
+// bookkeeping are cem_rollout_common.h's (with RC = 1), on the same per-member feature table; the hidden layers' biases
 // are two table rows per layer here (256 features).
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void cem_rollout_wide_kernel(const WideParams wp)
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void cem_rollout_wide_kernel(const WidePara
         }
         if (t >= 0) {
             __syncthreads();                               // the previous step's next-input blocks and scorer terms are in LDS
-            CEM_BOOKKEEP(t - 1);
+            CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, t - 1);
             // ---- dense layers: h = act(h W + b)  (mlp_ensemble.py:18-22): wave w computes output blocks w, w + 4, w + 8, w + 12 ----
             for (int l = 0; l < L; ++l) {
                 const int nbK = l == 0 ? nbIn : nbU;
@@ -227,25 +227,8 @@ __global__ __launch_bounds__(256, 2) void cem_rollout_wide_kernel(const WidePara
                 const f4 om4 = cem_ld_tab(et_rs, tv, CEM_ET_OBS * 512) * live, isact4 = cem_ld_tab(et_rs, tv, CEM_ET_ACT * 512);
                 const f4 sel0 = cem_ld_tab(et_rs, tv, CEM_ET_SEL0 * 512), sel1 = cem_ld_tab(et_rs, tv, CEM_ET_SEL1 * 512);
                 f4 act4, eps4;
-                if (MODE == 0) act4 = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(act_rs, actv[i][0], tn * p.act_nq * 16, 0));
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int af = 16 * Fo + 4 * q + r - O; af = af < 0 ? 0 : (af >= A ? A - 1 : af);
-                        act4[r] = actrow[0][tn * A + af];
-                    }
-                }
-                if (MODE == 1 && p.eps_model) {
-                    const int f0 = 16 * Fo + 4 * q, tc = t < 0 ? 0 : t;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int fc = (f0 + r < O) ? f0 + r : O - 1;
-                        eps4[r] = p.eps_model[((size_t)tc * p.Btot + td.noise_row_base + slot0) * O + fc];
-                    }
-                    eps4 = eps4 * (p.sampling ? 1.0f : 0.0f);
-                } else {
-                    eps4 = cem_normal4((uint32_t)(td.noise_row_base + slot0), (uint32_t)t, (uint32_t)p.it, (uint32_t)(4 * Fo + q), CEM_STREAM_MODEL, key, rscale);
-                }
+                CEM_LOAD_ACT(act4, MODE, p, act_rs, actv, actrow, w, q, O, A, i, 0, tn);
+                CEM_MODEL_NOISE4(eps4, MODE, p, td, 0, O, t, (t < 0 ? 0 : t), slot0, Fo, q, key, rscale);
                 f4 ah[CEM_WIDE_OB] = {bm, bv, bm, bm};
                 if (t >= 0 && Fo < nbO) {                  // wave-uniform: mean and variance heads of observation block Fo
                     if (i == 1) cem_wide_prime(ring, img, lane16, baseH + Fo, nbO, nbU * nbO, glast);
@@ -283,15 +266,11 @@ __global__ __launch_bounds__(256, 2) void cem_rollout_wide_kernel(const WidePara
         }
         if (!primed0) cem_wide_prime(ring, img, lane16, w, nbU, 4, glast);             // a wave without an input block
         CEM_WIDE_NEXT_BIAS(0);
-        CEM_RARE_KINDS_AND_STORE();
+        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_MEM, et_rs);
         xw ^= XB;
     }
     __syncthreads();
-    CEM_BOOKKEEP(H - 1);
+    CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, H - 1);
     if (w == wbk && lane < td.cnt) p.ret[td.row_base + lane] = cum;
 }
 #undef CEM_WIDE_NEXT_BIAS
-#undef CEM_BOOKKEEP
-#undef CEM_PART_MIN4
-#undef CEM_PAIR_MIN_STORE
-#undef CEM_RARE_KINDS_AND_STORE

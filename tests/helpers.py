@@ -21,8 +21,7 @@ def device_assembly():
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     if not os.path.exists(hipcc):
         pytest.skip('no hipcc')
-    mk = open(os.path.join(CSRC, 'Makefile')).read()
-    flags = [f for f in re.search(r'^FLAGS\s*:=\s*(.*)$', mk, re.M).group(1).replace('$(ARCH)', 'gfx950').split() if f not in ('-fPIC', '-shared')]
+    flags = makefile_flags()
     h = hashlib.sha256()
     for f in sorted(os.listdir(CSRC)):
         if f.endswith(('.h', '.hip')) or f == 'Makefile':
@@ -35,6 +34,35 @@ def device_assembly():
         assert r.returncode == 0, r.stderr[-3000:]
         os.replace(out + '.tmp', out)
     return open(out).read()
+
+
+
+def kernel_bodies(isa, pattern):
+    """{mangled name: [instruction lines]} of the kernels whose name matches."""
+    out = {}
+    for m in re.finditer(r'^(_Z\w+):.*?\n(.*?)^\.Lfunc_end', isa, re.M | re.S):       # (to the end of the function: a kernel may hold early s_endpgm's)
+        if re.search(pattern, m.group(1)):
+            out[m.group(1)] = [l.split(';')[0].strip() for l in m.group(2).splitlines() if l.strip() and not l.lstrip().startswith((';', '.'))]
+    return out
+
+
+def kernel_meta(isa, pattern):
+    """{mangled name: {vgpr_count, vgpr_spill_count, private_segment_fixed_size}} from the code-object metadata."""
+    out = {}
+    for m in re.finditer(r'\.name:\s+(_Z\w+)\s*\n(.*?)(?=\n\s+- \.|\namdhsa\.target|\Z)', isa, re.S):
+        if re.search(pattern, m.group(1)):
+            d = {}
+            for k in ('vgpr_count', 'vgpr_spill_count', 'private_segment_fixed_size'):
+                mm = re.search(r'\.%s:\s+(\d+)' % k, m.group(0))
+                d[k] = int(mm.group(1)) if mm else None
+            out[m.group(1)] = d
+    return out
+
+
+def makefile_flags():
+    """The device compile flags of csrc/Makefile (without the link flags)."""
+    mk = open(os.path.join(CSRC, 'Makefile')).read()
+    return [f for f in re.search(r'^FLAGS\s*:=\s*(.*)$', mk, re.M).group(1).replace('$(ARCH)', 'gfx950').split() if f not in ('-fPIC', '-shared')]
 
 
 def make_problem(obs_dim=60, act_dim=2, E=5, n_layers=4, seed=1234, bias_noise=0.05, units=128, **kw):

@@ -1,7 +1,9 @@
 """Build-time checks on the device ISA (no GPU): properties of the generated code that the memory model of the hand-over paths
 depends on and that the compiler is free to break silently.  The kernels are compiled to assembly with the Makefile's own
 flags (hipcc -S --cuda-device-only, ~25 s; cached under /tmp on the hash of the device sources)."""
+import os
 import re
+import subprocess
 
 import pytest
 
@@ -13,21 +15,12 @@ def isa():
     return hp.device_assembly()
 
 
-def _kernel_bodies(isa, pattern):
-    """{mangled name: [instruction lines]} of the kernels whose name matches."""
-    out = {}
-    for m in re.finditer(r'^(_Z\w+):.*?\n(.*?)^\.Lfunc_end', isa, re.M | re.S):       # (to the end of the function: a kernel may hold early s_endpgm's)
-        if re.search(pattern, m.group(1)):
-            out[m.group(1)] = [l.split(';')[0].strip() for l in m.group(2).splitlines() if l.strip() and not l.lstrip().startswith((';', '.'))]
-    return out
-
-
 def test_floating_segment_hand_over_drains_its_stores_before_the_flag(isa):
     """cem_rollout_seg_kernel: a tile's state crosses CUs (and XCDs, whose L2s are not coherent with each other) as sc1 stores
     followed by a flag.  Every wave must wait for the acknowledgement of ITS OWN stores (s_waitcnt vmcnt(0)) before the workgroup
     barrier that precedes the flag store: s_barrier does not drain stores on gfx940+, and a workgroup-scope fence compiles to no
     wait (round 2's code relied on both).  Checked for all eight <chunks, input blocks> instantiations."""
-    bodies = _kernel_bodies(isa, r'cem_rollout_seg_kernel')
+    bodies = hp.kernel_bodies(isa, r'cem_rollout_seg_kernel')
     assert len(bodies) == 8, sorted(bodies)
     for name, ins in bodies.items():
         stores = [i for i, l in enumerate(ins) if l.startswith('buffer_store_dwordx4') and l.endswith('sc1')]
@@ -44,7 +37,7 @@ def test_floating_segment_hand_over_drains_its_stores_before_the_flag(isa):
 def test_fused_select_grid_barrier_drains_before_arriving(isa):
     """cem_msel_fused_kernel: seven grid barriers; before each, every wave's sc1 stores / atomics are acknowledged
     (s_waitcnt vmcnt(0) directly before the workgroup barrier that precedes the arrival atomic)."""
-    bodies = _kernel_bodies(isa, r'cem_msel_fused_kernel')
+    bodies = hp.kernel_bodies(isa, r'cem_msel_fused_kernel')
     assert len(bodies) == 1
     ins = next(iter(bodies.values()))
     # an arrival = the atomic add that is followed by the polling loop (sc1 load + s_sleep)
@@ -57,7 +50,7 @@ def test_fused_select_grid_barrier_drains_before_arriving(isa):
         assert any(x.startswith('s_waitcnt') and 'vmcnt(0)' in x for x in prev), (a, prev)
     # the recovery form of the same body (one workgroup plays every slice): no arrivals, no polling — its phases are separated by
     # the workgroup's own barrier, each behind a drain of the wave's stores
-    solo = _kernel_bodies(isa, r'cem_msel_solo_kernel')
+    solo = hp.kernel_bodies(isa, r'cem_msel_solo_kernel')
     assert len(solo) == 1
     sins = next(iter(solo.values()))
     assert not any(l.startswith('s_sleep') for l in sins), 'the solo select must not poll'
@@ -65,24 +58,11 @@ def test_fused_select_grid_barrier_drains_before_arriving(isa):
     assert len(drained) >= 5, len(drained)       # zeroing, histogram loop, counts, compaction, moments loop
 
 
-def _kernel_meta(isa, pattern):
-    """{mangled name: {vgpr_count, vgpr_spill_count, private_segment_fixed_size}} from the code-object metadata."""
-    out = {}
-    for m in re.finditer(r'\.name:\s+(_Z\w+)\s*\n(.*?)(?=\n\s+- \.|\namdhsa\.target|\Z)', isa, re.S):
-        if re.search(pattern, m.group(1)):
-            d = {}
-            for k in ('vgpr_count', 'vgpr_spill_count', 'private_segment_fixed_size'):
-                mm = re.search(r'\.%s:\s+(\d+)' % k, m.group(0))
-                d[k] = int(mm.group(1)) if mm else None
-            out[m.group(1)] = d
-    return out
-
-
 def test_split_rollout_kernels_fit_the_residency_their_tile_rule_assumes(isa):
     """cem_rollout_split_kernel (planning instantiations): no scratch, no spilled VGPRs, the products really are bf16 MFMAs, and the
     register counts the automatic tile sizes rest on (make_plan: up to 3 chunks at obs+act <= 64, 2 above — two resident workgroups,
     i.e. at most 256 VGPRs; a one-chunk tile of the small family keeps three, at most 170)."""
-    meta = _kernel_meta(isa, r'cem_rollout_split_kernelILi\dELi\dELi0EE')
+    meta = hp.kernel_meta(isa, r'cem_rollout_split_kernelILi\dELi\dELi0EE')
     assert len(meta) == 8, sorted(meta)
     for name, d in meta.items():
         rc, nfw = int(re.search(r'ILi(\d)ELi(\d)E', name).group(1)), int(re.search(r'ILi(\d)ELi(\d)E', name).group(2))
@@ -94,3 +74,20 @@ def test_split_rollout_kernels_fit_the_residency_their_tile_rule_assumes(isa):
     assert sum(1 for l in ins if l.startswith('v_mfma_f32_16x16x32_bf16')) >= 12 * (2 + 4 + 4), 'six products x two output blocks per chunk'
     assert not any(l.startswith('v_mfma_f32_16x16x4_f32') for l in ins), 'the split kernel must not fall back to fp32 MFMAs'
     assert any(l.startswith('v_cvt_pk_bf16_f32') for l in ins), 'the split rounds to nearest with the hardware conversion'
+
+
+@pytest.mark.parametrize('headers', [('cem_rollout_wide.h',), ('cem_rollout_split.h',), ('cem_rollout_wide.h', 'cem_rollout_split.h')],
+                         ids=['wide_alone', 'split_alone', 'wide_then_split'])
+def test_secondary_rollout_headers_stand_alone_and_in_either_order(headers, tmp_path):
+    """cem_rollout_split.h and cem_rollout_wide.h take what they share with cem_rollout_tile from cem_rollout_common.h (file scope, every
+    name an argument), not from macros another header happened to leave defined: each compiles alone, and wide-then-split — the order
+    cem_capi.hip does NOT use — compiles too (it failed while the wide header undefined the macros the split header expands)."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    if not os.path.exists(hipcc):
+        pytest.skip('no hipcc')
+    kernel = ('template __global__ void cem_rollout_split_kernel<1, 1, 0>(const RolloutParams);' if headers[-1] == 'cem_rollout_split.h'
+              else 'template __global__ void cem_rollout_wide_kernel<0>(const WideParams);')
+    tu = tmp_path / 'tu.hip'
+    tu.write_text(''.join('#include "%s"\n' % h for h in headers) + kernel + '\n')
+    r = subprocess.run([hipcc] + hp.makefile_flags() + ['--cuda-device-only', '-fsyntax-only', '-I', hp.CSRC, str(tu)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]

@@ -131,21 +131,13 @@ def isa():
     return hp.device_assembly()
 
 
-def _kernel_meta(isa, pattern):
-    out = {}
-    for m in re.finditer(r'\.name:\s+(_Z\w+)\s*\n(.*?)(?=\n\s+- \.|\namdhsa\.target|\Z)', isa, re.S):
-        if re.search(pattern, m.group(1)):
-            out[m.group(1)] = {k: int(re.search(r'\.%s:\s+(\d+)' % k, m.group(0)).group(1)) for k in ('vgpr_count', 'vgpr_spill_count', 'private_segment_fixed_size')}
-    return out
-
-
 def test_planning_kernels_keep_their_register_counts(isa):
     """Warm start lives in the plan's first kernel alone.  tests/golden/kernel_registers_before_warm_start.json records vgpr_count, spilled
     VGPRs (none anywhere) and scratch of every other kernel as the code-object metadata gave them for the device sources of the commit
     before the feature, compiled with these flags; they must still be exactly those."""
     import json
     want = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'kernel_registers_before_warm_start.json')))
-    got = _kernel_meta(isa, r'.')
+    got = hp.kernel_meta(isa, r'.')
     assert len(want) > 40 and all(d['vgpr_spill_count'] == 0 for d in want.values())
     for name, d in want.items():
         assert name in got, name

@@ -16,6 +16,7 @@ CEM_COMM_ID_BYTES = 128
 CEM_MAX_BATCH = 256
 CEM_TRAIN_MAX_BATCH = 4096
 CEM_INIT_COLD, CEM_INIT_EXPLICIT, CEM_INIT_SHIFT = 0, 1, 2      # enum cem_init_mode
+CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds
@@ -30,7 +31,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
     'cem_planner_get_carry', 'cem_planner_set_carry_slots',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
-    'cem_trainer_get_state', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval',
+    'cem_trainer_get_state', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
 
 
@@ -166,6 +167,7 @@ def load():
     lib.cem_trainer_step.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp]
     lib.cem_trainer_steps.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.cem_trainer_eval.argtypes = [vp, vp, vp, C.c_int32, fp]
+    lib.cem_trainer_forward.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)          # raises AttributeError if the symbol is not exported
         if name not in ('cem_status_string', 'cem_weight_blob_floats', 'cem_packed_weight_floats', 'cem_workspace_bytes',

@@ -3,6 +3,7 @@
 #include "cem_device.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
+#include "cem_forward.h"
 #include "cem_rollout_split.h"
 #include "cem_rollout_wide.h"
 #include "../../include/cem_mpc.h"
@@ -2300,6 +2301,45 @@ int cem_trainer_eval(cem_trainer_t *t, const float *x_dev, const float *y_dev, i
     double total = 0;
     for (int m = 0; m < E; ++m) total += (0.5 * sums[2 * m] / cnt + 0.5 * sums[2 * m + 1] / cnt) / E;
     *loss_out = (float)total;
+    return CEM_OK;
+}
+
+int cem_trainer_forward(cem_trainer_t *t, const float *x_dev, int32_t n_rows, int32_t map, const float *eps_dev, uint64_t seed, uint64_t call,
+                        float *mu_out_dev, float *var_out_dev, float *sd_out_dev, float *sample_out_dev)
+{
+    if (!t || !x_dev || n_rows < 1 || (map != CEM_FORWARD_SPLIT && map != CEM_FORWARD_ALL)) return CEM_ERR_INVALID_ARG;
+    if (!mu_out_dev && !var_out_dev && !sd_out_dev && !sample_out_dev) return CEM_ERR_INVALID_ARG;
+    const cem_train_config_t &c = t->cfg;
+    const int E = c.ensemble_size;
+    if (map == CEM_FORWARD_SPLIT && n_rows % E != 0) return CEM_ERR_SPLIT;
+    ForwardParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.W = (const float *)(t->ws + t->oW); p.x = x_dev; p.eps = sample_out_dev ? eps_dev : nullptr;
+    p.mu = mu_out_dev; p.var = var_out_dev; p.sd = sd_out_dev; p.sample = sample_out_dev;
+    p.rpm = map == CEM_FORWARD_ALL ? n_rows : n_rows / E; p.all = map == CEM_FORWARD_ALL;
+    p.D = c.inputs_dim; p.O = c.outputs_dim; p.U = c.units; p.L = c.n_layers; p.E = E; p.nat = (uint32_t)t->nat; p.act = c.activation;
+    // the key of cem_philox_words: (seed_lo, seed_hi ^ call_hi), counter word 3 = call_lo
+    p.key.k0 = (uint32_t)seed; p.key.k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(call >> 32); p.key.c3 = (uint32_t)call;
+    const long long ntiles = ((long long)p.rpm + CEM_TROWS - 1) / CEM_TROWS;
+    // the Philox counter holds the output row in 32 bits; a launch grid holds fewer than 2^32 threads
+    if ((long long)E * p.rpm > 0xffffffffll || E > 65535 || ntiles * E * (64 * CEM_TT_WAVES) > 0xffffffffll) return CEM_ERR_UNSUPPORTED;
+    // the tile form is 8 blocks wide and relu only, with one instantiation per layer count (dropout plays no part in inference)
+    const bool tile = c.n_layers <= CEM_TT_MAXL && c.units <= CEM_U && c.activation == CEM_ACT_RELU && std::getenv("CEM_TRAIN_GEMM_KERNEL") == nullptr;
+    if (tile) {
+        const size_t lds = (size_t)2 * CEM_TT_NB * CEM_TT_BLK;
+        const dim3 grid((unsigned)ntiles, (unsigned)E);
+        switch (c.n_layers) {
+#define CEM_CASE(LL) case LL: hipLaunchKernelGGL((cem_trainer_forward_tile_kernel<LL>), grid, dim3(64 * CEM_TT_WAVES), lds, t->stream, p); break;
+        CEM_CASE(1) CEM_CASE(2) CEM_CASE(3) CEM_CASE(4) CEM_CASE(5) CEM_CASE(6)
+#undef CEM_CASE
+        }
+    } else {
+        // one scratch slot of a training step per workgroup (five of its L + 8 matrices are used); a workgroup walks its member's tiles
+        p.scratch = (float *)(t->ws + t->oS); p.scratch_per_member = (uint32_t)t->scratch_pm; p.ts = c.units > CEM_TS ? CEM_TWIDE : CEM_TS;
+        p.nslots = (int)std::min<long long>(train_parts_alloc(c), ntiles);
+        hipLaunchKernelGGL(cem_trainer_forward_gemm_kernel, dim3((unsigned)(E * p.nslots)), dim3(CEM_TNT), 0, t->stream, p);
+    }
+    HIPCHK(hipGetLastError());
     return CEM_OK;
 }
 

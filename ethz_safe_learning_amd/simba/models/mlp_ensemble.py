@@ -1,6 +1,8 @@
 """MlpEnsemble, reference simba/models/mlp_ensemble.py:91-193: E independent Gaussian MLPs, L x (Dense U + ReLU) ->
 (mu Dense, softplus+1e-4 var Dense).  Holds the weights in Keras layout ([in, out], Glorot-uniform kernels, zero
-biases: Keras Dense defaults of mlp_ensemble.py:13,28-29).  Inference happens in the fused HIP rollout kernel;
+biases: Keras Dense defaults of mlp_ensemble.py:13,28-29).  Planning-time inference happens in the fused HIP rollout kernel; the class surface of
+the reference, ``forward`` (:122-132) and ``__call__`` (:189-193), plus ``forward_members``, runs the forward-only ensemble kernel
+(csrc/cem_forward.h) on the trainer handle's weights;
 ``fit`` (mlp_ensemble.py:163-187) keeps the reference's host loop (train/validation split, per-epoch bootstrap
 shuffles, np.array_split batches, EpochLearningRateSchedule :70-88) and runs every training_step (:134-145) on the
 GPU through cem_trainer_step (forward, NLL, backward, Adam with clipvalue=1 / epsilon=1e-5)."""
@@ -41,6 +43,8 @@ class MlpEnsemble(object):
         rng = np.random.default_rng(seed)
         self._weights = [self._init_member(rng) for _ in range(ensemble_size)]
         self.version = 0
+        self.seed = int(seed) if seed is not None else 0          # key of the Philox noise of __call__ (with the call counter below)
+        self._calls = 0                                           # every __call__ without explicit noise draws fresh noise
 
     def _init_member(self, rng):
         U, L = self.mlp_params['units'], self.mlp_params['n_layers']
@@ -92,6 +96,43 @@ class MlpEnsemble(object):
             self._trainer.set_state(self._weights)
             self._trainer_version = self.version
         return self._trainer
+
+    # ---- inference (mlp_ensemble.py:122-132,189-193) on the device, through the trainer handle that holds the weights ---------------
+    def _forward(self, inputs, map, want, **kw):
+        import torch
+        as_numpy = not torch.is_tensor(inputs)
+        if as_numpy:
+            inputs = np.ascontiguousarray(np.asarray(inputs, np.float32))
+        if inputs.ndim != 2 or inputs.shape[1] != self.inputs_dim:
+            raise ValueError('inputs of shape %r: expected [n, %d]' % (tuple(inputs.shape), self.inputs_dim))
+        if map == 'split' and (inputs.shape[0] % self.ensemble_size != 0 or inputs.shape[0] == 0):
+            raise ValueError('tf.split requires B %% E == 0 (B=%d, E=%d)' % (inputs.shape[0], self.ensemble_size))
+        tr = self._get_trainer()
+        x_dev = torch.from_numpy(inputs).to(tr.device) if as_numpy else inputs
+        eps = kw.pop('eps', None)
+        if eps is not None and not torch.is_tensor(eps):
+            eps = torch.from_numpy(np.ascontiguousarray(np.asarray(eps, np.float32))).to(tr.device)
+        out = tr.forward(x_dev, map=map, eps=eps, want=want, **kw)
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+    def forward(self, inputs):
+        """mlp_ensemble.py:122-132: inputs [B, inputs_dim] (already scaled; NumPy or a device tensor), B a multiple of ensemble_size
+        (else ValueError, as tf.split raises); row r is evaluated by member r // (B / E).  Returns (mu, var), NumPy fp32 for NumPy
+        inputs and device tensors for device inputs."""
+        return self._forward(inputs, 'split', ('mu', 'var'))
+
+    def __call__(self, inputs, eps=None, seed=None, call=None):
+        """mlp_ensemble.py:189-193: Normal(mu, sqrt(var)) -> (mean, stddev, sample).  Like Normal.sample() every call draws fresh
+        noise: Philox keyed on (the model's seed, a per-model call counter) unless ``seed`` / ``call`` pin it, or ``eps`` [B, O]
+        gives the standard normals outright."""
+        if call is None and eps is None:
+            call = self._calls
+            self._calls += 1
+        return self._forward(inputs, 'split', ('mu', 'sd', 'sample'), eps=eps, seed=self.seed if seed is None else seed, call=call or 0)
+
+    def forward_members(self, inputs):
+        """Every member on every row (the map of validation_step, :150-154): inputs [n, inputs_dim] -> (mu [E, n, O], var [E, n, O])."""
+        return self._forward(inputs, 'all', ('mu', 'var'))
 
     def fit(self, inputs, targets):
         import torch

@@ -103,6 +103,25 @@ class TransitionModel(BaseModel):
         return self.simulate_trajectories(inputs[..., :self.observation_space_dim],
                                           np.expand_dims(inputs[..., -self.action_space_dim:], axis=1), **kw)
 
+    def predictive_moments(self, inputs):
+        """inputs [n, obs + act] (unscaled) -> (mean, aleatoric_var, epistemic_var), each [n, obs]: over the members' predictions on
+        the same scaled rows (MlpEnsemble.forward_members), the mean of mu, the mean of var and the population variance of mu."""
+        import torch
+        as_numpy = not torch.is_tensor(inputs)
+        if as_numpy:
+            x = self.scale(np.asarray(inputs, np.float32))
+        elif self.scale_features:
+            lo = torch.from_numpy(self.inputs_min).to(inputs.device)
+            delta = torch.from_numpy(self.inputs_max).to(inputs.device) - lo
+            x = (inputs.float() - lo) / torch.where(delta < 1e-5, torch.full_like(delta, 1.01), delta)
+        else:
+            x = inputs.float()
+        tr = self.model._get_trainer()
+        mu, var = self.model.forward_members(torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(tr.device) if as_numpy else x)
+        mean = mu.mean(dim=0)
+        out = (mean, var.mean(dim=0), ((mu - mean) ** 2).mean(dim=0))
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
     def save(self):
         pass
 

@@ -125,6 +125,44 @@ class CemTrainer:
         _capi.check(self.lib.cem_trainer_eval(self.h, _ptr(x_dev), _ptr(y_dev), x_dev.shape[0], C.byref(out)), 'cem_trainer_eval')
         return float(out.value)
 
+    def forward(self, x_dev, map='split', eps=None, seed=0, call=0, want=('mu', 'var')):
+        """MlpEnsemble.forward / __call__ (mlp_ensemble.py:122-132,189-193) on the trainer's current weights: x_dev [n, inputs_dim]
+        (already scaled, on the device) -> the tensors named in ``want`` (any of 'mu', 'var', 'sd', 'sample'), in that order.
+        map='split': row r goes to member r // (n / E), outputs [n, O]; map='all': every member on every row (validation_step's map,
+        :150-154), outputs [E, n, O].  'sample' = mu + sd * eps with ``eps`` a device tensor in the output's shape, or Philox noise
+        keyed on (seed, call).  Runs on the trainer's stream; the calling stream waits for it."""
+        torch = self._torch
+        D, O, _, _, E = self.dims
+        code = {'split': _capi.CEM_FORWARD_SPLIT, 'all': _capi.CEM_FORWARD_ALL}.get(map)
+        if code is None:
+            raise ValueError("map %r: 'split' or 'all'" % (map,))
+        want = tuple(want)
+        if not want or any(w not in ('mu', 'var', 'sd', 'sample') for w in want):
+            raise ValueError("want %r: a non-empty choice of 'mu', 'var', 'sd', 'sample'" % (want,))
+        if x_dev.dim() != 2 or x_dev.shape[1] != D or x_dev.shape[0] < 1:
+            raise ValueError('inputs of shape %r: expected [n >= 1, %d]' % (tuple(x_dev.shape), D))
+        n = x_dev.shape[0]
+        if map == 'split' and n % E != 0:
+            raise ValueError('tf.split requires B %% E == 0 (B=%d, E=%d)' % (n, E))      # before any launch, as tf.split raises
+        x_dev = x_dev.to(device=self.device, dtype=torch.float32).contiguous()
+        shape = (n, O) if map == 'split' else (E, n, O)
+        if eps is not None:
+            if tuple(eps.shape) != shape:
+                raise ValueError('eps of shape %r: expected %r' % (tuple(eps.shape), shape))
+            eps = eps.to(device=self.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(self.device):
+            out = {w: torch.empty(shape, dtype=torch.float32, device=self.device) for w in want}
+            cur = torch.cuda.current_stream(self.device)
+            self.stream.wait_stream(cur)
+            _capi.check(self.lib.cem_trainer_forward(self.h, _ptr(x_dev), n, code, _ptr(eps), int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1),
+                                                     _ptr(out.get('mu')), _ptr(out.get('var')), _ptr(out.get('sd')), _ptr(out.get('sample'))),
+                        'cem_trainer_forward')
+            for t in [x_dev, eps] + list(out.values()):
+                if t is not None:
+                    t.record_stream(self.stream)
+            cur.wait_stream(self.stream)
+        return tuple(out[w] for w in want)
+
     def synchronize(self):
         self.stream.synchronize()
 

@@ -432,6 +432,24 @@ int cem_trainer_steps(cem_trainer_t *h, const float *x_dev, const float *y_dev, 
 /* validation_step on rows [0, n) of x_dev / y_dev: *loss_out = sum over members of NLL / ensemble_size (synchronises) */
 int cem_trainer_eval(cem_trainer_t *h, const float *x_dev, const float *y_dev, int32_t n, float *loss_out);
 
+/* Ensemble inference on the trainer's weights: MlpEnsemble.forward (mlp_ensemble.py:122-132: tf.split of the batch over the members,
+ * mu and var concatenated back) and MlpEnsemble.__call__ (:189-193: Normal(mu, sqrt(var)) -> mean, stddev, sample), and with
+ * CEM_FORWARD_ALL the member x row map of validation_step (:150-154: every member on the same rows).
+ * x_dev[n_rows][inputs_dim] holds inputs that are already scaled; nothing is normalised and no state is added.
+ *   CEM_FORWARD_SPLIT  n_rows must be a multiple of ensemble_size (else CEM_ERR_SPLIT, as tf.split raises); row r is evaluated by member
+ *                      r / (n_rows / ensemble_size); outputs are [n_rows][outputs_dim]
+ *   CEM_FORWARD_ALL    every member evaluates every row; outputs are [ensemble_size][n_rows][outputs_dim]
+ * Outputs (device pointers, each may be NULL = not written; all four NULL is CEM_ERR_INVALID_ARG): mu; var = softplus(v) + 1e-4, the value
+ * training_step's loss sees; sd = sqrt(var); sample = mu + sd * eps with one rounding per operation.  eps_dev: standard normals in the
+ * sample's shape, or NULL for Philox noise at the counters documented for cem_philox_words: stream 0, idx = output row (SPLIT: r, ALL:
+ * member * n_rows + r), t = iteration = 0, sub = feature quad, key from (seed, call).  No noise is drawn when sample_out_dev is NULL.
+ * Stream-ordered on the trainer's stream like cem_trainer_steps (no synchronisation); reads the weights only: the Adam moments and the
+ * step counter are untouched.  CEM_ERR_INVALID_ARG for a NULL handle or x_dev, n_rows < 1 or an unknown map; CEM_ERR_UNSUPPORTED for
+ * ensemble_size x rows per member >= 2^32. */
+enum cem_forward_map { CEM_FORWARD_SPLIT = 0, CEM_FORWARD_ALL = 1 };
+int cem_trainer_forward(cem_trainer_t *h, const float *x_dev, int32_t n_rows, int32_t map, const float *eps_dev, uint64_t seed, uint64_t call,
+                        float *mu_out_dev, float *var_out_dev, float *sd_out_dev, float *sample_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

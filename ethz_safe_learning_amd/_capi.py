@@ -24,14 +24,14 @@ LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_m
 EXPORTED_SYMBOLS = [
     'cem_abi_version', 'cem_status_string', 'cem_last_hip_error', 'cem_weight_blob_floats',
     'cem_packed_weight_floats', 'cem_workspace_bytes', 'cem_pack_weights_host', 'cem_plan_tiles_host', 'cem_plan_segments_host', 'cem_rollout_residency',
-    'cem_planner_create', 'cem_planner_destroy', 'cem_planner_layout', 'cem_planner_set_weights',
+    'cem_planner_create', 'cem_planner_destroy', 'cem_planner_layout', 'cem_planner_set_weights', 'cem_planner_set_weights_dev',
     'cem_planner_set_normaliser', 'cem_planner_plan', 'cem_plan_begin', 'cem_plan_rollout', 'cem_plan_select',
     'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_launches_per_iteration', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
     'cem_batch_workspace_bytes', 'cem_batch_planner_create', 'cem_planner_plan_batch', 'cem_planner_batch_capacity',
     'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
     'cem_planner_get_carry', 'cem_planner_set_carry_slots',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
-    'cem_trainer_get_state', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
+    'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
 
 
@@ -76,7 +76,8 @@ class CemWarmStart(C.Structure):
 
 class CemLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in
-                ('scores_local', 'scores_global', 'actions', 'mu_sigma', 'elite_idx', 'returns', 'costs', 'result', 'stamps', 'total')]
+                ('scores_local', 'scores_global', 'actions', 'mu_sigma', 'elite_idx', 'returns', 'costs', 'result', 'stamps', 'total',
+                 'wpack', 'wpack_bytes', 'bias_h', 'bias_mu', 'bias_var', 'etab', 'etab_bytes')]
 
 
 class CemError(RuntimeError):
@@ -121,6 +122,7 @@ def load():
     lib.cem_planner_destroy.argtypes = [vp]
     lib.cem_planner_layout.argtypes = [vp, C.POINTER(CemLayout)]
     lib.cem_planner_set_weights.argtypes = [vp, vp, C.c_size_t]
+    lib.cem_planner_set_weights_dev.argtypes = [vp, vp, C.c_size_t]
     lib.cem_planner_set_normaliser.argtypes = [vp, vp, vp]
     lib.cem_planner_plan.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, fp, i32p]
     lib.cem_plan_begin.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp]
@@ -164,6 +166,7 @@ def load():
     lib.cem_trainer_destroy.argtypes = [vp]
     lib.cem_trainer_set_state.argtypes = [vp, vp, vp, vp]
     lib.cem_trainer_get_state.argtypes = [vp, vp, vp, vp]
+    lib.cem_trainer_weights_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.cem_trainer_step.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp]
     lib.cem_trainer_steps.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.cem_trainer_eval.argtypes = [vp, vp, vp, C.c_int32, fp]

@@ -6,6 +6,7 @@
 #include "cem_forward.h"
 #include "cem_rollout_split.h"
 #include "cem_rollout_wide.h"
+#include "cem_pack.h"
 #include "../../include/cem_mpc.h"
 
 #include <dlfcn.h>
@@ -256,6 +257,52 @@ void pack_member_wide(const Dims &d, const float *nat, float *out)
             emit(nat + no.Wmu, d.U, d.O, gh + kb * nbO + ob, kb, ob);
             emit(nat + no.Wvar, d.U, d.O, gh + nbU * nbO + kb * nbO + ob, kb, ob);
         }
+}
+
+// The unit table of cem_pack.h for this shape: which matrix block every unit of a member's image holds, written down in the loops of
+// the three packers above (same order, same permutations), so that the device kernels gather what those packers store.
+std::vector<PackDesc> build_pack_table(const Dims &d)
+{
+    const NatOff no = nat_offsets(d);
+    std::vector<PackDesc> t;
+    auto unit = [&](size_t src, int in_dim, int out_dim, int kb, int ob) {
+        PackDesc u{}; u.src = (uint32_t)src; u.in_dim = (uint16_t)in_dim; u.out_dim = (uint16_t)out_dim; u.kb = (uint16_t)kb; u.ob = (uint16_t)ob;
+        t.push_back(u);
+    };
+    if (d.wide) {
+        const int nbU = (d.U + 15) / 16, nbIn = d.KB_in, nbO = d.KB_obs;
+        for (int l = 0; l < d.L; ++l) {
+            const int in = l == 0 ? d.Din : d.U, nbK = l == 0 ? nbIn : nbU;
+            for (int kb = 0; kb < nbK; ++kb)
+                for (int ob = 0; ob < nbU; ++ob) unit(no.W[l], in, d.U, kb, ob);         // group cem_wide_base(l) + kb * nbU + ob
+        }
+        for (int kb = 0; kb < nbU; ++kb) for (int ob = 0; ob < nbO; ++ob) unit(no.Wmu, d.U, d.O, kb, ob);
+        for (int kb = 0; kb < nbU; ++kb) for (int ob = 0; ob < nbO; ++ob) unit(no.Wvar, d.U, d.O, kb, ob);
+        return t;
+    }
+    for (int w = 0; w < 4; ++w) {                         // the waves' streams follow each other (Dims::wave_off_f4)
+        const int n0 = d.split ? cem_split_l0_chunks(d.NFW) : d.KF0, per_stage = d.split ? CEM_SPLIT_CHUNKS : CEM_NG;
+        for (int P = 0; P < n0; ++P) {
+            const int F = d.split ? P : cem_perm_l0(w, d.NFW, P);
+            unit(no.W[0], d.Din, d.U, F, 2 * w); unit(no.W[0], d.Din, d.U, F, 2 * w + 1);
+        }
+        for (int l = 1; l < d.L; ++l)
+            for (int P = 0; P < per_stage; ++P) {
+                const int F = d.split ? cem_split_perm(w, P) : cem_perm_hidden(w, P);
+                const int Fb = d.split ? F : cem_perm_hidden(w, P < 2 ? (P ^ 1) : P);     // fp32: the second accumulator takes its own blocks swapped
+                unit(no.W[l], d.U, d.U, F, 2 * w); unit(no.W[l], d.U, d.U, Fb, 2 * w + 1);
+            }
+        for (int i = 0; i < d.NFW; ++i) {
+            const int Fo = w + 4 * i;
+            if (Fo >= d.KB_obs) continue;
+            for (int P = 0; P < per_stage; ++P) {
+                const int F = d.split ? cem_split_perm(w, P) : cem_perm_hidden(w, P);
+                const int Fb = d.split ? F : cem_perm_hidden(w, P < 2 ? (P ^ 1) : P);
+                unit(no.Wmu, d.U, d.O, F, Fo); unit(no.Wvar, d.U, d.O, Fb, Fo);
+            }
+        }
+    }
+    return t;
 }
 
 struct Tile6 { int32_t v[6]; };
@@ -681,7 +728,8 @@ struct cem_planner {
     uint32_t inject_next;                    // cem_planner_inject_fault: CtrlBlock::inject of the next plan
     // grow-only device scratch of the standalone ops (unfold_sequences tiles + returns, compute_objective returns + costs)
     char *scratch; size_t scratch_bytes;
-    std::vector<float> h_etab;               // host copy of RolloutParams::etab ([E][CEM_ET_ROWS + L][128]); re-uploaded whole by create / set_weights / set_normaliser
+    std::vector<float> h_etab;               // host copy of RolloutParams::etab ([E][CEM_ET_ROWS + L][128]); uploaded whole by create / set_weights; set_normaliser uploads its two rows
+    PackDesc *pack_desc; uint32_t n_pack_desc;   // cem_pack.h's unit table of this shape, a device allocation of the handle's own (cem_planner_set_weights_dev)
     int batch;                               // problems of a batch handle (cem_batch_planner_create); 0: a single-state handle
     int n_states;                            // problems of the batched plan being enqueued / last run (the rest are staged as done)
     // warm start (cem_mpc.h): per carry slot [max(batch, 1)]
@@ -723,6 +771,7 @@ void release_handle(cem_planner *h)
     if (h->h_ctrl) hipHostFree(h->h_ctrl);
     if (h->h_result) hipHostFree(h->h_result);
     if (h->h_warm) hipHostFree(h->h_warm);
+    if (h->pack_desc) hipFree(h->pack_desc);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -856,7 +905,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false;
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
-    h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr;
+    h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
     h->warm = cem_warm_start_t{}; h->warm.shift = 1; h->warm_staged = 0; h->warm_save_skipped = false;
     h->slot_mode.assign(nb, CEM_INIT_COLD); h->carry_valid.assign(nb, 0); h->have_expl.assign(nb, 0); h->carry_at.assign(nb, -1);
     h->slot_of.resize(nb); for (size_t b = 0; b < nb; ++b) h->slot_of[b] = (int32_t)b;
@@ -870,6 +919,15 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     if (hipHostMalloc((void **)&h->h_ctrl, nb * sizeof(CtrlBlock), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostMalloc((void **)&h->h_result, result_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostMalloc((void **)&h->h_warm, sizeof(WarmCtl) + nb * sizeof(WarmProb), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail(CEM_ERR_HIP);
+    {   // the device packers' unit table (cem_pack.h): a function of the shape alone
+        const std::vector<PackDesc> table = build_pack_table(h->d);
+        h->n_pack_desc = (uint32_t)table.size();
+        // the table must tile a member's image exactly: the pack kernels write one unit per descriptor (plus 4 KB of slack)
+        const size_t image_bytes = h->d.wide ? wide_image_floats(h->d) * 4 : (size_t)h->d.member_stride_f4 * 16 - 4096;
+        if (table.size() * (h->d.split ? 3072 : 1024) != image_bytes) return fail(CEM_ERR_STATE);
+        if (hipMalloc((void **)&h->pack_desc, table.size() * sizeof(PackDesc)) != hipSuccess ||
+            hipMemcpy(h->pack_desc, table.data(), table.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) return fail(CEM_ERR_HIP);
+    }
     std::memset(h->h_warm, 0, sizeof(WarmCtl) + nb * sizeof(WarmProb));
     std::memset(h->h_ctrl, 0, nb * sizeof(CtrlBlock));
     std::memset(h->h_result, 0, result_bytes);
@@ -1004,6 +1062,8 @@ int cem_planner_layout(const cem_planner_t *h, cem_layout_t *o)
     o->scores_local = h->lay.scores_local; o->scores_global = h->lay.scores_global; o->actions = h->lay.actions;
     o->mu_sigma = h->lay.musig; o->elite_idx = h->lay.elite; o->returns = h->lay.returns; o->costs = h->lay.costs;
     o->result = h->lay.result; o->stamps = h->lay.stamps; o->total = h->lay.total;
+    o->wpack = h->lay.wpack; o->wpack_bytes = h->d.wide ? align256(h->d.nat_member_floats * h->d.E * 4) + wide_image_floats(h->d) * 4 * h->d.E : (size_t)h->d.E * h->d.member_stride_f4 * 16; o->bias_h = h->lay.bias_h; o->bias_mu = h->lay.bias_mu; o->bias_var = h->lay.bias_var;
+    o->etab = h->lay.etab; o->etab_bytes = (size_t)h->d.E * etab_rows(h->d) * CEM_U * 4;
     return CEM_OK;
 }
 
@@ -1064,6 +1124,35 @@ int cem_planner_set_weights(cem_planner_t *h, const float *blob, size_t n_floats
     return CEM_OK;
 }
 
+int cem_planner_set_weights_dev(cem_planner_t *h, const float *blob_dev, size_t n_floats)
+{
+    if (!h || !blob_dev) return CEM_ERR_INVALID_ARG;
+    const Dims &d = h->d;
+    if (n_floats != d.nat_member_floats * d.E) return CEM_ERR_INVALID_ARG;
+    cem_pack_trained_t p{};
+    p.blob = blob_dev; p.desc = h->pack_desc; p.nat = (uint32_t)d.nat_member_floats; p.n_desc = h->n_pack_desc; p.E = (uint32_t)d.E;
+    if (d.wide) {
+        p.blob_copy = (float *)(h->ws + h->lay.wpack); p.dst = h->ws + h->lay.wpack + align256(n_floats * 4);
+        p.member_bytes = wide_image_floats(d) * 4; p.n_slack = 0;
+    } else {
+        p.dst = h->ws + h->lay.wpack; p.member_bytes = (unsigned long long)d.member_stride_f4 * 16; p.n_slack = 4;     // the +256 float4 of slack
+    }
+    const unsigned wgs = (p.n_desc + p.n_slack + CEM_PACK_WAVES - 1) / CEM_PACK_WAVES;
+    const dim3 grid(wgs * (unsigned)d.E), block(64 * CEM_PACK_WAVES);
+    if (d.wide) hipLaunchKernelGGL(cem_pack_wide_kernel, grid, block, 0, h->stream, p);
+    else if (d.split) hipLaunchKernelGGL(cem_pack_split_kernel, grid, block, 0, h->stream, p);
+    else hipLaunchKernelGGL(cem_pack_fp32_kernel, grid, block, 0, h->stream, p);
+    cem_pack_trained_bias_t b{};
+    b.blob = blob_dev; b.bias_h = (float *)(h->ws + h->lay.bias_h); b.bias_mu = (float *)(h->ws + h->lay.bias_mu);
+    b.bias_var = (float *)(h->ws + h->lay.bias_var); b.etab = (float *)(h->ws + h->lay.etab);
+    b.nat = p.nat; b.Din = (uint32_t)d.Din; b.U = (uint32_t)d.U; b.L = (uint32_t)d.L; b.O = (uint32_t)d.O; b.E = p.E; b.wide = d.wide ? 1u : 0u;
+    const size_t quads = (size_t)d.E * (2 + (d.wide ? 2 : 1) * (size_t)d.L) * (CEM_U / 4);
+    hipLaunchKernelGGL(cem_pack_bias_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, h->stream, b);
+    HIPCHK(hipGetLastError());
+    h->have_weights = true;                              // (no synchronise: plans queued behind this on the handle's stream see the new images)
+    return CEM_OK;
+}
+
 int cem_planner_set_normaliser(cem_planner_t *h, const float *imin, const float *imax)
 {
     if (!h || !imin || !imax) return CEM_ERR_INVALID_ARG;
@@ -1085,7 +1174,11 @@ int cem_planner_set_normaliser(cem_planner_t *h, const float *imin, const float 
             std::memcpy(et + CEM_ET_NMIN * CEM_U, mn.data(), CEM_U * 4);
             std::memcpy(et + CEM_ET_RDELTA * CEM_U, dl.data(), CEM_U * 4);
         }
-        HIPCHK(hipMemcpyAsync(h->ws + h->lay.etab, h->h_etab.data(), h->h_etab.size() * 4, hipMemcpyHostToDevice, h->stream));
+        // only the two rows this call owns, in every member's table: the bias rows of the host copy are those of the last HOST
+        // set_weights, and after cem_planner_set_weights_dev the device holds newer ones
+        for (int row : {CEM_ET_NMIN, CEM_ET_RDELTA})
+            HIPCHK(hipMemcpy2DAsync(h->ws + h->lay.etab + (size_t)row * CEM_U * 4, et_rows * CEM_U * 4, h->h_etab.data() + (size_t)row * CEM_U,
+                                    et_rows * CEM_U * 4, CEM_U * 4, (size_t)d.E, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return CEM_OK;
@@ -2221,6 +2314,14 @@ int cem_trainer_get_state(cem_trainer_t *t, float *weights, float *m, float *v)
     if (m) HIPCHK(hipMemcpyAsync(m, t->ws + t->oM, bytes, hipMemcpyDeviceToHost, t->stream));
     if (v) HIPCHK(hipMemcpyAsync(v, t->ws + t->oV, bytes, hipMemcpyDeviceToHost, t->stream));
     HIPCHK(hipStreamSynchronize(t->stream));
+    return CEM_OK;
+}
+
+int cem_trainer_weights_dev(cem_trainer_t *t, const float **blob_dev_out, size_t *n_floats_out)
+{
+    if (!t || !blob_dev_out || !n_floats_out) return CEM_ERR_INVALID_ARG;
+    *blob_dev_out = (const float *)(t->ws + t->oW);
+    *n_floats_out = t->nat * t->cfg.ensemble_size;
     return CEM_OK;
 }
 

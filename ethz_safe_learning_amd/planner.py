@@ -188,6 +188,7 @@ class CemPlanner:
         self.layout = lay
         self._call = 0
         self.has_comm = False
+        self.have_device_weights = False              # the last weight sync came from device memory (set_weights_dev / set_weights_from)
         # the generate_action hot path: staging buffers and their ctypes views are made once (a.ctypes.data_as and the two small
         # numpy allocations were 12 of the 17 us the wrapper added to a 1.9-ms plan)
         self._st_buf = np.zeros(cfg.obs_dim, np.float32)
@@ -270,6 +271,42 @@ class CemPlanner:
         if blob.size != expect:
             raise ValueError('weight blob has %d floats, expected %d' % (blob.size, expect))
         _capi.check(self.lib.cem_planner_set_weights(self.h, _np_ptr(blob), blob.size), 'cem_planner_set_weights')
+        self.have_device_weights = False
+
+    def set_weights_dev(self, blob):
+        """The same sync from the device (cem_planner_set_weights_dev): ``blob`` is a contiguous fp32 tensor on the planner's device
+        holding the natural blob (flatten_weights' layout; CemTrainer.weights_dev() is one).  The images are packed by kernels on the
+        planner's stream, which first waits for what torch's current stream has queued; nothing synchronises with the host."""
+        t = self._torch
+        if not (t.is_tensor(blob) and blob.is_cuda and blob.device == self.device and blob.dtype == t.float32 and blob.is_contiguous()):
+            raise ValueError('set_weights_dev takes a contiguous float32 tensor on %s' % (self.device,))
+        self._wait_inputs()
+        _capi.check(self.lib.cem_planner_set_weights_dev(self.h, _ptr(blob), blob.numel()), 'cem_planner_set_weights_dev')
+        blob.record_stream(self.stream)
+        self.have_device_weights = True
+
+    def set_weights_from(self, trainer):
+        """Take a CemTrainer's current weights where they live.  Same device: the planner's stream waits on an event recorded on the
+        trainer's stream and the pack kernels read the trainer's workspace; no host synchronise.  Another device: the host route."""
+        if trainer.device != self.device:
+            self.set_weights(trainer.get_weights())
+            return
+        t = self._torch
+        blob = trainer.weights_dev()
+        if trainer.stream != self.stream:
+            ev = t.cuda.Event()
+            ev.record(trainer.stream)
+            self.stream.wait_event(ev)
+        _capi.check(self.lib.cem_planner_set_weights_dev(self.h, _ptr(blob), blob.numel()), 'cem_planner_set_weights_dev')
+        self.have_device_weights = True
+
+    def weight_images(self):
+        """The device arrays the rollout kernels read their weights from, as uint32 NumPy copies: wpack, bias_h, bias_mu, bias_var, etab
+        (cem_layout_t).  Waits for the planner's stream.  For tests and debugging."""
+        t, lay, c = self._torch, self.layout, self.cfg
+        sizes = dict(wpack=lay.wpack_bytes, bias_h=c.ensemble_size * c.n_layers * 512, bias_mu=c.ensemble_size * 512,
+                     bias_var=c.ensemble_size * 512, etab=lay.etab_bytes)
+        return {k: self._view(getattr(lay, k), n // 4, t.int32).cpu().numpy().view(np.uint32) for k, n in sizes.items()}
 
     def set_normaliser(self, inputs_min, inputs_max):
         mn = np.ascontiguousarray(np.asarray(inputs_min, np.float32))
@@ -641,6 +678,20 @@ class BatchCemPlanner(CemPlanner):
             _capi.check(self.lib.cem_planner_plan_batch(self.h, n, sp, seed, cp, _ptr(ea), _ptr(em), _np_ptr(eo), ap, scp, ip),
                         'cem_planner_plan_batch')
         return self._acts_buf[:n].copy(), self._scores_buf[:n].copy(), self._iters_buf[:n].copy()
+
+
+def stage_model_weights(planner, ensemble):
+    """The weight sync of the model-holding classes (TransitionModel._get_planner, the policies): on the device when the ensemble's
+    weights live there (MlpEnsemble.weights_device) on the planner's device and the planner can take them (a stand-in that only knows
+    set_weights cannot), else over the host as before.  The trainer's stream is drained wherever it last wrote the weights (fit,
+    set_state), so the planner's stream needs no more than its usual wait on the current stream."""
+    get_dev = getattr(ensemble, 'weights_device', None)
+    blob = get_dev() if get_dev is not None and hasattr(planner, 'set_weights_dev') else None
+    if blob is not None and blob.device == planner.device:
+        planner.set_weights_dev(blob)
+        ensemble.weights_read_on(planner.stream)         # the trainer's next write of the blob waits for the pack kernels
+    else:
+        planner.set_weights(ensemble.get_weights())
 
 
 def warm_sigma_floor(cfg: PlannerConfig, floor_frac) -> np.ndarray:

@@ -45,6 +45,7 @@ class MlpEnsemble(object):
         self.version = 0
         self.seed = int(seed) if seed is not None else 0          # key of the Philox noise of __call__ (with the call counter below)
         self._calls = 0                                           # every __call__ without explicit noise draws fresh noise
+        self._device_readers = []                                 # events behind planners' reads of weights_device() (weights_read_on)
 
     def _init_member(self, rng):
         U, L = self.mlp_params['units'], self.mlp_params['n_layers']
@@ -92,10 +93,30 @@ class MlpEnsemble(object):
                                        self.ensemble_size, batch_size=self.batch_size, device=device, activation=self.activation,
                                        dropout_rate=self.dropout_rate, dropout_seed=self._dropout_seed)
             self._trainer_version = None
+        for ev in self._device_readers:                     # planners still packing from the trainer's blob: its stream writes after them
+            self._trainer.stream.wait_event(ev)
+        self._device_readers = []
         if self._trainer_version != self.version:           # weights were replaced from outside: Adam moments restart
             self._trainer.set_state(self._weights)
             self._trainer_version = self.version
         return self._trainer
+
+    def weights_device(self):
+        """The model's current weights as a device tensor — CemTrainer.weights_dev(), a view of the live trainer handle's workspace, no
+        copy — when that handle holds them (after fit, or once weights given to set_weights have been re-staged by a training or
+        inference call), else None.  Never stale: weights replaced from outside make it None until the trainer holds them.  Planners
+        take it without a trip over the host (planner.stage_model_weights)."""
+        tr = getattr(self, '_trainer', None)
+        if tr is None or tr.h is None or self._trainer_version != self.version:
+            return None
+        return tr.weights_dev()
+
+    def weights_read_on(self, stream):
+        """A reader of weights_device() has queued its read on ``stream`` (a torch stream): the trainer's next writes wait for it."""
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._device_readers.append(ev)
 
     # ---- inference (mlp_ensemble.py:122-132,189-193) on the device, through the trainer handle that holds the weights ---------------
     def _forward(self, inputs, map, want, **kw):

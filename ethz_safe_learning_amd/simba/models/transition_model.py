@@ -68,7 +68,7 @@ class TransitionModel(BaseModel):
 
     # ---- device rollouts ----------------------------------------------------------------------------------------
     def _get_planner(self, device='cuda:0'):
-        from ...planner import CemPlanner, PlannerConfig, ScorerConfig
+        from ...planner import CemPlanner, PlannerConfig, ScorerConfig, stage_model_weights
         if self._planner is None:
             ens = self.model
             cfg = PlannerConfig(obs_dim=self.observation_space_dim, act_dim=self.action_space_dim,
@@ -79,7 +79,7 @@ class TransitionModel(BaseModel):
                                 sampling_propagation=self.sampling_propagation, scale_features=self.scale_features)
             self._planner = CemPlanner(cfg, device=device)
         if self._planner_version != self.version:
-            self._planner.set_weights(self.model.get_weights())
+            stage_model_weights(self._planner, self.model)
             self._planner.set_normaliser(self.inputs_min, self.inputs_max)
             self._planner_version = self.version
         return self._planner

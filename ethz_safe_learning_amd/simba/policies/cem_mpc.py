@@ -17,7 +17,7 @@ A warm-started policy also numbers its plans per ENVIRONMENT: the Philox call nu
 import logging
 import numpy as np
 
-from ...planner import PlannerConfig, cached_batch_planner, cached_planner
+from ...planner import PlannerConfig, cached_batch_planner, cached_planner, stage_model_weights
 from .mpc_policy import MpcPolicy
 
 
@@ -82,7 +82,7 @@ class CemMpc(MpcPolicy):
         planner = self._planner if planner is None else planner
         tag = (self.model.uid, self.model.version)            # uid, not id(): ids are reused after garbage collection
         if planner.staged != tag:
-            planner.set_weights(self.model.model.get_weights())
+            stage_model_weights(planner, self.model.model)
             planner.set_normaliser(self.model.inputs_min, self.model.inputs_max)
             planner.staged = tag
 

@@ -84,6 +84,14 @@ class CemTrainer:
         _capi.check(self.lib.cem_trainer_get_state(self.h, _np_ptr(blob), None, None), 'cem_trainer_get_state')
         return unflatten_weights(blob, *self.dims)
 
+    def weights_dev(self):
+        """The trainer's current weights where they live: a float32 view of its workspace in the natural blob layout (no copy; the
+        contents follow the trainer's stream).  What CemPlanner.set_weights_dev / set_weights_from take."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        _capi.check(self.lib.cem_trainer_weights_dev(self.h, C.byref(ptr), C.byref(n)), 'cem_trainer_weights_dev')
+        off = ptr.value - self._ws_view.data_ptr()
+        return self._ws_view[off:off + 4 * n.value].view(self._torch.float32)
+
     def get_moments(self):
         n = self.lib.cem_trainer_blob_floats(C.byref(self.ccfg))
         m, v = np.empty(n, np.float32), np.empty(n, np.float32)

@@ -167,6 +167,11 @@ typedef struct cem_layout {
                             * drained (see cem_planner_plan) */
     size_t stamps;         /* int64 [tiles][4][8] — cycle stamps of the last rollout; written only by -DCEM_STAMPS diagnostic builds */
     size_t total;
+    /* the weights as the rollout kernels read them (test / debug views; written by set_weights and set_weights_dev alike) */
+    size_t wpack, wpack_bytes;   /* the members' packed weight images; wide shapes: the natural blobs, then the images */
+    size_t bias_h;         /* float [E][L][128]  — hidden-layer biases, zero padded (tuned and split kernels) */
+    size_t bias_mu, bias_var;    /* float [E][128] each */
+    size_t etab, etab_bytes;     /* float [E][rows][128] — the per-member feature table: normaliser, head and hidden-layer biases, masks */
 } cem_layout_t;
 
 typedef struct cem_planner cem_planner_t;
@@ -203,6 +208,14 @@ int cem_planner_layout(const cem_planner_t *h, cem_layout_t *out);
  * (mlp_ensemble.py:143-144, transition_model.py:42-50).  Host pointers. */
 int cem_planner_set_weights(cem_planner_t *h, const float *blob, size_t n_floats);
 int cem_planner_set_normaliser(cem_planner_t *h, const float *inputs_min, const float *inputs_max /* [obs+act] */);
+/* The same weight sync from DEVICE memory (after a fit the weights already live there: cem_trainer_weights_dev): the images are packed
+ * by kernels (csrc/cem_pack.h), bit for bit what cem_planner_set_weights uploads.
+ * blob_dev: E members x cem_weight_blob_floats / E floats in DEVICE memory, the layout cem_planner_set_weights takes on the host.
+ * Enqueued on the planner's stream and NOT synchronised: plans queued afterwards on that stream see the new weights, a captured graph
+ * stays valid (the images keep their addresses), the warm-start carry is kept (as set_weights keeps it).  The source must stay
+ * unchanged until the stream has passed the call; ordering against another stream is the caller's business.
+ * CEM_ERR_INVALID_ARG for a NULL handle or pointer or a wrong n_floats, before any device call. */
+int cem_planner_set_weights_dev(cem_planner_t *h, const float *blob_dev, size_t n_floats);
 
 /* CemMpc.generate_action (cem_mpc.py:31-33): state[obs] (host) -> action[act] (host).
  * Noise: Philox4x32-7 keyed (seed, call) when the eps pointers are NULL, otherwise explicit
@@ -419,6 +432,9 @@ int cem_trainer_destroy(cem_trainer_t *h);
 /* weights + Adam moments (host blobs; moments may be NULL = zeros) */
 int cem_trainer_set_state(cem_trainer_t *h, const float *weights, const float *m, const float *v);
 int cem_trainer_get_state(cem_trainer_t *h, float *weights, float *m, float *v);
+/* the trainer's current weights where they live: a device pointer into its workspace (valid until destroy; contents follow the
+ * trainer's stream) and the float count — what cem_planner_set_weights_dev takes */
+int cem_trainer_weights_dev(cem_trainer_t *h, const float **blob_dev_out, size_t *n_floats_out);
 /* one training_step on rows perm[member][offset .. offset+bt) of x_dev[n][inputs_dim] / y_dev[n][outputs_dim];
  * lr_t = lr * sqrt(1-beta2^t)/(1-beta1^t) (Keras folds the bias correction into the step size);
  * loss_dev[ensemble_size] receives every member's share of the loss (their sum is training_step's return value) */

@@ -16,6 +16,7 @@ CEM_COMM_ID_BYTES = 128
 CEM_MAX_BATCH = 256
 CEM_TRAIN_MAX_BATCH = 4096
 CEM_INIT_COLD, CEM_INIT_EXPLICIT, CEM_INIT_SHIFT = 0, 1, 2      # enum cem_init_mode
+CEM_VARIANT_CEM, CEM_VARIANT_SAFE, CEM_VARIANT_COST = 0, 1, 2    # enum cem_variant
 CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

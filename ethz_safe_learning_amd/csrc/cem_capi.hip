@@ -1,6 +1,7 @@
 // cem_capi.hip — host side of the C ABI declared in include/cem_mpc.h.
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC (see csrc/build.sh).
 #include "cem_device.h"
+#include "cem_constraint.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -97,7 +98,9 @@ int validate(const cem_config_t *c)
         const long long nq = (c->obs_dim + c->act_dim + 3) / 4 - c->obs_dim / 4;
         if ((long long)c->n_samples * c->horizon * nq * 16 > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;
     }
-    if (c->variant != CEM_VARIANT_CEM && c->variant != CEM_VARIANT_SAFE) return CEM_ERR_INVALID_ARG;
+    if (c->variant != CEM_VARIANT_CEM && c->variant != CEM_VARIANT_SAFE && c->variant != CEM_VARIANT_COST) return CEM_ERR_INVALID_ARG;
+    // the cost objective's reduce is rank-local and would serve a shard as it is; no multi-rank run of it has been made, so it is not offered
+    if (c->variant == CEM_VARIANT_COST && c->world_size > 1) return CEM_ERR_UNSUPPORTED;
     if (c->chunks_per_tile < 0 || c->chunks_per_tile > 4) return CEM_ERR_INVALID_ARG;
     if (c->rollout_segments < 0 || c->rollout_segments > 64) return CEM_ERR_INVALID_ARG;
     if (c->select_mode < 0 || c->select_mode > 3) return CEM_ERR_INVALID_ARG;
@@ -715,7 +718,9 @@ struct cem_planner {
     std::vector<std::pair<int, int>> ev_kind;   // (event index of start, kind 0 rollout / 1 select / 2 reduce / 3 sampler launch)
     // graph
     hipGraph_t graph; hipGraphExec_t gexec; bool graph_ready;
-    ScorerDev sc;
+    ScorerDev sc;                            // the scorer as configured: cem_scorer_reward / cem_scorer_cost
+    ScorerDev sc_roll;                       // what the rollouts and cem_compute_objective score with: sc — on a CEM_VARIANT_COST handle with a goal
+                                             // threshold of -inf, so that no row is ever done and the cost bytes are un-masked (cem_constraint.h)
     float alpha, beta;
     void *comm;                              // ncclComm_t of cem_planner_comm_init, or null (the host exchanges scores_local -> scores_global)
     int plans_since_comm;                    // the first plan after comm_init runs eagerly (RCCL sets itself up lazily), then the graph is captured
@@ -949,6 +954,8 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     sc.reward_distance = s.reward_distance; sc.reward_goal = s.reward_goal; sc.reward_clip = s.reward_clip;
     sc.indicator = s.constrain_indicator; sc.n_cost = s.n_cost_kinds;
     for (int i = 0; i < 4; ++i) { sc.cost_lo[i] = s.cost_lo[i]; sc.cost_hi[i] = s.cost_hi[i]; sc.cost_size[i] = s.cost_size[i]; }
+    h->sc_roll = sc;
+    if (cfg->variant == CEM_VARIANT_COST) h->sc_roll.goal_thresh = -std::numeric_limits<float>::infinity();   // goal distances are >= 0: never reached
     {   // Beta prior of safe_cem_mpc.py:113-115 in fp32 tensor arithmetic (mu = 0.5, sigma = 0.27 from :81)
         const float mu = 0.5f, sg = 0.27f;
         const float alpha = (((1.0f - mu) / (sg * sg)) - 1.0f / mu) * (mu * mu);
@@ -1259,7 +1266,7 @@ void fill_rollout_common(const cem_planner *h, RolloutParams &p)
     p.member_stride_f4 = d.member_stride_f4;
     for (int w = 0; w < 4; ++w) { p.wave_off_f4[w] = d.wave_off_f4[w]; p.wave_groups[w] = (uint32_t)d.wave_groups[w]; }
     p.O = d.O; p.A = d.A; p.L = d.L; p.KB_in = d.KB_in; p.KB_obs = d.KB_obs;
-    p.sampling = h->cfg.sampling_propagation; p.sc = h->sc;
+    p.sampling = h->cfg.sampling_propagation; p.sc = h->sc_roll;
 }
 
 hipEvent_t get_event(cem_planner *h, size_t i)
@@ -1313,8 +1320,10 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     RolloutParams rp; fill_rollout_common(h, rp);
     rp.tiles = (const TileDesc *)(ws + l.tiles); rp.s0 = nullptr; rp.actions = (const float *)(ws + l.actions);
     rp.eps_model = h->eps_model ? h->eps_model + (size_t)it * d.H * d.Btot * d.O : nullptr;
-    rp.ret = (float *)(ws + l.returns); rp.costs = h->cfg.variant == CEM_VARIANT_SAFE ? (uint8_t *)(ws + l.costs) : nullptr;
-    rp.H = d.H; rp.Bloc = d.Bloc; rp.Btot = d.Btot; rp.it = it; rp.variant = h->cfg.variant; rp.check_done = 1;
+    // CEM_VARIANT_COST: the safe variant's launch (its cost bytes, un-masked by sc_roll's threshold); the returns it also writes mean nothing
+    const bool cost_obj = h->cfg.variant == CEM_VARIANT_COST;
+    rp.ret = (float *)(ws + l.returns); rp.costs = h->cfg.variant != CEM_VARIANT_CEM ? (uint8_t *)(ws + l.costs) : nullptr;
+    rp.H = d.H; rp.Bloc = d.Bloc; rp.Btot = d.Btot; rp.it = it; rp.variant = cost_obj ? (int)CEM_VARIANT_SAFE : h->cfg.variant; rp.check_done = 1;
     rp.stamps = (long long *)(ws + l.stamps);
     // the sampler's inputs and outputs (cem_mpc.py:44-48)
     rp.musig = (const float *)(ws + l.musig); rp.eps_act = h->eps_act ? h->eps_act + (size_t)it * d.N * d.H * d.A : nullptr;
@@ -1344,6 +1353,15 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     timed.stop();
     if (fold_reduce) return CEM_OK;
 
+    if (cost_obj) {                                         // scores = -mean cost (cem_constraint.h); timed as the reduce launch it replaces
+        ConstraintReduceParams cp{}; cp.costs = rp.costs; cp.scores = (float *)(ws + l.scores_local); cp.ctrl = rp.ctrl;
+        cp.Nloc = d.Nloc; cp.P = d.P; cp.H = d.H; cp.check_done = 1;
+        cp.zero = (uint32_t *)(ws + l.ms_hist); cp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;
+        TimedLaunch timed_reduce(h, 2);
+        hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((d.Nloc + 63) / 64, nb), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
+        HIPCHK(hipGetLastError());
+        return CEM_OK;
+    }
     ReduceParams qp{}; qp.ret = rp.ret; qp.costs = rp.costs; qp.scores = (float *)(ws + l.scores_local); qp.ctrl = rp.ctrl;
     qp.Nloc = d.Nloc; qp.P = d.P; qp.H = d.H; qp.variant = h->cfg.variant; qp.check_done = 1;
     qp.alpha = h->alpha; qp.beta = h->beta; qp.thr = h->cfg.posterior_mean_threashold;
@@ -1429,10 +1447,11 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
             if (folded) *folded = true;
         }
         if (cache) lds += (size_t)CEM_SEL_KWORDS(d.N) * 4;
-        // (SafeCemMpc's scores have a crowd near -100: the instantiation that counts and ranks wave by wave; same results either way)
+        // (SafeCemMpc's scores have a crowd near -100, the cost objective's crowd into a few multiples of 1 / P: the instantiation that
+        // counts and ranks wave by wave; same results either way)
         // one workgroup per problem (batch handles: blockIdx.x is the problem)
         const dim3 grid(warm_slots(h));
-        if (cache && h->cfg.variant == CEM_VARIANT_SAFE) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
+        if (cache && h->cfg.variant != CEM_VARIANT_CEM) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
         else if (cache) hipLaunchKernelGGL((cem_select_kernel<true, false>), grid, dim3(1024), lds, h->stream, p);
         else hipLaunchKernelGGL((cem_select_kernel<false, false>), grid, dim3(1024), lds, h->stream, p);
     }
@@ -2031,13 +2050,22 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
     const Dims &d = h->d;
     if (n_rows % d.P != 0) return CEM_ERR_INVALID_ARG;                 // reshape(cum, (particles, -1)) would raise (mpc_policy.py:38)
     if ((long long)n_rows * horizon > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;
-    const bool safe = h->cfg.variant == CEM_VARIANT_SAFE;
+    const bool cost_obj = h->cfg.variant == CEM_VARIANT_COST;             // compute_mean_costs (safe_cem_mpc.py:98-108): scores = -mean cost
+    const bool safe = h->cfg.variant == CEM_VARIANT_SAFE || cost_obj;     // (the safe variant's cost bytes, un-masked by sc_roll's threshold)
     const size_t ret_bytes = align256((size_t)n_rows * 4);
     int st = ensure_scratch(h, ret_bytes + (safe ? (size_t)n_rows * horizon : 0)); if (st) return st;
     ObjectiveParams op{}; op.traj = traj_dev; op.ret = (float *)h->scratch; op.costs = safe ? (uint8_t *)(h->scratch + ret_bytes) : nullptr;
-    op.B = n_rows; op.H = horizon; op.O = d.O; op.variant = h->cfg.variant; op.sc = h->sc;
+    op.B = n_rows; op.H = horizon; op.O = d.O; op.variant = safe ? (int)CEM_VARIANT_SAFE : h->cfg.variant; op.sc = h->sc_roll;
     hipLaunchKernelGGL(cem_objective_kernel, dim3((unsigned)(((size_t)n_rows * 16 + 255) / 256)), dim3(256), 0, h->stream, op);
     HIPCHK(hipGetLastError());
+    if (cost_obj) {
+        ConstraintReduceParams cp{}; cp.costs = op.costs; cp.scores = scores_out_dev; cp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
+        cp.Nloc = n_rows / d.P; cp.P = d.P; cp.H = horizon; cp.check_done = 0;
+        hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((cp.Nloc + 63) / 64), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return CEM_OK;
+    }
     ReduceParams qp{}; qp.ret = op.ret; qp.costs = op.costs; qp.scores = scores_out_dev; qp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
     qp.Nloc = n_rows / d.P; qp.P = d.P; qp.H = horizon; qp.variant = h->cfg.variant; qp.check_done = 0;
     qp.alpha = h->alpha; qp.beta = h->beta; qp.thr = h->cfg.posterior_mean_threashold;

@@ -52,7 +52,7 @@ class PlannerConfig:
     smoothing: float = 0.0
     stddev_threshold: float = -1.0
     noise_stddev: float = 0.0
-    variant: str = 'cem'
+    variant: str = 'cem'               # 'cem' | 'safe' | 'cost' (enum cem_variant; 'cost': scores = -mean cost, SafeCemMpc.optimize_for_safety)
     posterior_mean_threashold: float = 0.15
     sampling_propagation: bool = True
     scale_features: bool = True
@@ -67,6 +67,9 @@ class PlannerConfig:
 
 # mlp_params['activation'] is a string the reference `eval`s (mlp_ensemble.py:14): the TensorFlow names that map onto enum cem_activation
 ACTIVATIONS = {'relu': 0, 'tanh': 1, 'sigmoid': 2, 'elu': 3, 'leaky_relu': 4, 'softplus': 5, 'selu': 6, 'swish': 7, 'silu': 7, 'gelu': 8}
+
+
+VARIANTS = {'cem': _capi.CEM_VARIANT_CEM, 'safe': _capi.CEM_VARIANT_SAFE, 'cost': _capi.CEM_VARIANT_COST}
 
 
 def activation_code(name) -> int:
@@ -101,9 +104,9 @@ def to_c_config(cfg: PlannerConfig) -> _capi.CemConfig:
     c.smoothing, c.stddev_threshold, c.noise_stddev = cfg.smoothing, cfg.stddev_threshold, cfg.noise_stddev
     # `(1.0 - self.smoothing)` is a Python-float difference that TF converts once to fp32 (cem_mpc.py:64-65)
     c.one_minus_smoothing = float(np.float32(1.0 - float(cfg.smoothing)))
-    if cfg.variant not in ('cem', 'safe'):
-        raise ValueError("variant must be 'cem' or 'safe'")
-    c.variant = 1 if cfg.variant == 'safe' else 0
+    if cfg.variant not in VARIANTS:
+        raise ValueError("variant must be 'cem', 'safe' or 'cost'")
+    c.variant = VARIANTS[cfg.variant]
     c.posterior_mean_threashold = cfg.posterior_mean_threashold
     c.sampling_propagation = int(bool(cfg.sampling_propagation))
     c.scale_features = int(bool(cfg.scale_features))
@@ -443,6 +446,12 @@ class CemPlanner:
             raise ValueError('eps_model must be [%sI,H,P*N,O]' % b)
         return ea, em
 
+    def take_calls(self, n=1):
+        """The next n call numbers of the handle's counter (what plan / plan_batch draw when given none), as uint64 [n]; the counter advances."""
+        first = self._call
+        self._call += int(n)
+        return np.arange(first, first + int(n), dtype=np.uint64)
+
     def plan(self, state, seed=0, call=None, eps_act=None, eps_model=None, eps_out=None):
         """CemMpc.generate_action (cem_mpc.py:31-33): state[O] -> (action[A], best_score, iters)."""
         if np.shape(state) != self._st_buf.shape:
@@ -513,7 +522,8 @@ class CemPlanner:
 
     def compute_objective(self, trajectories):
         """MpcPolicy.compute_objective (mpc_policy.py:26-39) / SafeCemMpc.compute_objective (safe_cem_mpc.py:76-96) on a
-        given trajectory tensor [P*n, H+1, O] (rows in the tf.tile order p*n + candidate) -> scores [n] (torch, on the GPU)."""
+        given trajectory tensor [P*n, H+1, O] (rows in the tf.tile order p*n + candidate) -> scores [n] (torch, on the GPU).
+        A 'cost' handle returns the planner's objective -compute_mean_costs (safe_cem_mpc.py:98-108): minus the mean cost, <= 0."""
         t = self._torch
         c = self.cfg
         traj = t.as_tensor(trajectories, dtype=t.float32, device=self.device).contiguous()

@@ -48,6 +48,7 @@ class CemMpc(MpcPolicy):
         self.last_score = None
         self.last_iterations = None
         self.last_scores = None
+        self.last_calls = None                         # Philox call numbers of the rows of the last generate_actions
 
     # ---- planner plumbing -------------------------------------------------------------------------------------
     def _extra_config(self):
@@ -162,8 +163,9 @@ class CemMpc(MpcPolicy):
             warm = dict(slots=sl, calls=np.array(self._next_calls(sl), np.uint64))
         else:
             pl = self.build_batch(st.shape[0])
+            warm = dict(calls=pl.take_calls(st.shape[0]))           # the numbers plan_batch would draw itself, kept for SafeCemMpc's recovery
         actions, scores, iters = pl.plan_batch(st, seed=self.seed, **warm)
-        self.last_scores, self.last_iterations = scores, iters
+        self.last_scores, self.last_iterations, self.last_calls = scores, iters, warm['calls']
         return actions
 
     def do_generate_action(self, state, eps_act=None, eps_model=None, eps_out=None):

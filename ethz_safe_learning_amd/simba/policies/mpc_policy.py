@@ -32,11 +32,12 @@ class MpcPolicy(PolicyBase):
     def _objective_extra_config(self):
         return {}
 
-    def _objective_planner(self):
+    def _objective_planner(self, variant=None):
         """A handle that carries this policy's objective (variant, particles, scorer): the planning handle of a built
-        CemMpc, otherwise a minimal one (its sampling shape is irrelevant to compute_objective)."""
+        CemMpc, otherwise a minimal one (its sampling shape is irrelevant to compute_objective).  variant: another objective than
+        the class's own (SafeCemMpc.compute_mean_costs: 'cost'), always on a minimal handle."""
         pl = getattr(self, '_planner', None)
-        if pl is not None and pl.h is not None:
+        if variant is None and pl is not None and pl.h is not None:
             return pl
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
         if scorer is None:
@@ -45,7 +46,7 @@ class MpcPolicy(PolicyBase):
         cfg = PlannerConfig(obs_dim=m.observation_space_dim, act_dim=m.action_space_dim, ensemble_size=ens.ensemble_size,
                             particles=self.particles, n_samples=ens.ensemble_size, horizon=1, n_elite=1, iterations=1,
                             scorer=scorer.to_scorer_config(), act_low=self.action_space.low, act_high=self.action_space.high,
-                            units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation, variant=self.variant,
+                            units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation, variant=variant or self.variant,
                             **self._objective_extra_config())
         return cached_planner(cfg, device=getattr(self, 'device', 'cuda:0'))
 

@@ -1,8 +1,27 @@
 """SafeCemMpc, reference simba/policies/safe_cem_mpc.py:7-120: CemMpc whose objective masks done trajectories
 before the reward and subtracts 100 from candidates a per-step Beta posterior over particle cost counts calls
 unsafe (:76-96,110-120).  Constructor kwargs as :8-19, including the YAML spelling ``posterior_mean_threashold``.
-``optimize_for_safety`` / ``compute_mean_costs`` (:40-74,98-108) have no callers in the reference and are not
-provided."""
+
+``optimize_for_safety`` (:40-74) is the same CEM loop on the objective ``-compute_mean_costs`` (:98-108), the particle mean of the
+cumulative cost, NOT masked by done: a plan that minimises the predicted cost, whatever it earns.  It runs on a planner handle of its
+own (``PlannerConfig(variant='cost')``, enum cem_variant CEM_VARIANT_COST) of the policy's shape that shares the model's weights;
+``compute_mean_costs`` is that objective as an op on a trajectory tensor and returns the reference's POSITIVE mean costs (the handle's
+scores are their negation).  The reference has no caller of either.
+
+Recovery (beyond the reference, off by default): ``recover_below``.  The safe objective has no way out of a state in which every
+candidate is deemed unsafe: all scores are shifted by -100 alike and the planner optimises the reward as if nothing were wrong.  With
+``recover_below`` a float, a plan whose best score lies below it is followed by ``optimize_for_safety`` on the same state with the same
+Philox call number, and THAT action is returned — by ``generate_action``, and for the rows of ``generate_actions`` that fall below it
+(re-planned together in one batched cost plan).  ``last_recovered`` says which.  Choosing it: a candidate deemed unsafe scores its
+return - 100, so a value such as -50 separates "the best candidate is unsafe" from "it is safe" only when returns are small against
+100; with returns of that size no constant does.  It is the caller's number: nothing is claimed here about the returns or the safety of
+the resulting agent.  ``None`` (the default, and what every shipped preset has): no cost handle is ever created and every result is bit
+for bit what it was.  The cost plans are always cold: warm start (``warm_start=True``) applies to the reward plans alone."""
+import dataclasses
+
+import numpy as np
+
+from ...planner import cached_batch_planner, cached_planner
 from .cem_mpc import CemMpc
 
 
@@ -10,14 +29,78 @@ class SafeCemMpc(CemMpc):
     variant = 'safe'
 
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
-                 stddev_threshold, noise_stddev, posterior_mean_threashold, **kwargs):
+                 stddev_threshold, noise_stddev, posterior_mean_threashold, recover_below=None, **kwargs):
         super().__init__(model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                          stddev_threshold, noise_stddev, **kwargs)
         self.cost = getattr(environment, 'get_cost', None)
         self.posterior_mean_threashold = posterior_mean_threashold
+        self.recover_below = None if recover_below is None else float(recover_below)
+        self._cost_planner = None                      # the CEM_VARIANT_COST handle of optimize_for_safety, built on first use
+        self._cost_batch_planners = {}                 # capacity (a power of two) -> cost batch handle (recovery in generate_actions)
+        self.last_safety_score = None                  # best score of the last optimize_for_safety: minus its mean cost
+        self.last_recovered = None                     # bool (generate_action) / bool [B] (generate_actions): the action is a recovery plan's
 
     def _extra_config(self):
         return dict(posterior_mean_threashold=self.posterior_mean_threashold)
 
     def _objective_extra_config(self):
         return dict(posterior_mean_threashold=self.posterior_mean_threashold)
+
+    # ---- the cost objective (safe_cem_mpc.py:40-74,98-108) --------------------------------------------------------
+    def cost_planner_config(self):
+        return dataclasses.replace(self.planner_config(), variant='cost')
+
+    def build_cost(self):
+        """The cost handle of the policy's shape (shared through the cache like the planning handle), the model's weights staged."""
+        if self._cost_planner is None or self._cost_planner.h is None:
+            self._cost_planner = cached_planner(self.cost_planner_config(), device=self.device)
+        self._sync_model(self._cost_planner)
+        return self._cost_planner
+
+    def build_cost_batch(self, n):
+        cap = 1 << max(int(n) - 1, 0).bit_length()
+        pl = self._cost_batch_planners.get(cap)
+        if pl is None or pl.h is None:
+            pl = self._cost_batch_planners[cap] = cached_batch_planner(self.cost_planner_config(), cap, device=self.device)
+        self._sync_model(pl)
+        return pl
+
+    def optimize_for_safety(self, state, call=None):
+        """safe_cem_mpc.py:40-74: state[O] -> np.float32[A], ``best_so_far + noise`` of the CEM loop that maximises minus the mean
+        cost (no score is returned, as :74; it is kept in ``last_safety_score``).  call: the Philox call number (None: the cost
+        handle's own counter)."""
+        action, score, _ = self.build_cost().plan(np.asarray(state, np.float32), seed=self.seed, call=call)
+        self.last_safety_score = score
+        return action
+
+    def compute_mean_costs(self, trajectories, action_sequences=None):
+        """safe_cem_mpc.py:98-108: trajectories [particles*n, H+1, obs] (rows p*n + candidate) -> the mean over particles of every
+        candidate's summed, un-masked cost, [n], >= 0.  ``action_sequences`` is accepted for signature parity (get_cost ignores
+        actions).  numpy in -> numpy out, torch in -> torch (GPU) out."""
+        pl = self._cost_planner if self._cost_planner is not None and self._cost_planner.h is not None else self._objective_planner('cost')
+        costs = -pl.compute_objective(trajectories)           # the handle's scores are minus the mean cost (cem_mpc.h)
+        return costs.cpu().numpy() if isinstance(trajectories, np.ndarray) else costs
+
+    # ---- opt-in recovery ------------------------------------------------------------------------------------------
+    def generate_action(self, state):
+        if self.recover_below is None:
+            return super().generate_action(state)
+        self.build()
+        call = self._next_calls([self.slot])[0] if self.warm_start else int(self._planner.take_calls()[0])
+        state = np.asarray(state, np.float32)
+        action, score, iters = self._planner.plan(state, seed=self.seed, call=call)
+        self.last_score, self.last_iterations = score, iters
+        self.last_recovered = bool(score < self.recover_below)
+        return self.optimize_for_safety(state, call=call) if self.last_recovered else action
+
+    def generate_actions(self, states, slots=None, reset=None):
+        actions = super().generate_actions(states, slots=slots, reset=reset)
+        if self.recover_below is None:
+            return actions
+        self.last_recovered = np.asarray(self.last_scores) < self.recover_below
+        rows = np.nonzero(self.last_recovered)[0]
+        if rows.size:                                   # the rows below the threshold, together, with the call numbers of the plans they replace
+            st = np.asarray(states, np.float32)
+            actions[rows], _, _ = self.build_cost_batch(rows.size).plan_batch(st[rows], seed=self.seed,
+                                                                              calls=np.asarray(self.last_calls, np.uint64)[rows])
+        return actions

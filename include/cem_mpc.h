@@ -62,7 +62,14 @@ enum cem_status {
                                     run): the plan's result is not valid */
 };
 
-enum cem_variant { CEM_VARIANT_CEM = 0 /* CemMpc */, CEM_VARIANT_SAFE = 1 /* SafeCemMpc */ };
+/* CEM_VARIANT_COST: SafeCemMpc.optimize_for_safety (safe_cem_mpc.py:40-74) — the same CEM loop on the objective -compute_mean_costs
+ * (:98-108): score[n] = -(sum over particles p and steps t < H of cost(s_t) of row p N + n) / P, the cost NOT masked by done.  Scores are
+ * <= 0, the planner maximises them (i.e. minimises the mean cost) and the best score it returns is such a negative mean.  Costs are small
+ * integers, so the sums are exact and the division by P is the only rounding.  One rank only (world_size > 1: CEM_ERR_UNSUPPORTED);
+ * posterior_mean_threashold is ignored.  The rollout of such a handle is the safe variant's launch with a goal threshold that is never
+ * reached: cem_layout_t::costs holds the un-masked per-step cost bytes, and what it leaves in cem_layout_t::returns holds nothing (it is
+ * neither a reward sum of the reference nor read by anything).  Workspace and tile plan are those of CEM_VARIANT_SAFE at the same shape. */
+enum cem_variant { CEM_VARIANT_CEM = 0 /* CemMpc */, CEM_VARIANT_SAFE = 1 /* SafeCemMpc */, CEM_VARIANT_COST = 2 /* SafeCemMpc.optimize_for_safety */ };
 
 /* mlp_params['activation'] of config/models.yaml:12, which the reference `eval`s (mlp_ensemble.py:14): the hidden layers'
  * nonlinearity.  relu (the shipped value) runs on the tuned kernels; the others on the generic rollout kernel and the
@@ -159,8 +166,8 @@ typedef struct cem_layout {
     size_t actions;        /* float [N][H][A]   — the current iteration's clipped action sequences */
     size_t mu_sigma;       /* float [2][H][A]   — sampling mean, stddev */
     size_t elite_idx;      /* int32 [k]         — elite set of the last select, ascending index */
-    size_t returns;        /* float [P*N/world] — per-row done-masked return of the last rollout */
-    size_t costs;          /* uint8 [H][P*N/world] — per-step masked cost (safe variant) */
+    size_t returns;        /* float [P*N/world] — per-row done-masked return of the last rollout (CEM_VARIANT_COST: nothing, see enum cem_variant) */
+    size_t costs;          /* uint8 [H][P*N/world] — per-step masked cost (safe variant); the un-masked cost (CEM_VARIANT_COST) */
     size_t result;         /* uint32 [38]: the last completed plan's result as the final kernel left it, word for word the pinned-host block
                             * cem_planner_plan reads: [0, A) action (float), [32] best score (float), [33] iterations run, [34] early-stop
                             * flag, [35] fault bits, [36] the handle's plan counter, [37] checksum.  Valid after the handle's stream has
@@ -268,7 +275,7 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out);
  * 2 = rollout (its tiles sample their own action sequences, cem_mpc.py:44-48) + select (which forms the particle mean of the CemMpc
  * objective itself, mpc_policy.py:38-39) — single-rank CemMpc plans whose tiles are all resident at once; + 1 where the sampler is a
  * launch of its own (tiles queue for slots), + 1 where the reduce kernel stays (SafeCemMpc's Beta filter, sharded plans, the
- * multi-workgroup selects), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
+ * multi-workgroup selects; CEM_VARIANT_COST: its own reduce, csrc/cem_constraint.h), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
  * chain.  The stepwise calls always launch the reduce kernel. */
 int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches_out);
 
@@ -284,7 +291,9 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
  * (the tf.tile order of cem_mpc.py:49-51) -> scores[n_rows / particles] (device).  Uses the handle's variant, particles,
  * posterior threshold and scorer; `horizon` need not be the handle's.  The planner's own rollouts never call this (their
  * objective is the rollout kernel's epilogue and the trajectory is never materialised); it serves callers that hold a
- * trajectory tensor, e.g. from cem_unfold_sequences. */
+ * trajectory tensor, e.g. from cem_unfold_sequences.
+ * On a CEM_VARIANT_COST handle this is SafeCemMpc.compute_mean_costs (safe_cem_mpc.py:98-108) with the SIGN of the planner's objective:
+ * scores[n] = -(mean over particles of the summed un-masked cost) <= 0; the reference's (positive) mean costs are their negation. */
 int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_rows, int32_t horizon, float *scores_out_dev);
 
 /* MbrlSafetyGym.get_reward / get_cost (safety_gym.py:62-66) -> SafetyGymStateScorer.reward / cost (:110-166), 'goal' task:
@@ -309,7 +318,7 @@ int cem_philox_words(cem_planner_t *h, uint64_t seed, uint64_t call, uint32_t st
  * (enabled by cem_planner_set_timing(h, 1); costs one event pair per launch). */
 int cem_planner_set_timing(cem_planner_t *h, int32_t enable);
 int cem_planner_last_timing(cem_planner_t *h, float *rollout_ms_total, int32_t *rollout_launches, float *select_ms_total);
-/* the same plan's other launches: the particle-mean / Beta-filter kernel (where it is a launch of its own) and the sampler launch (where the
+/* the same plan's other launches: the particle-mean / Beta-filter kernel (where it is a launch of its own; CEM_VARIANT_COST: its cost reduce) and the sampler launch (where the
  * sampler is not the rollout tiles' prologue); 0 where the plan has no such launch */
 int cem_planner_last_timing_detail(cem_planner_t *h, float *reduce_ms_total, float *sampler_ms_total);
 

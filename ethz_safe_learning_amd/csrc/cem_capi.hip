@@ -2186,12 +2186,17 @@ struct cem_trainer {
 static_assert(CEM_TBMAX == CEM_TRAIN_MAX_BATCH, "cem_train.h and cem_mpc.h agree on the largest minibatch");
 
 namespace {
+// on the bit pattern: this file is built with -fno-honor-nans, which lets the compiler fold a NaN test on the value away
+bool finite_positive(float v) { uint32_t u; std::memcpy(&u, &v, 4); return u > 0u && u < 0x7f800000u; }                  // 0 < v < inf
+bool unit_fraction(float v) { uint32_t u; std::memcpy(&u, &v, 4); return u < 0x3f800000u || u == 0x80000000u; }           // 0 <= v < 1
 int validate_train(const cem_train_config_t *c)
 {
     if (!c || c->abi_version != CEM_ABI_VERSION) return CEM_ERR_INVALID_ARG;
     if (c->inputs_dim < 1 || c->outputs_dim < 1 || c->n_layers < 1 || c->ensemble_size < 1 || c->batch_size < 1) return CEM_ERR_INVALID_ARG;
     if (c->units < 1 || c->activation < CEM_ACT_RELU || c->activation > CEM_ACT_GELU) return CEM_ERR_INVALID_ARG;
     if (!(c->dropout_rate >= 0.f && c->dropout_rate < 1.f)) return CEM_ERR_INVALID_ARG;
+    // Adam's constants: a clipvalue of 0 (or below, or NaN) would zero or flip every gradient, an epsilon of 0 divides by sqrt(v) = 0
+    if (!finite_positive(c->clipvalue) || !finite_positive(c->epsilon) || !unit_fraction(c->beta1) || !unit_fraction(c->beta2)) return CEM_ERR_INVALID_ARG;
     if (c->units > CEM_TWIDE || c->inputs_dim > CEM_U || c->outputs_dim > CEM_U || c->batch_size > CEM_TBMAX) return CEM_ERR_UNSUPPORTED;
     return CEM_OK;
 }

@@ -430,7 +430,9 @@ typedef struct cem_train_config {
                                    * counted from cem_trainer_create — cem_trainer_set_state does not restart it, so re-staged weights do not replay masks) is a pure function of (dropout_seed, s, member,
                                    * layer, row of the minibatch, unit): cem_train.h GemmEpi */
     uint32_t dropout_seed_lo, dropout_seed_hi;
-    float beta1, beta2, epsilon, clipvalue;
+    float beta1, beta2, epsilon, clipvalue;      /* Adam: 0 <= beta < 1; epsilon and clipvalue finite and > 0 (anything else is CEM_ERR_INVALID_ARG
+                                   * and a workspace size of 0).  Every gradient element — the sum over the row parts — is clipped to
+                                   * +-clipvalue; for "no clip" pass a large finite value such as 1e30 (infinity is refused) */
 } cem_train_config_t;
 typedef struct cem_trainer cem_trainer_t;
 

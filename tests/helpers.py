@@ -65,6 +65,17 @@ def makefile_flags():
     return [f for f in re.search(r'^FLAGS\s*:=\s*(.*)$', mk, re.M).group(1).replace('$(ARCH)', 'gfx950').split() if f not in ('-fPIC', '-shared')]
 
 
+def train_config(D, O, U, L, E, act=0, rate=0.0, batch_size=64):
+    """A cem_train_config_t with Keras' Adam constants (mlp_ensemble.py:113-117) for the CPU-side checks of the training ABI."""
+    from ethz_safe_learning_amd import _capi
+    c = _capi.CemTrainConfig()
+    c.abi_version = _capi.CEM_ABI_VERSION
+    c.inputs_dim, c.outputs_dim, c.units, c.n_layers, c.ensemble_size = D, O, U, L, E
+    c.batch_size, c.activation, c.dropout_rate = batch_size, act, rate
+    c.beta1, c.beta2, c.epsilon, c.clipvalue = 0.9, 0.999, 1e-5, 1.0
+    return c
+
+
 def make_problem(obs_dim=60, act_dim=2, E=5, n_layers=4, seed=1234, bias_noise=0.05, units=128, **kw):
     pb = o.synthetic_problem(obs_dim=obs_dim, act_dim=act_dim, ensemble_size=E, units=units, n_layers=n_layers, seed=seed, **kw)
     if bias_noise:

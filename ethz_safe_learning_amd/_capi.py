@@ -17,6 +17,7 @@ CEM_MAX_BATCH = 256
 CEM_TRAIN_MAX_BATCH = 4096
 CEM_INIT_COLD, CEM_INIT_EXPLICIT, CEM_INIT_SHIFT = 0, 1, 2      # enum cem_init_mode
 CEM_VARIANT_CEM, CEM_VARIANT_SAFE, CEM_VARIANT_COST = 0, 1, 2    # enum cem_variant
+CEM_PARTICLES_MEAN, CEM_PARTICLES_LOWER_TAIL = 0, 1             # enum cem_particle_objective
 CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,7 +31,7 @@ EXPORTED_SYMBOLS = [
     'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_launches_per_iteration', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
     'cem_batch_workspace_bytes', 'cem_batch_planner_create', 'cem_planner_plan_batch', 'cem_planner_batch_capacity',
     'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
-    'cem_planner_get_carry', 'cem_planner_set_carry_slots',
+    'cem_planner_get_carry', 'cem_planner_set_carry_slots', 'cem_planner_set_particle_objective', 'cem_planner_get_particle_objective',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -159,6 +160,8 @@ def load():
     lib.cem_planner_reset_carry.argtypes = [vp, C.c_int32]
     lib.cem_planner_get_carry.argtypes = [vp, C.c_int32, vp, vp, i32p]
     lib.cem_planner_set_carry_slots.argtypes = [vp, C.c_int32, vp]
+    lib.cem_planner_set_particle_objective.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.cem_planner_get_particle_objective.argtypes = [vp, i32p, i32p]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

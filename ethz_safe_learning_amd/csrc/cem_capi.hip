@@ -2,6 +2,7 @@
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC (see csrc/build.sh).
 #include "cem_device.h"
 #include "cem_constraint.h"
+#include "cem_particle_tail.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -746,6 +747,7 @@ struct cem_planner {
     bool warm_save_skipped;                  // the staged plan overwrites the one slot's carry without a copy (stage_warm)
     int warm_staged;                       // problems of the plan whose warm control is staged and whose outcome finish_warm has not seen yet
     std::vector<float> h_expl;               // host copy of the explicit uploads [slots][2][HA]: the source of their stream-ordered copies
+    int tail_m;                              // cem_planner_set_particle_objective: 0 = the particle mean, 1 .. P = the mean of the m smallest returns (cem_particle_tail.h)
 };
 
 namespace {
@@ -908,7 +910,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
           h->sample_in_rollout = std::strcmp(e, "kernel") != 0; }
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
-    h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false;
+    h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
     h->warm = cem_warm_start_t{}; h->warm.shift = 1; h->warm_staged = 0; h->warm_save_skipped = false;
@@ -1362,6 +1364,15 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         HIPCHK(hipGetLastError());
         return CEM_OK;
     }
+    if (h->tail_m) {                                        // the mean of the m smallest particle returns (cem_particle_tail.h); timed as the reduce launch it replaces
+        ConstraintTailParams tp{}; tp.ret = rp.ret; tp.costs = rp.costs; tp.scores = (float *)(ws + l.scores_local); tp.ctrl = rp.ctrl;
+        tp.Nloc = d.Nloc; tp.P = d.P; tp.H = d.H; tp.m = h->tail_m; tp.variant = h->cfg.variant; tp.check_done = 1;
+        tp.alpha = h->alpha; tp.beta = h->beta; tp.thr = h->cfg.posterior_mean_threashold;
+        tp.zero = (uint32_t *)(ws + l.ms_hist); tp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;
+        TimedLaunch timed_reduce(h, 2);
+        HIPCHK(launch_constraint_tail(tp, nb, h->stream));
+        return CEM_OK;
+    }
     ReduceParams qp{}; qp.ret = rp.ret; qp.costs = rp.costs; qp.scores = (float *)(ws + l.scores_local); qp.ctrl = rp.ctrl;
     qp.Nloc = d.Nloc; qp.P = d.P; qp.H = d.H; qp.variant = h->cfg.variant; qp.check_done = 1;
     qp.alpha = h->alpha; qp.beta = h->beta; qp.thr = h->cfg.posterior_mean_threashold;
@@ -1378,6 +1389,7 @@ bool folds_reduce(const cem_planner *h)
 {
     const Dims &d = h->d;
     if (d.W != 1 || h->comm || h->cfg.variant != CEM_VARIANT_CEM) return false;
+    if (h->tail_m) return false;                       // what the select folds IS the mean
     bool cache = false;
     return select_mode_now(h, &cache) == 1 && cache;
 }
@@ -1844,6 +1856,33 @@ int cem_planner_set_warm_start(cem_planner_t *h, const cem_warm_start_t *ws)
     return CEM_OK;
 }
 
+int cem_planner_set_particle_objective(cem_planner_t *h, int32_t kind, int32_t m)
+{
+    if (!h || (kind != CEM_PARTICLES_MEAN && kind != CEM_PARTICLES_LOWER_TAIL)) return CEM_ERR_INVALID_ARG;
+    if (kind == CEM_PARTICLES_LOWER_TAIL && (m < 1 || m > h->d.P)) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    if (kind == CEM_PARTICLES_LOWER_TAIL) {
+        // the kernel is rank-local and would serve a shard as it is; no multi-rank run of it has been made, so it is not offered
+        if (h->cfg.variant == CEM_VARIANT_COST || h->d.W > 1) return CEM_ERR_UNSUPPORTED;
+        if (h->d.P > CEM_TAIL_MAX_P) return CEM_ERR_UNSUPPORTED;
+    }
+    const int tail_m = kind == CEM_PARTICLES_LOWER_TAIL ? m : 0;
+    if (tail_m == h->tail_m) return CEM_OK;
+    // the captured plan holds the other objective's launches (and, changing m alone, the old m): the next plan captures anew
+    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));   // (it may still be draining behind the polled result)
+    drop_graph(h);
+    h->tail_m = tail_m;
+    return CEM_OK;
+}
+
+int cem_planner_get_particle_objective(const cem_planner_t *h, int32_t *kind_out, int32_t *m_out)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (kind_out) *kind_out = h->tail_m ? CEM_PARTICLES_LOWER_TAIL : CEM_PARTICLES_MEAN;
+    if (m_out) *m_out = h->tail_m;
+    return CEM_OK;
+}
+
 int cem_planner_set_initial_distribution(cem_planner_t *h, int32_t slot, const float *mu, const float *sigma)
 {
     if (!h || !mu || !sigma || slot < 0 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
@@ -2063,6 +2102,14 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
         cp.Nloc = n_rows / d.P; cp.P = d.P; cp.H = horizon; cp.check_done = 0;
         hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((cp.Nloc + 63) / 64), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
         HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return CEM_OK;
+    }
+    if (h->tail_m) {
+        ConstraintTailParams tp{}; tp.ret = op.ret; tp.costs = op.costs; tp.scores = scores_out_dev; tp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
+        tp.Nloc = n_rows / d.P; tp.P = d.P; tp.H = horizon; tp.m = h->tail_m; tp.variant = h->cfg.variant; tp.check_done = 0;
+        tp.alpha = h->alpha; tp.beta = h->beta; tp.thr = h->cfg.posterior_mean_threashold;
+        HIPCHK(launch_constraint_tail(tp, 1, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         return CEM_OK;
     }

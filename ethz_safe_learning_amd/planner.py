@@ -8,6 +8,7 @@ corresponds to one compiled ``@tf.function`` graph of the reference
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -63,6 +64,8 @@ class PlannerConfig:
     rollout_segments: int = 0          # 0 auto, 1 off, n > 1: horizon-segment work queue (cem_mpc.h)
     precision: str = 'fp32'            # 'fp32' | 'bf16x3' (enum cem_precision: exact three-way bf16 split products, opt-in)
     select_mode: int = 0               # 0 auto, 1 one-workgroup select, 2 multi-workgroup chain, 3 the chain fused into one launch (cem_mpc.h)
+    worst_particles: int = 0           # 0: score = the particle mean (the reference); m in 1 .. particles: the mean of the m smallest particle
+                                       # returns (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL); not in cem_config_t: set after create
 
 
 # mlp_params['activation'] is a string the reference `eval`s (mlp_ensemble.py:14): the TensorFlow names that map onto enum cem_activation
@@ -70,6 +73,18 @@ ACTIVATIONS = {'relu': 0, 'tanh': 1, 'sigmoid': 2, 'elu': 3, 'leaky_relu': 4, 's
 
 
 VARIANTS = {'cem': _capi.CEM_VARIANT_CEM, 'safe': _capi.CEM_VARIANT_SAFE, 'cost': _capi.CEM_VARIANT_COST}
+PARTICLE_OBJECTIVES = {'mean': _capi.CEM_PARTICLES_MEAN, 'lower_tail': _capi.CEM_PARTICLES_LOWER_TAIL}
+
+
+def risk_particles(risk_level, particles) -> int:
+    """The m of the lower-tail particle objective for a CVaR level: m = min(P, max(1, ceil(risk_level * P - 1e-9))), risk_level in (0, 1].
+    (The guard: 0.07 * 100 is 7.000000000000001 in float64 and would round up to 8.)"""
+    level, P = float(risk_level), int(particles)
+    if not 0.0 < level <= 1.0:                      # (NaN fails both comparisons)
+        raise ValueError('risk_level must lie in (0, 1], got %r' % (risk_level,))
+    if P < 1:
+        raise ValueError('particles must be >= 1')
+    return min(P, max(1, int(math.ceil(level * P - 1e-9))))
 
 
 def activation_code(name) -> int:
@@ -191,6 +206,12 @@ class CemPlanner:
         self.layout = lay
         self._call = 0
         self.has_comm = False
+        if cfg.worst_particles:
+            try:
+                self.set_particle_objective('lower_tail', cfg.worst_particles)
+            except Exception:
+                self.close()
+                raise
         self.have_device_weights = False              # the last weight sync came from device memory (set_weights_dev / set_weights_from)
         # the generate_action hot path: staging buffers and their ctypes views are made once (a.ctypes.data_as and the two small
         # numpy allocations were 12 of the 17 us the wrapper added to a 1.9-ms plan)
@@ -366,6 +387,19 @@ class CemPlanner:
         n = C.c_int32()
         _capi.check(self.lib.cem_planner_launches_per_iteration(self.h, C.byref(n)), 'cem_planner_launches_per_iteration')
         return n.value
+
+    def set_particle_objective(self, kind='mean', m=0):
+        """How a candidate's particle returns become its score (cem_planner_set_particle_objective): 'mean' (the reference, the default)
+        or 'lower_tail' with m in 1 .. particles, the mean of the m smallest returns.  Sticky; a change re-captures the graph."""
+        if kind not in PARTICLE_OBJECTIVES:
+            raise ValueError("kind is 'mean' or 'lower_tail'")
+        _capi.check(self.lib.cem_planner_set_particle_objective(self.h, PARTICLE_OBJECTIVES[kind], int(m)), 'cem_planner_set_particle_objective')
+
+    def particle_objective(self):
+        """('mean', 0) or ('lower_tail', m) (cem_planner_get_particle_objective)."""
+        kind, m = C.c_int32(), C.c_int32()
+        _capi.check(self.lib.cem_planner_get_particle_objective(self.h, C.byref(kind), C.byref(m)), 'cem_planner_get_particle_objective')
+        return ('mean', 'lower_tail')[kind.value], m.value
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')

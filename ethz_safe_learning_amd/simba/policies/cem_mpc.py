@@ -13,11 +13,17 @@ objects of one shape; a warm-started policy therefore gets handles of its OWN (`
 so two policies of one shape never continue each other's plans.
 A warm-started policy also numbers its plans per ENVIRONMENT: the Philox call number of environment e's d-th decision is
 ``e * 2**32 + d``, whether the decision is planned alone (``generate_action``, environment ``self.slot``, 0 by default) or as a row of
-``generate_actions(..., slots=)`` — so an environment sees the same plans however it is batched with others."""
+``generate_actions(..., slots=)`` — so an environment sees the same plans however it is batched with others.
+
+Risk-averse planning (beyond the reference, off by default): with ``risk_level`` a float in (0, 1] a candidate's score is the mean of
+the ``m = planner.risk_particles(risk_level, particles)`` SMALLEST of its particle returns (CVaR at level m / particles;
+``PlannerConfig.worst_particles``, cem_mpc.h CEM_PARTICLES_LOWER_TAIL) instead of the mean of all of them: ``generate_action``,
+``generate_actions`` and ``compute_objective`` then run on that lower tail.  ``None`` (the default, and what every shipped preset has)
+changes no handle and no bit.  Nothing is claimed about the returns or the safety of an agent that uses it."""
 import logging
 import numpy as np
 
-from ...planner import PlannerConfig, cached_batch_planner, cached_planner, stage_model_weights
+from ...planner import PlannerConfig, cached_batch_planner, cached_planner, risk_particles, stage_model_weights
 from .mpc_policy import MpcPolicy
 
 
@@ -26,7 +32,7 @@ class CemMpc(MpcPolicy):
 
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
-                 warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25):
+                 warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -39,6 +45,9 @@ class CemMpc(MpcPolicy):
         self.precision = precision                     # 'fp32' | 'bf16x3' (PlannerConfig.precision; beyond the reference's kwargs)
         # warm start (beyond the reference's kwargs, like precision): see the module docstring
         self.warm_start, self.warm_shift, self.warm_tail, self.warm_sigma, self.warm_sigma_floor = bool(warm_start), warm_shift, warm_tail, warm_sigma, warm_sigma_floor
+        # risk-averse planning (beyond the reference's kwargs): see the module docstring
+        self.risk_level = None if risk_level is None else float(risk_level)
+        self.worst_particles = 0 if risk_level is None else risk_particles(risk_level, particles)
         self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
         self._warm_cap = 1                             # slots the warm-started batch handle must hold
         self.slot = 0                                  # the environment generate_action plans for (warm start: its call numbers)
@@ -71,7 +80,7 @@ class CemMpc(MpcPolicy):
             act_high=self.action_space.high, units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation,
             smoothing=self.smoothing, stddev_threshold=self.stddev_threshold, noise_stddev=self.noise_stddev,
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
-            use_graph=self.use_graph, precision=self.precision, **self._extra_config())
+            use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._extra_config())
 
     def build(self):
         if self._planner is None or self._planner.h is None:      # never built, or closed by its owner

@@ -35,7 +35,8 @@ class MpcPolicy(PolicyBase):
     def _objective_planner(self, variant=None):
         """A handle that carries this policy's objective (variant, particles, scorer): the planning handle of a built
         CemMpc, otherwise a minimal one (its sampling shape is irrelevant to compute_objective).  variant: another objective than
-        the class's own (SafeCemMpc.compute_mean_costs: 'cost'), always on a minimal handle."""
+        the class's own (SafeCemMpc.compute_mean_costs: 'cost'), always on a minimal handle, which aggregates with the particle mean
+        whatever the policy's risk_level."""
         pl = getattr(self, '_planner', None)
         if variant is None and pl is not None and pl.h is not None:
             return pl
@@ -47,7 +48,7 @@ class MpcPolicy(PolicyBase):
                             particles=self.particles, n_samples=ens.ensemble_size, horizon=1, n_elite=1, iterations=1,
                             scorer=scorer.to_scorer_config(), act_low=self.action_space.low, act_high=self.action_space.high,
                             units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation, variant=variant or self.variant,
-                            **self._objective_extra_config())
+                            worst_particles=getattr(self, 'worst_particles', 0) if variant is None else 0, **self._objective_extra_config())
         return cached_planner(cfg, device=getattr(self, 'device', 'cuda:0'))
 
     def compute_objective(self, trajectories, action_sequences=None):

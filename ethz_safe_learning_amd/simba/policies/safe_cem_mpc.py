@@ -16,7 +16,12 @@ Philox call number, and THAT action is returned — by ``generate_action``, and 
 return - 100, so a value such as -50 separates "the best candidate is unsafe" from "it is safe" only when returns are small against
 100; with returns of that size no constant does.  It is the caller's number: nothing is claimed here about the returns or the safety of
 the resulting agent.  ``None`` (the default, and what every shipped preset has): no cost handle is ever created and every result is bit
-for bit what it was.  The cost plans are always cold: warm start (``warm_start=True``) applies to the reward plans alone."""
+for bit what it was.  The cost plans are always cold: warm start (``warm_start=True``) applies to the reward plans alone.
+
+``risk_level`` (CemMpc's, off by default): the reward plans and ``compute_objective`` score a candidate by the mean of its worst particle
+returns, and the Beta filter and its -100 apply to that value unchanged.  ``optimize_for_safety``, ``compute_mean_costs`` and the
+recovery plans of ``recover_below`` keep running on their cost handle with the particle MEAN of the costs: a tail of the particle costs is
+not offered (cem_mpc.h, cem_planner_set_particle_objective)."""
 import dataclasses
 
 import numpy as np
@@ -48,7 +53,7 @@ class SafeCemMpc(CemMpc):
 
     # ---- the cost objective (safe_cem_mpc.py:40-74,98-108) --------------------------------------------------------
     def cost_planner_config(self):
-        return dataclasses.replace(self.planner_config(), variant='cost')
+        return dataclasses.replace(self.planner_config(), variant='cost', worst_particles=0)      # (the cost objective has no lower tail)
 
     def build_cost(self):
         """The cost handle of the policy's shape (shared through the cache like the planning handle), the model's weights staged."""

@@ -275,7 +275,7 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out);
  * 2 = rollout (its tiles sample their own action sequences, cem_mpc.py:44-48) + select (which forms the particle mean of the CemMpc
  * objective itself, mpc_policy.py:38-39) — single-rank CemMpc plans whose tiles are all resident at once; + 1 where the sampler is a
  * launch of its own (tiles queue for slots), + 1 where the reduce kernel stays (SafeCemMpc's Beta filter, sharded plans, the
- * multi-workgroup selects; CEM_VARIANT_COST: its own reduce, csrc/cem_constraint.h), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
+ * multi-workgroup selects; CEM_VARIANT_COST: its own reduce, csrc/cem_constraint.h; CEM_PARTICLES_LOWER_TAIL: its reduce, csrc/cem_particle_tail.h, which no select folds), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
  * chain.  The stepwise calls always launch the reduce kernel. */
 int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches_out);
 
@@ -293,7 +293,8 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
  * objective is the rollout kernel's epilogue and the trajectory is never materialised); it serves callers that hold a
  * trajectory tensor, e.g. from cem_unfold_sequences.
  * On a CEM_VARIANT_COST handle this is SafeCemMpc.compute_mean_costs (safe_cem_mpc.py:98-108) with the SIGN of the planner's objective:
- * scores[n] = -(mean over particles of the summed un-masked cost) <= 0; the reference's (positive) mean costs are their negation. */
+ * scores[n] = -(mean over particles of the summed un-masked cost) <= 0; the reference's (positive) mean costs are their negation.
+ * With CEM_PARTICLES_LOWER_TAIL set (cem_planner_set_particle_objective) the particle returns are aggregated that way here too. */
 int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_rows, int32_t horizon, float *scores_out_dev);
 
 /* MbrlSafetyGym.get_reward / get_cost (safety_gym.py:62-66) -> SafetyGymStateScorer.reward / cost (:110-166), 'goal' task:
@@ -408,6 +409,32 @@ int cem_planner_get_carry(cem_planner_t *h, int32_t slot, float *mu, float *sigm
  * distinct and in 0 .. max_batch - 1, else CEM_ERR_INVALID_ARG (the previous map stays).  A slot that takes no part in a call (its problem
  * index is >= that call's n_states) keeps its carry and its mode. */
 int cem_planner_set_carry_slots(cem_planner_t *h, int32_t n, const int32_t *slots);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The particle objective: how the P particle returns of a candidate become its score.  Beyond the reference, off by default.
+ *   CEM_PARTICLES_MEAN        the reference's reduce_mean (mpc_policy.py:38-39): what every handle does unless told otherwise, with the
+ *                             launches, graph nodes and bits it always had.
+ *   CEM_PARTICLES_LOWER_TAIL  the mean of the m SMALLEST of the P returns, CVaR at level m / P (m = 1: the worst particle).  For
+ *                             candidate n with r_p = returns[p][n]: order the particles ascending by (r_p, p) — equal returns go in
+ *                             particle order —, take the first m, add them in that order as a sequential fp32 sum starting from 0.f,
+ *                             divide once by (float)m.  (m = P is therefore the mean summed in ANOTHER order: not MEAN's bits.)
+ *                             NaN returns are outside the contract.
+ * On a CEM_VARIANT_SAFE handle the Beta filter and the penalty are unchanged and apply to this value: score = value - (unsafe ? 1 : 0) * 100.
+ * The rollouts are untouched; one kernel (csrc/cem_particle_tail.h) takes the place of the particle-mean kernel, and a plan that folded the
+ * mean into its select launches it in addition (cem_planner_launches_per_iteration says so).  Whole plans (graph and eager), the
+ * stepwise calls, batch handles, warm start, every rollout family and cem_compute_objective serve it.
+ * The setting is sticky per handle; changing it drops the captured graph (the next plan captures again) and waits for the stream.  Back
+ * on MEAN the handle gives the bits of one that never left it.
+ *   CEM_ERR_INVALID_ARG  null handle, unknown kind, LOWER_TAIL with m outside 1 .. particles (MEAN ignores m)
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  LOWER_TAIL on a CEM_VARIANT_COST handle (a tail of the particle COSTS is not offered), on world_size > 1 (the
+ *                        kernel is rank-local and would serve a shard; no multi-rank run of it has been made), and for particles > 128
+ *                        (the kernel keeps a block's P x 64 returns in LDS and eight particles per wave in registers)
+ * The handle keeps its previous setting after any of these. */
+enum cem_particle_objective { CEM_PARTICLES_MEAN = 0, CEM_PARTICLES_LOWER_TAIL = 1 };
+int cem_planner_set_particle_objective(cem_planner_t *h, int32_t kind, int32_t m);
+/* kind and m as set (MEAN: m = 0); either pointer may be NULL */
+int cem_planner_get_particle_objective(const cem_planner_t *h, int32_t *kind_out, int32_t *m_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step

@@ -1344,7 +1344,8 @@ __device__ __forceinline__ uint32_t cem_f2key(float f)
 {
     const uint32_t u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;          // NaN sorts lowest (bit test: immune to -fno-honor-nans)
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    // -0.0 takes +0.0's key: tf.nn.top_k compares VALUES, the two zeros tie and the lower index wins (key 0x7FFFFFFF is never produced)
+    return (u & 0x80000000u) && u != 0x80000000u ? ~u : (u | 0x80000000u);
 }
 
 // Histogram add for a whole wave when few bins are hot (the first counted radix pass: sign + exponent bits): LDS atomics
@@ -1365,7 +1366,7 @@ __device__ __forceinline__ void cem_hist_add_clustered(uint32_t *hist, bool matc
     if (match) atomicAdd(&hist[digit], 1u);
 }
 
-__device__ __forceinline__ float cem_key2f(const uint32_t key)       // inverse of cem_f2key (a NaN comes back as a NaN)
+__device__ __forceinline__ float cem_key2f(const uint32_t key)       // inverse of cem_f2key (a NaN comes back as a NaN, either zero as +0.0)
 {
     return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }

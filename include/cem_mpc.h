@@ -151,7 +151,10 @@ typedef struct cem_config {
                                    * to stderr and the handle uses mode 2 from then on (cem_planner_select_mode reports it) — what auto picks
                                    * from 24 000 candidates on (the replicated select of a many-GPU plan; below, mode 1 is faster).  Same elite set, best action and
                                    * early stop in every mode; 2 and 3 are bit-identical; mu / sigma of 1 vs 2 / 3 agree to fp32 rounding
-                                   * (the moments are summed in a different, still fixed, order) */
+                                   * (the moments are summed in a different, still fixed, order).  In every mode equal VALUES tie by candidate
+                                   * index, the lower index first (tf.nn.top_k): -0.0 and +0.0 are one value (the best score of a plan whose best
+                                   * candidate scored -0.0 may be reported as +0.0; the two compare equal); a NaN score ranks below -inf and is
+                                   * never elite while n_elite other candidates exist (fewer than n_elite non-NaN scores: unspecified) */
     int32_t rollout_segments;     /* 0 = auto; 1 = one workgroup per tile for the whole horizon; n > 1 = the rollout launch is a
                                    * work queue of (tile, horizon/n) items drawn by resident workgroups — evens out CU load when the
                                    * tile count is not a multiple of the CU count; results are bit-identical either way */

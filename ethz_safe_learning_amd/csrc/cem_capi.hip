@@ -3,6 +3,7 @@
 #include "cem_device.h"
 #include "cem_constraint.h"
 #include "cem_particle_tail.h"
+#include "cem_constrained.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -748,6 +749,12 @@ struct cem_planner {
     int warm_staged;                       // problems of the plan whose warm control is staged and whose outcome finish_warm has not seen yet
     std::vector<float> h_expl;               // host copy of the explicit uploads [slots][2][HA]: the source of their stream-ordered copies
     int tail_m;                              // cem_planner_set_particle_objective: 0 = the particle mean, 1 .. P = the mean of the m smallest returns (cem_particle_tail.h)
+    // cem_planner_set_constraint (cem_constrained.h)
+    int cost_m;                              // 0 = CEM_CONSTRAINT_BETA; 1 .. P = CEM_CONSTRAINT_BUDGET on the m largest particle costs (P: their mean)
+    float *budget_dev;                       // a device allocation of the handle's own, made on first use: budgets [slots], then cstat [slots][Nloc]
+    std::vector<float> h_budget;             // host copy of the budgets [slots]: the source of their stream-ordered copies
+    float *cstat_obj; size_t cstat_obj_n;    // grow-only cstat of cem_compute_objective (its candidate count is the caller's)
+    const float *last_cstat; int last_cstat_n, last_cstat_problems;   // the C array of the last constrained reduce: per problem [last_cstat_n]
 };
 
 namespace {
@@ -779,6 +786,8 @@ void release_handle(cem_planner *h)
     if (h->h_result) hipHostFree(h->h_result);
     if (h->h_warm) hipHostFree(h->h_warm);
     if (h->pack_desc) hipFree(h->pack_desc);
+    if (h->budget_dev) hipFree(h->budget_dev);
+    if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -911,6 +920,8 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
+    h->cost_m = 0; h->budget_dev = nullptr; h->cstat_obj = nullptr; h->cstat_obj_n = 0; h->last_cstat = nullptr; h->last_cstat_n = h->last_cstat_problems = 0;
+    h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
     h->warm = cem_warm_start_t{}; h->warm.shift = 1; h->warm_staged = 0; h->warm_save_skipped = false;
@@ -1312,6 +1323,14 @@ int enqueue_begin(cem_planner *h)
     return CEM_OK;
 }
 
+// cem_planner_constraint_costs reads the PLAN's C array from here on (not cem_compute_objective's own): said by every constrained reduce
+// that is enqueued and by run_plan, since a replayed graph passes through no enqueue function
+void note_plan_cstat(cem_planner *h)
+{
+    const int nb = warm_slots(h);
+    h->last_cstat = h->budget_dev + nb; h->last_cstat_n = h->d.Nloc; h->last_cstat_problems = nb;
+}
+
 // One iteration up to the scores: the rollout launch (its tiles sample their own action sequences first: cem_tile_sample_actions), then
 // the particle mean / Beta filter — unless `fold_reduce`: a single-rank whole plan on the CemMpc objective lets the select kernel form
 // the particle mean while it stages its keys (same sum, same order, one launch and one graph node fewer per iteration).
@@ -1362,6 +1381,16 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         TimedLaunch timed_reduce(h, 2);
         hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((d.Nloc + 63) / 64, nb), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
         HIPCHK(hipGetLastError());
+        return CEM_OK;
+    }
+    if (h->cost_m) {                                        // return within the cost budget (cem_constrained.h); timed as the reduce launch it replaces
+        ConstrainedBudgetParams bp{}; bp.ret = rp.ret; bp.costs = rp.costs; bp.scores = (float *)(ws + l.scores_local); bp.ctrl = rp.ctrl;
+        bp.budget = h->budget_dev; bp.cstat = h->budget_dev + nb;
+        bp.Nloc = d.Nloc; bp.P = d.P; bp.H = d.H; bp.m = h->cost_m; bp.check_done = 1;
+        bp.zero = (uint32_t *)(ws + l.ms_hist); bp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;
+        note_plan_cstat(h);
+        TimedLaunch timed_reduce(h, 2);
+        HIPCHK(launch_constrained_budget(bp, nb, h->stream));
         return CEM_OK;
     }
     if (h->tail_m) {                                        // the mean of the m smallest particle returns (cem_particle_tail.h); timed as the reduce launch it replaces
@@ -1730,6 +1759,7 @@ int run_plan(cem_planner *h, const PlanCall &pc)
     { const int wst = check_warm(h, pc.n); if (wst) return wst; }
     if (!noise_pair_ok(h, pc)) return CEM_ERR_INVALID_ARG;
     stage_ctrl(h, pc);
+    if (h->cost_m) note_plan_cstat(h);
     if (graph) { const int st = ensure_graph(h); if (st) return st; graph = h->graph_ready; }
     if (graph) {
         HIPCHK(hipGraphLaunch(h->gexec, h->stream));
@@ -1865,6 +1895,7 @@ int cem_planner_set_particle_objective(cem_planner_t *h, int32_t kind, int32_t m
         // the kernel is rank-local and would serve a shard as it is; no multi-rank run of it has been made, so it is not offered
         if (h->cfg.variant == CEM_VARIANT_COST || h->d.W > 1) return CEM_ERR_UNSUPPORTED;
         if (h->d.P > CEM_TAIL_MAX_P) return CEM_ERR_UNSUPPORTED;
+        if (h->cost_m) return CEM_ERR_UNSUPPORTED;         // a lower tail of the returns within a cost budget is not offered (cem_planner_set_constraint)
     }
     const int tail_m = kind == CEM_PARTICLES_LOWER_TAIL ? m : 0;
     if (tail_m == h->tail_m) return CEM_OK;
@@ -1880,6 +1911,72 @@ int cem_planner_get_particle_objective(const cem_planner_t *h, int32_t *kind_out
     if (!h) return CEM_ERR_INVALID_ARG;
     if (kind_out) *kind_out = h->tail_m ? CEM_PARTICLES_LOWER_TAIL : CEM_PARTICLES_MEAN;
     if (m_out) *m_out = h->tail_m;
+    return CEM_OK;
+}
+
+// the handle's budget allocation (cem_planner::budget_dev), made on first use: the budgets as the host copy holds them, cstat zeroed
+static int ensure_budget(cem_planner *h)
+{
+    if (h->budget_dev) return CEM_OK;
+    const size_t nb = (size_t)warm_slots(h), floats = nb + nb * (size_t)h->d.Nloc;
+    HIPCHK(hipMalloc((void **)&h->budget_dev, floats * 4));
+    HIPCHK(hipMemsetAsync(h->budget_dev, 0, floats * 4, h->stream));
+    HIPCHK(hipMemcpyAsync(h->budget_dev, h->h_budget.data(), nb * 4, hipMemcpyHostToDevice, h->stream));
+    return CEM_OK;
+}
+
+int cem_planner_set_constraint(cem_planner_t *h, int32_t kind, int32_t worst_cost_particles)
+{
+    if (!h || (kind != CEM_CONSTRAINT_BETA && kind != CEM_CONSTRAINT_BUDGET)) return CEM_ERR_INVALID_ARG;
+    if (kind == CEM_CONSTRAINT_BUDGET && (worst_cost_particles < 0 || worst_cost_particles > h->d.P)) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    int cost_m = 0;
+    if (kind == CEM_CONSTRAINT_BUDGET) {
+        cost_m = worst_cost_particles ? worst_cost_particles : h->d.P;
+        if (h->cfg.variant != CEM_VARIANT_SAFE) return CEM_ERR_UNSUPPORTED;            // the SAFE rollout's masked cost bytes are what it reads
+        // the kernel is rank-local and would serve a shard as it is; no multi-rank run of it has been made, so it is not offered
+        if (h->d.W > 1) return CEM_ERR_UNSUPPORTED;
+        if (cost_m < h->d.P && h->d.P > CEM_BUDGET_MAX_TAIL_P) return CEM_ERR_UNSUPPORTED;
+        if ((long long)h->d.H * cost_m * CEM_MAX_COST_KINDS >= (1ll << 23)) return CEM_ERR_UNSUPPORTED;   // T must stay below 2^23 (cem_f32_encode_infeasible)
+        if (h->tail_m) return CEM_ERR_UNSUPPORTED;
+    }
+    if (cost_m == h->cost_m) return CEM_OK;
+    // the captured plan holds the other constraint's launches (and, changing m_c alone, the old m_c): the next plan captures anew
+    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));   // (it may still be draining behind the polled result)
+    if (cost_m) { const int st = ensure_budget(h); if (st) return st; }
+    drop_graph(h);
+    h->cost_m = cost_m;
+    return CEM_OK;
+}
+
+int cem_planner_get_constraint(const cem_planner_t *h, int32_t *kind_out, int32_t *worst_cost_particles_out)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (kind_out) *kind_out = h->cost_m ? CEM_CONSTRAINT_BUDGET : CEM_CONSTRAINT_BETA;
+    if (worst_cost_particles_out) *worst_cost_particles_out = h->cost_m;
+    return CEM_OK;
+}
+
+int cem_planner_set_cost_budget(cem_planner_t *h, const float *budgets, int32_t n)
+{
+    if (!h || !budgets || n < 1 || n > warm_slots(h)) return CEM_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i) { uint32_t u; std::memcpy(&u, &budgets[i], 4); if ((u & 0x7fffffffu) > 0x7f800000u) return CEM_ERR_INVALID_ARG; }   // NaN, by its bits (-fno-honor-nans)
+    if (h->in_plan) return CEM_ERR_STATE;
+    const int st = ensure_budget(h); if (st) return st;
+    // through a copy the handle owns (as cem_planner_set_initial_distribution): the caller's array need not outlive this call
+    const int rows = n == 1 ? warm_slots(h) : n;
+    for (int i = 0; i < rows; ++i) h->h_budget[i] = budgets[n == 1 ? 0 : i];
+    HIPCHK(hipMemcpyAsync(h->budget_dev, h->h_budget.data(), (size_t)rows * 4, hipMemcpyHostToDevice, h->stream));
+    return CEM_OK;
+}
+
+int cem_planner_constraint_costs(cem_planner_t *h, int32_t problem, float *out_host, int32_t n)
+{
+    if (!h || !out_host || n < 1 || problem < 0) return CEM_ERR_INVALID_ARG;
+    if (!h->last_cstat) return CEM_ERR_STATE;
+    if (problem >= std::max(h->last_cstat_problems, 1) || n > h->last_cstat_n) return CEM_ERR_INVALID_ARG;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out_host, h->last_cstat + (size_t)problem * h->last_cstat_n, (size_t)n * 4, hipMemcpyDeviceToHost));
     return CEM_OK;
 }
 
@@ -2091,6 +2188,7 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
     if ((long long)n_rows * horizon > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;
     const bool cost_obj = h->cfg.variant == CEM_VARIANT_COST;             // compute_mean_costs (safe_cem_mpc.py:98-108): scores = -mean cost
     const bool safe = h->cfg.variant == CEM_VARIANT_SAFE || cost_obj;     // (the safe variant's cost bytes, un-masked by sc_roll's threshold)
+    if (h->cost_m && (long long)horizon * h->cost_m * CEM_MAX_COST_KINDS >= (1ll << 23)) return CEM_ERR_UNSUPPORTED;   // (the encoding of infeasible scores)
     const size_t ret_bytes = align256((size_t)n_rows * 4);
     int st = ensure_scratch(h, ret_bytes + (safe ? (size_t)n_rows * horizon : 0)); if (st) return st;
     ObjectiveParams op{}; op.traj = traj_dev; op.ret = (float *)h->scratch; op.costs = safe ? (uint8_t *)(h->scratch + ret_bytes) : nullptr;
@@ -2103,6 +2201,21 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
         hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((cp.Nloc + 63) / 64), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
+        return CEM_OK;
+    }
+    if (h->cost_m) {
+        const size_t n_cand = (size_t)(n_rows / d.P);
+        if (n_cand > h->cstat_obj_n) {
+            if (h->cstat_obj) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipFree(h->cstat_obj)); h->cstat_obj = nullptr; h->cstat_obj_n = 0; if (h->last_cstat_problems == 0) h->last_cstat = nullptr; }
+            HIPCHK(hipMalloc((void **)&h->cstat_obj, (n_cand + n_cand / 2) * 4));
+            h->cstat_obj_n = n_cand + n_cand / 2;
+        }
+        ConstrainedBudgetParams bp{}; bp.ret = op.ret; bp.costs = op.costs; bp.scores = scores_out_dev; bp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
+        bp.budget = h->budget_dev; bp.cstat = h->cstat_obj;
+        bp.Nloc = (int32_t)n_cand; bp.P = d.P; bp.H = horizon; bp.m = h->cost_m; bp.check_done = 0;
+        HIPCHK(launch_constrained_budget(bp, 1, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->last_cstat = bp.cstat; h->last_cstat_n = (int)n_cand; h->last_cstat_problems = 0;      // (0: the op's own array)
         return CEM_OK;
     }
     if (h->tail_m) {

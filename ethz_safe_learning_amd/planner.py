@@ -64,6 +64,11 @@ class PlannerConfig:
     rollout_segments: int = 0          # 0 auto, 1 off, n > 1: horizon-segment work queue (cem_mpc.h)
     precision: str = 'fp32'            # 'fp32' | 'bf16x3' (enum cem_precision: exact three-way bf16 split products, opt-in)
     select_mode: int = 0               # 0 auto, 1 one-workgroup select, 2 multi-workgroup chain, 3 the chain fused into one launch (cem_mpc.h)
+    constraint: str = 'beta'           # 'beta': the reference's Beta filter | 'budget': return within a cost budget (cem_planner_set_constraint,
+                                       # CEM_CONSTRAINT_BUDGET; 'safe' handles only); not in cem_config_t: set after create.  The budget VALUE is
+                                       # handle state (CemPlanner.set_cost_budget, default +inf), not configuration
+    worst_cost_particles: int = 0      # 'budget': 0 (or particles) = the particle mean of the cumulative cost; m_c in 1 .. particles - 1: the mean
+                                       # of the m_c largest particle costs (CVaR at level m_c / particles)
     worst_particles: int = 0           # 0: score = the particle mean (the reference); m in 1 .. particles: the mean of the m smallest particle
                                        # returns (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL); not in cem_config_t: set after create
 
@@ -74,6 +79,26 @@ ACTIVATIONS = {'relu': 0, 'tanh': 1, 'sigmoid': 2, 'elu': 3, 'leaky_relu': 4, 's
 
 VARIANTS = {'cem': _capi.CEM_VARIANT_CEM, 'safe': _capi.CEM_VARIANT_SAFE, 'cost': _capi.CEM_VARIANT_COST}
 PARTICLE_OBJECTIVES = {'mean': _capi.CEM_PARTICLES_MEAN, 'lower_tail': _capi.CEM_PARTICLES_LOWER_TAIL}
+CONSTRAINTS = {'beta': _capi.CEM_CONSTRAINT_BETA, 'budget': _capi.CEM_CONSTRAINT_BUDGET}
+INFEASIBLE_BELOW = np.float32(-2.0 ** 100)          # cem_mpc.h CEM_INFEASIBLE_BELOW: a constrained score is feasible iff it lies above
+
+
+def encode_infeasible(total) -> np.float32:
+    """cem_f32_encode_infeasible (cem_mpc.h): the score of an infeasible candidate whose summed cost is the integer `total` in [0, 2^23):
+    -(float)(2^23 + total) * 2^77, exact in fp32 and strictly decreasing in total.  Arrays in, arrays out."""
+    t = np.asarray(total, np.int64)
+    if ((t < 0) | (t >= 1 << 23)).any():
+        raise ValueError('total must lie in [0, 2^23)')
+    return -((t + (1 << 23)).astype(np.float32)) * np.float32(2.0 ** 77)
+
+
+def decode_constrained_score(score):
+    """(feasible, total_or_None) of one score of a 'budget' handle (cem_f32_score_is_feasible / cem_f32_decode_infeasible): feasible iff
+    score > -2^100, and then the score is the mean return; otherwise total = -score * 2^-77 - 2^23, the integer cost that ranked it."""
+    s = np.float32(score)
+    if s > INFEASIBLE_BELOW:
+        return True, None
+    return False, int(-s * np.float32(2.0 ** -77)) - (1 << 23)
 
 
 def risk_particles(risk_level, particles) -> int:
@@ -209,6 +234,12 @@ class CemPlanner:
         if cfg.worst_particles:
             try:
                 self.set_particle_objective('lower_tail', cfg.worst_particles)
+            except Exception:
+                self.close()
+                raise
+        if cfg.constraint != 'beta' or cfg.worst_cost_particles:
+            try:
+                self.set_constraint(cfg.constraint, cfg.worst_cost_particles)
             except Exception:
                 self.close()
                 raise
@@ -400,6 +431,34 @@ class CemPlanner:
         kind, m = C.c_int32(), C.c_int32()
         _capi.check(self.lib.cem_planner_get_particle_objective(self.h, C.byref(kind), C.byref(m)), 'cem_planner_get_particle_objective')
         return ('mean', 'lower_tail')[kind.value], m.value
+
+    def set_constraint(self, kind='beta', worst_cost_particles=0):
+        """What a 'safe' handle's cost bytes do to the scores (cem_planner_set_constraint): 'beta' (the reference's filter, the default) or
+        'budget' — return within the cost budget of set_cost_budget, on the particle mean of the cumulative cost (worst_cost_particles 0)
+        or on the mean of its m_c largest particles.  Sticky; a change re-captures the graph."""
+        if kind not in CONSTRAINTS:
+            raise ValueError("kind is 'beta' or 'budget'")
+        _capi.check(self.lib.cem_planner_set_constraint(self.h, CONSTRAINTS[kind], int(worst_cost_particles)), 'cem_planner_set_constraint')
+
+    def constraint(self):
+        """('beta', 0) or ('budget', m_c), m_c = particles for the mean form (cem_planner_get_constraint)."""
+        kind, m = C.c_int32(), C.c_int32()
+        _capi.check(self.lib.cem_planner_get_constraint(self.h, C.byref(kind), C.byref(m)), 'cem_planner_get_constraint')
+        return ('beta', 'budget')[kind.value], m.value
+
+    def set_cost_budget(self, budget):
+        """The budget(s) of the 'budget' constraint: a scalar sets every problem row of the handle, an array rows 0 .. n - 1 of a batch
+        handle.  A stream-ordered copy: later plans see it, the captured graph stays (cem_planner_set_cost_budget).  Default +inf."""
+        b = np.ascontiguousarray(np.asarray(budget, np.float32).reshape(-1))
+        self.budget_staged = None                     # (whatever a policy noted about the handle's budget no longer holds: SafeCemMpc._stage_budget)
+        _capi.check(self.lib.cem_planner_set_cost_budget(self.h, _np_ptr(b), b.size), 'cem_planner_set_cost_budget')
+
+    def constraint_costs(self, problem=0, n=None):
+        """The cost statistic C [n] of every candidate of `problem` as the last constrained reduce left it (cem_planner_constraint_costs);
+        n defaults to the handle's candidates.  Waits for the planner's stream."""
+        out = np.zeros(self.n_local if n is None else int(n), np.float32)
+        _capi.check(self.lib.cem_planner_constraint_costs(self.h, int(problem), _np_ptr(out), out.size), 'cem_planner_constraint_costs')
+        return out
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')

@@ -82,10 +82,15 @@ class CemMpc(MpcPolicy):
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
             use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._extra_config())
 
+    def _owns_handles(self):
+        """Whether this policy's planning handles carry state of its own (the warm-start carry; SafeCemMpc: a cost budget) and so must
+        not be shared through the cache with other policies of the shape."""
+        return self.warm_start
+
     def build(self):
         if self._planner is None or self._planner.h is None:      # never built, or closed by its owner
             # one handle per distinct shape, shared by every policy object of that shape (tune_cem_policy.py:109-115)
-            self._planner = self._own(cached_planner(self.planner_config(), device=self.device, owner=self if self.warm_start else None))
+            self._planner = self._own(cached_planner(self.planner_config(), device=self.device, owner=self if self._owns_handles() else None))
         self._sync_model()
 
     def _sync_model(self, planner=None):
@@ -128,7 +133,7 @@ class CemMpc(MpcPolicy):
         pl = self._batch_planners.get(cap)
         if pl is None or pl.h is None:
             pl = self._batch_planners[cap] = self._own(cached_batch_planner(self.planner_config(), cap, device=self.device,
-                                                                            owner=self if self.warm_start else None))
+                                                                            owner=self if self._owns_handles() else None))
         self._sync_model(pl)
         return pl
 

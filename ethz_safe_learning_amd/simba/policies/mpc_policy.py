@@ -32,6 +32,18 @@ class MpcPolicy(PolicyBase):
     def _objective_extra_config(self):
         return {}
 
+    def _objective_config(self, variant=None):
+        """The minimal configuration that carries this policy's objective (its sampling shape is irrelevant to compute_objective)."""
+        scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
+        if scorer is None:
+            raise ValueError('environment must expose its SafetyGymStateScorer as `_scorer` (safety_gym.py:27-29)')
+        m, ens = self.model, self.model.model
+        return PlannerConfig(obs_dim=m.observation_space_dim, act_dim=m.action_space_dim, ensemble_size=ens.ensemble_size,
+                             particles=self.particles, n_samples=ens.ensemble_size, horizon=1, n_elite=1, iterations=1,
+                             scorer=scorer.to_scorer_config(), act_low=self.action_space.low, act_high=self.action_space.high,
+                             units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation, variant=variant or self.variant,
+                             worst_particles=getattr(self, 'worst_particles', 0) if variant is None else 0, **self._objective_extra_config())
+
     def _objective_planner(self, variant=None):
         """A handle that carries this policy's objective (variant, particles, scorer): the planning handle of a built
         CemMpc, otherwise a minimal one (its sampling shape is irrelevant to compute_objective).  variant: another objective than
@@ -40,16 +52,7 @@ class MpcPolicy(PolicyBase):
         pl = getattr(self, '_planner', None)
         if variant is None and pl is not None and pl.h is not None:
             return pl
-        scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
-        if scorer is None:
-            raise ValueError('environment must expose its SafetyGymStateScorer as `_scorer` (safety_gym.py:27-29)')
-        m, ens = self.model, self.model.model
-        cfg = PlannerConfig(obs_dim=m.observation_space_dim, act_dim=m.action_space_dim, ensemble_size=ens.ensemble_size,
-                            particles=self.particles, n_samples=ens.ensemble_size, horizon=1, n_elite=1, iterations=1,
-                            scorer=scorer.to_scorer_config(), act_low=self.action_space.low, act_high=self.action_space.high,
-                            units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation, variant=variant or self.variant,
-                            worst_particles=getattr(self, 'worst_particles', 0) if variant is None else 0, **self._objective_extra_config())
-        return cached_planner(cfg, device=getattr(self, 'device', 'cuda:0'))
+        return cached_planner(self._objective_config(variant), device=getattr(self, 'device', 'cuda:0'))
 
     def compute_objective(self, trajectories, action_sequences=None):
         """mpc_policy.py:26-39 (SafeCemMpc: safe_cem_mpc.py:76-96): trajectories [particles*n, H+1, obs] in the tf.tile row

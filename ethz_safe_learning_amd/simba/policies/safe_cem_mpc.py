@@ -21,12 +21,26 @@ for bit what it was.  The cost plans are always cold: warm start (``warm_start=T
 ``risk_level`` (CemMpc's, off by default): the reward plans and ``compute_objective`` score a candidate by the mean of its worst particle
 returns, and the Beta filter and its -100 apply to that value unchanged.  ``optimize_for_safety``, ``compute_mean_costs`` and the
 recovery plans of ``recover_below`` keep running on their cost handle with the particle MEAN of the costs: a tail of the particle costs is
-not offered (cem_mpc.h, cem_planner_set_particle_objective)."""
+not offered there (cem_mpc.h, cem_planner_set_particle_objective).
+
+Budget-constrained planning (beyond the reference, off by default): ``cost_budget``.  With ``cost_budget`` a float the reward plans rank
+candidates by return WITHIN a budget on the predicted cumulative cost instead of by the Beta filter (``PlannerConfig.constraint =
+'budget'``, cem_mpc.h CEM_CONSTRAINT_BUDGET): a candidate is feasible when its cost statistic — the particle mean of its
+summed, done-masked cost, or with ``cost_risk_level`` in (0, 1] the mean of its ``planner.risk_particles(cost_risk_level, particles)``
+WORST particles — is at most the budget; feasible candidates rank by return and, below all of them, infeasible ones by ascending cost.
+``posterior_mean_threashold`` then plays no part.  The budget is state of the planner handle, so such a policy plans on handles of its
+own (as a warm-started one does); ``set_cost_budget`` changes it between decisions without re-capturing anything — to lower it as an
+episode's costs accrue, or, with an array, to give the rows of ``generate_actions`` budgets of their own.  After a plan
+``last_feasible`` says whether the best candidate was feasible (a bool, or a bool array over the rows) and ``last_cost_total`` holds the
+summed cost T that ranked an infeasible best (``None`` where it is feasible).  An infeasible best scores below -2^100, hence below any
+``recover_below``, which keeps working unchanged and replaces it by the ``optimize_for_safety`` action.  ``optimize_for_safety`` and
+``compute_mean_costs`` are untouched.  ``None`` (the default, and what every shipped preset has) touches no handle and changes no bit.
+Nothing is claimed about the returns or the safety of an agent that uses it."""
 import dataclasses
 
 import numpy as np
 
-from ...planner import cached_batch_planner, cached_planner
+from ...planner import cached_batch_planner, cached_planner, decode_constrained_score, risk_particles
 from .cem_mpc import CemMpc
 
 
@@ -34,7 +48,8 @@ class SafeCemMpc(CemMpc):
     variant = 'safe'
 
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
-                 stddev_threshold, noise_stddev, posterior_mean_threashold, recover_below=None, **kwargs):
+                 stddev_threshold, noise_stddev, posterior_mean_threashold, recover_below=None, cost_budget=None, cost_risk_level=None,
+                 **kwargs):
         super().__init__(model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                          stddev_threshold, noise_stddev, **kwargs)
         self.cost = getattr(environment, 'get_cost', None)
@@ -44,16 +59,91 @@ class SafeCemMpc(CemMpc):
         self._cost_batch_planners = {}                 # capacity (a power of two) -> cost batch handle (recovery in generate_actions)
         self.last_safety_score = None                  # best score of the last optimize_for_safety: minus its mean cost
         self.last_recovered = None                     # bool (generate_action) / bool [B] (generate_actions): the action is a recovery plan's
+        # budget-constrained planning (beyond the reference's kwargs): see the module docstring
+        if cost_budget is None and cost_risk_level is not None:
+            raise ValueError('cost_risk_level needs a cost_budget')
+        self.cost_budget = None if cost_budget is None else self._as_budget(cost_budget)
+        self.cost_risk_level = None if cost_risk_level is None else float(cost_risk_level)
+        self.worst_cost_particles = 0 if cost_risk_level is None else risk_particles(cost_risk_level, particles)
+        self._objective_budget_planner = None          # compute_objective's own minimal handle while the planning handle is not built
+        self.last_feasible = None                      # bool (generate_action) / bool [B] (generate_actions): the best candidate met the budget
+        self.last_cost_total = None                    # the summed cost T of an infeasible best, None where it is feasible (per row: an object array)
 
     def _extra_config(self):
-        return dict(posterior_mean_threashold=self.posterior_mean_threashold)
+        if self.cost_budget is None:
+            return dict(posterior_mean_threashold=self.posterior_mean_threashold)
+        return dict(posterior_mean_threashold=self.posterior_mean_threashold, constraint='budget', worst_cost_particles=self.worst_cost_particles)
+
+    # ---- the cost budget ------------------------------------------------------------------------------
+    @staticmethod
+    def _as_budget(value):
+        b = np.asarray(value, np.float32)
+        if b.ndim > 1 or b.size < 1 or np.isnan(b).any():
+            raise ValueError('cost_budget is a float or one float per row, not NaN')
+        return np.float32(b) if b.ndim == 0 else b.copy()
+
+    def set_cost_budget(self, value):
+        """The budget of the following plans: a float, or an array with one budget per row of the following generate_actions calls.
+        A stream-ordered copy on the policy's own handles; nothing is re-captured."""
+        if self.cost_budget is None:
+            raise ValueError('this policy was built without a cost budget (the constraint is part of its handles\' configuration): '
+                             'construct it with cost_budget=')
+        self.cost_budget = self._as_budget(value)
+
+    def _owns_handles(self):
+        return self.warm_start or self.cost_budget is not None
+
+    def _stage_budget(self, planner, scalar_only=False):
+        """The policy's budget onto one of its handles, when it is not what the handle holds already."""
+        b = self.cost_budget
+        if np.ndim(b) and (scalar_only or b.size > planner.max_batch):
+            raise ValueError('%d budgets for a handle of %d problem row(s)' % (b.size, planner.max_batch))
+        tag = np.atleast_1d(b).tobytes() + bytes([np.ndim(b)])
+        if getattr(planner, 'budget_staged', None) != tag:
+            planner.set_cost_budget(b)
+            planner.budget_staged = tag
+
+    def build(self):
+        super().build()
+        if self.cost_budget is not None:
+            self._stage_budget(self._planner, scalar_only=True)
+
+    def build_batch(self, n):
+        pl = super().build_batch(n)
+        if self.cost_budget is not None:
+            self._stage_budget(pl)
+        return pl
+
+    def _objective_planner(self, variant=None):
+        if variant is not None or self.cost_budget is None:
+            return super()._objective_planner(variant)
+        pl = self._planner
+        if pl is None or pl.h is None:                 # not built: a minimal handle of the policy's own carries the constraint and the budget
+            pl = self._objective_budget_planner
+            if pl is None or pl.h is None:
+                cfg = dataclasses.replace(self._objective_config(), constraint='budget', worst_cost_particles=self.worst_cost_particles)
+                pl = self._objective_budget_planner = cached_planner(cfg, device=self.device, owner=self)
+        self._stage_budget(pl, scalar_only=True)
+        return pl
+
+    def _note_feasibility(self, scores):
+        """last_feasible / last_cost_total from the best score(s) of the plan just made."""
+        if self.cost_budget is None:
+            return
+        dec = [decode_constrained_score(s) for s in np.atleast_1d(scores)]
+        if np.ndim(scores) == 0:
+            self.last_feasible, self.last_cost_total = dec[0]
+        else:
+            self.last_feasible = np.array([f for f, _ in dec], bool)
+            self.last_cost_total = np.array([t for _, t in dec], object)
 
     def _objective_extra_config(self):
         return dict(posterior_mean_threashold=self.posterior_mean_threashold)
 
     # ---- the cost objective (safe_cem_mpc.py:40-74,98-108) --------------------------------------------------------
     def cost_planner_config(self):
-        return dataclasses.replace(self.planner_config(), variant='cost', worst_particles=0)      # (the cost objective has no lower tail)
+        return dataclasses.replace(self.planner_config(), variant='cost', worst_particles=0,      # (the cost objective has no lower tail
+                                   constraint='beta', worst_cost_particles=0)                     # and no budget)
 
     def build_cost(self):
         """The cost handle of the policy's shape (shared through the cache like the planning handle), the model's weights staged."""
@@ -89,17 +179,23 @@ class SafeCemMpc(CemMpc):
     # ---- opt-in recovery ------------------------------------------------------------------------------------------
     def generate_action(self, state):
         if self.recover_below is None:
-            return super().generate_action(state)
+            action = super().generate_action(state)
+            self._note_feasibility(self.last_score)
+            return action
         self.build()
         call = self._next_calls([self.slot])[0] if self.warm_start else int(self._planner.take_calls()[0])
         state = np.asarray(state, np.float32)
         action, score, iters = self._planner.plan(state, seed=self.seed, call=call)
         self.last_score, self.last_iterations = score, iters
+        self._note_feasibility(score)
         self.last_recovered = bool(score < self.recover_below)
         return self.optimize_for_safety(state, call=call) if self.last_recovered else action
 
     def generate_actions(self, states, slots=None, reset=None):
+        if self.cost_budget is not None and np.ndim(self.cost_budget) and self.cost_budget.size != np.shape(states)[0]:
+            raise ValueError('%d budgets for %d rows of states' % (self.cost_budget.size, np.shape(states)[0]))
         actions = super().generate_actions(states, slots=slots, reset=reset)
+        self._note_feasibility(np.asarray(self.last_scores))
         if self.recover_below is None:
             return actions
         self.last_recovered = np.asarray(self.last_scores) < self.recover_below

@@ -430,7 +430,9 @@ int cem_planner_set_carry_slots(cem_planner_t *h, int32_t n, const int32_t *slot
  * on MEAN the handle gives the bits of one that never left it.
  *   CEM_ERR_INVALID_ARG  null handle, unknown kind, LOWER_TAIL with m outside 1 .. particles (MEAN ignores m)
  *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
- *   CEM_ERR_UNSUPPORTED  LOWER_TAIL on a CEM_VARIANT_COST handle (a tail of the particle COSTS is not offered), on world_size > 1 (the
+ *   CEM_ERR_UNSUPPORTED  LOWER_TAIL on a CEM_VARIANT_COST handle (a tail of the particle COSTS is not offered there; as a CONSTRAINT on a
+ *                        CEM_VARIANT_SAFE handle it is: cem_planner_set_constraint, worst_cost_particles), on a handle whose constraint
+ *                        is CEM_CONSTRAINT_BUDGET (a lower tail of the returns within a budget is not offered), on world_size > 1 (the
  *                        kernel is rank-local and would serve a shard; no multi-rank run of it has been made), and for particles > 128
  *                        (the kernel keeps a block's P x 64 returns in LDS and eight particles per wave in registers)
  * The handle keeps its previous setting after any of these. */
@@ -438,6 +440,70 @@ enum cem_particle_objective { CEM_PARTICLES_MEAN = 0, CEM_PARTICLES_LOWER_TAIL =
 int cem_planner_set_particle_objective(cem_planner_t *h, int32_t kind, int32_t m);
 /* kind and m as set (MEAN: m = 0); either pointer may be NULL */
 int cem_planner_get_particle_objective(const cem_planner_t *h, int32_t *kind_out, int32_t *m_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The constraint of a CEM_VARIANT_SAFE handle: what its cost bytes do to a candidate's score.  Beyond the reference, off by default
+ * (DESIGN.md 4.9).
+ *   CEM_CONSTRAINT_BETA    the reference's per-step Beta filter (safe_cem_mpc.py:90-96,110-120): score = return - (unsafe ? 100 : 0).
+ *                          What every handle does unless told otherwise, with the launches, graph nodes and bits it always had.
+ *   CEM_CONSTRAINT_BUDGET  constrained CEM (Wen & Topcu 2018): maximise the return subject to `predicted cumulative cost <= budget`.
+ *                          For candidate n of problem b, from the done-masked cost bytes costs[H][P][N] and returns[P][N] of the rollout:
+ *                            c_p = sum over t of costs[t][p][n]                       an integer
+ *                            T   = the sum of the m_c largest c_p                     m_c = worst_cost_particles; 0 or P: every particle,
+ *                                                                                     the particle MEAN of the cumulative cost; m_c < P:
+ *                                                                                     its upper tail, CVaR at level m_c / P (1: the worst particle)
+ *                            C   = (float)T / (float)m_c                              one fp32 division
+ *                            feasible iff C <= budget[b]                              in fp32, inclusive
+ *                            R   = (((0.f + r_0) + r_1) + ... + r_{P-1}) / (float)P   the particle mean as CEM_CONSTRAINT_BETA forms it
+ *                            score = feasible ? R : cem_f32_encode_infeasible(T) = -(float)(2^23 + T) * 2^77
+ *                          Infeasible scores are exact, strictly ordered by T and at or below -2^100, so the unchanged select does the
+ *                          whole rule: feasible candidates rank by return and, below all of them, infeasible ones by ascending cost
+ *                          (ties to the lowest index); the best-so-far (strict >) prefers any feasible candidate to any infeasible one and,
+ *                          among infeasible ones, the cheaper.  A mean return at or below -2^100 is outside the contract (reward_clip
+ *                          bounds returns far above it).  The Beta filter and posterior_mean_threashold play no part.
+ * One kernel (csrc/cem_constrained.h) takes the place of the particle-mean / Beta kernel: cem_planner_launches_per_iteration is unchanged.
+ * Whole plans (graph and eager), the stepwise calls, batch handles, warm start, every rollout family, every select form and
+ * cem_compute_objective (which then returns these scores) serve it.  The setting is sticky per handle; a change waits for the stream and
+ * drops the captured graph.  Back on BETA the handle launches exactly what it launched before.
+ *   CEM_ERR_INVALID_ARG  null handle, unknown kind, BUDGET with worst_cost_particles outside 0 .. particles (BETA ignores it)
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  BUDGET on a CEM_VARIANT_CEM or CEM_VARIANT_COST handle (it needs the SAFE rollout's cost bytes); world_size > 1
+ *                        (the kernel is rank-local; no multi-rank run of it has been made); 0 < m_c < particles with particles > 128 (the
+ *                        tail form keeps eight particles per wave in registers); horizon * m_c * CEM_MAX_COST_KINDS >= 2^23 (the encoding);
+ *                        BUDGET while CEM_PARTICLES_LOWER_TAIL is set (and LOWER_TAIL while BUDGET is set)
+ * The handle keeps its previous setting after any of these. */
+enum cem_constraint_kind { CEM_CONSTRAINT_BETA = 0, CEM_CONSTRAINT_BUDGET = 1 };
+int cem_planner_set_constraint(cem_planner_t *h, int32_t kind, int32_t worst_cost_particles);
+/* kind and m_c as they act (BETA: 0; BUDGET: 1 .. particles, the mean form reads back as particles); either pointer may be NULL */
+int cem_planner_get_constraint(const cem_planner_t *h, int32_t *kind_out, int32_t *worst_cost_particles_out);
+/* budgets[n] (host): n == 1 sets every problem row of the handle, 1 < n <= max_batch rows 0 .. n - 1 of a batch handle.  Default +inf
+ * (everything feasible); +-inf are allowed, NaN is CEM_ERR_INVALID_ARG (nothing is written), as are a null pointer and n outside
+ * 1 .. max(max_batch, 1); CEM_ERR_STATE between the begin and end calls of a stepwise plan.  The values live in a small device
+ * allocation the handle owns (created on first use, not part of the workspace) and are read by the kernel at run time: the write is a
+ * stream-ordered copy — plans queued earlier keep the old values, plans queued later see the new ones — and never drops or re-captures
+ * the graph.  May be called on any handle and before cem_planner_set_constraint; only CEM_CONSTRAINT_BUDGET reads the values. */
+int cem_planner_set_cost_budget(cem_planner_t *h, const float *budgets, int32_t n);
+/* C of the first n candidates of `problem` as the last constrained reduce left them (a plan's last iteration, a stepwise rollout, or
+ * cem_compute_objective) -> out_host[n].  Drains the handle's stream; may be called inside a stepwise plan.  CEM_ERR_INVALID_ARG for a
+ * null handle or pointer, a problem outside the last launch, n < 1 or beyond its candidates; CEM_ERR_STATE when no constrained reduce
+ * has run on the handle. */
+int cem_planner_constraint_costs(cem_planner_t *h, int32_t problem, float *out_host, int32_t n);
+
+/* The encoding of infeasible scores, both directions (planner.py mirrors them: encode_infeasible, decode_constrained_score).  T < 2^23:
+ * (float)(2^23 + T) is an integer below 2^24 and the power of two scales it exactly.
+ * On the names: these are inline, not symbols of the library, and every OTHER `cem_<lower-case name>(` of this header is an exported
+ * symbol — tests/test_capi_cpu.py checks exactly that by scanning for such names.  The `f32` (the encoding is an fp32 one) keeps the
+ * three helpers recognisably apart from the exported calls, for that scan and for a reader. */
+#if defined(__HIPCC__)
+#define CEM_INLINE static inline __host__ __device__
+#else
+#define CEM_INLINE static inline
+#endif
+#define CEM_INFEASIBLE_BELOW (-0x1p100f)          /* feasible iff score > CEM_INFEASIBLE_BELOW */
+CEM_INLINE float cem_f32_encode_infeasible(int32_t total) { return -((float)(8388608 + total)) * 0x1p77f; }
+CEM_INLINE int cem_f32_score_is_feasible(float score) { return score > CEM_INFEASIBLE_BELOW; }
+/* T of an infeasible score (call only where !cem_f32_score_is_feasible(score)) */
+CEM_INLINE int32_t cem_f32_decode_infeasible(float score) { return (int32_t)(-score * 0x1p-77f) - 8388608; }
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step

@@ -1,0 +1,158 @@
+"""Budget-constrained planning (cem_planner_set_constraint, CEM_CONSTRAINT_BUDGET), the parts that need no GPU: the symbols, what they
+refuse without a handle, the encoding of infeasible scores in both directions, config_key, the NumPy restatement against hand-written
+arrays, the shape table and the new kernel's code-object metadata.  (tests/test_warm_capi_cpu.py::
+test_planning_kernels_keep_their_register_counts covers the other kernels: every one keeps its registers with the new kernel present,
+whose name it admits.)"""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+from ethz_safe_learning_amd import _capi, planner
+from ethz_safe_learning_amd.planner import PlannerConfig, ScorerConfig, config_key, decode_constrained_score, encode_infeasible, to_c_config
+from tests import constrained_cases as kc
+from tests import helpers as hp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ('cem_planner_set_constraint', 'cem_planner_get_constraint', 'cem_planner_set_cost_budget', 'cem_planner_constraint_costs')
+INVALID_ARG = 1
+
+
+def _cfg(**kw):
+    base = dict(obs_dim=60, act_dim=2, ensemble_size=5, particles=5, n_samples=2000, horizon=30, n_elite=200, iterations=5, variant='safe',
+                scorer=ScorerConfig(goal_slice=(3, 19), cost_kinds=[(22, 38, 0.2)]), act_low=[-1, -1], act_high=[1, 1])
+    base.update(kw)
+    return PlannerConfig(**base)
+
+
+def test_symbols_are_declared_exported_and_listed(built_lib):
+    hdr = open(os.path.join(ROOT, 'include', 'cem_mpc.h')).read()
+    for name in SYMBOLS:
+        assert re.search(r'^int %s\(' % name, hdr, re.M), name
+        assert name in _capi.EXPORTED_SYMBOLS
+        assert getattr(built_lib, name) is not None
+    assert re.search(r'CEM_CONSTRAINT_BETA = 0, CEM_CONSTRAINT_BUDGET = 1', hdr)
+    assert (_capi.CEM_CONSTRAINT_BETA, _capi.CEM_CONSTRAINT_BUDGET) == (0, 1)
+    assert planner.CONSTRAINTS == {'beta': 0, 'budget': 1}
+    assert re.search(r'#define CEM_ABI_VERSION 4\b', hdr) and built_lib.cem_abi_version() == 4
+    for helper in ('cem_f32_encode_infeasible', 'cem_f32_score_is_feasible', 'cem_f32_decode_infeasible'):
+        assert re.search(r'^CEM_INLINE \w+ %s\(' % helper, hdr, re.M), helper
+
+
+def test_null_handle_is_an_invalid_argument_and_writes_nothing(built_lib):
+    for kind, m in ((0, 0), (1, 0), (1, 1), (2, 0)):
+        assert built_lib.cem_planner_set_constraint(None, kind, m) == INVALID_ARG
+    kind, m = C.c_int32(7), C.c_int32(7)
+    assert built_lib.cem_planner_get_constraint(None, C.byref(kind), C.byref(m)) == INVALID_ARG
+    assert (kind.value, m.value) == (7, 7)
+    one = np.array([25.0], np.float32)
+    assert built_lib.cem_planner_set_cost_budget(None, one.ctypes.data_as(C.c_void_p), 1) == INVALID_ARG
+    out = np.full(4, 7.0, np.float32)
+    assert built_lib.cem_planner_constraint_costs(None, 0, out.ctypes.data_as(C.c_void_p), 4) == INVALID_ARG
+    assert (out == 7.0).all() and one[0] == 25.0
+
+
+def test_encoding_round_trips_and_is_strictly_monotone():
+    ts = [0, 1, 2, 3, 1000, (1 << 22), (1 << 23) - 2, (1 << 23) - 1]
+    enc = [encode_infeasible(t) for t in ts]
+    for t, e in zip(ts, enc):
+        assert isinstance(e, np.float32) and e <= np.float32(-2.0 ** 100)
+        assert float(e) == -float((1 << 23) + t) * 2.0 ** 77            # exact: no rounding anywhere
+        assert decode_constrained_score(e) == (False, t)
+        assert kc.decode(e) == (False, t) and kc.encode_infeasible(t) == e
+    assert all(a > b for a, b in zip(enc, enc[1:]))                    # a larger total ranks strictly lower
+    assert enc[0] == np.float32(-2.0 ** 100)                           # the boundary itself is infeasible (T = 0 with a negative budget)
+    for s in (0.0, -100.0, 3.5, -1e30, float(np.nextafter(np.float32(-2.0 ** 100), np.float32(0)))):
+        assert decode_constrained_score(s) == (True, None)
+    np.testing.assert_array_equal(encode_infeasible(np.array(ts)), np.array(enc, np.float32))
+    for bad in (-1, 1 << 23):
+        with pytest.raises(ValueError):
+            encode_infeasible(bad)
+
+
+def test_config_key_tells_the_settings_apart_and_the_c_config_does_not():
+    cfgs = [_cfg(), _cfg(constraint='budget'), _cfg(constraint='budget', worst_cost_particles=1), _cfg(constraint='budget', worst_cost_particles=2)]
+    assert len({config_key(c) for c in cfgs}) == 4
+    assert (_cfg().constraint, _cfg().worst_cost_particles) == ('beta', 0)
+    # not fields of cem_config_t (its size is part of the ABI): the C configuration is the same bytes whatever the setting
+    for c in cfgs[1:]:
+        assert bytes(to_c_config(c)) == bytes(to_c_config(cfgs[0]))
+    assert not any('budget' in f for f in PlannerConfig.__dataclass_fields__)      # the budget VALUE is handle state, not configuration
+
+
+def test_restatement_against_hand_written_arrays():
+    P, N = kc.HAND_P, kc.HAND_N
+    np.testing.assert_array_equal(kc.particle_costs(kc.HAND_COSTS, P, N), kc.HAND_PARTICLE_COSTS)
+    for m_c, want in kc.HAND_TOTALS.items():
+        np.testing.assert_array_equal(kc.totals(kc.HAND_COSTS, P, N, m_c), want, err_msg='m_c = %d' % m_c)
+        got = kc.scores(kc.HAND_RETURNS, kc.HAND_COSTS, P, N, m_c, kc.HAND_BUDGET)
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, kc.HAND_SCORES[m_c], err_msg='m_c = %d' % m_c)
+        stats = kc.cost_stats(kc.HAND_COSTS, P, N, m_c)
+        assert stats.dtype == np.float32
+        np.testing.assert_array_equal(stats, want.astype(np.float32) / np.float32(m_c))
+    # candidate 0 sits exactly ON the budget: <= is inclusive; a hair below the budget it is not feasible
+    assert kc.cost_stats(kc.HAND_COSTS, P, N, 3)[0] == np.float32(kc.HAND_BUDGET) and kc.feasible(kc.HAND_COSTS, P, N, 3, kc.HAND_BUDGET)[0]
+    assert not kc.feasible(kc.HAND_COSTS, P, N, 3, np.nextafter(np.float32(1), np.float32(0)))[0]
+    # candidates 0 and 1: equal T over all particles
+    assert kc.HAND_TOTALS[3][0] == kc.HAND_TOTALS[3][1]
+    # candidate 1: feasible on the mean, not on its worst particle
+    assert kc.feasible(kc.HAND_COSTS, P, N, 3, 1.0)[1] and not kc.feasible(kc.HAND_COSTS, P, N, 1, 1.0)[1]
+    # the elites: at least k feasible -> by return; fewer -> the cheapest infeasible ones fill up, ties to the lowest index
+    np.testing.assert_array_equal(kc.top_k(kc.HAND_SCORES[3], 2), [0, 1])
+    np.testing.assert_array_equal(kc.top_k(kc.HAND_SCORES[1], 3), [0, 2, 3])          # T = 2 (candidate 2) before T = 3 (candidate 1)
+    for m_c in (1, 2, 3):
+        for k in (1, 2, 3, 4):
+            np.testing.assert_array_equal(kc.top_k(kc.HAND_SCORES[m_c], k), kc.constrained_elites(kc.HAND_RETURNS, kc.HAND_COSTS, P, N, m_c, 1.0, k))
+    # budget -1: nothing is feasible, the order is ascending T with ties to the lowest index (candidates 0 and 1 tie at 3)
+    none = kc.scores(kc.HAND_RETURNS, kc.HAND_COSTS, P, N, 3, -1.0)
+    assert [kc.decode(s) for s in none] == [(False, 3), (False, 3), (False, 5), (False, 0)]
+    np.testing.assert_array_equal(kc.top_k(none, 2), [0, 3])
+    # budget +inf: the plain particle mean, in cem_reduce_kernel's order
+    np.testing.assert_array_equal(kc.scores(kc.HAND_RETURNS, kc.HAND_COSTS, P, N, 1, np.inf), kc.mean_returns(kc.HAND_RETURNS))
+    r = np.array([[1e8], [1.0], [-1e8], [1.0]], np.float32)
+    assert kc.mean_returns(r)[0] == np.float32(((np.float32(1e8) + np.float32(1)) + np.float32(-1e8)) + np.float32(1)) / np.float32(4)
+
+
+def test_hand_trajectory_carries_the_hand_costs():
+    from oracle import cem_oracle as o
+    traj = kc.hand_trajectory(6)
+    bytes_ = np.stack([o.cost(traj[:, t], kc.HAND_SP) for t in range(kc.HAND_H)]).reshape(kc.HAND_H, kc.HAND_P, kc.HAND_N)
+    np.testing.assert_array_equal(bytes_.astype(np.uint8), kc.HAND_COSTS)
+    for t in range(kc.HAND_H):                                         # no row ever reaches the goal: nothing is masked
+        assert not o.reward(traj[:, t], traj[:, t + 1], kc.HAND_SP)[1].any()
+
+
+def test_shape_table_is_well_formed():
+    for name, (P, N, H, E, size_frac) in kc.SHAPES.items():
+        assert (P * N) % E == 0 and 0 < size_frac <= 1, name
+    assert {s[0] for s in kc.SHAPES.values()} == {1, 5, 16, 17, 45}
+    assert {s[1] for s in kc.SHAPES.values()} == {70, 130} and {s[2] for s in kc.SHAPES.values()} == {3, 8, 17, 33}
+    hp_ = sorted(s[0] * s[2] for s in kc.SHAPES.values())
+    assert hp_[0] < 256 < hp_[-1]                                      # H P on both sides of one trip of 256 rows
+
+
+@pytest.fixture(scope='module')
+def isa():
+    return hp.device_assembly()
+
+
+def test_budget_kernel_has_no_spills_and_no_scratch(isa):
+    meta = hp.kernel_meta(isa, r'cem_constrained_budget_kernel')
+    assert len(meta) == 1, list(meta)
+    (name, d), = meta.items()
+    assert 'train' in name                                             # what test_planning_kernels_keep_their_register_counts admits
+    assert d['vgpr_spill_count'] == 0 and d['private_segment_fixed_size'] == 0, d
+    assert 0 < d['vgpr_count'] <= 64, d                                # 1024-thread blocks: two resident per CU need <= 64
+    block = re.search(r'\.name:\s+%s\s*\n(.*?)(?=\n\s+- \.|\namdhsa\.target|\Z)' % re.escape(name), isa, re.S).group(0)
+    assert re.search(r'\.sgpr_spill_count:\s+0\b', block), 'SGPRs spilled into vector lanes'
+
+
+def test_policy_constructor_defaults_are_none():
+    from ethz_safe_learning_amd.simba.policies.safe_cem_mpc import SafeCemMpc
+    sig = inspect.signature(SafeCemMpc.__init__).parameters
+    assert sig['cost_budget'].default is None and sig['cost_risk_level'].default is None
+    assert hasattr(SafeCemMpc, 'set_cost_budget')

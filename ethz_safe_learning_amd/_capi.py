@@ -19,6 +19,7 @@ CEM_INIT_COLD, CEM_INIT_EXPLICIT, CEM_INIT_SHIFT = 0, 1, 2      # enum cem_init_
 CEM_VARIANT_CEM, CEM_VARIANT_SAFE, CEM_VARIANT_COST = 0, 1, 2    # enum cem_variant
 CEM_PARTICLES_MEAN, CEM_PARTICLES_LOWER_TAIL = 0, 1             # enum cem_particle_objective
 CEM_CONSTRAINT_BETA, CEM_CONSTRAINT_BUDGET = 0, 1               # enum cem_constraint_kind
+CEM_REFIT_UNIFORM, CEM_REFIT_SOFTMAX = 0, 1                       # enum cem_refit
 CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -34,6 +35,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
     'cem_planner_get_carry', 'cem_planner_set_carry_slots', 'cem_planner_set_particle_objective', 'cem_planner_get_particle_objective',
     'cem_planner_set_constraint', 'cem_planner_get_constraint', 'cem_planner_set_cost_budget', 'cem_planner_constraint_costs',
+    'cem_planner_set_refit', 'cem_planner_get_refit', 'cem_planner_refit_stats',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -168,6 +170,9 @@ def load():
     lib.cem_planner_get_constraint.argtypes = [vp, i32p, i32p]
     lib.cem_planner_set_cost_budget.argtypes = [vp, vp, C.c_int32]
     lib.cem_planner_constraint_costs.argtypes = [vp, C.c_int32, vp, C.c_int32]
+    lib.cem_planner_set_refit.argtypes = [vp, C.c_int32, C.c_float]
+    lib.cem_planner_get_refit.argtypes = [vp, i32p, fp]
+    lib.cem_planner_refit_stats.argtypes = [vp, C.c_int32, vp, C.c_int32]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

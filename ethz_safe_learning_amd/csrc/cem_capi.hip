@@ -4,6 +4,7 @@
 #include "cem_constraint.h"
 #include "cem_particle_tail.h"
 #include "cem_constrained.h"
+#include "cem_refit_weighted.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -755,6 +756,11 @@ struct cem_planner {
     std::vector<float> h_budget;             // host copy of the budgets [slots]: the source of their stream-ordered copies
     float *cstat_obj; size_t cstat_obj_n;    // grow-only cstat of cem_compute_objective (its candidate count is the caller's)
     const float *last_cstat; int last_cstat_n, last_cstat_problems;   // the C array of the last constrained reduce: per problem [last_cstat_n]
+    // cem_planner_set_refit (cem_refit_weighted.h)
+    int refit_kind;                          // CEM_REFIT_UNIFORM: the select's own refit; CEM_REFIT_SOFTMAX: cem_constraint_refit_kernel behind the select
+    float refit_tau, refit_beta;             // the temperature as set and fl32(1 / temperature), rounded once here
+    float *refit_dev;                        // a device allocation of the handle's own, made on first use: the select's discarded blend [slots][2][HA], then ESS [slots][I]
+    bool refit_ran;                          // a weighted select has been put on the stream (cem_planner_refit_stats)
 };
 
 namespace {
@@ -787,6 +793,7 @@ void release_handle(cem_planner *h)
     if (h->h_warm) hipHostFree(h->h_warm);
     if (h->pack_desc) hipFree(h->pack_desc);
     if (h->budget_dev) hipFree(h->budget_dev);
+    if (h->refit_dev) hipFree(h->refit_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
@@ -921,6 +928,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
     h->cost_m = 0; h->budget_dev = nullptr; h->cstat_obj = nullptr; h->cstat_obj_n = 0; h->last_cstat = nullptr; h->last_cstat_n = h->last_cstat_problems = 0;
+    h->refit_kind = CEM_REFIT_UNIFORM; h->refit_tau = 0.f; h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
@@ -1454,6 +1462,11 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     bool cache = false;
     const int mode = select_mode_now(h, &cache);
     if (mode == 0) return CEM_ERR_UNSUPPORTED;          // (an explicit select_mode 1 on a device that grants less dynamic LDS than validate() assumed)
+    // The score-weighted refit (cem_refit_weighted.h): the one-workgroup select as it is, blending into a scratch slice, never stopping and
+    // never handing over the result; cem_constraint_refit_kernel behind it refits the plan's mu / sigma and decides the early stop.
+    const bool weighted = h->refit_kind == CEM_REFIT_SOFTMAX;
+    if (weighted && (mode != 1 || !h->refit_dev)) return CEM_ERR_UNSUPPORTED;      // (cem_planner_set_refit admitted one-workgroup handles only)
+    if (weighted) { p.musig = h->refit_dev; p.threshold = -std::numeric_limits<float>::infinity(); }
     TimedLaunch timed(h, 1);
     if (mode >= 2) {
         MSelParams m{}; m.scores = p.scores; m.actions = p.actions; m.musig = p.musig; m.ctrl = p.ctrl; m.elite_idx = p.elite_idx;
@@ -1482,7 +1495,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
             hipLaunchKernelGGL(cem_msel_final_kernel, dim3(1), dim3(256), 0, h->stream, m);
         }
     } else {
-        if (fold_final && !h->batch) {     // (a batch handle: the final kernel writes every problem's result, then the completion markers)
+        if (fold_final && !h->batch && !weighted) {     // (a batch handle: the final kernel writes every problem's result, then the completion markers)
             p.is_last = it == d.I - 1;
             p.result = h->d_h_result; p.result_dev = (uint32_t *)(ws + l.result); p.eps_out = have_eps_out ? (const float *)(ws + l.eps_out) : nullptr; p.noise_stddev = h->cfg.noise_stddev;
             if (folded) *folded = true;
@@ -1495,6 +1508,15 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
         if (cache && h->cfg.variant != CEM_VARIANT_CEM) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
         else if (cache) hipLaunchKernelGGL((cem_select_kernel<true, false>), grid, dim3(1024), lds, h->stream, p);
         else hipLaunchKernelGGL((cem_select_kernel<false, false>), grid, dim3(1024), lds, h->stream, p);
+        if (weighted) {
+            HIPCHK(hipGetLastError());
+            RefitWeightedParams rw{}; rw.scores = p.scores; rw.actions = p.actions; rw.musig = (float *)(ws + l.musig); rw.ctrl = p.ctrl; rw.elite_idx = p.elite_idx;
+            rw.stat = h->refit_dev + (size_t)warm_slots(h) * 2 * p.HA;
+            rw.N = d.N; rw.k = d.k; rw.HA = p.HA; rw.I = d.I; rw.beta = h->refit_beta;
+            rw.smoothing = p.smoothing; rw.one_minus_smoothing = p.one_minus_smoothing; rw.threshold = h->cfg.stddev_threshold;
+            HIPCHK(launch_refit_weighted(rw, warm_slots(h), h->stream));
+            h->refit_ran = true;
+        }
     }
     HIPCHK(hipGetLastError());
     return CEM_OK;
@@ -1980,6 +2002,60 @@ int cem_planner_constraint_costs(cem_planner_t *h, int32_t problem, float *out_h
     return CEM_OK;
 }
 
+// the handle's refit allocation (cem_planner::refit_dev), made on first use and zeroed: the scratch slices the select of a weighted
+// iteration blends into (finite from the start, so they stay finite), then the ESS rows
+static int ensure_refit(cem_planner *h)
+{
+    if (h->refit_dev) return CEM_OK;
+    const size_t floats = (size_t)warm_slots(h) * (2 * (size_t)h->d.H * h->d.A + (size_t)h->d.I);
+    // the weights of up to 24576 elites: beyond the default 64 KB of dynamic LDS the runtime has to be asked (as the select kernels are, at create)
+    if (CEM_REFIT_LDS_BYTES(h->d.k, h->d.H * h->d.A) > 48 * 1024)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&cem_constraint_refit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipMalloc((void **)&h->refit_dev, floats * 4));
+    HIPCHK(hipMemsetAsync(h->refit_dev, 0, floats * 4, h->stream));
+    return CEM_OK;
+}
+
+int cem_planner_set_refit(cem_planner_t *h, int32_t kind, float temperature)
+{
+    if (!h || (kind != CEM_REFIT_UNIFORM && kind != CEM_REFIT_SOFTMAX)) return CEM_ERR_INVALID_ARG;
+    if (kind == CEM_REFIT_SOFTMAX && (!finite_bits(temperature) || !(temperature > 0.f))) return CEM_ERR_INVALID_ARG;   // (NaN: by its bits, -fno-honor-nans)
+    if (h->in_plan) return CEM_ERR_STATE;
+    if (kind == CEM_REFIT_SOFTMAX) {
+        // one rank and the one-workgroup select: the multi-workgroup forms keep their own moment kernels, which this one does not replace
+        if (h->d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
+        if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;
+        if (CEM_REFIT_LDS_BYTES(h->d.k, h->d.H * h->d.A) > h->sel_dyn_limit) return CEM_ERR_UNSUPPORTED;
+    }
+    const float tau = kind == CEM_REFIT_SOFTMAX ? temperature : 0.f;
+    if (kind == h->refit_kind && std::memcmp(&tau, &h->refit_tau, 4) == 0) return CEM_OK;
+    // the captured plan holds the other refit's launches (and, changing the temperature alone, the old 1 / temperature): the next plan captures anew
+    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));   // (it may still be draining behind the polled result)
+    if (kind == CEM_REFIT_SOFTMAX) { const int st = ensure_refit(h); if (st) return st; }
+    drop_graph(h);
+    h->refit_kind = kind; h->refit_tau = tau; h->refit_beta = kind == CEM_REFIT_SOFTMAX ? 1.0f / temperature : 0.f;
+    return CEM_OK;
+}
+
+int cem_planner_get_refit(const cem_planner_t *h, int32_t *kind_out, float *temperature_out)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (kind_out) *kind_out = h->refit_kind;
+    if (temperature_out) *temperature_out = h->refit_tau;
+    return CEM_OK;
+}
+
+int cem_planner_refit_stats(cem_planner_t *h, int32_t problem, float *ess_out_host, int32_t n)
+{
+    if (!h || !ess_out_host || n < 1 || problem < 0) return CEM_ERR_INVALID_ARG;
+    if (problem >= warm_slots(h) || n > h->d.I) return CEM_ERR_INVALID_ARG;
+    if (!h->refit_ran) return CEM_ERR_STATE;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const float *stat = h->refit_dev + (size_t)warm_slots(h) * 2 * h->d.H * h->d.A + (size_t)problem * h->d.I;
+    HIPCHK(hipMemcpy(ess_out_host, stat, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return CEM_OK;
+}
+
 int cem_planner_set_initial_distribution(cem_planner_t *h, int32_t slot, const float *mu, const float *sigma)
 {
     if (!h || !mu || !sigma || slot < 0 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
@@ -2109,7 +2185,8 @@ int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches
 {
     if (!h || !launches_out) return CEM_ERR_INVALID_ARG;
     const int mode = select_mode_now(h);
-    *launches_out = 1 + (h->sample_in_rollout ? 0 : 1) + (folds_reduce(h) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1));
+    *launches_out = 1 + (h->sample_in_rollout ? 0 : 1) + (folds_reduce(h) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
+                    (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0);
     return CEM_OK;
 }
 

@@ -69,6 +69,9 @@ class PlannerConfig:
                                        # handle state (CemPlanner.set_cost_budget, default +inf), not configuration
     worst_cost_particles: int = 0      # 'budget': 0 (or particles) = the particle mean of the cumulative cost; m_c in 1 .. particles - 1: the mean
                                        # of the m_c largest particle costs (CVaR at level m_c / particles)
+    refit: str = 'uniform'             # 'uniform': every elite counts 1 / k (the reference) | 'softmax': elite j counts exp((s_j - s_max) / temperature)
+                                       # (cem_planner_set_refit, CEM_REFIT_SOFTMAX; n_elite = n_samples is MPPI); not in cem_config_t: set after create
+    refit_temperature: float = 0.0     # 'softmax': the temperature, finite and > 0 ('uniform' ignores it)
     worst_particles: int = 0           # 0: score = the particle mean (the reference); m in 1 .. particles: the mean of the m smallest particle
                                        # returns (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL); not in cem_config_t: set after create
 
@@ -80,6 +83,7 @@ ACTIVATIONS = {'relu': 0, 'tanh': 1, 'sigmoid': 2, 'elu': 3, 'leaky_relu': 4, 's
 VARIANTS = {'cem': _capi.CEM_VARIANT_CEM, 'safe': _capi.CEM_VARIANT_SAFE, 'cost': _capi.CEM_VARIANT_COST}
 PARTICLE_OBJECTIVES = {'mean': _capi.CEM_PARTICLES_MEAN, 'lower_tail': _capi.CEM_PARTICLES_LOWER_TAIL}
 CONSTRAINTS = {'beta': _capi.CEM_CONSTRAINT_BETA, 'budget': _capi.CEM_CONSTRAINT_BUDGET}
+REFITS = {'uniform': _capi.CEM_REFIT_UNIFORM, 'softmax': _capi.CEM_REFIT_SOFTMAX}
 INFEASIBLE_BELOW = np.float32(-2.0 ** 100)          # cem_mpc.h CEM_INFEASIBLE_BELOW: a constrained score is feasible iff it lies above
 
 
@@ -240,6 +244,12 @@ class CemPlanner:
         if cfg.constraint != 'beta' or cfg.worst_cost_particles:
             try:
                 self.set_constraint(cfg.constraint, cfg.worst_cost_particles)
+            except Exception:
+                self.close()
+                raise
+        if cfg.refit != 'uniform':
+            try:
+                self.set_refit(cfg.refit, cfg.refit_temperature)
             except Exception:
                 self.close()
                 raise
@@ -458,6 +468,27 @@ class CemPlanner:
         n defaults to the handle's candidates.  Waits for the planner's stream."""
         out = np.zeros(self.n_local if n is None else int(n), np.float32)
         _capi.check(self.lib.cem_planner_constraint_costs(self.h, int(problem), _np_ptr(out), out.size), 'cem_planner_constraint_costs')
+        return out
+
+    def set_refit(self, kind='uniform', temperature=0.0):
+        """What an iteration does with the elites' scores (cem_planner_set_refit): 'uniform' (the reference's 1 / k, the default) or
+        'softmax' — elite j counts exp((s_j - s_max) / temperature) in the mean and the variance (MPPI when n_elite = n_samples).
+        Sticky; a change, of the temperature alone too, re-captures the graph."""
+        if kind not in REFITS:
+            raise ValueError("kind is 'uniform' or 'softmax'")
+        _capi.check(self.lib.cem_planner_set_refit(self.h, REFITS[kind], float(temperature)), 'cem_planner_set_refit')
+
+    def refit(self):
+        """('uniform', 0.0) or ('softmax', temperature) (cem_planner_get_refit)."""
+        kind, t = C.c_int32(), C.c_float()
+        _capi.check(self.lib.cem_planner_get_refit(self.h, C.byref(kind), C.byref(t)), 'cem_planner_get_refit')
+        return ('uniform', 'softmax')[kind.value], t.value
+
+    def refit_stats(self, problem=0, n=None):
+        """The effective sample size W^2 / sum w^2 of iterations 0 .. n - 1 of `problem`'s last weighted plan (cem_planner_refit_stats);
+        n defaults to the handle's iterations — pass the plan's `iters` after an early stop.  Waits for the planner's stream."""
+        out = np.zeros(self.cfg.iterations if n is None else int(n), np.float32)
+        _capi.check(self.lib.cem_planner_refit_stats(self.h, int(problem), _np_ptr(out), out.size), 'cem_planner_refit_stats')
         return out
 
     def plan_exchange(self):
@@ -817,6 +848,33 @@ def shift_distribution(mu, sigma, mu0, sigma0, shift=1, tail=0, sigma_rule=0, si
     if sigma_rule:
         s[:H - shift] = np.maximum(sigma[shift:], np.asarray(sigma_floor, np.float32))
     return m, s
+
+
+def softmax_refit(scores, elite, actions, mu, sigma, smoothing, temperature):
+    """Host restatement of one CEM_REFIT_SOFTMAX iteration (cem_mpc.h) for users, in fp32 with NumPy's own summation order — the device's
+    values, not its bits.  scores [N], elite [k] candidate indices, actions [N, H, A] (or [N, H * A]), mu / sigma of the actions' trailing
+    shape -> (mu_new, sigma_new, ess)."""
+    f = np.float32
+    tau = f(temperature)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError('temperature must be finite and > 0')
+    e = np.asarray(elite, np.int64).reshape(-1)
+    s = np.asarray(scores, f)[e]
+    a = np.asarray(actions, f)[e]
+    mu, sigma = np.asarray(mu, f), np.asarray(sigma, f)
+    if a.shape[1:] != mu.shape or sigma.shape != mu.shape:
+        raise ValueError('mu / sigma must have the shape of one action row')
+    smax = s.max()
+    beta = f(1.0) / tau
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        w = np.where(s == smax, f(1.0), np.exp(((s - smax) * beta).astype(f)).astype(f)).astype(f)
+    W = w.sum(dtype=f)
+    wb = w.reshape((-1,) + (1,) * mu.ndim)
+    mean = ((wb * a).sum(axis=0, dtype=f) / W).astype(f)
+    d = (a - mean).astype(f)
+    var = ((wb * (d * d)).sum(axis=0, dtype=f) / W).astype(f)
+    sm, osm = f(smoothing), f(1.0 - float(smoothing))
+    return (sm * mu + osm * mean).astype(f), (sm * sigma + osm * np.sqrt(var)).astype(f), f(W * W / (w * w).sum(dtype=f))
 
 
 def plan_tiles(cfg: PlannerConfig):

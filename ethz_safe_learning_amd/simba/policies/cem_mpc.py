@@ -19,7 +19,15 @@ Risk-averse planning (beyond the reference, off by default): with ``risk_level``
 the ``m = planner.risk_particles(risk_level, particles)`` SMALLEST of its particle returns (CVaR at level m / particles;
 ``PlannerConfig.worst_particles``, cem_mpc.h CEM_PARTICLES_LOWER_TAIL) instead of the mean of all of them: ``generate_action``,
 ``generate_actions`` and ``compute_objective`` then run on that lower tail.  ``None`` (the default, and what every shipped preset has)
-changes no handle and no bit.  Nothing is claimed about the returns or the safety of an agent that uses it."""
+changes no handle and no bit.  Nothing is claimed about the returns or the safety of an agent that uses it.
+
+Score-weighted refit (beyond the reference, off by default): with ``elite_temperature`` a float > 0 an iteration refits mu and sigma
+from the elites weighted by ``exp((score - best elite score) / elite_temperature)`` instead of 1 / n_elite each
+(``PlannerConfig.refit = 'softmax'``, cem_mpc.h CEM_REFIT_SOFTMAX): MPPI's update when n_elite = n_samples, "weighted
+elites" below that.  ``generate_action``, ``generate_actions`` and warm-started plans use it; ``last_ess`` holds the effective sample
+size of every iteration of the last plan (a float array; one per row after ``generate_actions``), each in [1, n_elite].  ``None`` (the
+default, and what every shipped preset has) changes no handle and no bit.  Nothing is claimed about the returns or the safety of an
+agent that uses it."""
 import logging
 import numpy as np
 
@@ -32,7 +40,8 @@ class CemMpc(MpcPolicy):
 
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
-                 warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None):
+                 warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None,
+                 elite_temperature=None):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -48,6 +57,11 @@ class CemMpc(MpcPolicy):
         # risk-averse planning (beyond the reference's kwargs): see the module docstring
         self.risk_level = None if risk_level is None else float(risk_level)
         self.worst_particles = 0 if risk_level is None else risk_particles(risk_level, particles)
+        # score-weighted refit (beyond the reference's kwargs): see the module docstring
+        self.elite_temperature = None if elite_temperature is None else float(elite_temperature)
+        if self.elite_temperature is not None and not (np.isfinite(self.elite_temperature) and self.elite_temperature > 0.0):
+            raise ValueError('elite_temperature must be finite and > 0, got %r' % (elite_temperature,))
+        self.last_ess = None                           # ESS per iteration of the last weighted plan (generate_actions: a list, one array per row)
         self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
         self._warm_cap = 1                             # slots the warm-started batch handle must hold
         self.slot = 0                                  # the environment generate_action plans for (warm start: its call numbers)
@@ -62,6 +76,11 @@ class CemMpc(MpcPolicy):
     # ---- planner plumbing -------------------------------------------------------------------------------------
     def _extra_config(self):
         return {}
+
+    def _refit_config(self):
+        if self.elite_temperature is None:
+            return {}
+        return dict(refit='softmax', refit_temperature=self.elite_temperature)
 
     def _scorer_config(self):
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
@@ -80,7 +99,8 @@ class CemMpc(MpcPolicy):
             act_high=self.action_space.high, units=ens.mlp_params['units'], n_layers=ens.mlp_params['n_layers'], activation=ens.activation,
             smoothing=self.smoothing, stddev_threshold=self.stddev_threshold, noise_stddev=self.noise_stddev,
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
-            use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._extra_config())
+            use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._refit_config(),
+            **self._extra_config())
 
     def _owns_handles(self):
         """Whether this policy's planning handles carry state of its own (the warm-start carry; SafeCemMpc: a cost budget) and so must
@@ -143,7 +163,17 @@ class CemMpc(MpcPolicy):
         action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed,
                                                   call=self._next_calls([self.slot])[0] if self.warm_start else None)
         self.last_score, self.last_iterations = score, iters
+        self._note_ess(self._planner, iters)
         return action
+
+    def _note_ess(self, planner, iters):
+        """last_ess from the handle that has just planned (iters: an int, or one per row of a batched plan)."""
+        if self.elite_temperature is None:
+            return
+        if np.ndim(iters) == 0:
+            self.last_ess = planner.refit_stats(0, n=max(int(iters), 1))
+        else:
+            self.last_ess = [planner.refit_stats(b, n=max(int(i), 1)) for b, i in enumerate(iters)]
 
     def _next_calls(self, slots):
         """Call numbers of the next decision of every environment in `slots` (module docstring), counted."""
@@ -180,6 +210,7 @@ class CemMpc(MpcPolicy):
             warm = dict(calls=pl.take_calls(st.shape[0]))           # the numbers plan_batch would draw itself, kept for SafeCemMpc's recovery
         actions, scores, iters = pl.plan_batch(st, seed=self.seed, **warm)
         self.last_scores, self.last_iterations, self.last_calls = scores, iters, warm['calls']
+        self._note_ess(pl, iters)
         return actions
 
     def do_generate_action(self, state, eps_act=None, eps_model=None, eps_out=None):

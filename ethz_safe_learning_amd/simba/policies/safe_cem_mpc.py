@@ -143,7 +143,8 @@ class SafeCemMpc(CemMpc):
     # ---- the cost objective (safe_cem_mpc.py:40-74,98-108) --------------------------------------------------------
     def cost_planner_config(self):
         return dataclasses.replace(self.planner_config(), variant='cost', worst_particles=0,      # (the cost objective has no lower tail
-                                   constraint='beta', worst_cost_particles=0)                     # and no budget)
+                                   constraint='beta', worst_cost_particles=0,                     # and no budget;
+                                   refit='uniform', refit_temperature=0.0)                        # recovery plans keep the uniform refit)
 
     def build_cost(self):
         """The cost handle of the policy's shape (shared through the cache like the planning handle), the model's weights staged."""
@@ -187,6 +188,7 @@ class SafeCemMpc(CemMpc):
         state = np.asarray(state, np.float32)
         action, score, iters = self._planner.plan(state, seed=self.seed, call=call)
         self.last_score, self.last_iterations = score, iters
+        self._note_ess(self._planner, iters)
         self._note_feasibility(score)
         self.last_recovered = bool(score < self.recover_below)
         return self.optimize_for_safety(state, call=call) if self.last_recovered else action

@@ -506,6 +506,46 @@ CEM_INLINE int cem_f32_score_is_feasible(float score) { return score > CEM_INFEA
 CEM_INLINE int32_t cem_f32_decode_infeasible(float score) { return (int32_t)(-score * 0x1p-77f) - 8388608; }
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The refit: what an iteration does with the scores once the k elites are chosen.  Beyond the reference, off by default.
+ *   CEM_REFIT_UNIFORM  the reference's update (cem_mpc.py:56-65): every elite counts 1 / k.  What every handle does unless told otherwise,
+ *                      with the launches, graph nodes and bits it always had.
+ *   CEM_REFIT_SOFTMAX  the score-weighted update of MPPI (n_elite = n_samples) and of "weighted elites" (n_elite < n_samples).  The elite
+ *                      set, the best-so-far rule and the iteration count are the select's, unchanged.  Then, for one problem and iteration:
+ *                        s_j   = scores[elite[j]],  s_max = max_j s_j           NaN among the elites is outside the contract
+ *                        beta  = fl32(1 / temperature)                          rounded once on the host
+ *                        w_j   = s_j == s_max ? 1 : expf((s_j - s_max) * beta)   fp32; ties, +-inf and an all -inf elite set take the first
+ *                                                                               branch; -inf, or a budget-encoded infeasible score at any
+ *                                                                               temperature below 2^93, beside a finite s_max gives 0
+ *                        W     = sum w_j (>= 1)
+ *                        mean  = sum w_j a_j / W,  var = sum w_j (a_j - mean)^2 / W      two-pass, per column of the [H][A] action rows
+ *                        mu    = s mu + fl32(1 - s) mean,  sigma = s sigma + fl32(1 - s) sqrtf(var)     the blend of cem_mpc.py:64-65
+ *                        stop iff mean(sigma) <= stddev_threshold                cem_mpc.py:66-67, summed in the select's order
+ *                        ESS   = W^2 / sum w_j^2                                 in [1, k]; reported (cem_planner_refit_stats), feeds nothing
+ *                      The summation order is fixed (csrc/cem_refit_weighted.h states it) and there are no floating-point atomics: equal
+ *                      inputs give equal bits.  As temperature -> inf the weights tend to 1 and the update to UNIFORM's values (not its
+ *                      bits: the sums run in another order).
+ * One kernel (csrc/cem_refit_weighted.h) runs behind the unchanged one-workgroup select, whose own blend goes to a scratch slice of a small
+ * device allocation the handle owns (made on first use; the workspace keeps its layout and size): cem_planner_launches_per_iteration
+ * reports one launch more, and the plan's result is written by the final kernel.  Every variant, particle objective, constraint and
+ * rollout family serves it (it reads the scores alone), as do batch handles, warm start (the carry is the weighted mu / sigma), graph and
+ * eager plans and the stepwise calls.  The setting is sticky per handle; a change (of the temperature alone, too) waits for the stream
+ * and drops the captured graph.  Back on UNIFORM the handle launches exactly what it launched before.
+ *   CEM_ERR_INVALID_ARG  null handle, unknown kind, SOFTMAX with a temperature that is NaN, infinite, zero or negative (UNIFORM ignores it)
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  SOFTMAX with world_size > 1 or a communicator, with select_mode 2 or 3, or with n_samples large enough that the
+ *                        automatic choice is a multi-workgroup select (about 24 000): those forms keep moment kernels of their own
+ * The handle keeps its previous setting after any of these. */
+enum cem_refit { CEM_REFIT_UNIFORM = 0, CEM_REFIT_SOFTMAX = 1 };
+int cem_planner_set_refit(cem_planner_t *h, int32_t kind, float temperature);
+/* kind and temperature as set (UNIFORM: 0); either pointer may be NULL */
+int cem_planner_get_refit(const cem_planner_t *h, int32_t *kind_out, float *temperature_out);
+/* ESS of iterations 0 .. n - 1 of `problem` as the handle's last weighted plan left them -> ess_out_host[n], n <= iterations.  An
+ * iteration the plan did not run (early stop) keeps what an earlier plan left there, 0 at first: read `iters` values.  Drains the
+ * handle's stream; may be called inside a stepwise plan.  CEM_ERR_INVALID_ARG for a null handle or pointer, a problem outside
+ * 0 .. max(max_batch, 1) - 1, n < 1 or n > iterations; CEM_ERR_STATE when no weighted select has run on the handle. */
+int cem_planner_refit_stats(cem_planner_t *h, int32_t problem, float *ess_out_host, int32_t n);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

@@ -10,6 +10,9 @@ by shape.  Results go to <log_dir>/grid_search.json (and scores.svg / costs.svg 
 --parallel_episodes K (K > 1) evaluates each configuration on K PointGoal environments of distinct seeds stepped in lockstep
 (BaseAgent.sample_trajectories_lockstep): one batched plan (CemMpc.generate_actions) per decision for all of them.  The default, 1,
 is the serial evaluation above.
+
+--elite_temperature T [T ...] adds a grid axis: every configuration is also evaluated with the score-weighted refit at each temperature
+(CemMpc(elite_temperature=T); the word `none` stands for the uniform refit).  Without the flag the grid and its records are the reference's.
 """
 import argparse
 import json
@@ -28,7 +31,7 @@ PROPOSALS_WITH_ITERATIONS = [(100, 15), (150, 10), (300, 5)]
 ELITE_RATIOS = [0.05, 0.1, 0.2]
 
 
-WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor')
+WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor', 'elite_temperature')
 
 
 def make_new_policy(model, environment, horizon, iterations, n_samples, elite_ratio, policy_kwargs):
@@ -57,14 +60,19 @@ def evaluate_lockstep(trainer, environments, eval_steps, eval_episode_length):
 
 
 def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=HORIZONS,
-                proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS, parallel_envs=None):
+                proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS, parallel_envs=None,
+                elite_temperatures=None):
+    """elite_temperatures: None (the reference's grid) or a list of temperatures, None among them for the uniform refit — a fourth axis."""
     from ethz_safe_learning_amd.simba.infrastructure.logging_utils import logger
     agent = trainer.agent
     results = []
     for horizon in horizons:
         for n_samples, iterations in proposals_with_iterations:
-            for ratio in elite_ratios:
-                agent.policy = make_new_policy(agent.model, env, horizon, iterations, n_samples, ratio, params['policies']['cem_mpc'])
+            for ratio, temperature in [(r, t) for r in elite_ratios for t in (elite_temperatures or [None])]:
+                kwargs = params['policies']['cem_mpc']
+                if elite_temperatures:
+                    kwargs = dict(kwargs, elite_temperature=temperature)
+                agent.policy = make_new_policy(agent.model, env, horizon, iterations, n_samples, ratio, kwargs)
                 t0 = time.perf_counter()
                 if parallel_envs:
                     m = evaluate_lockstep(trainer, parallel_envs, eval_steps, eval_episode_length)
@@ -74,6 +82,8 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
                            n_elite=agent.policy.elite, score_mean=float(m['training_rl_objective']),
                            score_std=float(m['sum_rewards_stddev']), cost_mean=float(m['sum_costs_mean']),
                            cost_std=float(m['sum_costs_stddev']), seconds=time.perf_counter() - t0)
+                if elite_temperatures:
+                    rec['elite_temperature'] = temperature
                 logger.info('H=%d (N,I)=(%d,%d) elite %.2f: score %.3f +- %.3f, cost %.3f +- %.3f', horizon, n_samples, iterations,
                             ratio, rec['score_mean'], rec['score_std'], rec['cost_mean'], rec['cost_std'])
                 results.append(rec)
@@ -97,6 +107,8 @@ def main(argv=None):
                     help='K > 1: evaluate on K environments of distinct seeds in lockstep, one batched plan per decision')
     ap.add_argument('--warm_start', action='store_true',
                     help="every grid point's policy warm-starts its plans (CemMpc(warm_start=True, warm_sigma='keep')): run the search both ways")
+    ap.add_argument('--elite_temperature', type=str, nargs='+', default=None, metavar='T',
+                    help="a grid axis of softmax refit temperatures (CemMpc(elite_temperature=T)); 'none' = the uniform refit")
     args = ap.parse_args(argv)
     if args.parallel_episodes < 1:
         ap.error('--parallel_episodes must be at least 1')
@@ -108,6 +120,8 @@ def main(argv=None):
     if args.warm_start:
         params['policies']['cem_mpc'] = dict(params['policies']['cem_mpc'], warm_start=True, warm_sigma='keep')
     grid = dict(horizons=HORIZONS[:2], proposals_with_iterations=PROPOSALS_WITH_ITERATIONS[1:], elite_ratios=ELITE_RATIOS[:2]) if args.quick else {}
+    if args.elite_temperature:
+        grid['elite_temperatures'] = [None if t.lower() == 'none' else float(t) for t in args.elite_temperature]
     if args.parallel_episodes > 1:
         grid['parallel_envs'] = make_parallel_environments(params, args.parallel_episodes, args.seed)
     results = grid_search(trainer, trainer.environment, params, args.eval_steps, args.eval_episode_length, **grid)

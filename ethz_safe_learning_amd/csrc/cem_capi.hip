@@ -1,9 +1,7 @@
 // cem_capi.hip — host side of the C ABI declared in include/cem_mpc.h.
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC (see csrc/build.sh).
 #include "cem_device.h"
-#include "cem_constraint.h"
-#include "cem_particle_tail.h"
-#include "cem_constrained.h"
+#include "cem_score.h"
 #include "cem_refit_weighted.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
@@ -723,7 +721,7 @@ struct cem_planner {
     hipGraph_t graph; hipGraphExec_t gexec; bool graph_ready;
     ScorerDev sc;                            // the scorer as configured: cem_scorer_reward / cem_scorer_cost
     ScorerDev sc_roll;                       // what the rollouts and cem_compute_objective score with: sc — on a CEM_VARIANT_COST handle with a goal
-                                             // threshold of -inf, so that no row is ever done and the cost bytes are un-masked (cem_constraint.h)
+                                             // threshold of -inf, so that no row is ever done and the cost bytes are un-masked (cem_score.h)
     float alpha, beta;
     void *comm;                              // ncclComm_t of cem_planner_comm_init, or null (the host exchanges scores_local -> scores_global)
     int plans_since_comm;                    // the first plan after comm_init runs eagerly (RCCL sets itself up lazily), then the graph is captured
@@ -749,8 +747,8 @@ struct cem_planner {
     bool warm_save_skipped;                  // the staged plan overwrites the one slot's carry without a copy (stage_warm)
     int warm_staged;                       // problems of the plan whose warm control is staged and whose outcome finish_warm has not seen yet
     std::vector<float> h_expl;               // host copy of the explicit uploads [slots][2][HA]: the source of their stream-ordered copies
-    int tail_m;                              // cem_planner_set_particle_objective: 0 = the particle mean, 1 .. P = the mean of the m smallest returns (cem_particle_tail.h)
-    // cem_planner_set_constraint (cem_constrained.h)
+    int tail_m;                              // cem_planner_set_particle_objective: 0 = the particle mean, 1 .. P = the mean of the m smallest returns (cem_score.h)
+    // cem_planner_set_constraint (cem_score.h)
     int cost_m;                              // 0 = CEM_CONSTRAINT_BETA; 1 .. P = CEM_CONSTRAINT_BUDGET on the m largest particle costs (P: their mean)
     float *budget_dev;                       // a device allocation of the handle's own, made on first use: budgets [slots], then cstat [slots][Nloc]
     std::vector<float> h_budget;             // host copy of the budgets [slots]: the source of their stream-ordered copies
@@ -783,6 +781,15 @@ void drop_graph(cem_planner *h)
     if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
     if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
     h->graph_ready = false;
+}
+
+// a setter changes what a plan launches: wait for the captured plan (it may still be draining behind the polled result), then drop it.
+// Whatever the setter allocates it allocates before this, so that a failed allocation leaves the handle as it was
+int retire_graph(cem_planner *h)
+{
+    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));
+    drop_graph(h);
+    return CEM_OK;
 }
 
 // what every handle owns from create on: the three pinned blocks, its stream if it made one, itself
@@ -1339,6 +1346,31 @@ void note_plan_cstat(cem_planner *h)
     h->last_cstat = h->budget_dev + nb; h->last_cstat_n = h->d.Nloc; h->last_cstat_problems = nb;
 }
 
+// The score stage (cem_score.h) of the handle's objective.  The caller says what differs between a plan and the standalone op — the
+// buffers, the shape, whether a finished plan skips it and whether it clears the select's words; the handle says the rest.
+ReduceParams fill_score(const cem_planner *h, const float *ret, const uint8_t *costs, float *scores, float *cstat, int Nloc, int H, int check_done, bool clear_select)
+{
+    ReduceParams p{}; p.ret = ret; p.costs = costs; p.scores = scores; p.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
+    p.Nloc = Nloc; p.P = h->d.P; p.H = H; p.variant = h->cfg.variant; p.check_done = check_done;
+    p.alpha = h->alpha; p.beta = h->beta; p.thr = h->cfg.posterior_mean_threashold;
+    if (clear_select) { p.zero = (uint32_t *)(h->ws + h->lay.ms_hist); p.zero_n = CEM_MS_CLEAR_BYTES / 4; }
+    // one m serves both: the setters refuse a lower tail on a budget handle and the reverse, and a COST handle refuses both, so at most one of
+    // cost_m / tail_m is set; a kernel that reads neither m nor budget ignores them
+    p.m = h->cost_m ? h->cost_m : h->tail_m; p.cstat = cstat; p.budget = h->budget_dev;
+    return p;
+}
+
+// the one place a score kernel is chosen: grid.x = blocks of 64 candidates, grid.y = problems of a batched plan
+hipError_t launch_score(const cem_planner *h, const ReduceParams &p, int n_problems)
+{
+    const dim3 grid((p.Nloc + 63) / 64, n_problems), block(CEM_SCORE_THREADS);
+    if (h->cfg.variant == CEM_VARIANT_COST) hipLaunchKernelGGL(cem_constraint_reduce_kernel, grid, block, 0, h->stream, p);
+    else if (h->cost_m) hipLaunchKernelGGL(cem_constrained_budget_kernel, grid, block, CEM_BUDGET_LDS_BYTES(p.P, p.m), h->stream, p);
+    else if (h->tail_m) hipLaunchKernelGGL(cem_constraint_tail_kernel, grid, block, CEM_TAIL_LDS_BYTES(p.P), h->stream, p);
+    else hipLaunchKernelGGL(cem_reduce_kernel, grid, block, 0, h->stream, p);
+    return hipGetLastError();
+}
+
 // One iteration up to the scores: the rollout launch (its tiles sample their own action sequences first: cem_tile_sample_actions), then
 // the particle mean / Beta filter — unless `fold_reduce`: a single-rank whole plan on the CemMpc objective lets the select kernel form
 // the particle mean while it stages its keys (same sum, same order, one launch and one graph node fewer per iteration).
@@ -1382,41 +1414,12 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     timed.stop();
     if (fold_reduce) return CEM_OK;
 
-    if (cost_obj) {                                         // scores = -mean cost (cem_constraint.h); timed as the reduce launch it replaces
-        ConstraintReduceParams cp{}; cp.costs = rp.costs; cp.scores = (float *)(ws + l.scores_local); cp.ctrl = rp.ctrl;
-        cp.Nloc = d.Nloc; cp.P = d.P; cp.H = d.H; cp.check_done = 1;
-        cp.zero = (uint32_t *)(ws + l.ms_hist); cp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;
-        TimedLaunch timed_reduce(h, 2);
-        hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((d.Nloc + 63) / 64, nb), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
-        HIPCHK(hipGetLastError());
-        return CEM_OK;
-    }
-    if (h->cost_m) {                                        // return within the cost budget (cem_constrained.h); timed as the reduce launch it replaces
-        ConstrainedBudgetParams bp{}; bp.ret = rp.ret; bp.costs = rp.costs; bp.scores = (float *)(ws + l.scores_local); bp.ctrl = rp.ctrl;
-        bp.budget = h->budget_dev; bp.cstat = h->budget_dev + nb;
-        bp.Nloc = d.Nloc; bp.P = d.P; bp.H = d.H; bp.m = h->cost_m; bp.check_done = 1;
-        bp.zero = (uint32_t *)(ws + l.ms_hist); bp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;
-        note_plan_cstat(h);
-        TimedLaunch timed_reduce(h, 2);
-        HIPCHK(launch_constrained_budget(bp, nb, h->stream));
-        return CEM_OK;
-    }
-    if (h->tail_m) {                                        // the mean of the m smallest particle returns (cem_particle_tail.h); timed as the reduce launch it replaces
-        ConstraintTailParams tp{}; tp.ret = rp.ret; tp.costs = rp.costs; tp.scores = (float *)(ws + l.scores_local); tp.ctrl = rp.ctrl;
-        tp.Nloc = d.Nloc; tp.P = d.P; tp.H = d.H; tp.m = h->tail_m; tp.variant = h->cfg.variant; tp.check_done = 1;
-        tp.alpha = h->alpha; tp.beta = h->beta; tp.thr = h->cfg.posterior_mean_threashold;
-        tp.zero = (uint32_t *)(ws + l.ms_hist); tp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;
-        TimedLaunch timed_reduce(h, 2);
-        HIPCHK(launch_constraint_tail(tp, nb, h->stream));
-        return CEM_OK;
-    }
-    ReduceParams qp{}; qp.ret = rp.ret; qp.costs = rp.costs; qp.scores = (float *)(ws + l.scores_local); qp.ctrl = rp.ctrl;
-    qp.Nloc = d.Nloc; qp.P = d.P; qp.H = d.H; qp.variant = h->cfg.variant; qp.check_done = 1;
-    qp.alpha = h->alpha; qp.beta = h->beta; qp.thr = h->cfg.posterior_mean_threashold;
-    qp.zero = (uint32_t *)(ws + l.ms_hist); qp.zero_n = (3 * CEM_MS_BINS * 4 + 256) / 4; h->sel_zeroed = true;     // for this iteration's multi-workgroup select
+    // the score kernel of the handle's objective, timed as the one reduce launch; it clears the words of this iteration's multi-workgroup select
+    const ReduceParams sp = fill_score(h, rp.ret, rp.costs, (float *)(ws + l.scores_local), h->cost_m ? h->budget_dev + nb : nullptr, d.Nloc, d.H, 1, true);
+    h->sel_zeroed = true;
+    if (h->cost_m) note_plan_cstat(h);
     TimedLaunch timed_reduce(h, 2);
-    hipLaunchKernelGGL(cem_reduce_kernel, dim3((d.Nloc + 63) / 64, nb), dim3(CEM_REDUCE_THREADS), 0, h->stream, qp);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_score(h, sp, nb));
     return CEM_OK;
 }
 
@@ -1478,7 +1481,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
         m.G = G; m.G2 = (d.k + CEM_MS_EPG - 1) / CEM_MS_EPG;
         // the histograms and the barrier counter (adjacent in the workspace) start at zero; within a plan the reduce kernel of the
         // same iteration has already cleared them (ReduceParams::zero), this memset covers a select called on its own
-        if (!h->sel_zeroed) HIPCHK(hipMemsetAsync(m.hist, 0, 3 * CEM_MS_BINS * 4 + 256, h->stream));
+        if (!h->sel_zeroed) HIPCHK(hipMemsetAsync(m.hist, 0, CEM_MS_CLEAR_BYTES, h->stream));
         h->sel_zeroed = false;
         if (mode == 3) {
             hipLaunchKernelGGL(cem_msel_fused_kernel, dim3(m.G), dim3(1024), 0, h->stream, m);
@@ -1922,8 +1925,7 @@ int cem_planner_set_particle_objective(cem_planner_t *h, int32_t kind, int32_t m
     const int tail_m = kind == CEM_PARTICLES_LOWER_TAIL ? m : 0;
     if (tail_m == h->tail_m) return CEM_OK;
     // the captured plan holds the other objective's launches (and, changing m alone, the old m): the next plan captures anew
-    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));   // (it may still be draining behind the polled result)
-    drop_graph(h);
+    { const int st = retire_graph(h); if (st) return st; }
     h->tail_m = tail_m;
     return CEM_OK;
 }
@@ -1964,9 +1966,8 @@ int cem_planner_set_constraint(cem_planner_t *h, int32_t kind, int32_t worst_cos
     }
     if (cost_m == h->cost_m) return CEM_OK;
     // the captured plan holds the other constraint's launches (and, changing m_c alone, the old m_c): the next plan captures anew
-    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));   // (it may still be draining behind the polled result)
     if (cost_m) { const int st = ensure_budget(h); if (st) return st; }
-    drop_graph(h);
+    { const int st = retire_graph(h); if (st) return st; }
     h->cost_m = cost_m;
     return CEM_OK;
 }
@@ -2030,9 +2031,8 @@ int cem_planner_set_refit(cem_planner_t *h, int32_t kind, float temperature)
     const float tau = kind == CEM_REFIT_SOFTMAX ? temperature : 0.f;
     if (kind == h->refit_kind && std::memcmp(&tau, &h->refit_tau, 4) == 0) return CEM_OK;
     // the captured plan holds the other refit's launches (and, changing the temperature alone, the old 1 / temperature): the next plan captures anew
-    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));   // (it may still be draining behind the polled result)
     if (kind == CEM_REFIT_SOFTMAX) { const int st = ensure_refit(h); if (st) return st; }
-    drop_graph(h);
+    { const int st = retire_graph(h); if (st) return st; }
     h->refit_kind = kind; h->refit_tau = tau; h->refit_beta = kind == CEM_REFIT_SOFTMAX ? 1.0f / temperature : 0.f;
     return CEM_OK;
 }
@@ -2272,43 +2272,17 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
     op.B = n_rows; op.H = horizon; op.O = d.O; op.variant = safe ? (int)CEM_VARIANT_SAFE : h->cfg.variant; op.sc = h->sc_roll;
     hipLaunchKernelGGL(cem_objective_kernel, dim3((unsigned)(((size_t)n_rows * 16 + 255) / 256)), dim3(256), 0, h->stream, op);
     HIPCHK(hipGetLastError());
-    if (cost_obj) {
-        ConstraintReduceParams cp{}; cp.costs = op.costs; cp.scores = scores_out_dev; cp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
-        cp.Nloc = n_rows / d.P; cp.P = d.P; cp.H = horizon; cp.check_done = 0;
-        hipLaunchKernelGGL(cem_constraint_reduce_kernel, dim3((cp.Nloc + 63) / 64), dim3(CEM_CONSTRAINT_THREADS), 0, h->stream, cp);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return CEM_OK;
+    const int n_cand = n_rows / d.P;
+    if (h->cost_m && (size_t)n_cand > h->cstat_obj_n) {
+        if (h->cstat_obj) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipFree(h->cstat_obj)); h->cstat_obj = nullptr; h->cstat_obj_n = 0; if (h->last_cstat_problems == 0) h->last_cstat = nullptr; }
+        const size_t want = (size_t)n_cand + (size_t)n_cand / 2;
+        HIPCHK(hipMalloc((void **)&h->cstat_obj, want * 4));
+        h->cstat_obj_n = want;
     }
-    if (h->cost_m) {
-        const size_t n_cand = (size_t)(n_rows / d.P);
-        if (n_cand > h->cstat_obj_n) {
-            if (h->cstat_obj) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipFree(h->cstat_obj)); h->cstat_obj = nullptr; h->cstat_obj_n = 0; if (h->last_cstat_problems == 0) h->last_cstat = nullptr; }
-            HIPCHK(hipMalloc((void **)&h->cstat_obj, (n_cand + n_cand / 2) * 4));
-            h->cstat_obj_n = n_cand + n_cand / 2;
-        }
-        ConstrainedBudgetParams bp{}; bp.ret = op.ret; bp.costs = op.costs; bp.scores = scores_out_dev; bp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
-        bp.budget = h->budget_dev; bp.cstat = h->cstat_obj;
-        bp.Nloc = (int32_t)n_cand; bp.P = d.P; bp.H = horizon; bp.m = h->cost_m; bp.check_done = 0;
-        HIPCHK(launch_constrained_budget(bp, 1, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->last_cstat = bp.cstat; h->last_cstat_n = (int)n_cand; h->last_cstat_problems = 0;      // (0: the op's own array)
-        return CEM_OK;
-    }
-    if (h->tail_m) {
-        ConstraintTailParams tp{}; tp.ret = op.ret; tp.costs = op.costs; tp.scores = scores_out_dev; tp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
-        tp.Nloc = n_rows / d.P; tp.P = d.P; tp.H = horizon; tp.m = h->tail_m; tp.variant = h->cfg.variant; tp.check_done = 0;
-        tp.alpha = h->alpha; tp.beta = h->beta; tp.thr = h->cfg.posterior_mean_threashold;
-        HIPCHK(launch_constraint_tail(tp, 1, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return CEM_OK;
-    }
-    ReduceParams qp{}; qp.ret = op.ret; qp.costs = op.costs; qp.scores = scores_out_dev; qp.ctrl = (const CtrlBlock *)(h->ws + h->lay.ctrl);
-    qp.Nloc = n_rows / d.P; qp.P = d.P; qp.H = horizon; qp.variant = h->cfg.variant; qp.check_done = 0;
-    qp.alpha = h->alpha; qp.beta = h->beta; qp.thr = h->cfg.posterior_mean_threashold;
-    hipLaunchKernelGGL(cem_reduce_kernel, dim3((qp.Nloc + 63) / 64), dim3(CEM_REDUCE_THREADS), 0, h->stream, qp);
-    HIPCHK(hipGetLastError());
+    const ReduceParams sp = fill_score(h, op.ret, op.costs, scores_out_dev, h->cost_m ? h->cstat_obj : nullptr, n_cand, horizon, 0, false);
+    HIPCHK(launch_score(h, sp, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->cost_m) { h->last_cstat = sp.cstat; h->last_cstat_n = n_cand; h->last_cstat_problems = 0; }      // (0: the op's own array)
     return CEM_OK;
 }
 

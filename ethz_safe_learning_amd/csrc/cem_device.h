@@ -8,7 +8,8 @@
 //                                               the reward/cost scorer (safety_gym.py:110-192) with the done
 //                                               masking of mpc_policy.py:26-37 / safe_cem_mpc.py:82-93, fused:
 //                                               traj[B][H+1][O] is never materialised.
-//   cem_reduce_kernel   mpc_policy.py:38-39, safe_cem_mpc.py:94-96,110-120   particle mean, Beta safety filter
+//   cem_reduce_kernel   mpc_policy.py:38-39, safe_cem_mpc.py:94-96,110-120   particle mean, Beta safety filter (cem_score.h, with the
+//                                               other objectives' score kernels)
 //   cem_select_kernel   cem_mpc.py:56-67        top_k, best-so-far, moments, smoothing, early stop
 //
 // Rollout kernel design: a workgroup of 4 waves owns a tile of 16*RC rows of ONE ensemble
@@ -1080,109 +1081,6 @@ __global__ void cem_init_kernel(const InitParams p)
     }
 }
 
-struct ReduceParams {
-    const float *ret; const uint8_t *costs; float *scores; const CtrlBlock *ctrl;
-    int32_t Nloc, P, H, variant, check_done;
-    float alpha, beta, thr;
-    uint32_t *zero; int32_t zero_n;        // words block 0 clears for the multi-workgroup select that follows (digit histograms + barrier counter), or null
-    // batched plans: blockIdx.y is the problem; its ret / costs / scores are the next [P][Nloc] / [H][P][Nloc] / [Nloc] slices, its
-    // control block ctrl[blockIdx.y]
-};
-
-// One block = 64 candidates (one per lane) x 16 waves.  The kernel is a latency chain — a few hundred bytes per candidate, one dependent
-// round of loads, a barrier, a store — so what matters is how many round trips to L2 a wave makes, not bandwidth (round 5, measured at
-// the shipped SafeCemMpc shape, P = 45, H = 8, where ten of the sixteen waves used to idle and the others made six trips each):
-//   * horizons of 16 steps and more: wave w counts the particle costs of steps t = w, w + 16, ..., TWO steps per trip, up to 8 particles each;
-//   * shorter horizons: the 16 waves share out (step, particle slice) pairs — 16 / H waves per step, each counting every (16 / H)-th
-//     particle, up to 16 loads per trip — and add their counts in LDS (integers: exact, order-free);
-//   * wave 0's return loads (the particle mean, summed in the reference's order q = 0 .. P-1) are requested before its cost loads.
-// Counts are small integers, exact in the reference's fp32 sums as well.
-#define CEM_REDUCE_THREADS 1024
-__global__ __launch_bounds__(CEM_REDUCE_THREADS) void cem_reduce_kernel(const ReduceParams p)
-{
-    __shared__ int32_t unsafe_w[16][64];
-    __shared__ uint32_t cnt_s[16][64];
-    const int b = (int)blockIdx.y;
-    if (p.check_done && p.ctrl[b].done) return;
-    if (p.zero && blockIdx.x == 0 && b == 0) for (int i = threadIdx.x; i < p.zero_n; i += CEM_REDUCE_THREADS) p.zero[i] = 0u;
-    const float *const ret = p.ret + (size_t)b * p.P * p.Nloc;
-    const uint8_t *const costs = p.costs ? p.costs + (size_t)b * p.H * p.P * p.Nloc : p.costs;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + lane;
-    const bool live = n < p.Nloc;
-    const int nn = live ? n : p.Nloc - 1;
-    const int P = p.P, H = p.H;
-    // wave 0: the first 16 particles' returns, in flight while the costs are counted
-    float r0[16];
-    if (w == 0) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) r0[j] = ret[(size_t)(j < P ? j : 0) * p.Nloc + nn];
-    }
-    int32_t unsafe = 0;
-    if (p.variant == 1) {                                              // safe_cem_mpc.py:90-96,110-120
-        const float denom = (p.alpha + p.beta) + (float)P;
-        const size_t Bloc = (size_t)P * p.Nloc;
-        if (H >= 16) {
-            for (int t = w; t < H; t += 32) {
-                const int t2 = t + 16 < H ? t + 16 : t;               // (clamped: the loads are unconditional, the second count is dropped)
-                const uint8_t *ca = costs + (size_t)t * Bloc + nn, *cb = costs + (size_t)t2 * Bloc + nn;
-                uint32_t cnta = 0, cntb = 0;
-                for (int q = 0; q < P; q += 8) {
-                    uint32_t va[8], vb[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { const size_t o = (size_t)(q + j < P ? q + j : q) * p.Nloc; va[j] = ca[o]; vb[j] = cb[o]; }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) if (q + j < P) { cnta += va[j]; cntb += vb[j]; }
-                }
-                unsafe |= ((p.alpha + (float)cnta) / denom <= p.thr) ? 0 : 1;
-                if (t + 16 < H) unsafe |= ((p.alpha + (float)cntb) / denom <= p.thr) ? 0 : 1;
-            }
-        } else {
-            const int wpt = 16 / H;                                    // waves per step (>= 1), H * wpt <= 16 of the waves count
-            cnt_s[w][lane] = 0u;
-            __syncthreads();
-            if (w < H * wpt) {
-                const int t = w / wpt, part = w % wpt;
-                const uint8_t *c = costs + (size_t)t * Bloc + nn;
-                uint32_t cnt = 0;
-                for (int q = part; q < P; q += 16 * wpt) {
-                    uint32_t v[16];
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) { const int qq = q + j * wpt; v[j] = c[(size_t)(qq < P ? qq : q) * p.Nloc]; }
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) if (q + j * wpt < P) cnt += v[j];
-                }
-                if (wpt > 1) atomicAdd(&cnt_s[t][lane], cnt); else cnt_s[t][lane] = cnt;
-            }
-            __syncthreads();
-            if (w < H) unsafe = ((p.alpha + (float)cnt_s[w][lane]) / denom <= p.thr) ? 0 : 1;
-        }
-        unsafe_w[w][lane] = unsafe;
-    }
-    float sum = 0.f;
-    if (w == 0) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) if (j < P) sum = sum + r0[j];
-        for (int q = 16; q < P; q += 16) {
-            float v[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = ret[(size_t)(q + j < P ? q + j : q) * p.Nloc + nn];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) if (q + j < P) sum = sum + v[j];
-        }
-    }
-    __syncthreads();
-    if (w != 0 || !live) return;
-    float score = sum / (float)P;                                      // reduce_mean over particles
-    if (p.variant == 1) {
-        int32_t u = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) u |= unsafe_w[i][lane];
-        score = score - (u ? 1.0f : 0.0f) * 100.0f;
-    }
-    p.scores[(size_t)b * p.Nloc + n] = score;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // the objective and the scorer as ops of their own, on tensors the caller holds (cem_compute_objective,
 // cem_scorer_reward, cem_scorer_cost).  HBM-bound: a group of 16 lanes owns one row and reads its features
@@ -1892,6 +1790,7 @@ __global__ __launch_bounds__(1024) void cem_select_kernel(const SelectParams p)
 // ---------------------------------------------------------------------------------------------------------
 #define CEM_MS_KEYS 4096              // keys per workgroup (1024 threads x 4) in the histogram / count / compaction kernels
 #define CEM_MS_BINS 2048
+#define CEM_MS_CLEAR_BYTES (3 * CEM_MS_BINS * 4 + 256)   // what starts an iteration's select at zero: the three digit histograms and, adjacent in the workspace, the barrier counter's block
 #define CEM_MS_EPG 256                // elites per workgroup in the moment kernels
 struct MSelParams {
     const float *scores; const float *actions; float *musig; CtrlBlock *ctrl; int32_t *elite_idx;

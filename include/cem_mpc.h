@@ -278,7 +278,7 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out);
  * 2 = rollout (its tiles sample their own action sequences, cem_mpc.py:44-48) + select (which forms the particle mean of the CemMpc
  * objective itself, mpc_policy.py:38-39) — single-rank CemMpc plans whose tiles are all resident at once; + 1 where the sampler is a
  * launch of its own (tiles queue for slots), + 1 where the reduce kernel stays (SafeCemMpc's Beta filter, sharded plans, the
- * multi-workgroup selects; CEM_VARIANT_COST: its own reduce, csrc/cem_constraint.h; CEM_PARTICLES_LOWER_TAIL: its reduce, csrc/cem_particle_tail.h, which no select folds), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
+ * multi-workgroup selects; CEM_VARIANT_COST: its own reduce, csrc/cem_score.h; CEM_PARTICLES_LOWER_TAIL: its reduce, csrc/cem_score.h, which no select folds), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
  * chain.  The stepwise calls always launch the reduce kernel. */
 int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches_out);
 
@@ -423,7 +423,7 @@ int cem_planner_set_carry_slots(cem_planner_t *h, int32_t n, const int32_t *slot
  *                             divide once by (float)m.  (m = P is therefore the mean summed in ANOTHER order: not MEAN's bits.)
  *                             NaN returns are outside the contract.
  * On a CEM_VARIANT_SAFE handle the Beta filter and the penalty are unchanged and apply to this value: score = value - (unsafe ? 1 : 0) * 100.
- * The rollouts are untouched; one kernel (csrc/cem_particle_tail.h) takes the place of the particle-mean kernel, and a plan that folded the
+ * The rollouts are untouched; one kernel (csrc/cem_score.h) takes the place of the particle-mean kernel, and a plan that folded the
  * mean into its select launches it in addition (cem_planner_launches_per_iteration says so).  Whole plans (graph and eager), the
  * stepwise calls, batch handles, warm start, every rollout family and cem_compute_objective serve it.
  * The setting is sticky per handle; changing it drops the captured graph (the next plan captures again) and waits for the stream.  Back
@@ -461,7 +461,7 @@ int cem_planner_get_particle_objective(const cem_planner_t *h, int32_t *kind_out
  *                          (ties to the lowest index); the best-so-far (strict >) prefers any feasible candidate to any infeasible one and,
  *                          among infeasible ones, the cheaper.  A mean return at or below -2^100 is outside the contract (reward_clip
  *                          bounds returns far above it).  The Beta filter and posterior_mean_threashold play no part.
- * One kernel (csrc/cem_constrained.h) takes the place of the particle-mean / Beta kernel: cem_planner_launches_per_iteration is unchanged.
+ * One kernel (csrc/cem_score.h) takes the place of the particle-mean / Beta kernel: cem_planner_launches_per_iteration is unchanged.
  * Whole plans (graph and eager), the stepwise calls, batch handles, warm start, every rollout family, every select form and
  * cem_compute_objective (which then returns these scores) serve it.  The setting is sticky per handle; a change waits for the stream and
  * drops the captured graph.  Back on BETA the handle launches exactly what it launched before.

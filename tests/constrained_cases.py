@@ -108,6 +108,10 @@ def configs(pb, constraint='budget', worst_cost=0, **kw):
 # per m_c — p1: 36 of 70; p5_n130_h8 (0.7): 71, 77, 95, 95 of 130; p5_n70_h33: 36, 35, 37, 39 of 70; p16 (0.85): 45, 39, 37, 37 of 70;
 # p17_n130_h33: 89, 72, 65, 65 of 130; p17_n70_h8 (0.7): 58, 60, 37, 37 of 70; p45_n70_h8 (0.7): 57, 58, 37, 37 of 70; p45_n130_h3
 # (0.7): 76, 76, 68, 68 of 130.  The tests assert on the device's own bytes that both classes occur.
+# P = 65 and 128: from five to eight particles a wave, the widest body of the tail form (the smallest P that takes it; H = 3 and 17: one
+# trip of two steps and nine of them; and the cap CEM_BUDGET_MAX_TAIL_P, 36 KiB of LDS).  p65_n70_h3 (0.65; at 0.7 the worst particle
+# of all 70 candidates sits at the median): 49, 49, 40, 40 of 70; p65_n70_h17 (0.7): 37, 37, 38, 38 of 70; p128_n70_h3 (0.7): 65, 66,
+# 40, 40 of 70.
 SHAPES = {
     'p1_n70_h3': (1, 70, 3, 5, 1.0),
     'p5_n130_h8': (5, 130, 8, 5, 0.7),
@@ -117,6 +121,9 @@ SHAPES = {
     'p17_n70_h8': (17, 70, 8, 5, 0.7),
     'p45_n70_h8': (45, 70, 8, 15, 0.7),
     'p45_n130_h3': (45, 130, 3, 5, 0.7),
+    'p65_n70_h3': (65, 70, 3, 5, 0.65),
+    'p65_n70_h17': (65, 70, 17, 5, 0.7),
+    'p128_n70_h3': (128, 70, 3, 4, 0.7),
 }
 NOISE_SEED = 5
 

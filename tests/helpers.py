@@ -46,17 +46,34 @@ def kernel_bodies(isa, pattern):
     return out
 
 
-def kernel_meta(isa, pattern):
-    """{mangled name: {vgpr_count, vgpr_spill_count, private_segment_fixed_size}} from the code-object metadata."""
+def kernel_meta(isa, pattern, keys=('vgpr_count', 'vgpr_spill_count', 'private_segment_fixed_size')):
+    """{mangled name: {key: value}} from the code-object metadata, for the integer `keys` of a kernel's entry (by default vgpr_count,
+    vgpr_spill_count, private_segment_fixed_size).  An entry is one item of the amdhsa.kernels list; its keys are in alphabetical order,
+    so some (group_segment_fixed_size) stand in front of .name and some behind it."""
     out = {}
-    for m in re.finditer(r'\.name:\s+(_Z\w+)\s*\n(.*?)(?=\n\s+- \.|\namdhsa\.target|\Z)', isa, re.S):
-        if re.search(pattern, m.group(1)):
+    for entry in re.split(r'\n  - ', isa[isa.index('amdhsa.kernels:'):])[1:]:
+        m = re.search(r'\.name:\s+(_Z\w+)', entry)
+        if m and re.search(pattern, m.group(1)):
             d = {}
-            for k in ('vgpr_count', 'vgpr_spill_count', 'private_segment_fixed_size'):
-                mm = re.search(r'\.%s:\s+(\d+)' % k, m.group(0))
+            for k in keys:
+                mm = re.search(r'^\s+\.%s:\s+(\d+)' % k, entry, re.M)
                 d[k] = int(mm.group(1)) if mm else None
             out[m.group(1)] = d
     return out
+
+
+# The four score kernels of csrc/cem_score.h, by function name (the mangled names carry the parameter type).
+SCORE_KERNELS = ('cem_reduce_kernel', 'cem_constraint_reduce_kernel', 'cem_constraint_tail_kernel', 'cem_constrained_budget_kernel')
+# Kernels added since warm start that are neither the trainer's nor the forward pass's (tests/test_warm_capi_cpu.py admits exactly these
+# beside tests/golden/kernel_registers_before_warm_start.json), by function name.
+KERNELS_SINCE_WARM_START = ('cem_pack_fp32_kernel', 'cem_pack_split_kernel', 'cem_pack_wide_kernel', 'cem_pack_bias_kernel',
+                            'cem_constraint_reduce_kernel', 'cem_constraint_tail_kernel', 'cem_constrained_budget_kernel', 'cem_constraint_refit_kernel')
+
+
+def kernel_function_name(mangled):
+    """_Z17cem_reduce_kernel12ReduceParams -> cem_reduce_kernel (a plain or templated function at global scope; any other name comes back as it is)."""
+    m = re.match(r'_Z(\d+)', mangled)
+    return mangled[m.end():m.end() + int(m.group(1))] if m else mangled      # (a nested name, _ZN...: as it is)
 
 
 def makefile_flags():

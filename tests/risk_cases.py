@@ -76,6 +76,10 @@ def configs(pb, worst=0, **kw):
 # alpha = beta = 1.2147 (half a count away from either neighbour).  c was read off the fp32 ORACLE's per-candidate largest step count for
 # problem() with noise seed 5 (the count histogram's middle: 30 of 70 candidates at or below c for p1, 91 of 130 for p5_n130_h8, ...), so
 # that both safe and unsafe candidates occur; the tests assert that they do on the device's own bytes.
+# P = 65 and 128: from five to eight particles a wave, the widest body of the ranking kernels (the smallest P that takes it, N no multiple
+# of 64, on both branches of the Beta count; and the cap CEM_TAIL_MAX_P, 40 KiB of LDS).  Their c, read off the same way: 33 of 70 at or
+# below 27 for p65_n70_h3 (0.4 P); 35 of 70 at or below 41 for p65_n70_h17 and at or below 59 for p128_n70_h3, whose smallest counts
+# are 38 and 52 (at 0.4 P every candidate of either would be unsafe).
 def _thr(P, c):
     return round((1.2147 + c + 0.5) / (2 * 1.2147 + P), 4)
 
@@ -89,6 +93,9 @@ SHAPES = {
     'p17_n70_h8': (17, 70, 8, 5, _thr(17, 9)),
     'p45_n70_h8': (45, 70, 8, 15, _thr(45, 19)),
     'p45_n130_h3': (45, 130, 3, 5, _thr(45, 19)),
+    'p65_n70_h3': (65, 70, 3, 5, _thr(65, 27)),
+    'p65_n70_h17': (65, 70, 17, 5, _thr(65, 41)),
+    'p128_n70_h3': (128, 70, 3, 4, _thr(128, 59)),
 }
 NOISE_SEED = 5
 

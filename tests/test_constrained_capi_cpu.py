@@ -129,7 +129,7 @@ def test_hand_trajectory_carries_the_hand_costs():
 def test_shape_table_is_well_formed():
     for name, (P, N, H, E, size_frac) in kc.SHAPES.items():
         assert (P * N) % E == 0 and 0 < size_frac <= 1, name
-    assert {s[0] for s in kc.SHAPES.values()} == {1, 5, 16, 17, 45}
+    assert {s[0] for s in kc.SHAPES.values()} == {1, 5, 16, 17, 45, 65, 128}
     assert {s[1] for s in kc.SHAPES.values()} == {70, 130} and {s[2] for s in kc.SHAPES.values()} == {3, 8, 17, 33}
     hp_ = sorted(s[0] * s[2] for s in kc.SHAPES.values())
     assert hp_[0] < 256 < hp_[-1]                                      # H P on both sides of one trip of 256 rows
@@ -144,7 +144,7 @@ def test_budget_kernel_has_no_spills_and_no_scratch(isa):
     meta = hp.kernel_meta(isa, r'cem_constrained_budget_kernel')
     assert len(meta) == 1, list(meta)
     (name, d), = meta.items()
-    assert 'train' in name                                             # what test_planning_kernels_keep_their_register_counts admits
+    assert hp.kernel_function_name(name) in hp.KERNELS_SINCE_WARM_START  # what test_planning_kernels_keep_their_register_counts admits
     assert d['vgpr_spill_count'] == 0 and d['private_segment_fixed_size'] == 0, d
     assert 0 < d['vgpr_count'] <= 64, d                                # 1024-thread blocks: two resident per CU need <= 64
     block = re.search(r'\.name:\s+%s\s*\n(.*?)(?=\n\s+- \.|\namdhsa\.target|\Z)' % re.escape(name), isa, re.S).group(0)

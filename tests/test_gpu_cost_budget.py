@@ -1,4 +1,4 @@
-"""Budget-constrained planning on the device (cem_planner_set_constraint, CEM_CONSTRAINT_BUDGET; csrc/cem_constrained.h) against its NumPy
+"""Budget-constrained planning on the device (cem_planner_set_constraint, CEM_CONSTRAINT_BUDGET; csrc/cem_score.h) against its NumPy
 restatement (tests/constrained_cases.py).
 
 Every expected score is computed from the handle's OWN returns() and costs() of the same rollout: integer sums, one division, one

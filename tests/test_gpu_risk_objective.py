@@ -1,4 +1,4 @@
-"""The lower-tail particle objective on the device (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL; csrc/cem_particle_tail.h)
+"""The lower-tail particle objective on the device (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL; csrc/cem_score.h)
 against its NumPy restatement (tests/risk_cases.py).
 
 Every expected score is computed from the handle's OWN returns() and costs() of the same rollout: a stable sort, a sequential fp32 sum,

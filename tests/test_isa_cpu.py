@@ -76,6 +76,22 @@ def test_split_rollout_kernels_fit_the_residency_their_tile_rule_assumes(isa):
     assert any(l.startswith('v_cvt_pk_bf16_f32') for l in ins), 'the split rounds to nearest with the hardware conversion'
 
 
+@pytest.mark.parametrize('kernel', hp.SCORE_KERNELS)
+def test_score_kernels_stay_within_the_resources_they_had_as_separate_headers(isa, kernel):
+    """csrc/cem_score.h composes the four score kernels from shared pieces.  tests/golden/score_kernel_resources.json holds, by function
+    name, what the code-object metadata gave for each while it still was a copy of its own (the device sources of the commit before the
+    header, these flags): no spills and no scratch, the same static LDS, and no more vector or scalar registers than then."""
+    import json
+    want = json.load(open(os.path.join(hp.ROOT, 'tests', 'golden', 'score_kernel_resources.json')))[kernel]
+    meta = hp.kernel_meta(isa, r'^_Z\d+%s\d' % kernel, keys=tuple(want))
+    assert len(meta) == 1, list(meta)
+    (name, d), = meta.items()
+    for k in ('vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size'):
+        assert want[k] == 0 and d[k] == 0, (name, k, d)
+    assert d['group_segment_fixed_size'] == want['group_segment_fixed_size'], (name, d, want)
+    assert d['vgpr_count'] <= want['vgpr_count'] and d['sgpr_count'] <= want['sgpr_count'], (name, d, want)
+
+
 @pytest.mark.parametrize('headers', [('cem_rollout_wide.h',), ('cem_rollout_split.h',), ('cem_rollout_wide.h', 'cem_rollout_split.h')],
                          ids=['wide_alone', 'split_alone', 'wide_then_split'])
 def test_secondary_rollout_headers_stand_alone_and_in_either_order(headers, tmp_path):

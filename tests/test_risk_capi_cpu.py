@@ -102,7 +102,7 @@ def test_restated_safe_rows_are_pushed_by_100():
 def test_shape_table_is_well_formed():
     for name, (P, N, H, E, thr) in rc.SHAPES.items():
         assert (P * N) % E == 0 and 0 < thr < 1, name
-    assert {s[0] for s in rc.SHAPES.values()} == {1, 5, 16, 17, 45}
+    assert {s[0] for s in rc.SHAPES.values()} == {1, 5, 16, 17, 45, 65, 128}
     assert {s[1] for s in rc.SHAPES.values()} == {70, 130} and {s[2] for s in rc.SHAPES.values()} == {3, 8, 17, 33}
 
 
@@ -115,7 +115,7 @@ def test_tail_kernel_has_no_spills_and_no_scratch(isa):
     meta = hp.kernel_meta(isa, r'cem_constraint_tail_kernel')
     assert len(meta) == 1, list(meta)
     (name, d), = meta.items()
-    assert 'train' in name                                             # what test_planning_kernels_keep_their_register_counts admits
+    assert hp.kernel_function_name(name) in hp.KERNELS_SINCE_WARM_START  # what test_planning_kernels_keep_their_register_counts admits
     assert d['vgpr_spill_count'] == 0 and d['private_segment_fixed_size'] == 0, d
     assert 0 < d['vgpr_count'] <= 64, d                                # 1024-thread blocks: two resident per CU need <= 64
 

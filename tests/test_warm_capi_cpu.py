@@ -134,7 +134,10 @@ def isa():
 def test_planning_kernels_keep_their_register_counts(isa):
     """Warm start lives in the plan's first kernel alone.  tests/golden/kernel_registers_before_warm_start.json records vgpr_count, spilled
     VGPRs (none anywhere) and scratch of every other kernel as the code-object metadata gave them for the device sources of the commit
-    before the feature, compiled with these flags; they must still be exactly those."""
+    before the feature, compiled with these flags; they must still be exactly those.  What may stand beside them is said by name: the
+    plan's first kernel, the trainer's and the forward pass's kernels (function names that begin with cem_train_ / cem_trainer_), and the
+    kernels added since, listed in helpers.KERNELS_SINCE_WARM_START — stricter than the earlier rule, which admitted every mangled name
+    that held the letters `train` (`constraint` and `constrained` among them)."""
     import json
     want = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'kernel_registers_before_warm_start.json')))
     got = hp.kernel_meta(isa, r'.')
@@ -142,6 +145,9 @@ def test_planning_kernels_keep_their_register_counts(isa):
     for name, d in want.items():
         assert name in got, name
         assert got[name] == d, (name, got[name], d)
-    assert set(got) - set(want) == {'_Z15cem_init_kernel10InitParams'} | {n for n in got if 'train' in n}
+    fn = {n: hp.kernel_function_name(n) for n in got}
+    admitted = {n for n in got if fn[n].startswith(('cem_train_', 'cem_trainer_')) or fn[n] in hp.KERNELS_SINCE_WARM_START}
+    assert set(got) - set(want) == {'_Z15cem_init_kernel10InitParams'} | admitted
+    assert set(hp.KERNELS_SINCE_WARM_START) <= set(fn.values())
     init = got['_Z15cem_init_kernel10InitParams']
     assert init['vgpr_spill_count'] == 0 and init['private_segment_fixed_size'] == 0, init

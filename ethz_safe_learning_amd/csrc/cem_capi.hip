@@ -1,6 +1,7 @@
 // cem_capi.hip — host side of the C ABI declared in include/cem_mpc.h.
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC (see csrc/build.sh).
 #include "cem_device.h"
+#include "cem_rollout_lean.h"
 #include "cem_score.h"
 #include "cem_refit_weighted.h"
 #include "cem_train.h"
@@ -707,6 +708,7 @@ struct cem_planner {
     bool have_weights;
     bool in_plan;
     bool sample_in_rollout;                  // the sampler runs as the rollout tiles' prologue (else: cem_sample_kernel in front of the rollout launch)
+    bool lean_rollout;                       // plans without caller noise tensors run cem_rollout_lean.hip's kernels (lean_eligible)
     const float *eps_act, *eps_model;       // current plan's explicit noise (device) or null
     // pinned host staging
     CtrlBlock *h_ctrl;
@@ -904,6 +906,17 @@ int cem_rollout_residency(int32_t chunks_per_tile, int32_t input_blocks_per_wave
 
 }  // extern "C"
 
+// The lean one-chunk rollout (cem_rollout_lean.hip: actions drawn in the lanes whose model noise is discarded, no materialised sample)
+// serves the one-chunk fp32 kernel of the obs + act <= 64 family with every feature quad all-observation or all-action, single-rank
+// single-state plans whose tiles sample inside the rollout launch (all resident at once: B1, B2), and a horizon whose mu / sigma quads
+// fit its LDS allowance.  Everything else — and any plan given explicit noise tensors — runs the generic kernels.
+static bool lean_eligible(const cem_planner *h, int rc)
+{
+    const Dims &d = h->d;
+    return launch_rollout_lean != nullptr && !d.wide && !d.split && rc == 1 && d.NFW == 1 && d.L == 4 && d.O % 4 == 0 && h->cfg.world_size == 1 && !h->batch &&
+           h->sample_in_rollout && CEM_LEAN_ACT_LDS_BYTES(d.H, (d.A + 3) / 4) <= CEM_LEAN_ACT_LDS_MAX;
+}
+
 // mb = 0: a single-state handle (cem_planner_create); mb > 0: a batch handle of mb problems (cem_batch_planner_create)
 static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, size_t workspace_bytes, void *hip_stream, cem_planner_t **out)
 {
@@ -930,7 +943,10 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
       const int slots = real_cus() * ((h->d.wide || h->d.split) ? 1 : resident_workgroups(h->d.NFW, pl.rc, pl.n_seg > 1));
       h->sample_in_rollout = (long long)nb * pl.n_tiles <= slots;        // (a batch handle: all its problems' tiles in one launch)
       if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
-          h->sample_in_rollout = std::strcmp(e, "kernel") != 0; }
+          h->sample_in_rollout = std::strcmp(e, "kernel") != 0;
+      h->lean_rollout = lean_eligible(h, pl.rc);
+      if (const char *e = std::getenv("CEM_FORCE_ROLLOUT"))      // diagnostic / tests: "generic" or "lean" — the results do not depend on it; "lean" on an ineligible handle is ignored
+          h->lean_rollout = h->lean_rollout && std::strcmp(e, "generic") != 0; }
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
@@ -1402,7 +1418,14 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         rp.musig = nullptr;
     }
     TimedLaunch timed(h, 0);
-    if (d.wide) HIPCHK(launch_rollout_wide(h, rp, h->n_tiles, rp.eps_model ? 1 : 0));
+    if (h->lean_rollout && !rp.eps_act && !rp.eps_model) {      // (the same tiles, segments and work queue as the generic launches below)
+        if (queued) {
+            rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = (uint32_t *)(ws + l.seg_flags); rp.seg_state = (f4 *)(ws + l.seg_state);
+            rp.seg_len = h->seg_len; rp.n_seg = h->n_seg; rp.n_pinned = h->n_pinned;
+        }
+        HIPCHK(launch_rollout_lean(rp, queued ? h->n_pinned + h->n_seg * (h->n_tiles - h->n_pinned) : h->n_tiles, h->stream, queued));
+    }
+    else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, h->n_tiles, rp.eps_model ? 1 : 0));
     else if (d.split) HIPCHK(launch_rollout_split(h->rc, d.NFW, rp.eps_model ? 1 : 0, rp, h->n_tiles, h->stream));
     else if (rp.eps_model) HIPCHK(launch_rollout<1>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
     else if (queued) {
@@ -2178,6 +2201,13 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out)
 {
     if (!h || !status_out) return CEM_ERR_INVALID_ARG;
     *status_out = h->graph_ready ? 1 : (h->graph_failed ? 2 : 0);
+    return CEM_OK;
+}
+
+int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out)
+{
+    if (!h || !path_out) return CEM_ERR_INVALID_ARG;
+    *path_out = h->lean_rollout ? 1 : 0;
     return CEM_OK;
 }
 

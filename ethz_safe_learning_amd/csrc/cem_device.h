@@ -548,6 +548,7 @@ __device__ __forceinline__ void cem_tile_sample_actions(const RolloutParams &p, 
 // at once, five particles — the prologue costs what this launch plus its graph node cost, and saves the node).  Host rule: cem_capi.hip
 // sample_in_rollout().
 // Batched plans: blockIdx.y is the problem (each problem skips on its own early stop).
+#ifndef CEM_DEVICE_PRIMITIVES_ONLY   // (a second translation unit takes the primitives and the templates, not the plain kernels: cem_rollout_lean.hip)
 __global__ __launch_bounds__(256) void cem_sample_kernel(const RolloutParams p)
 {
     const int b = (int)blockIdx.y;
@@ -560,6 +561,7 @@ __global__ __launch_bounds__(256) void cem_sample_kernel(const RolloutParams p)
         cem_sample_store(p, n, t, z, key, true, true, b);
     }
 }
+#endif
 
 #include "cem_rollout_common.h"
 
@@ -981,6 +983,7 @@ __global__ __launch_bounds__(256) void cem_rollout_seg_kernel(const RolloutParam
     }
 }
 
+#ifndef CEM_DEVICE_PRIMITIVES_ONLY
 // ---------------------------------------------------------------------------------------------------------
 // small kernels of the optimiser loop
 // ---------------------------------------------------------------------------------------------------------
@@ -2365,3 +2368,4 @@ __global__ __launch_bounds__(256) void cem_fill_noise_kernel(const FillParams p)
         p.eps_out[gid] = e[gid & 3];
     }
 }
+#endif  // CEM_DEVICE_PRIMITIVES_ONLY

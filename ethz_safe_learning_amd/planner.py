@@ -429,6 +429,12 @@ class CemPlanner:
         _capi.check(self.lib.cem_planner_launches_per_iteration(self.h, C.byref(n)), 'cem_planner_launches_per_iteration')
         return n.value
 
+    def rollout_path(self):
+        """'generic' | 'lean': the rollout kernels plan() launches on this handle when it is given no noise tensors (cem_planner_rollout_path)."""
+        n = C.c_int32()
+        _capi.check(self.lib.cem_planner_rollout_path(self.h, C.byref(n)), 'cem_planner_rollout_path')
+        return ('generic', 'lean')[n.value]
+
     def set_particle_objective(self, kind='mean', m=0):
         """How a candidate's particle returns become its score (cem_planner_set_particle_objective): 'mean' (the reference, the default)
         or 'lower_tail' with m in 1 .. particles, the mean of the m smallest returns.  Sticky; a change re-captures the graph."""

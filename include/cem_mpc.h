@@ -281,6 +281,12 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out);
  * multi-workgroup selects; CEM_VARIANT_COST: its own reduce, csrc/cem_score.h; CEM_PARTICLES_LOWER_TAIL: its reduce, csrc/cem_score.h, which no select folds), + 1 for select_mode 3's recovery kernel (returns at once unless a barrier expired), + 7 for select_mode 2's
  * chain.  The stepwise calls always launch the reduce kernel. */
 int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches_out);
+/* Which rollout kernels cem_planner_plan launches on this handle when the plan is given no explicit noise tensors: 0 = the generic
+ * kernels; 1 = the lean one-chunk kernels (csrc/cem_rollout_lean.hip), which draw every action in the lane that needs it instead of
+ * reading a stored sample — fp32, one chunk per tile, obs + act <= 64 with obs a multiple of 4, single rank, single state, all tiles
+ * resident at once.  Same results bit for bit; CEM_FORCE_ROLLOUT=generic at create keeps an eligible handle on the generic kernels.
+ * A plan with eps_act / eps_model tensors always runs the generic kernels. */
+int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out);
 
 /* TransitionModel.unfold_sequences (transition_model.py:64-77) as an API of its own:
  * s0[B][obs], actions[B][H][A] (device) -> traj[B][H+1][obs] (device); optional mu/stddev[B][H][obs].

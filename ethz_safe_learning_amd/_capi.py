@@ -20,6 +20,7 @@ CEM_VARIANT_CEM, CEM_VARIANT_SAFE, CEM_VARIANT_COST = 0, 1, 2    # enum cem_vari
 CEM_PARTICLES_MEAN, CEM_PARTICLES_LOWER_TAIL = 0, 1             # enum cem_particle_objective
 CEM_CONSTRAINT_BETA, CEM_CONSTRAINT_BUDGET = 0, 1               # enum cem_constraint_kind
 CEM_REFIT_UNIFORM, CEM_REFIT_SOFTMAX = 0, 1                       # enum cem_refit
+CEM_NOISE_WHITE, CEM_NOISE_MIXED = 0, 1                         # enum cem_action_noise
 CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,6 +37,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_get_carry', 'cem_planner_set_carry_slots', 'cem_planner_set_particle_objective', 'cem_planner_get_particle_objective',
     'cem_planner_set_constraint', 'cem_planner_get_constraint', 'cem_planner_set_cost_budget', 'cem_planner_constraint_costs',
     'cem_planner_set_refit', 'cem_planner_get_refit', 'cem_planner_refit_stats',
+    'cem_planner_set_action_noise', 'cem_planner_get_action_noise', 'cem_planner_action_noise_dev',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -174,6 +176,9 @@ def load():
     lib.cem_planner_set_refit.argtypes = [vp, C.c_int32, C.c_float]
     lib.cem_planner_get_refit.argtypes = [vp, i32p, fp]
     lib.cem_planner_refit_stats.argtypes = [vp, C.c_int32, vp, C.c_int32]
+    lib.cem_planner_set_action_noise.argtypes = [vp, C.c_int32, vp]
+    lib.cem_planner_get_action_noise.argtypes = [vp, i32p, vp]
+    lib.cem_planner_action_noise_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

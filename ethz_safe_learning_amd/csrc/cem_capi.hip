@@ -4,6 +4,7 @@
 #include "cem_rollout_lean.h"
 #include "cem_score.h"
 #include "cem_refit_weighted.h"
+#include "cem_noise_mix.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -761,6 +762,12 @@ struct cem_planner {
     float refit_tau, refit_beta;             // the temperature as set and fl32(1 / temperature), rounded once here
     float *refit_dev;                        // a device allocation of the handle's own, made on first use: the select's discarded blend [slots][2][HA], then ESS [slots][I]
     bool refit_ran;                          // a weighted select has been put on the stream (cem_planner_refit_stats)
+    // cem_planner_set_action_noise (cem_noise_mix.h)
+    int noise_kind;                          // CEM_NOISE_WHITE: the samplers draw their own Philox normals; CEM_NOISE_MIXED: they read noise_eps, which
+                                             // cem_mix_action_noise_kernel fills behind the plan's first kernel
+    std::vector<float> h_mix, h_mix_t;       // M [H][H] as set, and transposed: the source of its stream-ordered upload
+    float *noise_dev;                        // a device allocation of the handle's own, made on first use: M transposed [H][H] (padded to a quad), then eps
+    float *noise_eps; size_t noise_floats;   // eps [slots][I][N][H][A] inside noise_dev, and its float count
 };
 
 namespace {
@@ -803,6 +810,7 @@ void release_handle(cem_planner *h)
     if (h->pack_desc) hipFree(h->pack_desc);
     if (h->budget_dev) hipFree(h->budget_dev);
     if (h->refit_dev) hipFree(h->refit_dev);
+    if (h->noise_dev) hipFree(h->noise_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
@@ -952,6 +960,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
     h->cost_m = 0; h->budget_dev = nullptr; h->cstat_obj = nullptr; h->cstat_obj_n = 0; h->last_cstat = nullptr; h->last_cstat_n = h->last_cstat_problems = 0;
     h->refit_kind = CEM_REFIT_UNIFORM; h->refit_tau = 0.f; h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
+    h->noise_kind = CEM_NOISE_WHITE; h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
@@ -1346,6 +1355,13 @@ int enqueue_begin(cem_planner *h)
     const int n = warm_slots(h) * std::max<int>(ip.HA, (int)(sizeof(CtrlBlock) / 4));
     hipLaunchKernelGGL(cem_init_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, ip);
     HIPCHK(hipGetLastError());
+    // time-correlated action noise: the plan's whole eps_act tensor, from the key the kernel above has just put into the workspace (one
+    // launch and one graph node per plan); a caller's own eps_act is taken as given
+    if (h->noise_kind == CEM_NOISE_MIXED && !h->eps_act) {
+        MixParams mp{}; mp.mix_t = h->noise_dev; mp.eps = h->noise_eps; mp.ctrl = (const CtrlBlock *)(h->ws + l.ctrl);
+        mp.I = d.I; mp.N = d.N; mp.H = d.H; mp.A = d.A;
+        HIPCHK(launch_mix_action_noise(mp, warm_slots(h), h->stream));
+    }
     {   // launched for real (not recorded into a graph): the pending carries are on their way to Layout::carry (stage_warm's invariant)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
@@ -1403,7 +1419,9 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     rp.H = d.H; rp.Bloc = d.Bloc; rp.Btot = d.Btot; rp.it = it; rp.variant = cost_obj ? (int)CEM_VARIANT_SAFE : h->cfg.variant; rp.check_done = 1;
     rp.stamps = (long long *)(ws + l.stamps);
     // the sampler's inputs and outputs (cem_mpc.py:44-48)
-    rp.musig = (const float *)(ws + l.musig); rp.eps_act = h->eps_act ? h->eps_act + (size_t)it * d.N * d.H * d.A : nullptr;
+    // (the handle's own mixed tensor stands in wherever the caller passed none: the lean kernels then step aside below, as for any tensor)
+    const float *eps_act = h->eps_act ? h->eps_act : (h->noise_kind == CEM_NOISE_MIXED ? h->noise_eps : nullptr);
+    rp.musig = (const float *)(ws + l.musig); rp.eps_act = eps_act ? eps_act + (size_t)it * d.N * d.H * d.A : nullptr;
     rp.act_bounds = (const float *)(ws + l.act_bounds); rp.actions_w = (float *)(ws + l.actions); rp.act_pad_w = (float *)(ws + l.act_pad);
     rp.pad_shift = d.O - 4 * d.act_q0; rp.pad_floats = 4 * d.act_nq; rp.N = d.N; rp.Nloc = d.Nloc; rp.n_off = d.n_off; rp.n_tiles = h->n_tiles;
     // a batch handle: ONE launch per stage for all its problems, problem b on tiles [b n_tiles, (b + 1) n_tiles) and its own slices
@@ -2079,6 +2097,71 @@ int cem_planner_refit_stats(cem_planner_t *h, int32_t problem, float *ess_out_ho
     return CEM_OK;
 }
 
+// the handle's noise allocation (cem_planner::noise_dev), made on first use and zeroed: M transposed, then the mixed tensor of every slot
+static int ensure_noise(cem_planner *h)
+{
+    if (h->noise_dev) return CEM_OK;
+    const Dims &d = h->d;
+    HIPCHK(prepare_mix_action_noise(d.H));
+    const size_t mt = ((size_t)d.H * d.H + 3) & ~(size_t)3;
+    const size_t eps = (size_t)warm_slots(h) * d.I * d.N * d.H * d.A;
+    float *p = nullptr;
+    HIPCHK(hipMalloc((void **)&p, (mt + eps) * 4));
+    if (hipMemsetAsync(p, 0, (mt + eps) * 4, h->stream) != hipSuccess) { g_last_hip = (int)hipGetLastError(); hipFree(p); return CEM_ERR_HIP; }
+    h->noise_dev = p; h->noise_eps = p + mt; h->noise_floats = eps;
+    return CEM_OK;
+}
+
+int cem_planner_set_action_noise(cem_planner_t *h, int32_t kind, const float *mix_host)
+{
+    if (!h || (kind != CEM_NOISE_WHITE && kind != CEM_NOISE_MIXED)) return CEM_ERR_INVALID_ARG;
+    if ((kind == CEM_NOISE_MIXED) != (mix_host != nullptr)) return CEM_ERR_INVALID_ARG;
+    const size_t HH = (size_t)h->d.H * h->d.H;
+    if (kind == CEM_NOISE_MIXED) for (size_t i = 0; i < HH; ++i) if (!finite_bits(mix_host[i])) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    if (kind == CEM_NOISE_MIXED) {
+        // the kernel mixes all N candidates of ONE rank's key; a sharded plan would need it per shard and no such run has been made
+        if (h->d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
+        if (h->d.H > CEM_MIX_MAX_H || !launch_mix_action_noise || !prepare_mix_action_noise) return CEM_ERR_UNSUPPORTED;
+    }
+    if (kind == CEM_NOISE_WHITE && h->noise_kind == CEM_NOISE_WHITE) return CEM_OK;
+    const bool fresh = kind == CEM_NOISE_MIXED && !h->noise_dev;
+    if (kind == CEM_NOISE_MIXED) { const int st = ensure_noise(h); if (st) return st; }
+    // a handle this call fails on keeps what it had: an allocation made just above goes again (cem_planner_action_noise_dev reports
+    // NULL on a handle that has never been MIXED)
+    auto fail = [&](hipError_t e) { g_last_hip = (int)e; if (fresh) { hipFree(h->noise_dev); h->noise_dev = h->noise_eps = nullptr; h->noise_floats = 0; } return CEM_ERR_HIP; };
+    // Not retire_graph, as the sibling setters: that waits only for a captured plan, and here an EAGER MIXED plan still draining behind
+    // its polled result may be reading the matrix about to be overwritten.  So the wait is unconditional.
+    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) return fail(e);
+    std::vector<float> mix, mix_t;
+    if (kind == CEM_NOISE_MIXED) {
+        const int H = h->d.H;
+        mix.assign(mix_host, mix_host + HH); mix_t.resize(HH);
+        for (int t = 0; t < H; ++t) for (int u = 0; u < H; ++u) mix_t[(size_t)u * H + t] = mix_host[(size_t)t * H + u];
+        // (the swap below keeps mix_t's storage alive in the handle for as long as the stream may read it)
+        if (const hipError_t e = hipMemcpyAsync(h->noise_dev, mix_t.data(), HH * 4, hipMemcpyHostToDevice, h->stream); e != hipSuccess) return fail(e);
+        h->h_mix.swap(mix); h->h_mix_t.swap(mix_t);
+    }
+    drop_graph(h);                                                              // the captured plan holds the other sampler's launches
+    h->noise_kind = kind;
+    return CEM_OK;
+}
+
+int cem_planner_get_action_noise(const cem_planner_t *h, int32_t *kind_out, float *mix_out_host)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (kind_out) *kind_out = h->noise_kind;
+    if (mix_out_host && h->noise_kind == CEM_NOISE_MIXED) std::memcpy(mix_out_host, h->h_mix.data(), h->h_mix.size() * 4);
+    return CEM_OK;
+}
+
+int cem_planner_action_noise_dev(cem_planner_t *h, const float **eps_dev_out, size_t *n_floats_out)
+{
+    if (!h || !eps_dev_out || !n_floats_out) return CEM_ERR_INVALID_ARG;
+    *eps_dev_out = h->noise_eps; *n_floats_out = h->noise_floats;
+    return CEM_OK;
+}
+
 int cem_planner_set_initial_distribution(cem_planner_t *h, int32_t slot, const float *mu, const float *sigma)
 {
     if (!h || !mu || !sigma || slot < 0 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
@@ -2161,6 +2244,7 @@ int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int
     if (h->batch) return CEM_ERR_STATE;                                        // batch handles are single-rank
     if (n_ranks != h->d.W || rank != h->d.R) return CEM_ERR_INVALID_ARG;       // the communicator IS the candidate sharding of this handle
     if (h->in_plan) return CEM_ERR_STATE;
+    if (h->noise_kind == CEM_NOISE_MIXED) return CEM_ERR_UNSUPPORTED;          // (cem_planner_set_action_noise refuses a communicator; so the reverse)
     Rccl *r = rccl(); if (!r) return CEM_ERR_COMM;
     if (h->comm) { r->CommDestroy(h->comm); h->comm = nullptr; }
     CemNcclId nid; std::memcpy(nid.internal, id, CEM_COMM_ID_BYTES);
@@ -2207,7 +2291,7 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out)
 int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out)
 {
     if (!h || !path_out) return CEM_ERR_INVALID_ARG;
-    *path_out = h->lean_rollout ? 1 : 0;
+    *path_out = (h->lean_rollout && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;    // (the lean kernels draw in place and cannot take a tensor)
     return CEM_OK;
 }
 

@@ -72,6 +72,10 @@ class PlannerConfig:
     refit: str = 'uniform'             # 'uniform': every elite counts 1 / k (the reference) | 'softmax': elite j counts exp((s_j - s_max) / temperature)
                                        # (cem_planner_set_refit, CEM_REFIT_SOFTMAX; n_elite = n_samples is MPPI); not in cem_config_t: set after create
     refit_temperature: float = 0.0     # 'softmax': the temperature, finite and > 0 ('uniform' ignores it)
+    action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
+                                       # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
+                                       # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
+    action_noise_param: float = 0.0    # 'powerlaw': the spectral exponent beta >= 0; 'ar1': the lag-1 correlation rho in (-1, 1); 'white' ignores it
     worst_particles: int = 0           # 0: score = the particle mean (the reference); m in 1 .. particles: the mean of the m smallest particle
                                        # returns (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL); not in cem_config_t: set after create
 
@@ -84,7 +88,76 @@ VARIANTS = {'cem': _capi.CEM_VARIANT_CEM, 'safe': _capi.CEM_VARIANT_SAFE, 'cost'
 PARTICLE_OBJECTIVES = {'mean': _capi.CEM_PARTICLES_MEAN, 'lower_tail': _capi.CEM_PARTICLES_LOWER_TAIL}
 CONSTRAINTS = {'beta': _capi.CEM_CONSTRAINT_BETA, 'budget': _capi.CEM_CONSTRAINT_BUDGET}
 REFITS = {'uniform': _capi.CEM_REFIT_UNIFORM, 'softmax': _capi.CEM_REFIT_SOFTMAX}
+ACTION_NOISES = ('white', 'powerlaw', 'ar1')
 INFEASIBLE_BELOW = np.float32(-2.0 ** 100)          # cem_mpc.h CEM_INFEASIBLE_BELOW: a constrained score is feasible iff it lies above
+
+
+def powerlaw_mixing(H, beta, dtype=np.float32) -> np.ndarray:
+    """The mixing matrix M [H, H] of power-law ("coloured") action noise, eps = M xi: stationary Gaussian noise along the horizon whose
+    power spectrum falls like f^-beta (beta 0 white, 1 pink, 2 red — the larger, the longer a sequence holds its direction).
+        k' = min(k, H - k),  f_k = k' / H,  f_0 := 1 / H                  the folded frequency of bin k; the DC bin takes the lowest one
+        lambda_k = f_k^-beta, scaled so that sum lambda = H
+        m = real(ifft(sqrt(lambda))),  M[t][u] = m[(t - u) mod H]
+    M is a symmetric circulant with unit rows (diag(M M^T) = 1: every step keeps unit variance, so sigma means what it meant); its
+    covariance M M^T is the circulant with spectrum lambda.  beta = 0 is the identity exactly.  Like the FFT sampler of iCEM (Pinneri et
+    al. 2020), which draws in the frequency domain, the correlation is PERIODIC in the horizon: step H - 1 is as correlated with step 0
+    as step 1 is.  ar1_mixing has no wrap-around.  Computed in float64, returned as `dtype` (the library takes float32)."""
+    H, beta = int(H), float(beta)
+    if H < 1:
+        raise ValueError('H must be >= 1')
+    if not (math.isfinite(beta) and beta >= 0.0):
+        raise ValueError('beta must be finite and >= 0, got %r' % (beta,))
+    if beta == 0.0:
+        return np.eye(H, dtype=dtype)
+    k = np.arange(H)
+    f = np.minimum(k, H - k).astype(np.float64) / H
+    f[0] = 1.0 / H
+    lam = f ** (-beta)
+    lam *= H / lam.sum()
+    m = np.real(np.fft.ifft(np.sqrt(lam)))
+    t = np.arange(H)
+    return np.ascontiguousarray(m[(t[:, None] - t[None, :]) % H]).astype(dtype)
+
+
+def ar1_mixing(H, rho, dtype=np.float32) -> np.ndarray:
+    """The mixing matrix M [H, H] of first-order autoregressive action noise, eps[t] = rho eps[t - 1] + sqrt(1 - rho^2) xi[t], eps[0] = xi[0]:
+        M[t][0] = rho^t,   M[t][u] = sqrt(1 - rho^2) rho^(t - u) for 1 <= u <= t,   0 above the diagonal.
+    Unit variance at every step, covariance rho^|t - t'|, no wrap-around (lower triangular: step t mixes steps 0 .. t only).  rho = 0 is
+    the identity.  Computed in float64, returned as `dtype`."""
+    H, rho = int(H), float(rho)
+    if H < 1:
+        raise ValueError('H must be >= 1')
+    if not -1.0 < rho < 1.0:                        # (NaN fails both comparisons)
+        raise ValueError('rho must lie in (-1, 1), got %r' % (rho,))
+    t = np.arange(H)
+    lag = t[:, None] - t[None, :]
+    M = np.where(lag >= 0, rho ** np.maximum(lag, 0).astype(np.float64), 0.0)
+    M[:, 1:] *= math.sqrt(1.0 - rho * rho)
+    return np.ascontiguousarray(M).astype(dtype)
+
+
+def mix_noise(M, xi) -> np.ndarray:
+    """Host restatement of CEM_NOISE_MIXED (cem_mpc.h), bit for bit: xi [..., H, A] white normals (CemPlanner.fill_noise's eps_act) ->
+    eps [..., H, A] with eps[..., t, a] = the fp32 sum over u = 0 .. H - 1, in that order and starting from +0, of fl32(M[t][u] * xi[..., u, a]).
+    The product and the sum are separate float32 operations, as on the device."""
+    M = np.asarray(M, np.float32)
+    x = np.asarray(xi, np.float32)
+    H = M.shape[0]
+    if M.shape != (H, H) or x.ndim < 2 or x.shape[-2] != H:
+        raise ValueError('M must be [H, H] and xi [..., H, A]')
+    acc = np.zeros(x.shape, np.float32)
+    for u in range(H):
+        acc = acc + M[:, u][:, None] * x[..., u, :][..., None, :]
+    return acc
+
+
+def mixing_matrix(kind, param, H):
+    """None for 'white', else the [H, H] float32 matrix of 'powerlaw' (param = beta) or 'ar1' (param = rho)."""
+    if kind not in ACTION_NOISES:
+        raise ValueError("action noise is 'white', 'powerlaw' or 'ar1', got %r" % (kind,))
+    if kind == 'white':
+        return None
+    return powerlaw_mixing(H, param) if kind == 'powerlaw' else ar1_mixing(H, param)
 
 
 def encode_infeasible(total) -> np.float32:
@@ -250,6 +323,12 @@ class CemPlanner:
         if cfg.refit != 'uniform':
             try:
                 self.set_refit(cfg.refit, cfg.refit_temperature)
+            except Exception:
+                self.close()
+                raise
+        if cfg.action_noise != 'white':
+            try:
+                self.set_action_noise(cfg.action_noise, cfg.action_noise_param)
             except Exception:
                 self.close()
                 raise
@@ -496,6 +575,52 @@ class CemPlanner:
         out = np.zeros(self.cfg.iterations if n is None else int(n), np.float32)
         _capi.check(self.lib.cem_planner_refit_stats(self.h, int(problem), _np_ptr(out), out.size), 'cem_planner_refit_stats')
         return out
+
+    def set_action_noise(self, kind_or_matrix='white', param=None):
+        """What the sampler multiplies by sigma (cem_planner_set_action_noise): 'white' (the reference, the default), 'powerlaw' with
+        param = beta, 'ar1' with param = rho, or an [H, H] mixing matrix of the caller's own (row = output step); then eps = M xi along
+        the horizon (mix_noise restates it).  Sticky; a change waits for the stream and re-captures the graph."""
+        H = self.cfg.horizon
+        if isinstance(kind_or_matrix, str):
+            M = mixing_matrix(kind_or_matrix, 0.0 if param is None else param, H)
+        else:
+            M = np.ascontiguousarray(np.asarray(kind_or_matrix, np.float32))
+            if M.shape != (H, H):
+                raise ValueError('the mixing matrix must have shape [%d, %d]' % (H, H))
+        kind = _capi.CEM_NOISE_WHITE if M is None else _capi.CEM_NOISE_MIXED
+        _capi.check(self.lib.cem_planner_set_action_noise(self.h, kind, _np_ptr(M)), 'cem_planner_set_action_noise')
+
+    def action_noise(self):
+        """('white', None) or ('mixed', M [H, H]) as set (cem_planner_get_action_noise)."""
+        kind = C.c_int32()
+        M = np.zeros((self.cfg.horizon, self.cfg.horizon), np.float32)
+        _capi.check(self.lib.cem_planner_get_action_noise(self.h, C.byref(kind), _np_ptr(M)), 'cem_planner_get_action_noise')
+        return ('white', None) if kind.value == _capi.CEM_NOISE_WHITE else ('mixed', M)
+
+    def action_noise_floats(self):
+        """Floats of the handle's mixed-noise allocation (cem_planner_action_noise_dev): 0 on a handle that has never been 'mixed'."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        _capi.check(self.lib.cem_planner_action_noise_dev(self.h, C.byref(ptr), C.byref(n)), 'cem_planner_action_noise_dev')
+        return int(n.value) if ptr.value else 0
+
+    def action_noise_tensor(self, problem=0):
+        """eps [I, N, H, A] of `problem` as the handle's last 'mixed' plan sampled from it (cem_planner_action_noise_dev), on the host.
+        Waits for the planner's stream.  Raises on a handle that has never been 'mixed'."""
+        c, t = self.cfg, self._torch
+        ptr, n = C.c_void_p(), C.c_size_t()
+        _capi.check(self.lib.cem_planner_action_noise_dev(self.h, C.byref(ptr), C.byref(n)), 'cem_planner_action_noise_dev')
+        per = c.iterations * c.n_samples * c.horizon * c.act_dim
+        if not ptr.value:
+            raise RuntimeError('the handle has no mixed action noise (set_action_noise was never given a matrix)')
+        if not 0 <= int(problem) < n.value // per:
+            raise ValueError('problem out of range')
+
+        class _Dev:                                   # the library's allocation as torch sees foreign device memory
+            __cuda_array_interface__ = dict(shape=(per,), typestr='<f4', data=(ptr.value + 4 * per * int(problem), False), version=2)
+        self.synchronize()
+        with t.cuda.device(self.device):
+            out = t.as_tensor(_Dev(), device=self.device).cpu().numpy().copy()
+        return out.reshape(c.iterations, c.n_samples, c.horizon, c.act_dim)
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')

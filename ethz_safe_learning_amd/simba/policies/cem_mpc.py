@@ -27,7 +27,16 @@ from the elites weighted by ``exp((score - best elite score) / elite_temperature
 elites" below that.  ``generate_action``, ``generate_actions`` and warm-started plans use it; ``last_ess`` holds the effective sample
 size of every iteration of the last plan (a float array; one per row after ``generate_actions``), each in [1, n_elite].  ``None`` (the
 default, and what every shipped preset has) changes no handle and no bit.  Nothing is claimed about the returns or the safety of an
-agent that uses it."""
+agent that uses it.
+
+Time-correlated action noise (beyond the reference, off by default): with ``noise_beta`` a float >= 0 the sampler draws every action
+sequence from power-law noise of that spectral exponent (planner.powerlaw_mixing: 1 pink, 2 red; periodic in the horizon, like iCEM's
+FFT sampler), with ``noise_rho`` a float in (-1, 1) from AR(1) noise of that lag-1 correlation (planner.ar1_mixing: no wrap-around) —
+``PlannerConfig.action_noise``, cem_mpc.h CEM_NOISE_MIXED; DESIGN.md 4.11 — instead of drawing every step independently, so that a
+candidate holds a direction for several steps.  Give at most one of the two.  ``generate_action``, ``generate_actions`` and warm-started
+plans use it; the plan then runs the generic rollout kernels (the lean ones draw in place).  ``None`` for both (the default, and what
+every shipped preset has) touches no handle and changes no bit.  Nothing is claimed about the returns or the safety of an agent that
+uses it."""
 import logging
 import numpy as np
 
@@ -41,7 +50,7 @@ class CemMpc(MpcPolicy):
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
                  warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None,
-                 elite_temperature=None):
+                 elite_temperature=None, noise_beta=None, noise_rho=None):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -61,6 +70,15 @@ class CemMpc(MpcPolicy):
         self.elite_temperature = None if elite_temperature is None else float(elite_temperature)
         if self.elite_temperature is not None and not (np.isfinite(self.elite_temperature) and self.elite_temperature > 0.0):
             raise ValueError('elite_temperature must be finite and > 0, got %r' % (elite_temperature,))
+        # time-correlated action noise (beyond the reference's kwargs): see the module docstring
+        if noise_beta is not None and noise_rho is not None:
+            raise ValueError('give at most one of noise_beta and noise_rho')
+        self.noise_beta = None if noise_beta is None else float(noise_beta)
+        self.noise_rho = None if noise_rho is None else float(noise_rho)
+        if self.noise_beta is not None and not (np.isfinite(self.noise_beta) and self.noise_beta >= 0.0):
+            raise ValueError('noise_beta must be finite and >= 0, got %r' % (noise_beta,))
+        if self.noise_rho is not None and not -1.0 < self.noise_rho < 1.0:
+            raise ValueError('noise_rho must lie in (-1, 1), got %r' % (noise_rho,))
         self.last_ess = None                           # ESS per iteration of the last weighted plan (generate_actions: a list, one array per row)
         self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
         self._warm_cap = 1                             # slots the warm-started batch handle must hold
@@ -82,6 +100,13 @@ class CemMpc(MpcPolicy):
             return {}
         return dict(refit='softmax', refit_temperature=self.elite_temperature)
 
+    def _noise_config(self):
+        if self.noise_beta is not None:
+            return dict(action_noise='powerlaw', action_noise_param=self.noise_beta)
+        if self.noise_rho is not None:
+            return dict(action_noise='ar1', action_noise_param=self.noise_rho)
+        return {}
+
     def _scorer_config(self):
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
         if scorer is None:
@@ -100,7 +125,7 @@ class CemMpc(MpcPolicy):
             smoothing=self.smoothing, stddev_threshold=self.stddev_threshold, noise_stddev=self.noise_stddev,
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
             use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._refit_config(),
-            **self._extra_config())
+            **self._noise_config(), **self._extra_config())
 
     def _owns_handles(self):
         """Whether this policy's planning handles carry state of its own (the warm-start carry; SafeCemMpc: a cost budget) and so must

@@ -35,7 +35,11 @@ episode's costs accrue, or, with an array, to give the rows of ``generate_action
 summed cost T that ranked an infeasible best (``None`` where it is feasible).  An infeasible best scores below -2^100, hence below any
 ``recover_below``, which keeps working unchanged and replaces it by the ``optimize_for_safety`` action.  ``optimize_for_safety`` and
 ``compute_mean_costs`` are untouched.  ``None`` (the default, and what every shipped preset has) touches no handle and changes no bit.
-Nothing is claimed about the returns or the safety of an agent that uses it."""
+Nothing is claimed about the returns or the safety of an agent that uses it.
+
+``noise_beta`` / ``noise_rho`` (CemMpc's, off by default): the reward plans sample time-correlated action sequences, and so do
+``optimize_for_safety`` and the recovery plans of ``recover_below`` — the cost handle is the policy's configuration with another
+objective, the sampler is shared and there is no reason for it to differ."""
 import dataclasses
 
 import numpy as np
@@ -144,7 +148,8 @@ class SafeCemMpc(CemMpc):
     def cost_planner_config(self):
         return dataclasses.replace(self.planner_config(), variant='cost', worst_particles=0,      # (the cost objective has no lower tail
                                    constraint='beta', worst_cost_particles=0,                     # and no budget;
-                                   refit='uniform', refit_temperature=0.0)                        # recovery plans keep the uniform refit)
+                                   refit='uniform', refit_temperature=0.0)                        # recovery plans keep the uniform refit;
+                                                                                                  # the action noise stays the policy's)
 
     def build_cost(self):
         """The cost handle of the policy's shape (shared through the cache like the planning handle), the model's weights staged."""

@@ -552,6 +552,46 @@ int cem_planner_get_refit(const cem_planner_t *h, int32_t *kind_out, float *temp
 int cem_planner_refit_stats(cem_planner_t *h, int32_t problem, float *ess_out_host, int32_t n);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The action noise: what the sampler of cem_mpc.py:44-48 multiplies by sigma.  Beyond the reference, off by default.
+ *   CEM_NOISE_WHITE  the reference's tf.random.normal: every step of every sequence independent.  What every handle does unless told
+ *                    otherwise, with the launches, graph nodes and bits it always had (the lean rollout where it is eligible).
+ *   CEM_NOISE_MIXED  time-correlated ("coloured") noise, eps = M xi: ONE mixing matrix M[H][H] per handle — fp32, row-major, row = output
+ *                    step t, column = input step u —, shared by all action dimensions, iterations and problems.  For problem b, iteration
+ *                    i, candidate n and action dimension a:
+ *                      xi[u]  = cem_normal4(n, u, i, a / 4, CEM_STREAM_ACT, key(b))[a % 4]     the white stream, unchanged: what
+ *                                                                                             cem_fill_noise dumps as eps_act
+ *                      eps[t] = acc after:  acc = +0.f;  for u = 0 .. H - 1 in order:  acc = fl32(acc + fl32(M[t][u] * xi[u]))
+ *                      action = clip(eps[t] * sigma[t][a] + mu[t][a], lb[a], ub[a])           the existing sampler, unchanged
+ *                    The multiply and the add are rounded separately, no term is skipped (zeros of M included: a white draw of -0.0
+ *                    under M = I comes out as +0.0, the one difference from WHITE, and it vanishes in the action), there are no
+ *                    floating-point atomics, and equal inputs give equal bits on every launch.  Model noise, eps_out, the select, the
+ *                    refit, the warm start and every objective are as they are.  Any Gaussian correlation along the horizon is such an
+ *                    M (planner.py: powerlaw_mixing, ar1_mixing; mix_noise restates the sum above in NumPy, bit for bit).
+ * One kernel (csrc/cem_noise_mix.h) runs once per plan behind the plan's first kernel and writes eps[slots][I][N][H][A] into a device
+ * allocation the handle owns (made on first use; the workspace keeps its layout and size); the samplers — as the rollout tiles' prologue,
+ * as a floating segment's prologue, as a launch of their own — then read it the way they read a caller's eps_act tensor.  The lean kernels
+ * draw in place and cannot take a tensor: while MIXED, cem_planner_rollout_path reports the generic path.
+ * cem_planner_launches_per_iteration is unchanged; a captured plan gains one node.  Whole plans (graph and eager), the stepwise calls
+ * (cem_plan_begin runs the mix), batch handles (one M for all problems; a problem staged as stopped is skipped and its slice of eps keeps
+ * its bytes), warm start, every variant, particle objective, constraint, refit and precision serve it.
+ * A caller's own eps_act tensor (cem_planner_plan, cem_plan_begin, cem_planner_plan_batch) is taken as given and is NOT mixed.
+ * The setting is sticky per handle; the setter waits for the stream and drops the captured graph.  Back on WHITE the handle launches
+ * exactly what a fresh handle launches.
+ *   CEM_ERR_INVALID_ARG  null handle, unknown kind, MIXED with a NULL matrix, WHITE with a non-NULL matrix, any non-finite entry
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  MIXED with world_size > 1 or a communicator (and cem_planner_comm_init on a MIXED handle); horizon > 128 (the
+ *                        kernel keeps M in LDS: 64 KB at 128)
+ * A failed allocation returns CEM_ERR_HIP.  The handle keeps its previous setting after any of these. */
+enum cem_action_noise { CEM_NOISE_WHITE = 0, CEM_NOISE_MIXED = 1 };
+int cem_planner_set_action_noise(cem_planner_t *h, int32_t kind, const float *mix_host /* [H][H] or NULL */);
+/* kind as set and, while MIXED, the matrix as set -> mix_out_host[H][H] (WHITE: not written); either pointer may be NULL */
+int cem_planner_get_action_noise(const cem_planner_t *h, int32_t *kind_out, float *mix_out_host /* [H][H] or NULL */);
+/* The mixed tensor of the handle's last MIXED plan where it lives: a device pointer into the handle's allocation, [slots][I][N][H][A]
+ * floats (slots = max(max_batch, 1)), and the float count.  Valid until destroy; contents follow the handle's stream (synchronise before
+ * reading); zeros until a MIXED plan has run.  NULL and 0 on a handle that has never been MIXED (it owns no such allocation). */
+int cem_planner_action_noise_dev(cem_planner_t *h, const float **eps_dev_out, size_t *n_floats_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

@@ -13,6 +13,9 @@ is the serial evaluation above.
 
 --elite_temperature T [T ...] adds a grid axis: every configuration is also evaluated with the score-weighted refit at each temperature
 (CemMpc(elite_temperature=T); the word `none` stands for the uniform refit).  Without the flag the grid and its records are the reference's.
+
+--noise_beta B [B ...] adds a grid axis in the same way: every configuration is also evaluated with power-law action noise of each
+spectral exponent (CemMpc(noise_beta=B); the word `none` stands for the reference's white noise).
 """
 import argparse
 import json
@@ -31,7 +34,7 @@ PROPOSALS_WITH_ITERATIONS = [(100, 15), (150, 10), (300, 5)]
 ELITE_RATIOS = [0.05, 0.1, 0.2]
 
 
-WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor', 'elite_temperature')
+WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor', 'elite_temperature', 'noise_beta')
 
 
 def make_new_policy(model, environment, horizon, iterations, n_samples, elite_ratio, policy_kwargs):
@@ -61,17 +64,20 @@ def evaluate_lockstep(trainer, environments, eval_steps, eval_episode_length):
 
 def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=HORIZONS,
                 proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS, parallel_envs=None,
-                elite_temperatures=None):
-    """elite_temperatures: None (the reference's grid) or a list of temperatures, None among them for the uniform refit — a fourth axis."""
+                elite_temperatures=None, noise_betas=None):
+    """elite_temperatures: None (the reference's grid) or a list of temperatures, None among them for the uniform refit — a fourth axis.
+    noise_betas: None or a list of power-law exponents, None among them for white noise — a further axis."""
     from ethz_safe_learning_amd.simba.infrastructure.logging_utils import logger
     agent = trainer.agent
     results = []
     for horizon in horizons:
         for n_samples, iterations in proposals_with_iterations:
-            for ratio, temperature in [(r, t) for r in elite_ratios for t in (elite_temperatures or [None])]:
+            for ratio, temperature, beta in [(r, t, b) for r in elite_ratios for t in (elite_temperatures or [None]) for b in (noise_betas or [None])]:
                 kwargs = params['policies']['cem_mpc']
                 if elite_temperatures:
                     kwargs = dict(kwargs, elite_temperature=temperature)
+                if noise_betas:
+                    kwargs = dict(kwargs, noise_beta=beta)
                 agent.policy = make_new_policy(agent.model, env, horizon, iterations, n_samples, ratio, kwargs)
                 t0 = time.perf_counter()
                 if parallel_envs:
@@ -84,6 +90,8 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
                            cost_std=float(m['sum_costs_stddev']), seconds=time.perf_counter() - t0)
                 if elite_temperatures:
                     rec['elite_temperature'] = temperature
+                if noise_betas:
+                    rec['noise_beta'] = beta
                 logger.info('H=%d (N,I)=(%d,%d) elite %.2f: score %.3f +- %.3f, cost %.3f +- %.3f', horizon, n_samples, iterations,
                             ratio, rec['score_mean'], rec['score_std'], rec['cost_mean'], rec['cost_std'])
                 results.append(rec)
@@ -109,6 +117,8 @@ def main(argv=None):
                     help="every grid point's policy warm-starts its plans (CemMpc(warm_start=True, warm_sigma='keep')): run the search both ways")
     ap.add_argument('--elite_temperature', type=str, nargs='+', default=None, metavar='T',
                     help="a grid axis of softmax refit temperatures (CemMpc(elite_temperature=T)); 'none' = the uniform refit")
+    ap.add_argument('--noise_beta', type=str, nargs='+', default=None, metavar='B',
+                    help="a grid axis of power-law action-noise exponents (CemMpc(noise_beta=B)); 'none' = the reference's white noise")
     args = ap.parse_args(argv)
     if args.parallel_episodes < 1:
         ap.error('--parallel_episodes must be at least 1')
@@ -122,6 +132,8 @@ def main(argv=None):
     grid = dict(horizons=HORIZONS[:2], proposals_with_iterations=PROPOSALS_WITH_ITERATIONS[1:], elite_ratios=ELITE_RATIOS[:2]) if args.quick else {}
     if args.elite_temperature:
         grid['elite_temperatures'] = [None if t.lower() == 'none' else float(t) for t in args.elite_temperature]
+    if args.noise_beta:
+        grid['noise_betas'] = [None if b.lower() == 'none' else float(b) for b in args.noise_beta]
     if args.parallel_episodes > 1:
         grid['parallel_envs'] = make_parallel_environments(params, args.parallel_episodes, args.seed)
     results = grid_search(trainer, trainer.environment, params, args.eval_steps, args.eval_episode_length, **grid)

@@ -160,6 +160,8 @@ def test_philox_plan_with_other_boxes(name):
     N, H, P, E, k, I = 128, 6, 5, 5, 13, 3
     ocfg, pcfg = hp.configs(pb, N=N, H=H, P=P, E=E, k=k, I=I, noise=0.02)
     pl = hp.make_planner(pb, pcfg)
+    # asym3 / unbounded2 cross the lean kernels (the Philox plans) with the tensor-fed generic ones; obs 100 has no lean path
+    assert pl.rollout_path() == {'asym3': 'lean', 'unbounded2': 'lean', 'asym12': 'generic'}[name]
     fa, fm, fo = pl.fill_noise(seed=9, call=4)
     a1, s1, i1 = pl.plan(pb['state'], seed=9, call=4)
     a2, s2, i2 = pl.plan(pb['state'], eps_act=fa, eps_model=fm, eps_out=fo.cpu().numpy())

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_constraint', 'cem_planner_get_constraint', 'cem_planner_set_cost_budget', 'cem_planner_constraint_costs',
     'cem_planner_set_refit', 'cem_planner_get_refit', 'cem_planner_refit_stats',
     'cem_planner_set_action_noise', 'cem_planner_get_action_noise', 'cem_planner_action_noise_dev',
+    'cem_planner_set_elite_carry', 'cem_planner_get_elite_carry', 'cem_planner_elite_store',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -80,6 +81,10 @@ class CemTrainConfig(C.Structure):
 
 class CemWarmStart(C.Structure):
     _fields_ = [('shift', C.c_int32), ('tail', C.c_int32), ('sigma_rule', C.c_int32), ('sigma_floor', C.c_float * CEM_MAX_ACT)]
+
+
+class CemEliteCarry(C.Structure):
+    _fields_ = [('n_keep', C.c_int32), ('across_plans', C.c_int32), ('shift', C.c_int32), ('reserved', C.c_int32)]
 
 
 class CemLayout(C.Structure):
@@ -179,6 +184,9 @@ def load():
     lib.cem_planner_set_action_noise.argtypes = [vp, C.c_int32, vp]
     lib.cem_planner_get_action_noise.argtypes = [vp, i32p, vp]
     lib.cem_planner_action_noise_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.cem_planner_set_elite_carry.argtypes = [vp, C.POINTER(CemEliteCarry)]
+    lib.cem_planner_get_elite_carry.argtypes = [vp, C.POINTER(CemEliteCarry)]
+    lib.cem_planner_elite_store.argtypes = [vp, C.c_int32, vp, i32p]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

@@ -5,6 +5,7 @@
 #include "cem_score.h"
 #include "cem_refit_weighted.h"
 #include "cem_noise_mix.h"
+#include "cem_elite_carry.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -768,12 +769,26 @@ struct cem_planner {
     std::vector<float> h_mix, h_mix_t;       // M [H][H] as set, and transposed: the source of its stream-ordered upload
     float *noise_dev;                        // a device allocation of the handle's own, made on first use: M transposed [H][H] (padded to a quad), then eps
     float *noise_eps; size_t noise_floats;   // eps [slots][I][N][H][A] inside noise_dev, and its float count
+    // cem_planner_set_elite_carry (cem_elite_carry.h)
+    cem_elite_carry_t elite;                 // as set; n_keep 0: off, and the handle launches what create chose
+    float *elite_dev;                        // a device allocation of the handle's own, made by the first enabling call: counts [slots] (int32, padded to
+                                             // 256 bytes), then the stores [slots][n_keep][H][A]
+    int elite_cap;                           // rows per slot the allocation has room for (grows with n_keep, never shrinks)
+    bool elite_clear;                        // a plan call returned an error: the counts are zeroed in front of the next plan
 };
 
 namespace {
 
 // problems side by side on the handle = its carry slots: a single-state handle is a handle of ONE problem
 int warm_slots(const cem_planner *h) { return h->batch ? h->batch : 1; }
+
+// Elite carry-over overwrites rows of a sample that lies in HBM between two launches: while it is on, the sampler is a launch of its own
+// and the rollouts are the generic kernels that read it, whatever create chose (which n_keep = 0 restores)
+bool samples_in_rollout(const cem_planner *h) { return h->sample_in_rollout && h->elite.n_keep == 0; }
+bool runs_lean(const cem_planner *h) { return h->lean_rollout && h->elite.n_keep == 0; }
+int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
+size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
+float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
 
 // The select form the handle's next iteration takes (resolve_select_mode): the fused form only while the device keeps all its
 // ceil(N / 4096) workgroups resident at once and none of its grid barriers has expired on this handle.
@@ -811,6 +826,7 @@ void release_handle(cem_planner *h)
     if (h->budget_dev) hipFree(h->budget_dev);
     if (h->refit_dev) hipFree(h->refit_dev);
     if (h->noise_dev) hipFree(h->noise_dev);
+    if (h->elite_dev) hipFree(h->elite_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
@@ -961,6 +977,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->cost_m = 0; h->budget_dev = nullptr; h->cstat_obj = nullptr; h->cstat_obj_n = 0; h->last_cstat = nullptr; h->last_cstat_n = h->last_cstat_problems = 0;
     h->refit_kind = CEM_REFIT_UNIFORM; h->refit_tau = 0.f; h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
     h->noise_kind = CEM_NOISE_WHITE; h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
+    h->elite = cem_elite_carry_t{}; h->elite.shift = 1; h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
@@ -1403,6 +1420,17 @@ hipError_t launch_score(const cem_planner *h, const ReduceParams &p, int n_probl
     return hipGetLastError();
 }
 
+// the parameter block of the two carry-over kernels in iteration `it`
+EliteCarryParams fill_elite(const cem_planner *h, int it)
+{
+    const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
+    EliteCarryParams ep{}; ep.scores = (const float *)(ws + l.scores_global); ep.actions = (float *)(ws + l.actions); ep.act_pad = (float *)(ws + l.act_pad);
+    ep.ctrl = (const CtrlBlock *)(ws + l.ctrl); ep.elite_idx = (const int32_t *)(ws + l.elite); ep.store = elite_store(h); ep.count = elite_counts(h);
+    ep.N = d.N; ep.k = d.k; ep.m = h->elite.n_keep; ep.H = d.H; ep.A = d.A; ep.it = it; ep.shift = h->elite.across_plans ? h->elite.shift : 0;
+    ep.pad_shift = d.O - 4 * d.act_q0; ep.pad_floats = 4 * d.act_nq;
+    return ep;
+}
+
 // One iteration up to the scores: the rollout launch (its tiles sample their own action sequences first: cem_tile_sample_actions), then
 // the particle mean / Beta filter — unless `fold_reduce`: a single-rank whole plan on the CemMpc objective lets the select kernel form
 // the particle mean while it stages its keys (same sum, same order, one launch and one graph node fewer per iteration).
@@ -1428,15 +1456,21 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     const int nb = warm_slots(h);
     rp.tiles_per_problem = h->batch ? h->n_tiles : 0;
     rp.eps_act_pstride = (long long)d.I * d.N * d.H * d.A; rp.eps_model_pstride = (long long)d.I * d.H * d.Btot * d.O;
-    if (!h->sample_in_rollout) {                          // all N candidates once, in front of the rollout launch (which then samples nothing)
+    if (!samples_in_rollout(h)) {                         // all N candidates once, in front of the rollout launch (which then samples nothing)
         const int total = d.N * d.H * ((d.A + 3) / 4);
         TimedLaunch timed(h, 3);
         hipLaunchKernelGGL(cem_sample_kernel, dim3(std::min((total + 255) / 256, 2048), nb), dim3(256), 0, h->stream, rp);
         HIPCHK(hipGetLastError());
         rp.musig = nullptr;
+        // elite carry-over: rows 0 .. count - 1 of the sample become the kept elites (cem_elite_carry.h).  Iteration 0 has nothing of this
+        // plan to take; across_plans lets the device-side count decide there, so that one captured graph serves the first plan and later ones
+        if (h->elite.n_keep && (it > 0 || h->elite.across_plans)) {
+            EliteCarryParams ep = fill_elite(h, it);
+            HIPCHK(launch_elite_inject(ep, nb, h->stream));
+        }
     }
     TimedLaunch timed(h, 0);
-    if (h->lean_rollout && !rp.eps_act && !rp.eps_model) {      // (the same tiles, segments and work queue as the generic launches below)
+    if (runs_lean(h) && !rp.eps_act && !rp.eps_model) {      // (the same tiles, segments and work queue as the generic launches below)
         if (queued) {
             rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = (uint32_t *)(ws + l.seg_flags); rp.seg_state = (f4 *)(ws + l.seg_state);
             rp.seg_len = h->seg_len; rp.n_seg = h->n_seg; rp.n_pinned = h->n_pinned;
@@ -1479,7 +1513,6 @@ bool folds_reduce(const cem_planner *h)
 // *folded whether it did (only the one-workgroup kernel does), so the caller knows whether a final kernel is still needed
 int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = false, bool have_eps_out = false, bool *folded = nullptr)
 {
-    (void)it;
     if (folded) *folded = false;
     const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
     SelectParams p{}; p.scores = (const float *)(ws + l.scores_global); p.actions = (const float *)(ws + l.actions);
@@ -1511,6 +1544,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     const bool weighted = h->refit_kind == CEM_REFIT_SOFTMAX;
     if (weighted && (mode != 1 || !h->refit_dev)) return CEM_ERR_UNSUPPORTED;      // (cem_planner_set_refit admitted one-workgroup handles only)
     if (weighted) { p.musig = h->refit_dev; p.threshold = -std::numeric_limits<float>::infinity(); }
+    if (h->elite.n_keep && (mode != 1 || !h->elite_dev)) return CEM_ERR_UNSUPPORTED;   // (cem_planner_set_elite_carry admitted one-workgroup handles only)
     TimedLaunch timed(h, 1);
     if (mode >= 2) {
         MSelParams m{}; m.scores = p.scores; m.actions = p.actions; m.musig = p.musig; m.ctrl = p.ctrl; m.elite_idx = p.elite_idx;
@@ -1560,6 +1594,12 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
             rw.smoothing = p.smoothing; rw.one_minus_smoothing = p.one_minus_smoothing; rw.threshold = h->cfg.stddev_threshold;
             HIPCHK(launch_refit_weighted(rw, warm_slots(h), h->stream));
             h->refit_ran = true;
+        }
+        // elite carry-over: the best n_keep of the elites just chosen, for the next iteration's (the next plan's) inject
+        if (h->elite.n_keep) {
+            HIPCHK(hipGetLastError());
+            const EliteCarryParams ep = fill_elite(h, it);
+            HIPCHK(launch_elite_keep(ep, warm_slots(h), h->stream));
         }
     }
     HIPCHK(hipGetLastError());
@@ -1814,6 +1854,14 @@ int ensure_graph(cem_planner *h)
     return CEM_OK;
 }
 
+// the counts of the elite stores go back to zero in front of a plan that follows a failed one (outside any capture)
+int clear_elite_after_failure(cem_planner *h)
+{
+    if (h->elite_clear && h->elite_dev) HIPCHK(hipMemsetAsync(elite_counts(h), 0, (size_t)warm_slots(h) * 4, h->stream));
+    h->elite_clear = false;
+    return CEM_OK;
+}
+
 // The one plan driver, behind cem_planner_plan (one problem) and cem_planner_plan_batch alike; the entry points have checked their
 // arguments.  Stage, then replay the graph or launch the same kernels eagerly, wait, read the n results.
 int run_plan(cem_planner *h, const PlanCall &pc)
@@ -1825,6 +1873,7 @@ int run_plan(cem_planner *h, const PlanCall &pc)
     { const int wst = check_warm(h, pc.n); if (wst) return wst; }
     if (!noise_pair_ok(h, pc)) return CEM_ERR_INVALID_ARG;
     stage_ctrl(h, pc);
+    { const int est = clear_elite_after_failure(h); if (est) return est; }
     if (h->cost_m) note_plan_cstat(h);
     if (graph) { const int st = ensure_graph(h); if (st) return st; graph = h->graph_ready; }
     if (graph) {
@@ -1848,6 +1897,7 @@ int run_plan(cem_planner *h, const PlanCall &pc)
 // before staging leaves them alone.
 int settle_warm(cem_planner *h, int status)
 {
+    if (h && status != CEM_OK) h->elite_clear = true;     // (cem_elite_carry.h: nothing of a plan call that failed is carried into the next plan)
     if (h && h->warm_staged) finish_warm(h, status);
     return status;
 }
@@ -1895,6 +1945,7 @@ static int plan_begin_impl(cem_planner_t *h, const float *state, uint64_t seed, 
     if (!noise_pair_ok(h, pc)) return CEM_ERR_INVALID_ARG;
     { const int wst = check_warm(h, 1); if (wst) return wst; }
     stage_ctrl(h, pc);
+    { const int est = clear_elite_after_failure(h); if (est) return est; }
     h->eps_act = eps_act_dev; h->eps_model = eps_model_dev;
     h->ev_kind.clear();
     int st = enqueue_begin(h); if (st) return st;
@@ -2162,6 +2213,57 @@ int cem_planner_action_noise_dev(cem_planner_t *h, const float **eps_dev_out, si
     return CEM_OK;
 }
 
+int cem_planner_set_elite_carry(cem_planner_t *h, const cem_elite_carry_t *ec)
+{
+    if (!h || !ec) return CEM_ERR_INVALID_ARG;
+    const Dims &d = h->d;
+    if (ec->n_keep < 0 || ec->n_keep > d.k || ec->n_keep >= d.N) return CEM_ERR_INVALID_ARG;
+    if ((ec->across_plans != 0 && ec->across_plans != 1) || ec->reserved != 0) return CEM_ERR_INVALID_ARG;
+    if (ec->across_plans && (ec->shift < 1 || ec->shift >= d.H)) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    if (ec->n_keep) {
+        // the keep reads ONE rank's select; a sharded plan would need the kept rows on every rank and no such run has been made
+        if (d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
+        if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;               // the multi-workgroup selects: the rule cem_planner_set_refit applies
+        if (d.k > CEM_ELITE_MAX_K || !launch_elite_keep || !launch_elite_inject) return CEM_ERR_UNSUPPORTED;
+        if (ec->across_plans && h->batch) return CEM_ERR_UNSUPPORTED;          // a batch handle's rows move between slots (cem_planner_set_carry_slots)
+    }
+    // a larger store is allocated before anything of the handle changes: a failed allocation leaves it as it was
+    float *grown = nullptr;
+    const size_t HA = (size_t)d.H * d.A, floats = elite_count_floats(h) + (size_t)warm_slots(h) * ec->n_keep * HA;
+    if (ec->n_keep > h->elite_cap) HIPCHK(hipMalloc((void **)&grown, floats * 4));
+    // Unconditional, as in cem_planner_set_action_noise: an eager plan still draining behind its polled result may be reading the store
+    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) { g_last_hip = (int)e; if (grown) hipFree(grown); return CEM_ERR_HIP; }
+    if (grown) {
+        if (h->elite_dev) hipFree(h->elite_dev);
+        h->elite_dev = grown; h->elite_cap = ec->n_keep;
+        if (const hipError_t e = hipMemsetAsync(grown, 0, floats * 4, h->stream); e != hipSuccess) {
+            g_last_hip = (int)e; hipFree(grown); h->elite_dev = nullptr; h->elite_cap = 0; h->elite.n_keep = 0; drop_graph(h); return CEM_ERR_HIP;
+        }
+    } else if (h->elite_dev) HIPCHK(hipMemsetAsync(elite_counts(h), 0, (size_t)warm_slots(h) * 4, h->stream));   // every call empties the stores
+    drop_graph(h);                                                              // the captured plan holds the other setting's launches
+    h->elite = *ec; h->elite_clear = false;
+    return CEM_OK;
+}
+
+int cem_planner_get_elite_carry(const cem_planner_t *h, cem_elite_carry_t *out)
+{
+    if (!h || !out) return CEM_ERR_INVALID_ARG;
+    *out = h->elite;
+    return CEM_OK;
+}
+
+int cem_planner_elite_store(cem_planner_t *h, int32_t problem, float *out_host, int32_t *count_out)
+{
+    if (!h || problem < 0 || problem >= warm_slots(h) || (!out_host && !count_out)) return CEM_ERR_INVALID_ARG;
+    if (!h->elite.n_keep || !h->elite_dev) return CEM_ERR_STATE;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t row = (size_t)h->elite.n_keep * h->d.H * h->d.A;
+    if (out_host) HIPCHK(hipMemcpy(out_host, elite_store(h) + (size_t)problem * row, row * 4, hipMemcpyDeviceToHost));
+    if (count_out) HIPCHK(hipMemcpy(count_out, elite_counts(h) + problem, 4, hipMemcpyDeviceToHost));
+    return CEM_OK;
+}
+
 int cem_planner_set_initial_distribution(cem_planner_t *h, int32_t slot, const float *mu, const float *sigma)
 {
     if (!h || !mu || !sigma || slot < 0 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
@@ -2189,6 +2291,8 @@ int cem_planner_reset_carry(cem_planner_t *h, int32_t slot)
 {
     if (!h || slot < -1 || slot >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
     for (int s = 0; s < warm_slots(h); ++s) if (slot < 0 || s == slot) { h->carry_valid[s] = 0; h->carry_at[s] = -1; }
+    // the kept elites of the slot(s) go with it (cem_elite_carry.h): stream-ordered, so a plan still draining finishes with what it had
+    if (h->elite_dev) HIPCHK(hipMemsetAsync(elite_counts(h) + (slot < 0 ? 0 : slot), 0, (size_t)(slot < 0 ? warm_slots(h) : 1) * 4, h->stream));
     return CEM_OK;
 }
 
@@ -2245,6 +2349,7 @@ int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int
     if (n_ranks != h->d.W || rank != h->d.R) return CEM_ERR_INVALID_ARG;       // the communicator IS the candidate sharding of this handle
     if (h->in_plan) return CEM_ERR_STATE;
     if (h->noise_kind == CEM_NOISE_MIXED) return CEM_ERR_UNSUPPORTED;          // (cem_planner_set_action_noise refuses a communicator; so the reverse)
+    if (h->elite.n_keep) return CEM_ERR_UNSUPPORTED;                           // (cem_planner_set_elite_carry likewise)
     Rccl *r = rccl(); if (!r) return CEM_ERR_COMM;
     if (h->comm) { r->CommDestroy(h->comm); h->comm = nullptr; }
     CemNcclId nid; std::memcpy(nid.internal, id, CEM_COMM_ID_BYTES);
@@ -2291,7 +2396,7 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out)
 int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out)
 {
     if (!h || !path_out) return CEM_ERR_INVALID_ARG;
-    *path_out = (h->lean_rollout && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;    // (the lean kernels draw in place and cannot take a tensor)
+    *path_out = (runs_lean(h) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;       // (the lean kernels draw in place and cannot take a tensor)
     return CEM_OK;
 }
 
@@ -2299,8 +2404,8 @@ int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches
 {
     if (!h || !launches_out) return CEM_ERR_INVALID_ARG;
     const int mode = select_mode_now(h);
-    *launches_out = 1 + (h->sample_in_rollout ? 0 : 1) + (folds_reduce(h) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
-                    (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0);
+    *launches_out = 1 + (samples_in_rollout(h) ? 0 : 1) + (folds_reduce(h) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
+                    (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0) + (h->elite.n_keep ? 2 : 0);      // (carry-over: the inject and the keep)
     return CEM_OK;
 }
 

@@ -983,6 +983,17 @@ __global__ __launch_bounds__(256) void cem_rollout_seg_kernel(const RolloutParam
     }
 }
 
+// The order-preserving integer key every select ranks fp32 scores by (a larger key is a better score), from the score's bits — what a
+// kernel that loads scores as integers calls, so that it holds no floating-point instruction (cem_elite_carry.h) — and from the score.
+// Above the primitives guard: the units that take the primitives only rank by it too.
+__device__ __forceinline__ uint32_t cem_bits2key(const uint32_t u)
+{
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;          // NaN sorts lowest (bit test: immune to -fno-honor-nans)
+    // -0.0 takes +0.0's key: tf.nn.top_k compares VALUES, the two zeros tie and the lower index wins (key 0x7FFFFFFF is never produced)
+    return (u & 0x80000000u) && u != 0x80000000u ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint32_t cem_f2key(float f) { return cem_bits2key(__float_as_uint(f)); }
+
 #ifndef CEM_DEVICE_PRIMITIVES_ONLY
 // ---------------------------------------------------------------------------------------------------------
 // small kernels of the optimiser loop
@@ -1241,13 +1252,6 @@ struct SelectParams {
 
 #define CEM_SEL_KIDX(i) ((i) + ((i) >> 5))        // LDS word of key i in the one-workgroup select's staged key list (one pad word per 32 keys)
 #define CEM_SEL_KWORDS(n) ((n) + ((n) >> 5) + 1)    // words that list takes
-__device__ __forceinline__ uint32_t cem_f2key(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;          // NaN sorts lowest (bit test: immune to -fno-honor-nans)
-    // -0.0 takes +0.0's key: tf.nn.top_k compares VALUES, the two zeros tie and the lower index wins (key 0x7FFFFFFF is never produced)
-    return (u & 0x80000000u) && u != 0x80000000u ? ~u : (u | 0x80000000u);
-}
 
 // Histogram add for a whole wave when few bins are hot (the first counted radix pass: sign + exponent bits): LDS atomics
 // on one address serialise, so up to four rounds of "leader's digit -> one add of the group size", plain adds for the rest.

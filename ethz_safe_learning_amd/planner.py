@@ -76,6 +76,10 @@ class PlannerConfig:
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
     action_noise_param: float = 0.0    # 'powerlaw': the spectral exponent beta >= 0; 'ar1': the lag-1 correlation rho in (-1, 1); 'white' ignores it
+    keep_elites: int = 0               # 0: every iteration resamples all candidates (the reference); m in 1 .. n_elite: the best m elites of an
+                                       # iteration are candidates 0 .. m - 1 of the next (cem_planner_set_elite_carry); not in cem_config_t: set after create
+    shift_elites: bool = False         # with keep_elites: a plan's first iteration takes the previous plan's last kept elites, shifted by elite_shift
+    elite_shift: int = 1               # steps executed between two plans (shift_elites only)
     worst_particles: int = 0           # 0: score = the particle mean (the reference); m in 1 .. particles: the mean of the m smallest particle
                                        # returns (cem_planner_set_particle_objective, CEM_PARTICLES_LOWER_TAIL); not in cem_config_t: set after create
 
@@ -329,6 +333,12 @@ class CemPlanner:
         if cfg.action_noise != 'white':
             try:
                 self.set_action_noise(cfg.action_noise, cfg.action_noise_param)
+            except Exception:
+                self.close()
+                raise
+        if cfg.keep_elites:
+            try:
+                self.set_elite_carry(cfg.keep_elites, cfg.shift_elites, cfg.elite_shift)
             except Exception:
                 self.close()
                 raise
@@ -621,6 +631,29 @@ class CemPlanner:
         with t.cuda.device(self.device):
             out = t.as_tensor(_Dev(), device=self.device).cpu().numpy().copy()
         return out.reshape(c.iterations, c.n_samples, c.horizon, c.act_dim)
+
+    def set_elite_carry(self, n_keep, across_plans=False, shift=1):
+        """Elite carry-over (cem_planner_set_elite_carry): the best `n_keep` elites of an iteration are candidates 0 .. n_keep - 1 of the
+        next one; with across_plans also of the next plan's first iteration, moved `shift` steps towards the present (the freed tail
+        keeps the sampler's draw).  0 switches it off.  keep_elites / inject_elites restate the two kernels.  Sticky; every call empties
+        the stores, waits for the stream and re-captures the graph.  The store lives on the HANDLE: with across_plans two users of one
+        handle would continue each other's plans (owner= of cached_planner)."""
+        ec = _capi.CemEliteCarry(n_keep=int(n_keep), across_plans=int(bool(across_plans)), shift=int(shift), reserved=0)
+        _capi.check(self.lib.cem_planner_set_elite_carry(self.h, C.byref(ec)), 'cem_planner_set_elite_carry')
+
+    def elite_carry(self):
+        """(n_keep, across_plans, shift) as set (cem_planner_get_elite_carry)."""
+        ec = _capi.CemEliteCarry()
+        _capi.check(self.lib.cem_planner_get_elite_carry(self.h, C.byref(ec)), 'cem_planner_get_elite_carry')
+        return ec.n_keep, bool(ec.across_plans), ec.shift
+
+    def elite_store(self, problem=0):
+        """(E [n_keep, H, A], count) of `problem` as the stream leaves them (cem_planner_elite_store).  Waits for the planner's stream."""
+        c = self.cfg
+        E = np.zeros((self.elite_carry()[0], c.horizon, c.act_dim), np.float32)
+        n = C.c_int32()
+        _capi.check(self.lib.cem_planner_elite_store(self.h, int(problem), _np_ptr(E), C.byref(n)), 'cem_planner_elite_store')
+        return E, n.value
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')
@@ -1006,6 +1039,50 @@ def softmax_refit(scores, elite, actions, mu, sigma, smoothing, temperature):
     var = ((wb * (d * d)).sum(axis=0, dtype=f) / W).astype(f)
     sm, osm = f(smoothing), f(1.0 - float(smoothing))
     return (sm * mu + osm * mean).astype(f), (sm * sigma + osm * np.sqrt(var)).astype(f), f(W * W / (w * w).sum(dtype=f))
+
+
+def score_keys(scores) -> np.ndarray:
+    """The uint32 keys the selects rank fp32 scores by (cem_f2key): a larger key is a better score, -0.0 and +0.0 share a key, every
+    NaN has key 0 (below -inf)."""
+    u = np.ascontiguousarray(np.asarray(scores, np.float32)).view(np.uint32)
+    nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    neg = ((u & np.uint32(0x80000000)) != 0) & (u != np.uint32(0x80000000))
+    return np.where(nan, np.uint32(0), np.where(neg, ~u, u | np.uint32(0x80000000))).astype(np.uint32)
+
+
+def keep_elites(scores, elite_idx, actions, m) -> np.ndarray:
+    """Host restatement of cem_elite_keep_kernel (cem_mpc.h, cem_planner_set_elite_carry) — comparisons and copies, so it is exact:
+    E [m, H, A], the best m of the k elites.  scores [N] as the select ranked them, elite_idx [k] as it stored them, actions [N, H, A].
+    Order: descending score key (score_keys), ties to the lower candidate index."""
+    e = np.asarray(elite_idx, np.int64).reshape(-1)
+    m = int(m)
+    if not 0 <= m <= e.size:
+        raise ValueError('m must lie in 0 .. k')
+    key = score_keys(np.asarray(scores, np.float32).reshape(-1)[e]).astype(np.int64)
+    order = np.lexsort((e, -key))                       # last key first: descending score key, then ascending candidate index
+    return np.ascontiguousarray(np.asarray(actions, np.float32)[e[order[:m]]])
+
+
+def inject_elites(actions, E, count, shift=0) -> np.ndarray:
+    """Host restatement of cem_elite_inject_kernel — copies, so it is exact: a copy of actions [N, H, A] whose rows n < count hold
+    E[n] moved `shift` steps towards the present at steps t < H - shift; later steps, later rows and everything at count == 0 keep what
+    the sampler drew.  shift is the handle's at a plan's first iteration (across_plans), 0 at every other."""
+    out = np.array(actions, np.float32, copy=True)
+    E = np.asarray(E, np.float32)
+    c, s, H = min(int(count), E.shape[0]), int(shift), out.shape[1]
+    if not 0 <= s <= H:
+        raise ValueError('shift must lie in 0 .. H')
+    if c > 0:
+        out[:c, :H - s] = E[:c, s:]
+    return out
+
+
+def elite_keep_count(fraction, n_elite) -> int:
+    """Elites a policy keeps for a fraction in (0, 1] of n_elite (iCEM's 0.3): max(1, floor(fraction * n_elite))."""
+    f = float(fraction)
+    if not 0.0 < f <= 1.0:
+        raise ValueError('keep_elites is a fraction of n_elite in (0, 1]')
+    return max(1, int(np.floor(f * int(n_elite))))
 
 
 def plan_tiles(cfg: PlannerConfig):

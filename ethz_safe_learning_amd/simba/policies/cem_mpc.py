@@ -36,11 +36,22 @@ FFT sampler), with ``noise_rho`` a float in (-1, 1) from AR(1) noise of that lag
 candidate holds a direction for several steps.  Give at most one of the two.  ``generate_action``, ``generate_actions`` and warm-started
 plans use it; the plan then runs the generic rollout kernels (the lean ones draw in place).  ``None`` for both (the default, and what
 every shipped preset has) touches no handle and changes no bit.  Nothing is claimed about the returns or the safety of an agent that
-uses it."""
+uses it.
+
+Elite carry-over (beyond the reference, off by default): with ``keep_elites`` a fraction in (0, 1] of ``n_elite`` (iCEM uses 0.3) the best
+``planner.elite_keep_count(keep_elites, n_elite)`` elites of an iteration are candidates of the next one, rolled out and scored again
+(``PlannerConfig.keep_elites``, cem_mpc.h cem_planner_set_elite_carry) instead of surviving as moments only.
+``generate_action``, ``generate_actions`` and warm-started plans use it; the plan then samples in a launch of its own and runs the generic
+rollout kernels.  With ``shift_elites=True`` (which requires ``keep_elites``) the first iteration of a plan also takes the previous plan's
+last kept elites, moved ``warm_shift`` steps towards the present, the freed tail drawn anew: the store lives on the planner handle, so
+such a policy plans on handles of its OWN (as a warm-started one does), ``reset()`` empties it, and ``generate_actions`` is refused with
+a ``ValueError`` — a batch handle's rows move between slots and carry nothing across plans.  ``None`` / ``False`` (the defaults, and what
+every shipped preset has) touch no handle and change no bit.  Nothing is claimed about the returns or the safety of an agent that uses
+it."""
 import logging
 import numpy as np
 
-from ...planner import PlannerConfig, cached_batch_planner, cached_planner, risk_particles, stage_model_weights
+from ...planner import PlannerConfig, cached_batch_planner, cached_planner, elite_keep_count, risk_particles, stage_model_weights
 from .mpc_policy import MpcPolicy
 
 
@@ -50,7 +61,7 @@ class CemMpc(MpcPolicy):
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
                  warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None,
-                 elite_temperature=None, noise_beta=None, noise_rho=None):
+                 elite_temperature=None, noise_beta=None, noise_rho=None, keep_elites=None, shift_elites=False):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -79,6 +90,12 @@ class CemMpc(MpcPolicy):
             raise ValueError('noise_beta must be finite and >= 0, got %r' % (noise_beta,))
         if self.noise_rho is not None and not -1.0 < self.noise_rho < 1.0:
             raise ValueError('noise_rho must lie in (-1, 1), got %r' % (noise_rho,))
+        # elite carry-over (beyond the reference's kwargs): see the module docstring
+        self.keep_elites = None if keep_elites is None else float(keep_elites)
+        self.n_keep = 0 if keep_elites is None else elite_keep_count(keep_elites, n_elite)
+        self.shift_elites = bool(shift_elites)
+        if self.shift_elites and self.keep_elites is None:
+            raise ValueError('shift_elites needs keep_elites')
         self.last_ess = None                           # ESS per iteration of the last weighted plan (generate_actions: a list, one array per row)
         self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
         self._warm_cap = 1                             # slots the warm-started batch handle must hold
@@ -107,6 +124,11 @@ class CemMpc(MpcPolicy):
             return dict(action_noise='ar1', action_noise_param=self.noise_rho)
         return {}
 
+    def _carry_config(self):
+        if not self.n_keep:
+            return {}
+        return dict(keep_elites=self.n_keep, shift_elites=self.shift_elites, elite_shift=self.warm_shift if self.shift_elites else 1)
+
     def _scorer_config(self):
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
         if scorer is None:
@@ -125,12 +147,12 @@ class CemMpc(MpcPolicy):
             smoothing=self.smoothing, stddev_threshold=self.stddev_threshold, noise_stddev=self.noise_stddev,
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
             use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._refit_config(),
-            **self._noise_config(), **self._extra_config())
+            **self._noise_config(), **self._carry_config(), **self._extra_config())
 
     def _owns_handles(self):
-        """Whether this policy's planning handles carry state of its own (the warm-start carry; SafeCemMpc: a cost budget) and so must
-        not be shared through the cache with other policies of the shape."""
-        return self.warm_start
+        """Whether this policy's planning handles carry state of its own (the warm-start carry, the elites kept across plans; SafeCemMpc:
+        a cost budget) and so must not be shared through the cache with other policies of the shape."""
+        return self.warm_start or self.shift_elites
 
     def build(self):
         if self._planner is None or self._planner.h is None:      # never built, or closed by its owner
@@ -147,17 +169,20 @@ class CemMpc(MpcPolicy):
             planner.staged = tag
 
     def _own(self, planner):
-        """A handle fresh from the cache: with warm start on, make it this policy's (shift mode on every slot, no carry)."""
-        if self.warm_start and getattr(planner, 'warm_owner', None) is not self._warm_token:
-            planner.set_warm_start(shift=self.warm_shift, tail=self.warm_tail, sigma=self.warm_sigma, floor_frac=self.warm_sigma_floor)
-            planner.set_init_mode('shift', slot=None)
+        """A handle fresh from the cache: with warm start on, make it this policy's (shift mode on every slot, no carry); with elites kept
+        across plans, empty its stores."""
+        if (self.warm_start or self.shift_elites) and getattr(planner, 'warm_owner', None) is not self._warm_token:
+            if self.warm_start:
+                planner.set_warm_start(shift=self.warm_shift, tail=self.warm_tail, sigma=self.warm_sigma, floor_frac=self.warm_sigma_floor)
+                planner.set_init_mode('shift', slot=None)
             planner.reset_carry()
             planner.warm_owner = self._warm_token
         return planner
 
     def reset(self):
-        """An episode begins: the next plan of every slot starts cold (no effect without warm start)."""
-        if not self.warm_start:
+        """An episode begins: the next plan of every slot starts cold and takes no elites of an earlier plan (no effect without warm
+        start or shift_elites)."""
+        if not (self.warm_start or self.shift_elites):
             return
         for pl in [self._planner] + list(self._batch_planners.values()):
             if pl is not None and pl.h is not None:
@@ -217,6 +242,9 @@ class CemMpc(MpcPolicy):
         Warm start: slots[B] is the environment index of every row (distinct; default: the row index) — row b continues the plans of
         ITS environment whichever rows the call holds — and reset[B] marks rows whose environment begins an episode (they plan cold).
         Both are ignored without warm start."""
+        if self.shift_elites:
+            raise ValueError('shift_elites=True carries elites across the plans of ONE environment; generate_actions plans on a batch handle, '
+                             'whose rows move between slots: use generate_action, or keep_elites alone')
         st = np.asarray(states, np.float32)
         if st.ndim != 2:
             raise ValueError('states must be [B, obs_dim]')

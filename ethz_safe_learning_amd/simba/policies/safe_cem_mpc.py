@@ -39,7 +39,11 @@ Nothing is claimed about the returns or the safety of an agent that uses it.
 
 ``noise_beta`` / ``noise_rho`` (CemMpc's, off by default): the reward plans sample time-correlated action sequences, and so do
 ``optimize_for_safety`` and the recovery plans of ``recover_below`` — the cost handle is the policy's configuration with another
-objective, the sampler is shared and there is no reason for it to differ."""
+objective, the sampler is shared and there is no reason for it to differ.
+
+``keep_elites`` / ``shift_elites`` (CemMpc's, off by default): the reward plans carry elites over as CemMpc's do.  ``optimize_for_safety``
+and the recovery plans of ``recover_below`` carry them from iteration to iteration only: their handle is shared through the cache and
+their plans follow no earlier cost plan."""
 import dataclasses
 
 import numpy as np
@@ -95,7 +99,7 @@ class SafeCemMpc(CemMpc):
         self.cost_budget = self._as_budget(value)
 
     def _owns_handles(self):
-        return self.warm_start or self.cost_budget is not None
+        return super()._owns_handles() or self.cost_budget is not None
 
     def _stage_budget(self, planner, scalar_only=False):
         """The policy's budget onto one of its handles, when it is not what the handle holds already."""
@@ -148,7 +152,8 @@ class SafeCemMpc(CemMpc):
     def cost_planner_config(self):
         return dataclasses.replace(self.planner_config(), variant='cost', worst_particles=0,      # (the cost objective has no lower tail
                                    constraint='beta', worst_cost_particles=0,                     # and no budget;
-                                   refit='uniform', refit_temperature=0.0)                        # recovery plans keep the uniform refit;
+                                   refit='uniform', refit_temperature=0.0,                        # recovery plans keep the uniform refit;
+                                   shift_elites=False, elite_shift=1)                             # they carry elites within a plan only;
                                                                                                   # the action noise stays the policy's)
 
     def build_cost(self):

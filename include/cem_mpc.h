@@ -592,6 +592,51 @@ int cem_planner_get_action_noise(const cem_planner_t *h, int32_t *kind_out, floa
 int cem_planner_action_noise_dev(cem_planner_t *h, const float **eps_dev_out, size_t *n_floats_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Elite carry-over: the best sequences an iteration has evaluated are candidates of the next one, and of the next plan (iCEM's "keep
+ * elites" and "shift elites").  Beyond the reference, off by default.
+ *   n_keep = m        0: off — what every handle does unless told otherwise, with the launches, graph nodes and bits it always had (the lean
+ *                     rollout and the folded sampler where create chose them).  m > 0: see below.
+ *   across_plans      0: nothing of an earlier plan is read.  1: the first iteration of a plan takes the previous plan's last kept elites,
+ *                     shifted by `shift` steps.
+ *   shift = s         steps executed between two plans; read with across_plans only.
+ * Every problem of the handle (max(max_batch, 1) of them) owns a store E[m][H][A] of fp32 and an int32 count, in ONE device allocation the
+ * handle owns (made by the first enabling call, grown by a call with a larger m, freed at destroy; the workspace keeps its layout and size).
+ *   KEEP    one kernel directly behind the select of iteration `it` (behind the weighted refit where that runs).  It acts iff that select
+ *           ran (the problem had not stopped before it; the select that stops the plan still keeps).  The k elites are ordered by the score
+ *           the select ranked — descending, -0.0 and +0.0 equal, NaN below -inf, ties to the lower candidate index — and
+ *           E[j] = actions[e_j] for the first m of them, as exact copies; count = m.
+ *   INJECT  one kernel in iteration `it` between the sampler launch and the rollout launch.  Nothing on a stopped problem or count == 0.
+ *           With c = count and s_it = (it == 0 ? s : 0): for n < c, t < H - s_it, a < A the action (n, t, a) of the sample is replaced by
+ *           E[n][t + s_it][a]; steps t >= H - s_it keep what the sampler drew for candidate n.  Nothing is clipped (stored values are clipped
+ *           samples of the same box).  Launched at it >= 1 always, at it == 0 on across_plans handles only, where the device-side count
+ *           decides: one captured graph serves the first plan and later ones.
+ * A carried sequence is a candidate like any other: rolled out with this iteration's model noise, scored, ranked; it can be elite again,
+ * enter the refit and become best-so-far.  mu / sigma, every candidate's Philox counters (rows n < c are drawn, then overwritten), model
+ * noise, eps_out, the select, the refit, early stop, best-so-far, warm start and every objective are as they are; an eps_act tensor (a
+ * caller's, or the handle's CEM_NOISE_MIXED one) feeds the sampler as before.  Neither kernel does floating-point arithmetic.
+ * count is zeroed, in stream order, by cem_planner_reset_carry (its slot), by every call of this setter, and in front of the next plan
+ * after any plan call that returned something other than CEM_OK.  cem_planner_set_weights* and cem_planner_set_normaliser keep the stores.
+ * While n_keep > 0 the sampler is a launch of its own (cem_sample_kernel) and the rollouts are the generic kernels:
+ * cem_planner_rollout_path reports 0 and cem_planner_launches_per_iteration counts the sampler launch where it had been folded, + 1 for the
+ * inject, + 1 for the keep.  With cem_planner_set_timing on, the inject's time is part of the sampler time and the keep's part of the select
+ * time (cem_planner_last_timing_detail, cem_planner_last_timing).  Tile plan, segments and work queue are unchanged.  Whole plans (graph and eager), the stepwise calls and
+ * batch handles (n_keep only) serve it.  The setter waits for the stream and drops the captured graph.
+ *   CEM_ERR_INVALID_ARG  null handle or pointer; n_keep < 0, > n_elite or >= n_samples; across_plans not 0 / 1; reserved != 0; with
+ *                        across_plans: shift < 1 or >= horizon
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  n_keep > 0 with world_size > 1 or a communicator (and cem_planner_comm_init on an enabled handle), on a handle
+ *                        outside the one-workgroup select (select_mode 2 / 3: the rule of cem_planner_set_refit), with n_elite > 4096, or
+ *                        with across_plans on a batch handle (its rows move between slots)
+ * A failed allocation (the first enabling call, or a call with a larger n_keep than the handle has room for) returns CEM_ERR_HIP.  The
+ * handle keeps its previous setting after any of these: off, unless an earlier call enabled it. */
+typedef struct { int32_t n_keep, across_plans, shift, reserved; } cem_elite_carry_t;
+int cem_planner_set_elite_carry(cem_planner_t *h, const cem_elite_carry_t *carry);
+int cem_planner_get_elite_carry(const cem_planner_t *h, cem_elite_carry_t *carry_out);
+/* The store and the count of `problem` as the stream leaves them -> out_host[n_keep][H][A], *count_out (either may be NULL, not both).
+ * Drains the handle's stream; may be called inside a stepwise plan.  CEM_ERR_STATE on a handle whose carry-over is off. */
+int cem_planner_elite_store(cem_planner_t *h, int32_t problem, float *out_host /* [n_keep][H][A] */, int32_t *count_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

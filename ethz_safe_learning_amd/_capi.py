@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_refit', 'cem_planner_get_refit', 'cem_planner_refit_stats',
     'cem_planner_set_action_noise', 'cem_planner_get_action_noise', 'cem_planner_action_noise_dev',
     'cem_planner_set_elite_carry', 'cem_planner_get_elite_carry', 'cem_planner_elite_store',
+    'cem_planner_set_population_schedule', 'cem_planner_get_population_schedule', 'cem_planner_iteration_plan',
+    'cem_planner_set_mean_candidate', 'cem_planner_get_mean_candidate',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -85,6 +87,10 @@ class CemWarmStart(C.Structure):
 
 class CemEliteCarry(C.Structure):
     _fields_ = [('n_keep', C.c_int32), ('across_plans', C.c_int32), ('shift', C.c_int32), ('reserved', C.c_int32)]
+
+
+class CemIterationPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('n_samples', 'chunks_per_tile', 'n_tiles', 'n_segments', 'n_pinned', 'launches', 'rollout_path', 'reserved')]
 
 
 class CemLayout(C.Structure):
@@ -187,6 +193,11 @@ def load():
     lib.cem_planner_set_elite_carry.argtypes = [vp, C.POINTER(CemEliteCarry)]
     lib.cem_planner_get_elite_carry.argtypes = [vp, C.POINTER(CemEliteCarry)]
     lib.cem_planner_elite_store.argtypes = [vp, C.c_int32, vp, i32p]
+    lib.cem_planner_set_population_schedule.argtypes = [vp, i32p, C.c_int32]
+    lib.cem_planner_get_population_schedule.argtypes = [vp, i32p, C.c_int32, i32p]
+    lib.cem_planner_iteration_plan.argtypes = [vp, C.c_int32, C.POINTER(CemIterationPlan)]
+    lib.cem_planner_set_mean_candidate.argtypes = [vp, C.c_int32]
+    lib.cem_planner_get_mean_candidate.argtypes = [vp, i32p]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

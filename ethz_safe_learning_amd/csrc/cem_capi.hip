@@ -6,6 +6,7 @@
 #include "cem_refit_weighted.h"
 #include "cem_noise_mix.h"
 #include "cem_elite_carry.h"
+#include "cem_population.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
 #include "cem_forward.h"
@@ -697,6 +698,14 @@ void warn_if_two_hip_runtimes()
 }
 }  // namespace
 
+// What one iteration launches: the handle's own plan (create), or — under a population schedule — that of the n[it]-wide configuration
+struct IterPlan {
+    Dims d;                                  // make_dims of the configuration with n_samples = n[it]
+    int rc, n_tiles, n_seg, seg_len, n_pinned;
+    bool sample_in_rollout, lean_rollout;
+    size_t tiles_off;                        // byte offset of its tile list in cem_planner::pop_dev; (size_t)-1: the workspace's list (n[it] == n_samples)
+};
+
 struct cem_planner {
     cem_config_t cfg;
     Dims d;
@@ -775,6 +784,13 @@ struct cem_planner {
                                              // 256 bytes), then the stores [slots][n_keep][H][A]
     int elite_cap;                           // rows per slot the allocation has room for (grows with n_keep, never shrinks)
     bool elite_clear;                        // a plan call returned an error: the counts are zeroed in front of the next plan
+    // cem_planner_set_population_schedule / cem_planner_set_mean_candidate (cem_population.h)
+    std::vector<IterPlan> pop;               // [I] the plan of every iteration while a schedule is on; empty: off, every iteration is the handle's own plan
+    char *pop_dev;                           // a device allocation of the handle's own: the tile lists of the iterations with n[it] != n_samples, then
+                                             // (only when some iteration needs more than the workspace holds) segment flags and hand-over state
+    uint32_t *pop_seg_flags; f4 *pop_seg_state;   // where a scheduled plan's floating tiles keep those two: the workspace's, or inside pop_dev
+    int pop_n_ready;                         // FIFO entries the plan's first kernel clears: the most any iteration uses
+    int mean_cand;                           // 1: the last iteration's last candidate is the clipped mean
 };
 
 namespace {
@@ -784,20 +800,42 @@ int warm_slots(const cem_planner *h) { return h->batch ? h->batch : 1; }
 
 // Elite carry-over overwrites rows of a sample that lies in HBM between two launches: while it is on, the sampler is a launch of its own
 // and the rollouts are the generic kernels that read it, whatever create chose (which n_keep = 0 restores)
-bool samples_in_rollout(const cem_planner *h) { return h->sample_in_rollout && h->elite.n_keep == 0; }
-bool runs_lean(const cem_planner *h) { return h->lean_rollout && h->elite.n_keep == 0; }
+// — and so does the mean candidate, in the one iteration it is written in (cem_population.h)
+bool injects_mean(const cem_planner *h, int it) { return h->mean_cand && it == h->d.I - 1; }
+
+// The plan iteration `it` launches, as the enqueue functions read it: the handle's own, or the scheduled iteration's (cem_population.h)
+struct IterView {
+    const Dims *d; int rc, n_tiles, n_seg, seg_len, n_pinned; bool sample_in_rollout, lean_rollout;
+    const TileDesc *tiles; uint32_t *seg_flags; f4 *seg_state;
+};
+IterView iter_view(const cem_planner *h, int it)
+{
+    const Layout &l = h->lay;
+    if (h->pop.empty())
+        return IterView{&h->d, h->rc, h->n_tiles, h->n_seg, h->seg_len, h->n_pinned, h->sample_in_rollout, h->lean_rollout,
+                        (const TileDesc *)(h->ws + l.tiles), (uint32_t *)(h->ws + l.seg_flags), (f4 *)(h->ws + l.seg_state)};
+    const IterPlan &ip = h->pop[std::min(std::max(it, 0), h->d.I - 1)];
+    return IterView{&ip.d, ip.rc, ip.n_tiles, ip.n_seg, ip.seg_len, ip.n_pinned, ip.sample_in_rollout, ip.lean_rollout,
+                    ip.tiles_off == (size_t)-1 ? (const TileDesc *)(h->ws + l.tiles) : (const TileDesc *)(h->pop_dev + ip.tiles_off),
+                    h->pop_seg_flags, h->pop_seg_state};
+}
+
+bool samples_in_rollout(const cem_planner *h, int it) { return iter_view(h, it).sample_in_rollout && h->elite.n_keep == 0 && !injects_mean(h, it); }
+bool runs_lean(const cem_planner *h, int it) { return iter_view(h, it).lean_rollout && h->elite.n_keep == 0 && !injects_mean(h, it); }
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
 size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
 float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
 
 // The select form the handle's next iteration takes (resolve_select_mode): the fused form only while the device keeps all its
 // ceil(N / 4096) workgroups resident at once and none of its grid barriers has expired on this handle.
-int select_mode_now(const cem_planner *h, bool *cache = nullptr)
+// (N: the population the select ranks — the handle's, or a scheduled iteration's)
+int select_mode_for(const cem_planner *h, int N, bool *cache = nullptr)
 {
     const Dims &d = h->d;
-    const bool can_fuse = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS <= h->fused_resident && !h->fuse_banned;
-    return resolve_select_mode(h->cfg.select_mode, d.N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, can_fuse, cache);
+    const bool can_fuse = (N + CEM_MS_KEYS - 1) / CEM_MS_KEYS <= h->fused_resident && !h->fuse_banned;
+    return resolve_select_mode(h->cfg.select_mode, N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, can_fuse, cache);
 }
+int select_mode_now(const cem_planner *h, bool *cache = nullptr) { return select_mode_for(h, h->d.N, cache); }
 
 // the captured plan no longer describes what the handle would launch (or never came to be): the next graphable plan captures anew
 void drop_graph(cem_planner *h)
@@ -827,6 +865,7 @@ void release_handle(cem_planner *h)
     if (h->refit_dev) hipFree(h->refit_dev);
     if (h->noise_dev) hipFree(h->noise_dev);
     if (h->elite_dev) hipFree(h->elite_dev);
+    if (h->pop_dev) hipFree(h->pop_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;
@@ -934,11 +973,28 @@ int cem_rollout_residency(int32_t chunks_per_tile, int32_t input_blocks_per_wave
 // serves the one-chunk fp32 kernel of the obs + act <= 64 family with every feature quad all-observation or all-action, single-rank
 // single-state plans whose tiles sample inside the rollout launch (all resident at once: B1, B2), and a horizon whose mu / sigma quads
 // fit its LDS allowance.  Everything else — and any plan given explicit noise tensors — runs the generic kernels.
-static bool lean_eligible(const cem_planner *h, int rc)
+static bool lean_eligible(const cem_planner *h, const Dims &d, int rc, bool sample_in_rollout)
 {
-    const Dims &d = h->d;
     return launch_rollout_lean != nullptr && !d.wide && !d.split && rc == 1 && d.NFW == 1 && d.L == 4 && d.O % 4 == 0 && h->cfg.world_size == 1 && !h->batch &&
-           h->sample_in_rollout && CEM_LEAN_ACT_LDS_BYTES(d.H, (d.A + 3) / 4) <= CEM_LEAN_ACT_LDS_MAX;
+           sample_in_rollout && CEM_LEAN_ACT_LDS_BYTES(d.H, (d.A + 3) / 4) <= CEM_LEAN_ACT_LDS_MAX;
+}
+
+// Where the sampler runs (cem_device.h: cem_tile_sample_actions vs cem_sample_kernel) and which rollout kernels serve the plan `pl` of
+// the shape `d` on this handle: create's rule, and — per iteration — the population schedule's.
+// Inside the rollout launch when ALL its tiles are resident at once (one round of prologues per launch: B1, B2) — one launch and one
+// graph node fewer per iteration for about what the launch cost; as a launch of its own when tiles queue for slots (B3: 8 tiles per CU;
+// every round of tiles would pay the prologue on its critical path, and each candidate is sampled once per particle: K = 16 measured
+// +1.5 % on the launch).
+static void place_sampler(const cem_planner *h, const Dims &d, const Plan &pl, bool *sample_in_rollout, bool *lean_rollout)
+{
+    const size_t nb = (size_t)warm_slots(h);
+    const int slots = real_cus() * ((d.wide || d.split) ? 1 : resident_workgroups(d.NFW, pl.rc, pl.n_seg > 1));
+    *sample_in_rollout = (long long)nb * pl.n_tiles <= slots;          // (a batch handle: all its problems' tiles in one launch)
+    if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
+        *sample_in_rollout = std::strcmp(e, "kernel") != 0;
+    *lean_rollout = lean_eligible(h, d, pl.rc, *sample_in_rollout);
+    if (const char *e = std::getenv("CEM_FORCE_ROLLOUT"))      // diagnostic / tests: "generic" or "lean" — the results do not depend on it; "lean" on an ineligible handle is ignored
+        *lean_rollout = *lean_rollout && std::strcmp(e, "generic") != 0;
 }
 
 // mb = 0: a single-state handle (cem_planner_create); mb > 0: a batch handle of mb problems (cem_batch_planner_create)
@@ -960,17 +1016,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
         h->own_stream = true;
     }
     { const Plan pl = make_plan(cfg, h->d, mb); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
-      // Where the sampler runs (cem_device.h: cem_tile_sample_actions vs cem_sample_kernel).  Inside the rollout launch when ALL its
-      // tiles are resident at once (one round of prologues per launch: B1, B2) — one launch and one graph node fewer per iteration for
-      // about what the launch cost; as a launch of its own when tiles queue for slots (B3: 8 tiles per CU; every round of tiles would
-      // pay the prologue on its critical path, and each candidate is sampled once per particle: K = 16 measured +1.5 % on the launch).
-      const int slots = real_cus() * ((h->d.wide || h->d.split) ? 1 : resident_workgroups(h->d.NFW, pl.rc, pl.n_seg > 1));
-      h->sample_in_rollout = (long long)nb * pl.n_tiles <= slots;        // (a batch handle: all its problems' tiles in one launch)
-      if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
-          h->sample_in_rollout = std::strcmp(e, "kernel") != 0;
-      h->lean_rollout = lean_eligible(h, pl.rc);
-      if (const char *e = std::getenv("CEM_FORCE_ROLLOUT"))      // diagnostic / tests: "generic" or "lean" — the results do not depend on it; "lean" on an ineligible handle is ignored
-          h->lean_rollout = h->lean_rollout && std::strcmp(e, "generic") != 0; }
+      place_sampler(h, h->d, pl, &h->sample_in_rollout, &h->lean_rollout); }
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
@@ -978,6 +1024,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->refit_kind = CEM_REFIT_UNIFORM; h->refit_tau = 0.f; h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
     h->noise_kind = CEM_NOISE_WHITE; h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
     h->elite = cem_elite_carry_t{}; h->elite.shift = 1; h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
+    h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0; h->mean_cand = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
@@ -1322,9 +1369,10 @@ hipError_t launch_rollout_wide(const cem_planner *h, const RolloutParams &rp, in
     return hipGetLastError();
 }
 
-void fill_rollout_common(const cem_planner *h, RolloutParams &p)
+// dv: the shape of a scheduled iteration (cem_population.h), else the handle's own
+void fill_rollout_common(const cem_planner *h, RolloutParams &p, const Dims *dv = nullptr)
 {
-    const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
+    const Dims &d = dv ? *dv : h->d; const Layout &l = h->lay; char *ws = h->ws;
     std::memset(&p, 0, sizeof(p));
     p.wpack = (const f4 *)(ws + l.wpack); p.bias_h = (const float *)(ws + l.bias_h);
     p.bias_mu = (const float *)(ws + l.bias_mu); p.bias_var = (const float *)(ws + l.bias_var);
@@ -1366,6 +1414,9 @@ int enqueue_begin(cem_planner *h)
     InitParams ip{}; ip.ctrl = (CtrlBlock *)(h->ws + l.ctrl); ip.musig = (float *)(h->ws + l.musig); ip.HA = d.H * d.A; ip.A = d.A;
     ip.host_ctrl = h->d_h_ctrl;                          // the block stage_ctrl filled, read from pinned host memory by the kernel itself
     for (int a = 0; a < d.A; ++a) { ip.mu0[a] = h->cfg.act_mu0[a]; ip.sigma0[a] = h->cfg.act_sigma0[a]; }
+    if (!h->pop.empty()) {                               // a schedule: the most FIFO entries any of its iterations uses (cem_population.h)
+        if (h->pop_n_ready > 0) { ip.seg_queue = (uint32_t *)(h->ws + l.seg_queue); ip.seg_flags = h->pop_seg_flags; ip.n_ready = h->pop_n_ready; }
+    } else
     if (h->n_seg > 1) { ip.seg_queue = (uint32_t *)(h->ws + l.seg_queue); ip.seg_flags = (uint32_t *)(h->ws + l.seg_flags); ip.n_ready = (h->n_tiles - h->n_pinned) * (h->n_seg - 1); }
     ip.n_prob = h->batch;                                // a batch handle: every problem's block and mu / sigma (the done ones included)
     ip.warm = h->d_h_warm; ip.carry = (float *)(h->ws + l.carry); ip.expl = (const float *)(h->ws + l.expl);
@@ -1423,7 +1474,8 @@ hipError_t launch_score(const cem_planner *h, const ReduceParams &p, int n_probl
 // the parameter block of the two carry-over kernels in iteration `it`
 EliteCarryParams fill_elite(const cem_planner *h, int it)
 {
-    const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
+    const IterView v = iter_view(h, it);
+    const Dims &d = *v.d; const Layout &l = h->lay; char *ws = h->ws;
     EliteCarryParams ep{}; ep.scores = (const float *)(ws + l.scores_global); ep.actions = (float *)(ws + l.actions); ep.act_pad = (float *)(ws + l.act_pad);
     ep.ctrl = (const CtrlBlock *)(ws + l.ctrl); ep.elite_idx = (const int32_t *)(ws + l.elite); ep.store = elite_store(h); ep.count = elite_counts(h);
     ep.N = d.N; ep.k = d.k; ep.m = h->elite.n_keep; ep.H = d.H; ep.A = d.A; ep.it = it; ep.shift = h->elite.across_plans ? h->elite.shift : 0;
@@ -1436,11 +1488,14 @@ EliteCarryParams fill_elite(const cem_planner *h, int it)
 // the particle mean while it stages its keys (same sum, same order, one launch and one graph node fewer per iteration).
 int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
 {
-    const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
-    const bool queued = h->n_seg > 1 && !h->eps_model;       // explicit eps_model tensors take the general (MODE 1) kernel
-    RolloutParams rp; fill_rollout_common(h, rp);
-    rp.tiles = (const TileDesc *)(ws + l.tiles); rp.s0 = nullptr; rp.actions = (const float *)(ws + l.actions);
-    rp.eps_model = h->eps_model ? h->eps_model + (size_t)it * d.H * d.Btot * d.O : nullptr;
+    // v: what this iteration launches — the handle's plan, or the scheduled iteration's (cem_population.h); d: its shape.  The caller's
+    // noise tensors keep the slabs of the handle's own n_samples (h->d), of which a narrower iteration reads the leading part
+    const IterView v = iter_view(h, it);
+    const Dims &d = *v.d; const Layout &l = h->lay; char *ws = h->ws;
+    const bool queued = v.n_seg > 1 && !h->eps_model;       // explicit eps_model tensors take the general (MODE 1) kernel
+    RolloutParams rp; fill_rollout_common(h, rp, v.d);
+    rp.tiles = v.tiles; rp.s0 = nullptr; rp.actions = (const float *)(ws + l.actions);
+    rp.eps_model = h->eps_model ? h->eps_model + (size_t)it * d.H * h->d.Btot * d.O : nullptr;
     // CEM_VARIANT_COST: the safe variant's launch (its cost bytes, un-masked by sc_roll's threshold); the returns it also writes mean nothing
     const bool cost_obj = h->cfg.variant == CEM_VARIANT_COST;
     rp.ret = (float *)(ws + l.returns); rp.costs = h->cfg.variant != CEM_VARIANT_CEM ? (uint8_t *)(ws + l.costs) : nullptr;
@@ -1449,14 +1504,14 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     // the sampler's inputs and outputs (cem_mpc.py:44-48)
     // (the handle's own mixed tensor stands in wherever the caller passed none: the lean kernels then step aside below, as for any tensor)
     const float *eps_act = h->eps_act ? h->eps_act : (h->noise_kind == CEM_NOISE_MIXED ? h->noise_eps : nullptr);
-    rp.musig = (const float *)(ws + l.musig); rp.eps_act = eps_act ? eps_act + (size_t)it * d.N * d.H * d.A : nullptr;
+    rp.musig = (const float *)(ws + l.musig); rp.eps_act = eps_act ? eps_act + (size_t)it * h->d.N * d.H * d.A : nullptr;
     rp.act_bounds = (const float *)(ws + l.act_bounds); rp.actions_w = (float *)(ws + l.actions); rp.act_pad_w = (float *)(ws + l.act_pad);
-    rp.pad_shift = d.O - 4 * d.act_q0; rp.pad_floats = 4 * d.act_nq; rp.N = d.N; rp.Nloc = d.Nloc; rp.n_off = d.n_off; rp.n_tiles = h->n_tiles;
+    rp.pad_shift = d.O - 4 * d.act_q0; rp.pad_floats = 4 * d.act_nq; rp.N = d.N; rp.Nloc = d.Nloc; rp.n_off = d.n_off; rp.n_tiles = v.n_tiles;
     // a batch handle: ONE launch per stage for all its problems, problem b on tiles [b n_tiles, (b + 1) n_tiles) and its own slices
     const int nb = warm_slots(h);
-    rp.tiles_per_problem = h->batch ? h->n_tiles : 0;
-    rp.eps_act_pstride = (long long)d.I * d.N * d.H * d.A; rp.eps_model_pstride = (long long)d.I * d.H * d.Btot * d.O;
-    if (!samples_in_rollout(h)) {                         // all N candidates once, in front of the rollout launch (which then samples nothing)
+    rp.tiles_per_problem = h->batch ? v.n_tiles : 0;
+    rp.eps_act_pstride = (long long)d.I * h->d.N * d.H * d.A; rp.eps_model_pstride = (long long)d.I * d.H * h->d.Btot * d.O;
+    if (!samples_in_rollout(h, it)) {                         // all N candidates once, in front of the rollout launch (which then samples nothing)
         const int total = d.N * d.H * ((d.A + 3) / 4);
         TimedLaunch timed(h, 3);
         hipLaunchKernelGGL(cem_sample_kernel, dim3(std::min((total + 255) / 256, 2048), nb), dim3(256), 0, h->stream, rp);
@@ -1468,24 +1523,31 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
             EliteCarryParams ep = fill_elite(h, it);
             HIPCHK(launch_elite_inject(ep, nb, h->stream));
         }
+        // the mean candidate: the iteration's last row becomes the clipped mu it was sampled from (cem_population.h)
+        if (injects_mean(h, it)) {
+            MeanCandidateParams mc{}; mc.musig = (const float *)(ws + l.musig); mc.act_bounds = rp.act_bounds; mc.ctrl = rp.ctrl;
+            mc.actions = rp.actions_w; mc.act_pad = rp.act_pad_w; mc.N = d.N; mc.row = d.N - 1; mc.H = d.H; mc.A = d.A;
+            mc.pad_shift = rp.pad_shift; mc.pad_floats = rp.pad_floats;
+            HIPCHK(launch_mean_candidate(mc, nb, h->stream));
+        }
     }
     TimedLaunch timed(h, 0);
-    if (runs_lean(h) && !rp.eps_act && !rp.eps_model) {      // (the same tiles, segments and work queue as the generic launches below)
+    if (runs_lean(h, it) && !rp.eps_act && !rp.eps_model) {      // (the same tiles, segments and work queue as the generic launches below)
         if (queued) {
-            rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = (uint32_t *)(ws + l.seg_flags); rp.seg_state = (f4 *)(ws + l.seg_state);
-            rp.seg_len = h->seg_len; rp.n_seg = h->n_seg; rp.n_pinned = h->n_pinned;
+            rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
+            rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
         }
-        HIPCHK(launch_rollout_lean(rp, queued ? h->n_pinned + h->n_seg * (h->n_tiles - h->n_pinned) : h->n_tiles, h->stream, queued));
+        HIPCHK(launch_rollout_lean(rp, queued ? v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned) : v.n_tiles, h->stream, queued));
     }
-    else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, h->n_tiles, rp.eps_model ? 1 : 0));
-    else if (d.split) HIPCHK(launch_rollout_split(h->rc, d.NFW, rp.eps_model ? 1 : 0, rp, h->n_tiles, h->stream));
-    else if (rp.eps_model) HIPCHK(launch_rollout<1>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
+    else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, rp.eps_model ? 1 : 0));
+    else if (d.split) HIPCHK(launch_rollout_split(v.rc, d.NFW, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
+    else if (rp.eps_model) HIPCHK(launch_rollout<1>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     else if (queued) {
-        rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = (uint32_t *)(ws + l.seg_flags); rp.seg_state = (f4 *)(ws + l.seg_state);
-        rp.seg_len = h->seg_len; rp.n_seg = h->n_seg; rp.n_pinned = h->n_pinned;
+        rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
+        rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
         // one workgroup per pinned tile, then one per (floating tile, segment) item
-        HIPCHK(launch_rollout_seg(h->rc, d.NFW, rp, h->n_pinned + h->n_seg * (h->n_tiles - h->n_pinned), h->stream));
-    } else HIPCHK(launch_rollout<0>(h->rc, d.NFW, rp, nb * h->n_tiles, h->stream));
+        HIPCHK(launch_rollout_seg(v.rc, d.NFW, rp, v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned), h->stream));
+    } else HIPCHK(launch_rollout<0>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     timed.stop();
     if (fold_reduce) return CEM_OK;
 
@@ -1500,13 +1562,23 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
 
 // whether a whole plan of this handle folds the particle mean into the select kernel: one rank (the scores need no exchange), the
 // CemMpc objective (no per-step Beta counts), and a population the one-workgroup select serves with its keys staged in LDS
-bool folds_reduce(const cem_planner *h)
+// (it: the iteration — a population schedule gives each its own population, hence its own answer)
+bool folds_reduce(const cem_planner *h, int it = 0)
 {
     const Dims &d = h->d;
     if (d.W != 1 || h->comm || h->cfg.variant != CEM_VARIANT_CEM) return false;
     if (h->tail_m) return false;                       // what the select folds IS the mean
     bool cache = false;
-    return select_mode_now(h, &cache) == 1 && cache;
+    return select_mode_for(h, iter_view(h, it).d->N, &cache) == 1 && cache;
+}
+
+// launches of iteration `it` (cem_planner_launches_per_iteration's rule): the rollout, the sampler where it is a launch of its own, the score
+// kernel unless the select folds it, the select's, the weighted refit, carry-over's inject and keep, the mean candidate
+int launches_of(const cem_planner *h, int it)
+{
+    const int mode = select_mode_for(h, iter_view(h, it).d->N);
+    return 1 + (samples_in_rollout(h, it) ? 0 : 1) + (folds_reduce(h, it) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
+           (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0) + (h->elite.n_keep ? 2 : 0) + (injects_mean(h, it) ? 1 : 0);
 }
 
 // fold_final: the select writes the plan's result itself (whole plans only: eps_out is known before the loop) — returns through
@@ -1514,7 +1586,7 @@ bool folds_reduce(const cem_planner *h)
 int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = false, bool have_eps_out = false, bool *folded = nullptr)
 {
     if (folded) *folded = false;
-    const Dims &d = h->d; const Layout &l = h->lay; char *ws = h->ws;
+    const Dims &d = *iter_view(h, it).d; const Layout &l = h->lay; char *ws = h->ws;    // (a scheduled iteration ranks its own n[it] candidates)
     SelectParams p{}; p.scores = (const float *)(ws + l.scores_global); p.actions = (const float *)(ws + l.actions);
     p.musig = (float *)(ws + l.musig); p.ctrl = (CtrlBlock *)(ws + l.ctrl); p.elite_idx = (int32_t *)(ws + l.elite);
     p.N = d.N; p.k = d.k; p.HA = d.H * d.A; p.A = d.A; p.check_done = 1;
@@ -1537,7 +1609,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     // select_mode_now.  select_mode 2 has no such assumption.
     const int G = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS;
     bool cache = false;
-    const int mode = select_mode_now(h, &cache);
+    const int mode = select_mode_for(h, d.N, &cache);
     if (mode == 0) return CEM_ERR_UNSUPPORTED;          // (an explicit select_mode 1 on a device that grants less dynamic LDS than validate() assumed)
     // The score-weighted refit (cem_refit_weighted.h): the one-workgroup select as it is, blending into a scratch slice, never stopping and
     // never handing over the result; cem_constraint_refit_kernel behind it refits the plan's mu / sigma and decides the early stop.
@@ -1545,6 +1617,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     if (weighted && (mode != 1 || !h->refit_dev)) return CEM_ERR_UNSUPPORTED;      // (cem_planner_set_refit admitted one-workgroup handles only)
     if (weighted) { p.musig = h->refit_dev; p.threshold = -std::numeric_limits<float>::infinity(); }
     if (h->elite.n_keep && (mode != 1 || !h->elite_dev)) return CEM_ERR_UNSUPPORTED;   // (cem_planner_set_elite_carry admitted one-workgroup handles only)
+    if (!h->pop.empty() && mode != 1) return CEM_ERR_UNSUPPORTED;                      // (cem_planner_set_population_schedule likewise)
     TimedLaunch timed(h, 1);
     if (mode >= 2) {
         MSelParams m{}; m.scores = p.scores; m.actions = p.actions; m.musig = p.musig; m.ctrl = p.ctrl; m.elite_idx = p.elite_idx;
@@ -1817,10 +1890,10 @@ int read_results(cem_planner *h, const PlanCall &pc)
 // the result itself (single-state handles on the one-workgroup select: enqueue_select).
 int enqueue_plan(cem_planner *h, bool have_eps_out)
 {
-    const bool fold = folds_reduce(h);
     bool final_folded = false;
     int st = enqueue_begin(h);
     for (int it = 0; it < h->d.I && !st; ++it) {
+        const bool fold = folds_reduce(h, it);
         st = enqueue_rollout(h, it, fold);
         if (!st) st = enqueue_exchange(h);
         if (!st) st = enqueue_select(h, it, fold, true, have_eps_out, &final_folded);
@@ -1971,6 +2044,7 @@ int cem_plan_select(cem_planner_t *h, int32_t it)
 {
     if (!h) return CEM_ERR_INVALID_ARG;
     if (!h->in_plan) return CEM_ERR_STATE;
+    if (!h->pop.empty() && (it < 0 || it >= h->d.I)) return CEM_ERR_INVALID_ARG;     // (a scheduled select needs to know whose population it ranks)
     return enqueue_select(h, it, false);
 }
 
@@ -2227,6 +2301,9 @@ int cem_planner_set_elite_carry(cem_planner_t *h, const cem_elite_carry_t *ec)
         if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;               // the multi-workgroup selects: the rule cem_planner_set_refit applies
         if (d.k > CEM_ELITE_MAX_K || !launch_elite_keep || !launch_elite_inject) return CEM_ERR_UNSUPPORTED;
         if (ec->across_plans && h->batch) return CEM_ERR_UNSUPPORTED;          // a batch handle's rows move between slots (cem_planner_set_carry_slots)
+        // (cem_population.h: the inject's rows must be candidates of every scheduled iteration, and none of them the mean candidate's)
+        for (const IterPlan &ip : h->pop) if (ip.d.N <= ec->n_keep) return CEM_ERR_UNSUPPORTED;
+        if (h->mean_cand && ec->n_keep >= iter_view(h, d.I - 1).d->N - 1) return CEM_ERR_UNSUPPORTED;
     }
     // a larger store is allocated before anything of the handle changes: a failed allocation leaves it as it was
     float *grown = nullptr;
@@ -2261,6 +2338,112 @@ int cem_planner_elite_store(cem_planner_t *h, int32_t problem, float *out_host, 
     const size_t row = (size_t)h->elite.n_keep * h->d.H * h->d.A;
     if (out_host) HIPCHK(hipMemcpy(out_host, elite_store(h) + (size_t)problem * row, row * 4, hipMemcpyDeviceToHost));
     if (count_out) HIPCHK(hipMemcpy(count_out, elite_counts(h) + problem, 4, hipMemcpyDeviceToHost));
+    return CEM_OK;
+}
+
+// what both setters of cem_population.h ask of a handle they enable something on
+static int population_admits(const cem_planner *h)
+{
+    if (h->d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;      // one rank's select ranks one rank's population
+    if (h->batch) return CEM_ERR_UNSUPPORTED;                   // (a batch handle's launch carries every problem's tiles of ONE plan)
+    if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;    // the multi-workgroup selects: the rule cem_planner_set_refit applies
+    return CEM_OK;
+}
+
+int cem_planner_set_population_schedule(cem_planner_t *h, const int32_t *n, int32_t count)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    const Dims &d = h->d;
+    if (count != 0 && count != d.I) return CEM_ERR_INVALID_ARG;
+    if (!n) count = 0;
+    bool on = false;
+    for (int it = 0; it < count; ++it) {
+        if (n[it] < d.k || n[it] > d.N || ((long long)d.P * n[it]) % d.E != 0) return CEM_ERR_INVALID_ARG;
+        on = on || n[it] != d.N;
+    }
+    if (h->in_plan) return CEM_ERR_STATE;
+    std::vector<IterPlan> plans;
+    std::vector<std::vector<Tile6>> lists;
+    char *block = nullptr; uint32_t *flags = (uint32_t *)(h->ws + h->lay.seg_flags); f4 *state = (f4 *)(h->ws + h->lay.seg_state);
+    size_t n_ready = 0, flags_off = 0, flags_bytes = 0, state_bytes = 0;
+    if (on) {
+        { const int st = population_admits(h); if (st) return st; }
+        for (int it = 0; it < count; ++it) if (h->elite.n_keep && n[it] <= h->elite.n_keep) return CEM_ERR_UNSUPPORTED;
+        if (h->mean_cand && h->elite.n_keep && h->elite.n_keep >= n[d.I - 1] - 1) return CEM_ERR_UNSUPPORTED;
+        // every iteration's plan, from the functions create uses, for the configuration that differs in n_samples alone
+        plans.resize(d.I); lists.resize(d.I);
+        size_t bytes = 0;
+        for (int it = 0; it < d.I; ++it) {
+            IterPlan &ip = plans[it];
+            if (n[it] == d.N) {
+                ip.d = h->d; ip.rc = h->rc; ip.n_tiles = h->n_tiles; ip.n_seg = h->n_seg; ip.seg_len = h->seg_len; ip.n_pinned = h->n_pinned;
+                ip.sample_in_rollout = h->sample_in_rollout; ip.lean_rollout = h->lean_rollout; ip.tiles_off = (size_t)-1;
+            } else {
+                cem_config_t c = h->cfg; c.n_samples = n[it];
+                { const int st = validate(&c); if (st) return st; }
+                ip.d = make_dims(&c);
+                const Plan pl = make_plan(&c, ip.d);
+                ip.rc = pl.rc; ip.n_seg = pl.n_seg; ip.seg_len = pl.seg_len; ip.n_pinned = pl.n_pinned;
+                build_plan_tiles(ip.d, ip.rc, lists[it]);
+                ip.n_tiles = (int)lists[it].size();
+                place_sampler(h, ip.d, pl, &ip.sample_in_rollout, &ip.lean_rollout);
+                if (select_mode_for(h, ip.d.N) != 1) return CEM_ERR_UNSUPPORTED;
+                ip.tiles_off = bytes; bytes += align256(lists[it].size() * sizeof(Tile6));
+            }
+            if (ip.n_seg > 1) {
+                const size_t n_float = (size_t)(ip.n_tiles - ip.n_pinned);
+                n_ready = std::max(n_ready, n_float * (ip.n_seg - 1));
+                state_bytes = std::max(state_bytes, n_float * (2 * (size_t)ip.d.NFW * ip.rc * 256 + 64) * 16);
+            }
+        }
+        flags_bytes = n_ready * 4;
+        // the workspace's two arrays serve while they are large enough (their sizes: up to the next array's offset); else both move
+        const bool own_seg = flags_bytes > h->lay.seg_state - h->lay.seg_flags || state_bytes > h->lay.ms_hist - h->lay.seg_state;
+        if (own_seg) { flags_off = bytes; bytes += align256(flags_bytes) + align256(state_bytes); }
+        // allocated and filled before anything of the handle changes: a failed call leaves it as it was
+        HIPCHK(hipMalloc((void **)&block, std::max<size_t>(bytes, 256)));
+        hipError_t e = hipSuccess;
+        for (int it = 0; it < d.I && e == hipSuccess; ++it)
+            if (plans[it].tiles_off != (size_t)-1)
+                e = hipMemcpy(block + plans[it].tiles_off, lists[it].data(), lists[it].size() * sizeof(Tile6), hipMemcpyHostToDevice);
+        if (e == hipSuccess && own_seg) e = hipMemset(block + flags_off, 0, align256(flags_bytes) + align256(state_bytes));
+        if (e != hipSuccess) { g_last_hip = (int)e; hipFree(block); return CEM_ERR_HIP; }
+        if (own_seg) { flags = (uint32_t *)(block + flags_off); state = (f4 *)(block + flags_off + align256(flags_bytes)); }
+    }
+    // Unconditional, as in cem_planner_set_elite_carry: an eager plan still draining behind its polled result may be reading the old lists
+    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) { g_last_hip = (int)e; if (block) hipFree(block); return CEM_ERR_HIP; }
+    drop_graph(h);                                                              // the captured plan holds the other setting's launches
+    if (h->pop_dev) hipFree(h->pop_dev);
+    h->pop_dev = block; h->pop.swap(plans); h->pop_seg_flags = flags; h->pop_seg_state = state; h->pop_n_ready = (int)n_ready;
+    return CEM_OK;
+}
+
+int cem_planner_get_population_schedule(const cem_planner_t *h, int32_t *n_out, int32_t count, int32_t *enabled_out)
+{
+    if (!h || (!n_out && !enabled_out) || (n_out && count != h->d.I)) return CEM_ERR_INVALID_ARG;
+    if (n_out) for (int it = 0; it < h->d.I; ++it) n_out[it] = iter_view(h, it).d->N;
+    if (enabled_out) *enabled_out = h->pop.empty() ? 0 : 1;
+    return CEM_OK;
+}
+
+int cem_planner_set_mean_candidate(cem_planner_t *h, int32_t enable)
+{
+    if (!h || (enable != 0 && enable != 1)) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    if (enable) {
+        { const int st = population_admits(h); if (st) return st; }
+        if (!launch_mean_candidate) return CEM_ERR_UNSUPPORTED;
+        if (h->elite.n_keep && h->elite.n_keep >= iter_view(h, h->d.I - 1).d->N - 1) return CEM_ERR_UNSUPPORTED;   // the inject's rows stay the inject's
+    }
+    { const int st = retire_graph(h); if (st) return st; }
+    h->mean_cand = enable;
+    return CEM_OK;
+}
+
+int cem_planner_get_mean_candidate(const cem_planner_t *h, int32_t *enable_out)
+{
+    if (!h || !enable_out) return CEM_ERR_INVALID_ARG;
+    *enable_out = h->mean_cand;
     return CEM_OK;
 }
 
@@ -2350,6 +2533,7 @@ int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int
     if (h->in_plan) return CEM_ERR_STATE;
     if (h->noise_kind == CEM_NOISE_MIXED) return CEM_ERR_UNSUPPORTED;          // (cem_planner_set_action_noise refuses a communicator; so the reverse)
     if (h->elite.n_keep) return CEM_ERR_UNSUPPORTED;                           // (cem_planner_set_elite_carry likewise)
+    if (!h->pop.empty() || h->mean_cand) return CEM_ERR_UNSUPPORTED;           // (cem_planner_set_population_schedule / _mean_candidate likewise)
     Rccl *r = rccl(); if (!r) return CEM_ERR_COMM;
     if (h->comm) { r->CommDestroy(h->comm); h->comm = nullptr; }
     CemNcclId nid; std::memcpy(nid.internal, id, CEM_COMM_ID_BYTES);
@@ -2396,16 +2580,25 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out)
 int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out)
 {
     if (!h || !path_out) return CEM_ERR_INVALID_ARG;
-    *path_out = (runs_lean(h) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;       // (the lean kernels draw in place and cannot take a tensor)
+    *path_out = (runs_lean(h, 0) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;       // (the lean kernels draw in place and cannot take a tensor)
     return CEM_OK;
 }
 
 int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches_out)
 {
     if (!h || !launches_out) return CEM_ERR_INVALID_ARG;
-    const int mode = select_mode_now(h);
-    *launches_out = 1 + (samples_in_rollout(h) ? 0 : 1) + (folds_reduce(h) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
-                    (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0) + (h->elite.n_keep ? 2 : 0);      // (carry-over: the inject and the keep)
+    *launches_out = launches_of(h, 0);
+    return CEM_OK;
+}
+
+int cem_planner_iteration_plan(const cem_planner_t *h, int32_t it, cem_iteration_plan_t *out)
+{
+    if (!h || !out || it < 0 || it >= h->d.I) return CEM_ERR_INVALID_ARG;
+    const IterView v = iter_view(h, it);
+    out->n_samples = v.d->N; out->chunks_per_tile = v.rc; out->n_tiles = v.n_tiles; out->n_segments = v.n_seg; out->n_pinned = v.n_pinned;
+    out->launches = launches_of(h, it);
+    out->rollout_path = (runs_lean(h, it) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;
+    out->reserved = 0;
     return CEM_OK;
 }
 

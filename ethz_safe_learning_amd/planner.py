@@ -72,6 +72,10 @@ class PlannerConfig:
     refit: str = 'uniform'             # 'uniform': every elite counts 1 / k (the reference) | 'softmax': elite j counts exp((s_j - s_max) / temperature)
                                        # (cem_planner_set_refit, CEM_REFIT_SOFTMAX; n_elite = n_samples is MPPI); not in cem_config_t: set after create
     refit_temperature: float = 0.0     # 'softmax': the temperature, finite and > 0 ('uniform' ignores it)
+    population: tuple = ()             # (): every iteration samples n_samples candidates (the reference); a tuple of `iterations` sizes: iteration
+                                       # `it` samples population[it] (population_schedule; cem_planner_set_population_schedule); not in
+                                       # cem_config_t: set after create
+    mean_candidate: bool = False       # True: the last candidate of the last iteration is the clipped mean (cem_planner_set_mean_candidate)
     action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
@@ -339,6 +343,18 @@ class CemPlanner:
         if cfg.keep_elites:
             try:
                 self.set_elite_carry(cfg.keep_elites, cfg.shift_elites, cfg.elite_shift)
+            except Exception:
+                self.close()
+                raise
+        if cfg.population:
+            try:
+                self.set_population_schedule(cfg.population)
+            except Exception:
+                self.close()
+                raise
+        if cfg.mean_candidate:
+            try:
+                self.set_mean_candidate(True)
             except Exception:
                 self.close()
                 raise
@@ -654,6 +670,40 @@ class CemPlanner:
         n = C.c_int32()
         _capi.check(self.lib.cem_planner_elite_store(self.h, int(problem), _np_ptr(E), C.byref(n)), 'cem_planner_elite_store')
         return E, n.value
+
+    def set_population_schedule(self, n=None):
+        """Per-iteration population sizes (cem_planner_set_population_schedule): iteration `it` samples, rolls out and ranks n[it] candidates,
+        exactly as a handle created with n_samples = n[it] would.  None, or every entry equal to n_samples, switches it off.  Sticky."""
+        if n is None or len(n) == 0:
+            _capi.check(self.lib.cem_planner_set_population_schedule(self.h, None, 0), 'cem_planner_set_population_schedule')
+            return
+        arr = (C.c_int32 * len(n))(*[int(x) for x in n])
+        _capi.check(self.lib.cem_planner_set_population_schedule(self.h, arr, len(n)), 'cem_planner_set_population_schedule')
+
+    def population_schedule(self):
+        """(sizes [iterations], enabled) as set (cem_planner_get_population_schedule): n_samples everywhere while off."""
+        arr = (C.c_int32 * self.cfg.iterations)()
+        on = C.c_int32()
+        _capi.check(self.lib.cem_planner_get_population_schedule(self.h, arr, self.cfg.iterations, C.byref(on)), 'cem_planner_get_population_schedule')
+        return list(arr), bool(on.value)
+
+    def iteration_plan(self, it):
+        """What iteration `it` launches (cem_planner_iteration_plan), on any handle: a dict of n_samples, chunks_per_tile, n_tiles,
+        n_segments, n_pinned, launches and rollout_path ('lean' / 'generic')."""
+        ip = _capi.CemIterationPlan()
+        _capi.check(self.lib.cem_planner_iteration_plan(self.h, int(it), C.byref(ip)), 'cem_planner_iteration_plan')
+        return dict(n_samples=ip.n_samples, chunks_per_tile=ip.chunks_per_tile, n_tiles=ip.n_tiles, n_segments=ip.n_segments,
+                    n_pinned=ip.n_pinned, launches=ip.launches, rollout_path='lean' if ip.rollout_path else 'generic')
+
+    def set_mean_candidate(self, enable=True):
+        """The last candidate of the last iteration becomes the clipped mean it was sampled around (cem_planner_set_mean_candidate;
+        mean_candidate restates the kernel).  Sticky."""
+        _capi.check(self.lib.cem_planner_set_mean_candidate(self.h, 1 if enable else 0), 'cem_planner_set_mean_candidate')
+
+    def mean_candidate(self):
+        on = C.c_int32()
+        _capi.check(self.lib.cem_planner_get_mean_candidate(self.h, C.byref(on)), 'cem_planner_get_mean_candidate')
+        return bool(on.value)
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')
@@ -1083,6 +1133,38 @@ def elite_keep_count(fraction, n_elite) -> int:
     if not 0.0 < f <= 1.0:
         raise ValueError('keep_elites is a fraction of n_elite in (0, 1]')
     return max(1, int(np.floor(f * int(n_elite))))
+
+
+def population_schedule(n_samples, n_elite, iterations, decay, particles, ensemble_size, min_population=None):
+    """iCEM's population decay as a list of `iterations` sizes for cem_planner_set_population_schedule: iteration i gets
+    ceil(n_samples / decay**i - 1e-9), not below min(n_samples, max(n_elite, min_population or 2 n_elite)), rounded up to a multiple of
+    ensemble_size // gcd(particles, ensemble_size) (so that particles * n splits evenly among the members) and capped at n_samples.
+    decay == 1 gives n_samples everywhere (off)."""
+    import math
+    N, k, I, P, E = int(n_samples), int(n_elite), int(iterations), int(particles), int(ensemble_size)
+    g = float(decay)
+    if not (math.isfinite(g) and g >= 1.0):
+        raise ValueError('population decay must be finite and >= 1')
+    if N < 1 or k < 1 or k > N or I < 1 or P < 1 or E < 1:
+        raise ValueError('population_schedule needs 1 <= n_elite <= n_samples and positive iterations, particles, ensemble_size')
+    if min_population is not None and int(min_population) < 1:
+        raise ValueError('min_population must be positive')
+    floor = min(N, max(k, int(min_population) if min_population is not None else 2 * k))
+    q = E // math.gcd(P, E)
+    out = []
+    for i in range(I):
+        n = max(int(math.ceil(N / g ** i - 1e-9)), floor)
+        out.append(min(N, -(-n // q) * q))
+    return out
+
+
+def mean_candidate(actions, mu, lb, ub) -> np.ndarray:
+    """Host restatement of cem_mean_candidate_kernel — a max, a min and copies, so it is exact: a copy of actions [n, H, A] whose LAST
+    row is min(max(mu, lb), ub); mu [H, A] as the iteration samples from it, lb / ub [A]."""
+    out = np.array(actions, np.float32, copy=True)
+    m = np.asarray(mu, np.float32).reshape(out.shape[1:])
+    out[-1] = np.minimum(np.maximum(m, np.asarray(lb, np.float32)), np.asarray(ub, np.float32))
+    return out
 
 
 def plan_tiles(cfg: PlannerConfig):

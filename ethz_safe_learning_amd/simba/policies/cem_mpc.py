@@ -47,11 +47,21 @@ last kept elites, moved ``warm_shift`` steps towards the present, the freed tail
 such a policy plans on handles of its OWN (as a warm-started one does), ``reset()`` empties it, and ``generate_actions`` is refused with
 a ``ValueError`` — a batch handle's rows move between slots and carry nothing across plans.  ``None`` / ``False`` (the defaults, and what
 every shipped preset has) touch no handle and change no bit.  Nothing is claimed about the returns or the safety of an agent that uses
-it."""
+it.
+
+Population decay and the mean candidate (beyond the reference, off by default): with ``population_decay`` a float >= 1 (iCEM uses 1.25)
+iteration i samples ``planner.population_schedule(n_samples, n_elite, iterations, population_decay, particles, ensemble_size,
+min_population)[i]`` candidates instead of ``n_samples`` — about ``n_samples / population_decay**i``, not below ``min_population``
+(default ``2 * n_elite``) — each iteration launched as a plan of that population would launch it (``PlannerConfig.population``, cem_mpc.h
+cem_planner_set_population_schedule): the one iCEM ingredient that saves work.  With ``mean_candidate=True`` the last
+candidate of the last iteration is the clipped mean itself (``PlannerConfig.mean_candidate``).  ``generate_action`` and warm-started
+plans use both; ``generate_actions`` is refused with a ``ValueError`` — a batch handle launches the tiles of ONE plan for all its rows.
+``None`` / ``False`` (the defaults, and what every shipped preset has) touch no handle and change no bit.  Nothing is claimed about the
+returns or the safety of an agent that uses them."""
 import logging
 import numpy as np
 
-from ...planner import PlannerConfig, cached_batch_planner, cached_planner, elite_keep_count, risk_particles, stage_model_weights
+from ...planner import PlannerConfig, cached_batch_planner, cached_planner, elite_keep_count, population_schedule, risk_particles, stage_model_weights
 from .mpc_policy import MpcPolicy
 
 
@@ -61,7 +71,8 @@ class CemMpc(MpcPolicy):
     def __init__(self, model, environment, horizon, iterations, smoothing, n_samples, n_elite, particles,
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
                  warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None,
-                 elite_temperature=None, noise_beta=None, noise_rho=None, keep_elites=None, shift_elites=False):
+                 elite_temperature=None, noise_beta=None, noise_rho=None, keep_elites=None, shift_elites=False,
+                 population_decay=None, min_population=None, mean_candidate=False):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -96,6 +107,14 @@ class CemMpc(MpcPolicy):
         self.shift_elites = bool(shift_elites)
         if self.shift_elites and self.keep_elites is None:
             raise ValueError('shift_elites needs keep_elites')
+        # population decay and the mean candidate (beyond the reference's kwargs): see the module docstring
+        self.population_decay = None if population_decay is None else float(population_decay)
+        self.min_population = None if min_population is None else int(min_population)
+        if self.population_decay is None and self.min_population is not None:
+            raise ValueError('min_population needs population_decay')
+        if self.population_decay is not None and not (np.isfinite(self.population_decay) and self.population_decay >= 1.0):
+            raise ValueError('population_decay must be finite and >= 1, got %r' % (population_decay,))
+        self.mean_candidate = bool(mean_candidate)
         self.last_ess = None                           # ESS per iteration of the last weighted plan (generate_actions: a list, one array per row)
         self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
         self._warm_cap = 1                             # slots the warm-started batch handle must hold
@@ -129,6 +148,17 @@ class CemMpc(MpcPolicy):
             return {}
         return dict(keep_elites=self.n_keep, shift_elites=self.shift_elites, elite_shift=self.warm_shift if self.shift_elites else 1)
 
+    def _population_config(self):
+        out = {}
+        if self.population_decay is not None:
+            sched = population_schedule(self.n_samples, self.elite, self.iterations, self.population_decay, self.particles,
+                                        self.model.model.ensemble_size, self.min_population)
+            if any(n != self.n_samples for n in sched):
+                out['population'] = tuple(sched)
+        if self.mean_candidate:
+            out['mean_candidate'] = True
+        return out
+
     def _scorer_config(self):
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
         if scorer is None:
@@ -147,7 +177,7 @@ class CemMpc(MpcPolicy):
             smoothing=self.smoothing, stddev_threshold=self.stddev_threshold, noise_stddev=self.noise_stddev,
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
             use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._refit_config(),
-            **self._noise_config(), **self._carry_config(), **self._extra_config())
+            **self._noise_config(), **self._carry_config(), **self._population_config(), **self._extra_config())
 
     def _owns_handles(self):
         """Whether this policy's planning handles carry state of its own (the warm-start carry, the elites kept across plans; SafeCemMpc:
@@ -245,6 +275,9 @@ class CemMpc(MpcPolicy):
         if self.shift_elites:
             raise ValueError('shift_elites=True carries elites across the plans of ONE environment; generate_actions plans on a batch handle, '
                              'whose rows move between slots: use generate_action, or keep_elites alone')
+        if self.population_decay is not None or self.mean_candidate:
+            raise ValueError('population_decay / mean_candidate give every iteration of ONE plan its own launches; generate_actions plans on a '
+                             'batch handle, which launches the tiles of one plan for all its rows and serves neither: use generate_action')
         st = np.asarray(states, np.float32)
         if st.ndim != 2:
             raise ValueError('states must be [B, obs_dim]')

@@ -43,7 +43,10 @@ objective, the sampler is shared and there is no reason for it to differ.
 
 ``keep_elites`` / ``shift_elites`` (CemMpc's, off by default): the reward plans carry elites over as CemMpc's do.  ``optimize_for_safety``
 and the recovery plans of ``recover_below`` carry them from iteration to iteration only: their handle is shared through the cache and
-their plans follow no earlier cost plan."""
+their plans follow no earlier cost plan.
+
+``population_decay`` / ``min_population`` / ``mean_candidate`` (CemMpc's, off by default): the reward plans, ``optimize_for_safety`` and the
+recovery plans of ``recover_below`` all follow the policy's setting; ``generate_actions`` is refused as CemMpc's is."""
 import dataclasses
 
 import numpy as np

@@ -637,6 +637,56 @@ int cem_planner_get_elite_carry(const cem_planner_t *h, cem_elite_carry_t *carry
 int cem_planner_elite_store(cem_planner_t *h, int32_t problem, float *out_host /* [n_keep][H][A] */, int32_t *count_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Per-iteration population sizes (iCEM's population decay) and the mean as a candidate of the last iteration.  Beyond the reference,
+ * off by default.
+ *
+ * cem_planner_set_population_schedule: n[it] is the population of iteration `it`.  NULL / count == 0, or every entry equal to
+ * n_samples, is OFF: the handle launches exactly what create chose (the lean rollout and the folded sampler included).  The schedule
+ * need not be monotone.  Iteration `it` of a scheduled plan is iteration `it` of a handle created with n_samples = n[it], on the same
+ * mu / sigma, best-so-far, seed and call:
+ *   plan      tile size, tile list (the row-to-member map (p n[it] + j) / (P n[it] / E), pinned / floating split), horizon segments,
+ *             sampler placement, lean eligibility, select caching and reduce folding are those of the n[it]-wide configuration, from the
+ *             functions create uses, priced with the handle's chunks_per_tile and rollout_segments.  cem_planner_iteration_plan reports them.
+ *   results   candidates are 0 .. n[it] - 1; scores, elite indices, actions and the padded actions occupy the LEADING n[it] entries of
+ *             their arrays; nothing beyond them is read or written.
+ *   noise     Philox counters are those of the n[it]-wide plan: the candidate index for actions, the global row p n[it] + j for the model.
+ *   tensors   eps_act stays [I][N][H][A] with N = n_samples: iteration `it` reads rows j < n[it] of slab `it`.  eps_model stays
+ *             [I][H][P N][O]: iteration `it` reads the leading H P n[it] O floats of slab `it` as [H][P n[it]][O] — what the kernels do
+ *             when handed the slab's base and P n[it] rows.  The handle's own CEM_NOISE_MIXED tensor is read the same way (its kernel keeps
+ *             filling all N rows).  cem_fill_noise is unchanged: it describes the n_samples-wide streams.
+ *   the rest  mu / sigma, refit, smoothing, early stop, iters, best-so-far, the result block and the warm-start carry are as they are.
+ * No workspace offset or size moves: the tile descriptors of iterations with n[it] != n_samples live in ONE device allocation the handle
+ * owns (freed at destroy), and so do the segment flags and the hand-over state when an iteration needs more of them than the base plan.
+ * The setter waits for the stream and drops the captured graph; it allocates before it changes anything, so a refused or failed call
+ * leaves the handle as it was.  Whole plans (graph and eager), the stepwise calls (cem_plan_rollout(h, it) uses iteration it's plan) and
+ * timing handles serve it, with every objective, refit, action noise and carry-over setting.
+ *   CEM_ERR_INVALID_ARG  null handle; count not 0 or `iterations`; an entry < n_elite, > n_samples, or with particles * n[it] not a
+ *                        multiple of ensemble_size
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  world_size > 1 or a communicator (and cem_planner_comm_init on a scheduled handle); batch handles; handles
+ *                        outside the one-workgroup select (the rule of cem_planner_set_refit); an entry <= n_keep while carry-over is on
+ *                        (and cem_planner_set_elite_carry with such an n_keep on a scheduled handle)
+ * The getter always fills all `iterations` entries (n_samples where the schedule is off) and says through *enabled_out whether one is on. */
+int cem_planner_set_population_schedule(cem_planner_t *h, const int32_t *n /* [iterations] or NULL */, int32_t count);
+int cem_planner_get_population_schedule(const cem_planner_t *h, int32_t *n_out /* [iterations] */, int32_t count, int32_t *enabled_out);
+/* What iteration `it` launches, on every handle, scheduled or not.  `launches` counts by the rule of cem_planner_launches_per_iteration,
+ * rollout_path is 1 for the lean kernels and 0 for the generic ones (cem_planner_rollout_path); those two functions keep their meaning
+ * and report iteration 0.  n_segments 1: one workgroup per tile; n_pinned: tiles that stay whole. */
+typedef struct { int32_t n_samples, chunks_per_tile, n_tiles, n_segments, n_pinned, launches, rollout_path, reserved; } cem_iteration_plan_t;
+int cem_planner_iteration_plan(const cem_planner_t *h, int32_t it, cem_iteration_plan_t *out);
+
+/* The mean as a candidate (iCEM): in iteration `iterations - 1` only — a plan that stops early never gets there — one kernel between
+ * the sampler launch and the rollout launch (behind the elite inject where that runs) overwrites the LAST candidate of that iteration,
+ * row n[I - 1] - 1 of `actions` and its words of the padded layout, with min(max(mu[t][a], lb[a]), ub[a]) from the mu the iteration
+ * samples from.  Padding words keep their zeros; no Philox counter moves (the row is drawn, then overwritten).  That iteration samples
+ * in a launch of its own and runs the generic rollout, as an iteration with carry-over does (+ 1 launch for the kernel, + 1 where the
+ * sampler had been folded); the other iterations keep what they had.  Refusals are those of the schedule's setter, plus
+ * CEM_ERR_UNSUPPORTED for n_keep >= n[I - 1] - 1 while carry-over is on (either order of the setters), and CEM_ERR_INVALID_ARG for
+ * enable not 0 / 1. */
+int cem_planner_set_mean_candidate(cem_planner_t *h, int32_t enable);
+int cem_planner_get_mean_candidate(const cem_planner_t *h, int32_t *enable_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

@@ -19,6 +19,10 @@ spectral exponent (CemMpc(noise_beta=B); the word `none` stands for the referenc
 
 --keep_elites F [F ...] adds a grid axis in the same way: every configuration is also evaluated with the best fraction F of its elites
 carried from iteration to iteration (CemMpc(keep_elites=F); the word `none` stands for the reference's resampling of every candidate).
+
+--population_decay F [F ...] adds a grid axis in the same way: every configuration is also evaluated with iteration i sampling about
+n_samples / F**i candidates (CemMpc(population_decay=F); the word `none` stands for the reference's full population in every iteration).
+Such a policy plans one state at a time: not together with --parallel_episodes.
 """
 import argparse
 import json
@@ -37,7 +41,8 @@ PROPOSALS_WITH_ITERATIONS = [(100, 15), (150, 10), (300, 5)]
 ELITE_RATIOS = [0.05, 0.1, 0.2]
 
 
-WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor', 'elite_temperature', 'noise_beta', 'keep_elites', 'shift_elites')
+WARM_KWARGS = ('warm_start', 'warm_shift', 'warm_tail', 'warm_sigma', 'warm_sigma_floor', 'elite_temperature', 'noise_beta', 'keep_elites', 'shift_elites',
+               'population_decay', 'min_population', 'mean_candidate')
 
 
 def make_new_policy(model, environment, horizon, iterations, n_samples, elite_ratio, policy_kwargs):
@@ -67,17 +72,19 @@ def evaluate_lockstep(trainer, environments, eval_steps, eval_episode_length):
 
 def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=HORIZONS,
                 proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS, parallel_envs=None,
-                elite_temperatures=None, noise_betas=None, keep_elites=None):
+                elite_temperatures=None, noise_betas=None, keep_elites=None, population_decays=None):
     """elite_temperatures: None (the reference's grid) or a list of temperatures, None among them for the uniform refit — a fourth axis.
     noise_betas: None or a list of power-law exponents, None among them for white noise — a further axis.
-    keep_elites: None or a list of kept fractions of n_elite, None among them for no carry-over — a further axis."""
+    keep_elites: None or a list of kept fractions of n_elite, None among them for no carry-over — a further axis.
+    population_decays: None or a list of decay factors >= 1, None among them for the full population — a further axis."""
     from ethz_safe_learning_amd.simba.infrastructure.logging_utils import logger
     agent = trainer.agent
     results = []
     for horizon in horizons:
         for n_samples, iterations in proposals_with_iterations:
-            for ratio, temperature, beta, keep in [(r, t, b, f) for r in elite_ratios for t in (elite_temperatures or [None])
-                                                   for b in (noise_betas or [None]) for f in (keep_elites or [None])]:
+            for ratio, temperature, beta, keep, decay in [(r, t, b, f, g) for r in elite_ratios for t in (elite_temperatures or [None])
+                                                          for b in (noise_betas or [None]) for f in (keep_elites or [None])
+                                                          for g in (population_decays or [None])]:
                 kwargs = params['policies']['cem_mpc']
                 if elite_temperatures:
                     kwargs = dict(kwargs, elite_temperature=temperature)
@@ -85,6 +92,8 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
                     kwargs = dict(kwargs, noise_beta=beta)
                 if keep_elites:
                     kwargs = dict(kwargs, keep_elites=keep)
+                if population_decays:
+                    kwargs = dict(kwargs, population_decay=decay)
                 agent.policy = make_new_policy(agent.model, env, horizon, iterations, n_samples, ratio, kwargs)
                 t0 = time.perf_counter()
                 if parallel_envs:
@@ -101,6 +110,8 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
                     rec['noise_beta'] = beta
                 if keep_elites:
                     rec['keep_elites'] = keep
+                if population_decays:
+                    rec['population_decay'] = decay
                 logger.info('H=%d (N,I)=(%d,%d) elite %.2f: score %.3f +- %.3f, cost %.3f +- %.3f', horizon, n_samples, iterations,
                             ratio, rec['score_mean'], rec['score_std'], rec['cost_mean'], rec['cost_std'])
                 results.append(rec)
@@ -130,9 +141,13 @@ def main(argv=None):
                     help="a grid axis of power-law action-noise exponents (CemMpc(noise_beta=B)); 'none' = the reference's white noise")
     ap.add_argument('--keep_elites', type=str, nargs='+', default=None, metavar='F',
                     help="a grid axis of kept elite fractions (CemMpc(keep_elites=F)); 'none' = every candidate resampled, as the reference does")
+    ap.add_argument('--population_decay', type=str, nargs='+', default=None, metavar='F',
+                    help="a grid axis of population decay factors (CemMpc(population_decay=F)); 'none' = n_samples candidates in every iteration")
     args = ap.parse_args(argv)
     if args.parallel_episodes < 1:
         ap.error('--parallel_episodes must be at least 1')
+    if args.population_decay and args.parallel_episodes > 1:
+        ap.error('--population_decay plans one state at a time (CemMpc.generate_actions refuses it): not with --parallel_episodes')
     from ethz_safe_learning_amd.config.config import load_config_or_die
     params = load_config_or_die(args.config_dir, args.config_basename)
     trainer = train_script.main(['--config_dir', args.config_dir, '--config_basename', args.config_basename, '--log_dir', args.log_dir,
@@ -147,6 +162,8 @@ def main(argv=None):
         grid['noise_betas'] = [None if b.lower() == 'none' else float(b) for b in args.noise_beta]
     if args.keep_elites:
         grid['keep_elites'] = [None if f.lower() == 'none' else float(f) for f in args.keep_elites]
+    if args.population_decay:
+        grid['population_decays'] = [None if g.lower() == 'none' else float(g) for g in args.population_decay]
     if args.parallel_episodes > 1:
         grid['parallel_envs'] = make_parallel_environments(params, args.parallel_episodes, args.seed)
     results = grid_search(trainer, trainer.environment, params, args.eval_steps, args.eval_episode_length, **grid)

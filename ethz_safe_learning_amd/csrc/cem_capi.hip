@@ -720,6 +720,7 @@ struct cem_planner {
     bool in_plan;
     bool sample_in_rollout;                  // the sampler runs as the rollout tiles' prologue (else: cem_sample_kernel in front of the rollout launch)
     bool lean_rollout;                       // plans without caller noise tensors run cem_rollout_lean.hip's kernels (lean_eligible)
+    bool lean_branchy;                       // CEM_FORCE_ROLLOUT=lean_branchy at create: never the straight-line form (lean_form)
     const float *eps_act, *eps_model;       // current plan's explicit noise (device) or null
     // pinned host staging
     CtrlBlock *h_ctrl;
@@ -822,6 +823,19 @@ IterView iter_view(const cem_planner *h, int it)
 
 bool samples_in_rollout(const cem_planner *h, int it) { return iter_view(h, it).sample_in_rollout && h->elite.n_keep == 0 && !injects_mean(h, it); }
 bool runs_lean(const cem_planner *h, int it) { return iter_view(h, it).lean_rollout && h->elite.n_keep == 0 && !injects_mean(h, it); }
+
+// Which form of the lean kernels a lean iteration launches: 2, the straight-line form (cem_rollout_lean_straight.hip), where the plan's
+// facts are the ones that form is compiled for — the goal a lidar kind, at most one constrained cost kind, every wave's weight stream
+// exactly the groups one step consumes (layer 0: 4, three hidden layers and, on the waves with an observation block, the heads: 8
+// each); else 1, the branchy form (cem_rollout_lean.hip), which CEM_FORCE_ROLLOUT=lean_branchy at create keeps for every plan.
+// (The objective is that form's template parameter: enqueue_rollout stores cost bytes exactly where it asks for the safe order.)
+int lean_form(const cem_planner *h, int it)
+{
+    const Dims &d = *iter_view(h, it).d; const ScorerDev &sc = h->sc_roll;
+    bool straight = launch_rollout_lean_straight != nullptr && !h->lean_branchy && !sc.goal_mode && sc.n_cost <= 1 && d.L == 4 && d.NFW == 1;
+    for (int w = 0; w < 4; ++w) straight = straight && d.wave_groups[w] == 4 + 3 * CEM_NG + (w < d.KB_obs ? CEM_NG : 0);
+    return straight ? 2 : 1;
+}
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
 size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
 float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
@@ -993,7 +1007,7 @@ static void place_sampler(const cem_planner *h, const Dims &d, const Plan &pl, b
     if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
         *sample_in_rollout = std::strcmp(e, "kernel") != 0;
     *lean_rollout = lean_eligible(h, d, pl.rc, *sample_in_rollout);
-    if (const char *e = std::getenv("CEM_FORCE_ROLLOUT"))      // diagnostic / tests: "generic" or "lean" — the results do not depend on it; "lean" on an ineligible handle is ignored
+    if (const char *e = std::getenv("CEM_FORCE_ROLLOUT"))      // diagnostic / tests: "generic", "lean" or "lean_branchy" (planner_create) — the results do not depend on it; "lean" on an ineligible handle is ignored
         *lean_rollout = *lean_rollout && std::strcmp(e, "generic") != 0;
 }
 
@@ -1017,6 +1031,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     }
     { const Plan pl = make_plan(cfg, h->d, mb); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
       place_sampler(h, h->d, pl, &h->sample_in_rollout, &h->lean_rollout); }
+    { const char *e = std::getenv("CEM_FORCE_ROLLOUT"); h->lean_branchy = e && std::strcmp(e, "lean_branchy") == 0; }
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
@@ -1537,7 +1552,9 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
             rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
             rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
         }
-        HIPCHK(launch_rollout_lean(rp, queued ? v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned) : v.n_tiles, h->stream, queued));
+        const int grid = queued ? v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned) : v.n_tiles;
+        if (lean_form(h, it) == 2 && (rp.variant == 1) == (rp.costs != nullptr)) HIPCHK(launch_rollout_lean_straight(rp, grid, h->stream, queued));
+        else HIPCHK(launch_rollout_lean(rp, grid, h->stream, queued));
     }
     else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, rp.eps_model ? 1 : 0));
     else if (d.split) HIPCHK(launch_rollout_split(v.rc, d.NFW, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
@@ -2581,6 +2598,13 @@ int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out)
 {
     if (!h || !path_out) return CEM_ERR_INVALID_ARG;
     *path_out = (runs_lean(h, 0) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;       // (the lean kernels draw in place and cannot take a tensor)
+    return CEM_OK;
+}
+
+int cem_planner_rollout_form(const cem_planner_t *h, int32_t it, int32_t *form_out)
+{
+    if (!h || !form_out || it < 0 || it >= h->d.I) return CEM_ERR_INVALID_ARG;
+    *form_out = (runs_lean(h, it) && h->noise_kind != CEM_NOISE_MIXED) ? lean_form(h, it) : 0;
     return CEM_OK;
 }
 

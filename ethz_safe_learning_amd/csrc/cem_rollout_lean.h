@@ -14,3 +14,6 @@
 // (floating tile, segment) item).  Weak: a library built from cem_capi.hip alone (the host sanitizer build) has no lean path and says so
 // (cem_planner_rollout_path).
 __attribute__((weak)) hipError_t launch_rollout_lean(const RolloutParams &p, int grid, hipStream_t st, bool seg);
+// The same launch in the straight-line form (cem_rollout_lean_straight.hip; p.variant picks the objective's instantiation): for the plans
+// cem_capi.hip's lean_form gives 2.  Weak for the same reason.
+__attribute__((weak)) hipError_t launch_rollout_lean_straight(const RolloutParams &p, int grid, hipStream_t st, bool seg);

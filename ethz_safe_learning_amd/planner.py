@@ -540,6 +540,12 @@ class CemPlanner:
         _capi.check(self.lib.cem_planner_rollout_path(self.h, C.byref(n)), 'cem_planner_rollout_path')
         return ('generic', 'lean')[n.value]
 
+    def rollout_form(self, it=0):
+        """0 generic | 1 lean, branchy form | 2 lean, straight-line form: what iteration `it` launches (cem_planner_rollout_form)."""
+        n = C.c_int32()
+        _capi.check(self.lib.cem_planner_rollout_form(self.h, int(it), C.byref(n)), 'cem_planner_rollout_form')
+        return n.value
+
     def set_particle_objective(self, kind='mean', m=0):
         """How a candidate's particle returns become its score (cem_planner_set_particle_objective): 'mean' (the reference, the default)
         or 'lower_tail' with m in 1 .. particles, the mean of the m smallest returns.  Sticky; a change re-captures the graph."""

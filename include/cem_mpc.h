@@ -287,6 +287,13 @@ int cem_planner_launches_per_iteration(const cem_planner_t *h, int32_t *launches
  * resident at once.  Same results bit for bit; CEM_FORCE_ROLLOUT=generic at create keeps an eligible handle on the generic kernels.
  * A plan with eps_act / eps_model tensors always runs the generic kernels. */
 int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out);
+/* Which form of them iteration `it` launches: 0 = the generic kernels; 1 = the lean kernels' branchy form (csrc/cem_rollout_lean.hip,
+ * every plan fact tested in the step loop); 2 = their straight-line form (csrc/cem_rollout_lean_straight.hip: the objective a template
+ * parameter, the weight ring's positions constants), which serves the lean plans whose scorer has its goal as a lidar kind and at most
+ * one constrained cost kind.  Same results bit for bit; CEM_FORCE_ROLLOUT=lean_branchy at create keeps an eligible handle on form 1.
+ * cem_planner_rollout_path and cem_iteration_plan_t.rollout_path report 1 for both lean forms.  CEM_ERR_INVALID_ARG: `it` outside
+ * [0, iterations). */
+int cem_planner_rollout_form(const cem_planner_t *h, int32_t it, int32_t *form_out);
 
 /* TransitionModel.unfold_sequences (transition_model.py:64-77) as an API of its own:
  * s0[B][obs], actions[B][H][A] (device) -> traj[B][H+1][obs] (device); optional mu/stddev[B][H][obs].

@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     'cem_packed_weight_floats', 'cem_workspace_bytes', 'cem_pack_weights_host', 'cem_plan_tiles_host', 'cem_plan_segments_host', 'cem_rollout_residency',
     'cem_planner_create', 'cem_planner_destroy', 'cem_planner_layout', 'cem_planner_set_weights', 'cem_planner_set_weights_dev',
     'cem_planner_set_normaliser', 'cem_planner_plan', 'cem_plan_begin', 'cem_plan_rollout', 'cem_plan_select',
-    'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_launches_per_iteration', 'cem_planner_rollout_path', 'cem_planner_rollout_form', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
+    'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_graph_nodes', 'cem_planner_launches_per_iteration', 'cem_planner_rollout_path', 'cem_planner_rollout_form', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
     'cem_batch_workspace_bytes', 'cem_batch_planner_create', 'cem_planner_plan_batch', 'cem_planner_batch_capacity',
     'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
     'cem_planner_get_carry', 'cem_planner_set_carry_slots', 'cem_planner_set_particle_objective', 'cem_planner_get_particle_objective',
@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_elite_carry', 'cem_planner_get_elite_carry', 'cem_planner_elite_store',
     'cem_planner_set_population_schedule', 'cem_planner_get_population_schedule', 'cem_planner_iteration_plan',
     'cem_planner_set_mean_candidate', 'cem_planner_get_mean_candidate',
+    'cem_planner_set_plan_readout', 'cem_planner_get_plan_readout', 'cem_planner_plan_readout',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -91,6 +92,10 @@ class CemEliteCarry(C.Structure):
 
 class CemIterationPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('n_samples', 'chunks_per_tile', 'n_tiles', 'n_segments', 'n_pinned', 'launches', 'rollout_path', 'reserved')]
+
+
+class CemPlanReadout(C.Structure):
+    _fields_ = [('score', C.c_float), ('candidate', C.c_int32), ('iteration', C.c_int32), ('flags', C.c_int32)]
 
 
 class CemLayout(C.Structure):
@@ -154,6 +159,7 @@ def load():
     lib.cem_planner_comm_destroy.argtypes = [vp]
     lib.cem_plan_exchange.argtypes = [vp]
     lib.cem_planner_graph_status.argtypes = [vp, i32p]
+    lib.cem_planner_graph_nodes.argtypes = [vp, i32p]
     lib.cem_planner_comm_ranks.argtypes = [vp, i32p]
     lib.cem_planner_launches_per_iteration.argtypes = [vp, i32p]
     lib.cem_planner_rollout_path.argtypes = [vp, i32p]
@@ -199,6 +205,9 @@ def load():
     lib.cem_planner_iteration_plan.argtypes = [vp, C.c_int32, C.POINTER(CemIterationPlan)]
     lib.cem_planner_set_mean_candidate.argtypes = [vp, C.c_int32]
     lib.cem_planner_get_mean_candidate.argtypes = [vp, i32p]
+    lib.cem_planner_set_plan_readout.argtypes = [vp, C.c_int32]
+    lib.cem_planner_get_plan_readout.argtypes = [vp, i32p]
+    lib.cem_planner_plan_readout.argtypes = [vp, C.c_int32, C.POINTER(CemPlanReadout), vp, vp, vp]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

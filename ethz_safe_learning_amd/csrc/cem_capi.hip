@@ -6,6 +6,7 @@
 #include "cem_refit_weighted.h"
 #include "cem_noise_mix.h"
 #include "cem_elite_carry.h"
+#include "cem_plan_readout.h"
 #include "cem_population.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
@@ -792,6 +793,10 @@ struct cem_planner {
     uint32_t *pop_seg_flags; f4 *pop_seg_state;   // where a scheduled plan's floating tiles keep those two: the workspace's, or inside pop_dev
     int pop_n_ready;                         // FIFO entries the plan's first kernel clears: the most any iteration uses
     int mean_cand;                           // 1: the last iteration's last candidate is the clipped mean
+    // cem_planner_set_plan_readout (cem_plan_readout.h)
+    int readout;                             // 1: cem_plan_track_kernel follows every select
+    uint32_t *readout_dev;                   // a device allocation of the handle's own, made by the first enabling call: [slots] blocks of
+                                             // CEM_READOUT_WORDS(H, A, P) words (the population never enters the size)
 };
 
 namespace {
@@ -879,6 +884,7 @@ void release_handle(cem_planner *h)
     if (h->refit_dev) hipFree(h->refit_dev);
     if (h->noise_dev) hipFree(h->noise_dev);
     if (h->elite_dev) hipFree(h->elite_dev);
+    if (h->readout_dev) hipFree(h->readout_dev);
     if (h->pop_dev) hipFree(h->pop_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
@@ -1039,6 +1045,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->refit_kind = CEM_REFIT_UNIFORM; h->refit_tau = 0.f; h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
     h->noise_kind = CEM_NOISE_WHITE; h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
     h->elite = cem_elite_carry_t{}; h->elite.shift = 1; h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
+    h->readout = 0; h->readout_dev = nullptr;
     h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0; h->mean_cand = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
@@ -1590,12 +1597,12 @@ bool folds_reduce(const cem_planner *h, int it = 0)
 }
 
 // launches of iteration `it` (cem_planner_launches_per_iteration's rule): the rollout, the sampler where it is a launch of its own, the score
-// kernel unless the select folds it, the select's, the weighted refit, carry-over's inject and keep, the mean candidate
+// kernel unless the select folds it, the select's, the weighted refit, carry-over's inject and keep, the mean candidate, the read-out's tracker
 int launches_of(const cem_planner *h, int it)
 {
     const int mode = select_mode_for(h, iter_view(h, it).d->N);
     return 1 + (samples_in_rollout(h, it) ? 0 : 1) + (folds_reduce(h, it) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
-           (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0) + (h->elite.n_keep ? 2 : 0) + (injects_mean(h, it) ? 1 : 0);
+           (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0) + (h->elite.n_keep ? 2 : 0) + (injects_mean(h, it) ? 1 : 0) + (h->readout ? 1 : 0);
 }
 
 // fold_final: the select writes the plan's result itself (whole plans only: eps_out is known before the loop) — returns through
@@ -1635,6 +1642,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     if (weighted) { p.musig = h->refit_dev; p.threshold = -std::numeric_limits<float>::infinity(); }
     if (h->elite.n_keep && (mode != 1 || !h->elite_dev)) return CEM_ERR_UNSUPPORTED;   // (cem_planner_set_elite_carry admitted one-workgroup handles only)
     if (!h->pop.empty() && mode != 1) return CEM_ERR_UNSUPPORTED;                      // (cem_planner_set_population_schedule likewise)
+    if (h->readout && (mode != 1 || !h->readout_dev)) return CEM_ERR_UNSUPPORTED;      // (cem_planner_set_plan_readout likewise)
     TimedLaunch timed(h, 1);
     if (mode >= 2) {
         MSelParams m{}; m.scores = p.scores; m.actions = p.actions; m.musig = p.musig; m.ctrl = p.ctrl; m.elite_idx = p.elite_idx;
@@ -1690,6 +1698,17 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
             HIPCHK(hipGetLastError());
             const EliteCarryParams ep = fill_elite(h, it);
             HIPCHK(launch_elite_keep(ep, warm_slots(h), h->stream));
+        }
+        // the plan read-out: the best-so-far candidate's sequence, returns and cost counts leave the workspace before the next rollout
+        // overwrites them (cem_plan_readout.h).  Last: every launch above stays where it was; device-side state only (the control
+        // block in the workspace, never the pinned staging the next plan call writes while this launch may still be running)
+        if (h->readout) {
+            HIPCHK(hipGetLastError());
+            PlanTrackParams tp{}; tp.scores = p.scores; tp.actions = p.actions; tp.ret = (const float *)(ws + l.returns);
+            tp.costs = h->cfg.variant != CEM_VARIANT_CEM ? (const uint8_t *)(ws + l.costs) : nullptr;
+            tp.ctrl = p.ctrl; tp.elite_idx = p.elite_idx; tp.block = h->readout_dev;
+            tp.N = d.N; tp.k = d.k; tp.H = d.H; tp.A = d.A; tp.P = d.P; tp.it = it; tp.stride = (int32_t)CEM_READOUT_WORDS(h->d.H, h->d.A, h->d.P);
+            HIPCHK(launch_plan_track(tp, warm_slots(h), h->stream));
         }
     }
     HIPCHK(hipGetLastError());
@@ -2340,6 +2359,67 @@ int cem_planner_set_elite_carry(cem_planner_t *h, const cem_elite_carry_t *ec)
     return CEM_OK;
 }
 
+int cem_planner_set_plan_readout(cem_planner_t *h, int32_t enable)
+{
+    if (!h || (enable != 0 && enable != 1)) return CEM_ERR_INVALID_ARG;
+    if (h->in_plan) return CEM_ERR_STATE;
+    const Dims &d = h->d;
+    if (enable) {
+        // the tracker reads ONE rank's select and the whole of a candidate's column of `ret`, which a sharded plan splits among the ranks
+        if (d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
+        if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;               // the multi-workgroup selects: the rule cem_planner_set_refit applies
+        if (d.P > CEM_READOUT_MAX_P || !launch_plan_track) return CEM_ERR_UNSUPPORTED;
+        for (const IterPlan &ip : h->pop) if (select_mode_for(h, ip.d.N) != 1) return CEM_ERR_UNSUPPORTED;
+    }
+    // the blocks are allocated before anything of the handle changes: a failed allocation leaves it as it was
+    uint32_t *made = nullptr;
+    const size_t words = (size_t)warm_slots(h) * CEM_READOUT_WORDS(d.H, d.A, d.P);
+    if (enable && !h->readout_dev) HIPCHK(hipMalloc((void **)&made, words * 4));
+    // Unconditional, as in cem_planner_set_elite_carry: an eager plan still draining behind its polled result may be writing the blocks
+    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) { g_last_hip = (int)e; if (made) hipFree(made); return CEM_ERR_HIP; }
+    if (made) {
+        // every block starts as the tracker's reset leaves it: a read-out asked for before any plan says "nothing found"
+        const size_t stride = CEM_READOUT_WORDS(d.H, d.A, d.P);
+        std::vector<uint32_t> init(words, 0u);
+        for (int b = 0; b < warm_slots(h); ++b) {
+            uint32_t *blk = init.data() + (size_t)b * stride;
+            blk[0] = 0xff800000u; blk[1] = 0xffffffffu; blk[2] = 0xffffffffu;
+            if (h->cfg.variant == CEM_VARIANT_CEM) for (int t = 0; t < d.H; ++t) blk[stride - d.H + t] = 0xffffffffu;
+        }
+        if (const hipError_t e = hipMemcpy(made, init.data(), words * 4, hipMemcpyHostToDevice); e != hipSuccess) { g_last_hip = (int)e; hipFree(made); return CEM_ERR_HIP; }
+        h->readout_dev = made;
+    }
+    drop_graph(h);                                                              // the captured plan holds the other setting's launches
+    h->readout = enable;
+    return CEM_OK;
+}
+
+int cem_planner_get_plan_readout(const cem_planner_t *h, int32_t *enable_out)
+{
+    if (!h || !enable_out) return CEM_ERR_INVALID_ARG;
+    *enable_out = h->readout;
+    return CEM_OK;
+}
+
+int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout_t *out, float *sequence_out_host,
+                             float *particle_returns_out_host, int32_t *cost_counts_out_host)
+{
+    if (!h || !out || problem < 0 || problem >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
+    if (!h->readout || !h->readout_dev) return CEM_ERR_STATE;
+    // the last iteration's tracker runs BEHIND the select that hands the polled result to the host: the stream is drained first
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const Dims &d = h->d;
+    const size_t HA = (size_t)d.H * d.A;
+    const uint32_t *blk = h->readout_dev + (size_t)problem * CEM_READOUT_WORDS(d.H, d.A, d.P);
+    uint32_t head[CEM_READOUT_HEAD];
+    HIPCHK(hipMemcpy(head, blk, sizeof head, hipMemcpyDeviceToHost));
+    std::memcpy(&out->score, &head[0], 4); out->candidate = (int32_t)head[1]; out->iteration = (int32_t)head[2]; out->flags = (int32_t)head[3];
+    if (sequence_out_host) HIPCHK(hipMemcpy(sequence_out_host, blk + CEM_READOUT_HEAD, HA * 4, hipMemcpyDeviceToHost));
+    if (particle_returns_out_host) HIPCHK(hipMemcpy(particle_returns_out_host, blk + CEM_READOUT_HEAD + HA, (size_t)d.P * 4, hipMemcpyDeviceToHost));
+    if (cost_counts_out_host) HIPCHK(hipMemcpy(cost_counts_out_host, blk + CEM_READOUT_HEAD + HA + d.P, (size_t)d.H * 4, hipMemcpyDeviceToHost));
+    return CEM_OK;
+}
+
 int cem_planner_get_elite_carry(const cem_planner_t *h, cem_elite_carry_t *out)
 {
     if (!h || !out) return CEM_ERR_INVALID_ARG;
@@ -2551,6 +2631,7 @@ int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int
     if (h->noise_kind == CEM_NOISE_MIXED) return CEM_ERR_UNSUPPORTED;          // (cem_planner_set_action_noise refuses a communicator; so the reverse)
     if (h->elite.n_keep) return CEM_ERR_UNSUPPORTED;                           // (cem_planner_set_elite_carry likewise)
     if (!h->pop.empty() || h->mean_cand) return CEM_ERR_UNSUPPORTED;           // (cem_planner_set_population_schedule / _mean_candidate likewise)
+    if (h->readout) return CEM_ERR_UNSUPPORTED;                                // (cem_planner_set_plan_readout likewise)
     Rccl *r = rccl(); if (!r) return CEM_ERR_COMM;
     if (h->comm) { r->CommDestroy(h->comm); h->comm = nullptr; }
     CemNcclId nid; std::memcpy(nid.internal, id, CEM_COMM_ID_BYTES);
@@ -2591,6 +2672,15 @@ int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out)
 {
     if (!h || !status_out) return CEM_ERR_INVALID_ARG;
     *status_out = h->graph_ready ? 1 : (h->graph_failed ? 2 : 0);
+    return CEM_OK;
+}
+
+int cem_planner_graph_nodes(const cem_planner_t *h, int32_t *nodes_out)
+{
+    if (!h || !nodes_out) return CEM_ERR_INVALID_ARG;
+    size_t n = 0;
+    if (h->graph_ready && h->graph) HIPCHK(hipGraphGetNodes(h->graph, nullptr, &n));
+    *nodes_out = (int32_t)n;
     return CEM_OK;
 }
 

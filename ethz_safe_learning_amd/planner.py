@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -76,6 +76,9 @@ class PlannerConfig:
                                        # `it` samples population[it] (population_schedule; cem_planner_set_population_schedule); not in
                                        # cem_config_t: set after create
     mean_candidate: bool = False       # True: the last candidate of the last iteration is the clipped mean (cem_planner_set_mean_candidate)
+    plan_readout: bool = False         # True: a tracker kernel behind every select keeps the best-so-far candidate's whole sequence, its particle
+                                       # returns and per-step cost counts (cem_planner_set_plan_readout; CemPlanner.plan_readout); not in
+                                       # cem_config_t: set after create
     action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
@@ -358,6 +361,12 @@ class CemPlanner:
             except Exception:
                 self.close()
                 raise
+        if cfg.plan_readout:
+            try:
+                self.set_plan_readout(True)
+            except Exception:
+                self.close()
+                raise
         self.have_device_weights = False              # the last weight sync came from device memory (set_weights_dev / set_weights_from)
         # the generate_action hot path: staging buffers and their ctypes views are made once (a.ctypes.data_as and the two small
         # numpy allocations were 12 of the 17 us the wrapper added to a 1.9-ms plan)
@@ -527,6 +536,12 @@ class CemPlanner:
         st = C.c_int32()
         _capi.check(self.lib.cem_planner_graph_status(self.h, C.byref(st)), 'cem_planner_graph_status')
         return ('eager', 'graph', 'graph-unsupported')[st.value]
+
+    def graph_nodes(self):
+        """Nodes of the captured plan as the runtime counts them (cem_planner_graph_nodes); 0 while no graph is held."""
+        n = C.c_int32()
+        _capi.check(self.lib.cem_planner_graph_nodes(self.h, C.byref(n)), 'cem_planner_graph_nodes')
+        return n.value
 
     def launches_per_iteration(self):
         """Kernel launches one CEM iteration of plan() takes on this handle (cem_planner_launches_per_iteration)."""
@@ -710,6 +725,29 @@ class CemPlanner:
         on = C.c_int32()
         _capi.check(self.lib.cem_planner_get_mean_candidate(self.h, C.byref(on)), 'cem_planner_get_mean_candidate')
         return bool(on.value)
+
+    def set_plan_readout(self, on=True):
+        """The plan read-out (cem_planner_set_plan_readout): a tracker kernel behind every select keeps the best-so-far candidate's whole
+        action sequence, its per-particle returns and per-step cost counts (plan_readout reads them; track_best restates the kernel).
+        Sticky; waits for the stream and re-captures the graph.  Sampler, rollout, select and refit launch as before."""
+        _capi.check(self.lib.cem_planner_set_plan_readout(self.h, 1 if on else 0), 'cem_planner_set_plan_readout')
+
+    def plan_readout_enabled(self):
+        on = C.c_int32()
+        _capi.check(self.lib.cem_planner_get_plan_readout(self.h, C.byref(on)), 'cem_planner_get_plan_readout')
+        return bool(on.value)
+
+    def plan_readout(self, problem=0) -> 'PlanReadout':
+        """The read-out block of `problem` (cem_planner_plan_readout) as a PlanReadout.  Waits for the planner's stream: plan() returns
+        as soon as action, score and iterations are on the host, and the last iteration's tracker runs behind that."""
+        c = self.cfg
+        seq = np.zeros((c.horizon, c.act_dim), np.float32)
+        pret = np.zeros(c.particles, np.float32)
+        cnt = np.zeros(c.horizon, np.int32)
+        head = _capi.CemPlanReadout()
+        _capi.check(self.lib.cem_planner_plan_readout(self.h, int(problem), C.byref(head), _np_ptr(seq), _np_ptr(pret), _np_ptr(cnt)),
+                    'cem_planner_plan_readout')
+        return PlanReadout(seq, np.float32(head.score), int(head.candidate), int(head.iteration), pret, cnt, int(head.flags))
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')
@@ -916,6 +954,14 @@ class CemPlanner:
         self._wait_inputs()
         _capi.check(self.lib.cem_fill_noise(self.h, seed, call, _ptr(ea), _ptr(em), _ptr(eo)), 'cem_fill_noise')
         return ea, em, eo
+
+    def output_noise(self, seed=0, call=0) -> np.ndarray:
+        """eps_out [A] of a (seed, call) plan alone (cem_fill_noise with no other tensor): the standard normals a plan's result adds,
+        scaled by noise_stddev, to the first action of its best sequence."""
+        eo = self._torch.empty((self.cfg.act_dim,), dtype=self._torch.float32, device=self.device)
+        self._wait_inputs()
+        _capi.check(self.lib.cem_fill_noise(self.h, seed, call, None, None, _ptr(eo)), 'cem_fill_noise')
+        return eo.cpu().numpy()
 
     def philox_words(self, seed, call, stream, iteration, t, sub, idx0, n):
         """The generator's raw Philox4x32-7 output words for n consecutive counters (test hook, cem_mpc.h): uint32 [n, 4]."""
@@ -1171,6 +1217,60 @@ def mean_candidate(actions, mu, lb, ub) -> np.ndarray:
     m = np.asarray(mu, np.float32).reshape(out.shape[1:])
     out[-1] = np.minimum(np.maximum(m, np.asarray(lb, np.float32)), np.asarray(ub, np.float32))
     return out
+
+
+class PlanReadout(NamedTuple):
+    """What a plan knew about the sequence it chose (cem_planner_plan_readout): sequence [H, A] fp32, the best-so-far candidate's whole
+    action sequence; score, its score; candidate / iteration, where it was found (-1 / -1: nothing was); particle_returns [P] fp32;
+    cost_counts [H] int32, particles with a non-zero cost byte per step (-1: the handle stores no cost bytes); flags (0)."""
+    sequence: np.ndarray
+    score: np.float32
+    candidate: int
+    iteration: int
+    particle_returns: np.ndarray
+    cost_counts: np.ndarray
+    flags: int
+
+
+def empty_readout(horizon, act_dim, particles, has_costs) -> PlanReadout:
+    """The block as the tracker's reset leaves it: nothing found."""
+    return PlanReadout(np.zeros((int(horizon), int(act_dim)), np.float32), np.float32(-np.inf), -1, -1, np.zeros(int(particles), np.float32),
+                       np.full(int(horizon), 0 if has_costs else -1, np.int32), 0)
+
+
+def track_best(block, it, iters, best_score, scores, elite_idx, actions, ret, costs, n=None) -> PlanReadout:
+    """Host restatement of ONE launch of cem_plan_track_kernel (cem_mpc.h, cem_planner_set_plan_readout) — comparisons, copies and integer
+    counts, so it is exact.  block: the PlanReadout before the launch; it: the launch's iteration; iters, best_score: ctrl.iters and
+    ctrl.best_score as the select in front left them; scores [>= n] as that select ranked them, elite_idx [k] as it stored them;
+    actions [>= n, H, A]; ret [P, n] (or flat, P n: the leading part of the workspace array); costs [H, P, n] bytes (or flat), or None on
+    handles whose rollout stores none; n: the iteration's population (default: len(scores)).  Returns the block after the launch."""
+    it = int(it)
+    sc = np.ascontiguousarray(np.asarray(scores, np.float32).reshape(-1))
+    n = sc.size if n is None else int(n)
+    H, A = block.sequence.shape
+    P = block.particle_returns.size
+    if it == 0:
+        block = empty_readout(H, A, P, costs is not None)
+    if int(iters) != it + 1:
+        return block
+    bs = np.float32(best_score)
+    # one fp32 comparison, strict; neither operand is a NaN (keys as the selects rank them: the two zeros tie)
+    if not int(score_keys(bs.reshape(1))[0]) > int(score_keys(np.float32(block.score).reshape(1))[0]):
+        return block
+    e = np.asarray(elite_idx, np.int64).reshape(-1)
+    e = np.where((e >= 0) & (e < n), e, 0)                   # (held to the population, as the kernel holds them)
+    hit = e[score_keys(sc[e]) == score_keys(bs.reshape(1))[0]]
+    if hit.size == 0:
+        return block._replace(flags=block.flags | 1)
+    c = int(hit.min())
+    act = np.asarray(actions, np.float32)
+    r = np.asarray(ret, np.float32).reshape(-1)[:P * n].reshape(P, n)
+    if costs is None:
+        cnt = np.full(H, -1, np.int32)
+    else:
+        cb = np.asarray(costs, np.uint8).reshape(-1)[:H * P * n].reshape(H, P, n)
+        cnt = (cb[:, :, c] != 0).sum(axis=1).astype(np.int32)
+    return PlanReadout(np.array(act[c], np.float32, copy=True).reshape(H, A), bs, c, it, np.array(r[:, c], np.float32, copy=True), cnt, block.flags)
 
 
 def plan_tiles(cfg: PlannerConfig):

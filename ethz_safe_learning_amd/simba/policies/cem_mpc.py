@@ -57,6 +57,22 @@ cem_planner_set_population_schedule): the one iCEM ingredient th
 candidate of the last iteration is the clipped mean itself (``PlannerConfig.mean_candidate``).  ``generate_action`` and warm-started
 plans use both; ``generate_actions`` is refused with a ``ValueError`` — a batch handle launches the tiles of ONE plan for all its rows.
 ``None`` / ``False`` (the defaults, and what every shipped preset has) touch no handle and change no bit.  Nothing is claimed about the
+returns or the safety of an agent that uses them.
+
+Plan read-out and open-loop steps (beyond the reference, off by default): with ``plan_readout=True`` a tracker kernel behind every
+select keeps what the plan knew about its choice (``PlannerConfig.plan_readout``, cem_mpc.h cem_planner_set_plan_readout; DESIGN.md
+4.14) and ``last_plan`` holds it after every ``generate_action`` as a ``planner.PlanReadout``: the whole best action sequence
+``sequence [H, A]``, its ``score``, the ``candidate`` and ``iteration`` that found it, the candidate's ``particle_returns [P]`` and, on
+the safe variant, ``cost_counts [H]`` — how many of the P particles predicted a cost at each step of the plan.  After
+``generate_actions`` ``last_plans`` holds one per row.  ``generate_action_sequence(state)`` plans and returns ``last_plan.sequence``.
+Sampler, rollout, select and refit launch as before (the lean rollout stays); every read of the block waits for the planner's stream.
+With ``replan_every=r``, 1 <= r <= horizon (which implies ``plan_readout``), ``generate_action`` plans at decisions 0, r, 2r, ... of an
+episode and in between returns step j of the kept sequence, plus ``noise_stddev`` times the output noise of that decision's own Philox
+call number (no draw, and an exact copy, when ``noise_stddev`` is 0): every decision consumes one call number, ``last_score`` /
+``last_iterations`` / ``last_plan`` stay those of the plan in force, ``reset()`` discards the kept sequence so that the next decision
+plans.  With ``warm_start`` or ``shift_elites`` the carried distribution and elites move ``warm_shift`` steps per plan, so ``warm_shift``
+must equal ``replan_every``; ``generate_actions`` is refused with ``replan_every > 1`` (no per-row sequences on batch handles).
+``False`` / 1 (the defaults, and what every shipped preset has) touch no handle and change no bit.  Nothing is claimed about the
 returns or the safety of an agent that uses them."""
 import logging
 import numpy as np
@@ -72,7 +88,7 @@ class CemMpc(MpcPolicy):
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
                  warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None,
                  elite_temperature=None, noise_beta=None, noise_rho=None, keep_elites=None, shift_elites=False,
-                 population_decay=None, min_population=None, mean_candidate=False):
+                 population_decay=None, min_population=None, mean_candidate=False, plan_readout=False, replan_every=1):
         super().__init__(model, environment, horizon, n_samples, particles)
         self.iterations = iterations
         self.smoothing = smoothing
@@ -115,6 +131,18 @@ class CemMpc(MpcPolicy):
         if self.population_decay is not None and not (np.isfinite(self.population_decay) and self.population_decay >= 1.0):
             raise ValueError('population_decay must be finite and >= 1, got %r' % (population_decay,))
         self.mean_candidate = bool(mean_candidate)
+        # plan read-out and open-loop steps (beyond the reference's kwargs): see the module docstring
+        self.replan_every = int(replan_every)
+        if self.replan_every != replan_every or not 1 <= self.replan_every <= int(horizon):
+            raise ValueError('replan_every must be an integer in [1, horizon = %d], got %r' % (int(horizon), replan_every))
+        if self.replan_every > 1 and (self.warm_start or self.shift_elites) and int(warm_shift) != self.replan_every:
+            raise ValueError('replan_every = %d executes %d steps between two plans, but warm_start / shift_elites move the carried distribution '
+                             'and elites warm_shift = %r steps: the two must be equal' % (self.replan_every, self.replan_every, warm_shift))
+        self.plan_readout = bool(plan_readout) or self.replan_every > 1
+        self.last_plan = None                          # planner.PlanReadout of the plan in force (plan_readout)
+        self.last_plans = None                         # ... one per row of the last generate_actions
+        self._kept = None                              # replan_every: the sequence being executed open loop,
+        self._kept_step = 0                            # and the step of it the next decision returns
         self.last_ess = None                           # ESS per iteration of the last weighted plan (generate_actions: a list, one array per row)
         self._warm_token = object()                    # marks the handles this policy has configured (ids are reused after garbage collection)
         self._warm_cap = 1                             # slots the warm-started batch handle must hold
@@ -159,6 +187,9 @@ class CemMpc(MpcPolicy):
             out['mean_candidate'] = True
         return out
 
+    def _readout_config(self):
+        return dict(plan_readout=True) if self.plan_readout else {}
+
     def _scorer_config(self):
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
         if scorer is None:
@@ -177,7 +208,8 @@ class CemMpc(MpcPolicy):
             smoothing=self.smoothing, stddev_threshold=self.stddev_threshold, noise_stddev=self.noise_stddev,
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
             use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._refit_config(),
-            **self._noise_config(), **self._carry_config(), **self._population_config(), **self._extra_config())
+            **self._noise_config(), **self._carry_config(), **self._population_config(), **self._readout_config(),
+            **self._extra_config())
 
     def _owns_handles(self):
         """Whether this policy's planning handles carry state of its own (the warm-start carry, the elites kept across plans; SafeCemMpc:
@@ -211,7 +243,8 @@ class CemMpc(MpcPolicy):
 
     def reset(self):
         """An episode begins: the next plan of every slot starts cold and takes no elites of an earlier plan (no effect without warm
-        start or shift_elites)."""
+        start or shift_elites), and the sequence kept for replan_every is discarded."""
+        self._kept, self._kept_step = None, 0          # replan_every: the next decision plans
         if not (self.warm_start or self.shift_elites):
             return
         for pl in [self._planner] + list(self._batch_planners.values()):
@@ -240,11 +273,42 @@ class CemMpc(MpcPolicy):
     # ---- the plugin boundary ------------------------------------------------------------------------------------
     def generate_action(self, state):
         self.build()                                   # cached handle + weights of the current model version
+        if self._kept is not None:                     # replan_every: a decision between two plans
+            return self._follow(self._next_calls([self.slot])[0] if self.warm_start else int(self._planner.take_calls()[0]))
         action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed,
                                                   call=self._next_calls([self.slot])[0] if self.warm_start else None)
         self.last_score, self.last_iterations = score, iters
         self._note_ess(self._planner, iters)
+        self._note_plan(self._planner)
         return action
+
+    def _note_plan(self, planner):
+        """last_plan from the handle whose action is being returned (its stream is drained: the last tracker runs behind the polled
+        result), and with replan_every the sequence the next decisions follow."""
+        if not self.plan_readout:
+            return
+        self.last_plan = planner.plan_readout(0)
+        if self.replan_every > 1:
+            self._kept, self._kept_step = self.last_plan.sequence, 1
+
+    def _follow(self, call):
+        """Step _kept_step of the kept sequence as the decision numbered `call`: plus that call's output noise where the policy adds any."""
+        action = np.array(self._kept[self._kept_step], np.float32, copy=True)
+        if self.noise_stddev != 0:
+            action = action + self._planner.output_noise(self.seed, call) * np.float32(self.noise_stddev)
+        self._kept_step += 1
+        if self._kept_step >= self.replan_every:
+            self._kept, self._kept_step = None, 0
+        return action
+
+    def generate_action_sequence(self, state):
+        """Plan for `state` and return the whole best action sequence, np.float32 [H, A] (last_plan.sequence): sequence[0] is the
+        planned action before the output noise.  Needs plan_readout=True."""
+        if not self.plan_readout:
+            raise ValueError('generate_action_sequence needs plan_readout=True (or replan_every > 1)')
+        self._kept, self._kept_step = None, 0          # (a plan, whatever was being followed)
+        self.generate_action(state)
+        return self.last_plan.sequence
 
     def _note_ess(self, planner, iters):
         """last_ess from the handle that has just planned (iters: an int, or one per row of a batched plan)."""
@@ -275,6 +339,9 @@ class CemMpc(MpcPolicy):
         if self.shift_elites:
             raise ValueError('shift_elites=True carries elites across the plans of ONE environment; generate_actions plans on a batch handle, '
                              'whose rows move between slots: use generate_action, or keep_elites alone')
+        if self.replan_every > 1:
+            raise ValueError('replan_every = %d keeps ONE sequence between plans; generate_actions plans on a batch handle, for whose rows '
+                             'no sequences are kept: use generate_action, or replan_every = 1' % self.replan_every)
         if self.population_decay is not None or self.mean_candidate:
             raise ValueError('population_decay / mean_candidate give every iteration of ONE plan its own launches; generate_actions plans on a '
                              'batch handle, which launches the tiles of one plan for all its rows and serves neither: use generate_action')
@@ -297,6 +364,8 @@ class CemMpc(MpcPolicy):
         actions, scores, iters = pl.plan_batch(st, seed=self.seed, **warm)
         self.last_scores, self.last_iterations, self.last_calls = scores, iters, warm['calls']
         self._note_ess(pl, iters)
+        if self.plan_readout:
+            self.last_plans = [pl.plan_readout(b) for b in range(st.shape[0])]
         return actions
 
     def do_generate_action(self, state, eps_act=None, eps_model=None, eps_out=None):

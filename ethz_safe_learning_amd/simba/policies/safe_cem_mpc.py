@@ -46,7 +46,14 @@ and the recovery plans of ``recover_below`` carry them from iteration to iterati
 their plans follow no earlier cost plan.
 
 ``population_decay`` / ``min_population`` / ``mean_candidate`` (CemMpc's, off by default): the reward plans, ``optimize_for_safety`` and the
-recovery plans of ``recover_below`` all follow the policy's setting; ``generate_actions`` is refused as CemMpc's is."""
+recovery plans of ``recover_below`` all follow the policy's setting; ``generate_actions`` is refused as CemMpc's is.
+
+``plan_readout`` / ``replan_every`` (CemMpc's, off by default): the cost handle gets the read-out too, and when ``recover_below`` replaces
+a plan by ``optimize_for_safety`` — in ``generate_action`` and for the replaced rows of ``generate_actions`` — ``last_plan`` /
+``last_plans`` and the sequence kept for ``replan_every`` are those of the plan whose action is returned, the cost plan's.  On the cost
+handle ``score`` is minus the mean un-masked cumulative cost and ``cost_counts`` count the non-zero ones among the cost bytes that
+score sums (cem_score.h, cem_constraint_reduce_kernel); ``particle_returns`` hold what the rollout leaves in ``ret`` there — the done-masked
+returns of the safe objective's launch, which the cost objective never reads: they describe the candidate, not its score."""
 import dataclasses
 
 import numpy as np
@@ -192,7 +199,7 @@ class SafeCemMpc(CemMpc):
 
     # ---- opt-in recovery ------------------------------------------------------------------------------------------
     def generate_action(self, state):
-        if self.recover_below is None:
+        if self.recover_below is None or self._kept is not None:      # (a decision between two plans follows the plan in force, whichever it was)
             action = super().generate_action(state)
             self._note_feasibility(self.last_score)
             return action
@@ -204,7 +211,10 @@ class SafeCemMpc(CemMpc):
         self._note_ess(self._planner, iters)
         self._note_feasibility(score)
         self.last_recovered = bool(score < self.recover_below)
-        return self.optimize_for_safety(state, call=call) if self.last_recovered else action
+        if self.last_recovered:
+            action = self.optimize_for_safety(state, call=call)
+        self._note_plan(self._cost_planner if self.last_recovered else self._planner)
+        return action
 
     def generate_actions(self, states, slots=None, reset=None):
         if self.cost_budget is not None and np.ndim(self.cost_budget) and self.cost_budget.size != np.shape(states)[0]:
@@ -217,6 +227,9 @@ class SafeCemMpc(CemMpc):
         rows = np.nonzero(self.last_recovered)[0]
         if rows.size:                                   # the rows below the threshold, together, with the call numbers of the plans they replace
             st = np.asarray(states, np.float32)
-            actions[rows], _, _ = self.build_cost_batch(rows.size).plan_batch(st[rows], seed=self.seed,
-                                                                              calls=np.asarray(self.last_calls, np.uint64)[rows])
+            cpl = self.build_cost_batch(rows.size)
+            actions[rows], _, _ = cpl.plan_batch(st[rows], seed=self.seed, calls=np.asarray(self.last_calls, np.uint64)[rows])
+            if self.plan_readout:
+                for j, b in enumerate(rows):
+                    self.last_plans[int(b)] = cpl.plan_readout(j)
         return actions

@@ -274,6 +274,9 @@ int cem_planner_inject_fault(cem_planner_t *h, int32_t kind);
 /* 0: cem_planner_plan launches kernel by kernel; 1: it replays a captured hipGraph; 2: capturing was tried and is not supported
  * with this communicator / runtime (the plan then stays kernel by kernel — same results) */
 int cem_planner_graph_status(const cem_planner_t *h, int32_t *status_out);
+/* Nodes of the captured plan as the runtime counts them (hipGraphGetNodes); 0 while no graph is held (graph_status 0 / 2, or a setter
+ * dropped it and no plan has captured anew). */
+int cem_planner_graph_nodes(const cem_planner_t *h, int32_t *nodes_out);
 /* Kernel launches one CEM iteration of cem_planner_plan takes on this handle (the collective of a sharded plan not counted):
  * 2 = rollout (its tiles sample their own action sequences, cem_mpc.py:44-48) + select (which forms the particle mean of the CemMpc
  * objective itself, mpc_policy.py:38-39) — single-rank CemMpc plans whose tiles are all resident at once; + 1 where the sampler is a
@@ -692,6 +695,54 @@ int cem_planner_iteration_plan(const cem_planner_t *h, int32_t it, cem_iteration
  * enable not 0 / 1. */
 int cem_planner_set_mean_candidate(cem_planner_t *h, int32_t enable);
 int cem_planner_get_mean_candidate(const cem_planner_t *h, int32_t *enable_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Plan read-out: the best-so-far action SEQUENCE and the particle evidence behind it.  Beyond the reference, off by default
+ * (DESIGN.md 4.14).  A plan returns the first action of the best sequence, its score and an iteration count; with the read-out on, one
+ * more kernel (cem_plan_track_kernel, csrc/cem_plan_readout.h) directly behind every iteration's select — behind the weighted refit and
+ * the elite keep where those run — keeps, per problem, in ONE device allocation the handle owns (made by the first enabling call, freed
+ * at destroy; the workspace keeps its layout and size):
+ *   sequence[H][A]       the best-so-far candidate's whole row of `actions`, an exact copy; sequence[0] is what the plan returns before
+ *                        the output noise (noise_stddev * eps_out) is added
+ *   score                its score: the plan's best_score
+ *   candidate, iteration its index in the population of the iteration that found it, and that iteration; -1 / -1: nothing was found
+ *                        (every score was -inf or NaN, or the problem is a batch row that was not live)
+ *   particle_returns[P]  ret[q * N_it + candidate], q = 0 .. P - 1, exact copies; N_it is that iteration's population
+ *                        (cem_planner_set_population_schedule).  On CEM_VARIANT_CEM with the mean objective
+ *                        score == (((0 + r_0) + r_1) + ... + r_{P-1}) / P in fp32, bit for bit.  On CEM_VARIANT_COST these are the returns
+ *                        the safe rollout also writes; that objective's score does not read them
+ *   cost_counts[H]       at step t the number of particles whose masked cost byte is non-zero; all -1 on CEM_VARIANT_CEM handles,
+ *                        whose rollout stores no cost bytes
+ *   flags                bit 0: a best-so-far update without a matching elite; never set by this library's selects
+ * Launch `it` of a plan: it == 0 resets the block (sequence and returns zero, score -inf, candidate and iteration -1, counts 0 or -1,
+ * flags 0) whether or not the problem is live; then, iff the select in front counted the iteration (the rule of the elite KEEP) and
+ * best_score > the block's score (fp32, strict: an equal score later in the plan is no update, -0.0 against +0.0 is none), the block
+ * takes the lowest-indexed elite whose score equals best_score — the select's own winner: maximum score, ties to the lowest candidate
+ * index.  Comparisons, word copies and integer counts only.  Sampler, rollout, reduce, select and refit launch exactly as before:
+ * cem_planner_rollout_path and cem_planner_rollout_form report what they reported, cem_planner_launches_per_iteration + 1; with
+ * cem_planner_set_timing on the tracker's time is part of the select time.  Whole plans (graph and eager), the stepwise calls (each
+ * cem_plan_select is followed by its tracker) and batch handles serve it, with every objective, refit, noise, carry-over and
+ * population setting.  The setter waits for the stream and drops the captured graph.
+ *   CEM_ERR_INVALID_ARG  null handle or pointer; enable not 0 / 1
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  enabling with world_size > 1 or a communicator (`ret` is a shard; and cem_planner_comm_init on an enabled
+ *                        handle), on a handle outside the one-workgroup select (select_mode 2 / 3: the rule of cem_planner_set_refit),
+ *                        or with more than 128 particles
+ * A failed allocation returns CEM_ERR_HIP; the handle keeps its previous setting after any of these.
+ *
+ * What is valid when: cem_planner_plan / cem_planner_plan_batch return as soon as the select that ends the plan has handed action,
+ * score and iterations to the host — the tracker of that iteration runs BEHIND it.  Those three are valid on return; the block is
+ * complete only once the stream has drained, which cem_planner_plan_readout does itself.  It copies the block of `problem` to *out and to
+ * the arrays given (each may be NULL); it may be called inside a stepwise plan, and before any plan (it then reads "nothing found").
+ *   CEM_ERR_STATE        the read-out is off
+ *   CEM_ERR_INVALID_ARG  null handle or `out`; problem outside [0, max(max_batch, 1)) */
+typedef struct { float score; int32_t candidate, iteration, flags; } cem_plan_readout_t;
+int cem_planner_set_plan_readout(cem_planner_t *h, int32_t enable);
+int cem_planner_get_plan_readout(const cem_planner_t *h, int32_t *enable_out);
+int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout_t *out,
+                             float *sequence_out_host /* [H][A] or NULL */,
+                             float *particle_returns_out_host /* [P] or NULL */,
+                             int32_t *cost_counts_out_host /* [H] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step

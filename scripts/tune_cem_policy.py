@@ -72,19 +72,21 @@ def evaluate_lockstep(trainer, environments, eval_steps, eval_episode_length):
 
 def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=HORIZONS,
                 proposals_with_iterations=PROPOSALS_WITH_ITERATIONS, elite_ratios=ELITE_RATIOS, parallel_envs=None,
-                elite_temperatures=None, noise_betas=None, keep_elites=None, population_decays=None):
+                elite_temperatures=None, noise_betas=None, keep_elites=None, population_decays=None, replan_everys=None):
     """elite_temperatures: None (the reference's grid) or a list of temperatures, None among them for the uniform refit — a fourth axis.
     noise_betas: None or a list of power-law exponents, None among them for white noise — a further axis.
     keep_elites: None or a list of kept fractions of n_elite, None among them for no carry-over — a further axis.
-    population_decays: None or a list of decay factors >= 1, None among them for the full population — a further axis."""
+    population_decays: None or a list of decay factors >= 1, None among them for the full population — a further axis.
+    replan_everys: None or a list of integers r >= 1, None among them for a plan at every decision — a further axis; a warm-started
+    policy's warm_shift follows r (the carried distribution moves as many steps as were executed)."""
     from ethz_safe_learning_amd.simba.infrastructure.logging_utils import logger
     agent = trainer.agent
     results = []
     for horizon in horizons:
         for n_samples, iterations in proposals_with_iterations:
-            for ratio, temperature, beta, keep, decay in [(r, t, b, f, g) for r in elite_ratios for t in (elite_temperatures or [None])
-                                                          for b in (noise_betas or [None]) for f in (keep_elites or [None])
-                                                          for g in (population_decays or [None])]:
+            for ratio, temperature, beta, keep, decay, every in [(r, t, b, f, g, e) for r in elite_ratios for t in (elite_temperatures or [None])
+                                                                 for b in (noise_betas or [None]) for f in (keep_elites or [None])
+                                                                 for g in (population_decays or [None]) for e in (replan_everys or [None])]:
                 kwargs = params['policies']['cem_mpc']
                 if elite_temperatures:
                     kwargs = dict(kwargs, elite_temperature=temperature)
@@ -94,6 +96,10 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
                     kwargs = dict(kwargs, keep_elites=keep)
                 if population_decays:
                     kwargs = dict(kwargs, population_decay=decay)
+                if replan_everys and every is not None:
+                    kwargs = dict(kwargs, replan_every=every)
+                    if kwargs.get('warm_start') or kwargs.get('shift_elites'):
+                        kwargs['warm_shift'] = every
                 agent.policy = make_new_policy(agent.model, env, horizon, iterations, n_samples, ratio, kwargs)
                 t0 = time.perf_counter()
                 if parallel_envs:
@@ -112,6 +118,8 @@ def grid_search(trainer, env, params, eval_steps, eval_episode_length, horizons=
                     rec['keep_elites'] = keep
                 if population_decays:
                     rec['population_decay'] = decay
+                if replan_everys:
+                    rec['replan_every'] = every
                 logger.info('H=%d (N,I)=(%d,%d) elite %.2f: score %.3f +- %.3f, cost %.3f +- %.3f', horizon, n_samples, iterations,
                             ratio, rec['score_mean'], rec['score_std'], rec['cost_mean'], rec['cost_std'])
                 results.append(rec)
@@ -143,7 +151,12 @@ def main(argv=None):
                     help="a grid axis of kept elite fractions (CemMpc(keep_elites=F)); 'none' = every candidate resampled, as the reference does")
     ap.add_argument('--population_decay', type=str, nargs='+', default=None, metavar='F',
                     help="a grid axis of population decay factors (CemMpc(population_decay=F)); 'none' = n_samples candidates in every iteration")
+    ap.add_argument('--replan_every', type=str, nargs='+', default=None, metavar='R',
+                    help="a grid axis of decisions per plan (CemMpc(replan_every=R), 1 <= R <= the smallest horizon of the grid); 'none' = a plan at "
+                         "every decision, as the reference does")
     args = ap.parse_args(argv)
+    if args.replan_every and args.parallel_episodes > 1:
+        ap.error('--replan_every keeps one sequence per policy (CemMpc.generate_actions refuses it): not with --parallel_episodes')
     if args.parallel_episodes < 1:
         ap.error('--parallel_episodes must be at least 1')
     if args.population_decay and args.parallel_episodes > 1:
@@ -164,6 +177,11 @@ def main(argv=None):
         grid['keep_elites'] = [None if f.lower() == 'none' else float(f) for f in args.keep_elites]
     if args.population_decay:
         grid['population_decays'] = [None if g.lower() == 'none' else float(g) for g in args.population_decay]
+    if args.replan_every:
+        grid['replan_everys'] = [None if r.lower() == 'none' else int(r) for r in args.replan_every]
+        lowest = min(grid.get('horizons', HORIZONS))
+        if any(r is not None and not 1 <= r <= lowest for r in grid['replan_everys']):
+            ap.error('--replan_every must lie in [1, %d], the smallest horizon of the grid' % lowest)
     if args.parallel_episodes > 1:
         grid['parallel_envs'] = make_parallel_environments(params, args.parallel_episodes, args.seed)
     results = grid_search(trainer, trainer.environment, params, args.eval_steps, args.eval_episode_length, **grid)

@@ -400,6 +400,9 @@ class CemPlanner:
     # block, not the stream (cem_mpc.h, cem_planner_plan) — and these arrays are written by the kernels behind that result, on a
     # stream torch's current stream knows nothing about: every accessor therefore drains the planner's stream first.  sync=False is for
     # callers that enqueue work on the planner's own stream (`with planner.stream_context():`), where stream order already holds.
+    # What stays the caller's job: a view is not a copy.  A kernel the caller queues on ANOTHER stream to read one is ordered behind the
+    # plan that wrote it (the drain above) but not in front of the NEXT plan, which overwrites the same bytes — the generator path of
+    # plan() waits for nobody.  Finish with the view (or clone it) before the next plan call, or queue the reader on the planner's stream.
     def _view(self, off, count, dtype, sync=True):
         t = self._torch
         if sync:
@@ -466,7 +469,9 @@ class CemPlanner:
 
     def set_weights_from(self, trainer):
         """Take a CemTrainer's current weights where they live.  Same device: the planner's stream waits on an event recorded on the
-        trainer's stream and the pack kernels read the trainer's workspace; no host synchronise.  Another device: the host route."""
+        trainer's stream and the pack kernels read the trainer's workspace; the trainer's stream in turn waits on an event recorded
+        behind the pack kernels, so its next step does not overwrite the blob while they read it; no host synchronise either way.
+        Another device: the host route."""
         if trainer.device != self.device:
             self.set_weights(trainer.get_weights())
             return
@@ -477,6 +482,10 @@ class CemPlanner:
             ev.record(trainer.stream)
             self.stream.wait_event(ev)
         _capi.check(self.lib.cem_planner_set_weights_dev(self.h, _ptr(blob), blob.numel()), 'cem_planner_set_weights_dev')
+        if trainer.stream != self.stream:
+            packed = t.cuda.Event()
+            packed.record(self.stream)
+            trainer.stream.wait_event(packed)
         self.have_device_weights = True
 
     def weight_images(self):

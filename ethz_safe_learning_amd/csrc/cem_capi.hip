@@ -15,6 +15,7 @@
 #include "cem_rollout_wide.h"
 #include "cem_pack.h"
 #include "../../include/cem_mpc.h"
+#include "cem_plan_options.h"
 
 #include <dlfcn.h>
 #include <link.h>
@@ -762,39 +763,34 @@ struct cem_planner {
     bool warm_save_skipped;                  // the staged plan overwrites the one slot's carry without a copy (stage_warm)
     int warm_staged;                       // problems of the plan whose warm control is staged and whose outcome finish_warm has not seen yet
     std::vector<float> h_expl;               // host copy of the explicit uploads [slots][2][HA]: the source of their stream-ordered copies
-    int tail_m;                              // cem_planner_set_particle_objective: 0 = the particle mean, 1 .. P = the mean of the m smallest returns (cem_score.h)
+    PlanOptions opt;                         // what the option setters set (cem_plan_options.h; its `comm` is filled by options_of); the fields below are what those options own
     // cem_planner_set_constraint (cem_score.h)
-    int cost_m;                              // 0 = CEM_CONSTRAINT_BETA; 1 .. P = CEM_CONSTRAINT_BUDGET on the m largest particle costs (P: their mean)
     float *budget_dev;                       // a device allocation of the handle's own, made on first use: budgets [slots], then cstat [slots][Nloc]
     std::vector<float> h_budget;             // host copy of the budgets [slots]: the source of their stream-ordered copies
     float *cstat_obj; size_t cstat_obj_n;    // grow-only cstat of cem_compute_objective (its candidate count is the caller's)
     const float *last_cstat; int last_cstat_n, last_cstat_problems;   // the C array of the last constrained reduce: per problem [last_cstat_n]
     // cem_planner_set_refit (cem_refit_weighted.h)
-    int refit_kind;                          // CEM_REFIT_UNIFORM: the select's own refit; CEM_REFIT_SOFTMAX: cem_constraint_refit_kernel behind the select
-    float refit_tau, refit_beta;             // the temperature as set and fl32(1 / temperature), rounded once here
+    float refit_beta;                        // fl32(1 / opt.refit_tau), rounded once here
     float *refit_dev;                        // a device allocation of the handle's own, made on first use: the select's discarded blend [slots][2][HA], then ESS [slots][I]
     bool refit_ran;                          // a weighted select has been put on the stream (cem_planner_refit_stats)
     // cem_planner_set_action_noise (cem_noise_mix.h)
-    int noise_kind;                          // CEM_NOISE_WHITE: the samplers draw their own Philox normals; CEM_NOISE_MIXED: they read noise_eps, which
-                                             // cem_mix_action_noise_kernel fills behind the plan's first kernel
+    // CEM_NOISE_WHITE: the samplers draw their own Philox normals; CEM_NOISE_MIXED: they read noise_eps, which
+    // cem_mix_action_noise_kernel fills behind the plan's first kernel
     std::vector<float> h_mix, h_mix_t;       // M [H][H] as set, and transposed: the source of its stream-ordered upload
     float *noise_dev;                        // a device allocation of the handle's own, made on first use: M transposed [H][H] (padded to a quad), then eps
     float *noise_eps; size_t noise_floats;   // eps [slots][I][N][H][A] inside noise_dev, and its float count
     // cem_planner_set_elite_carry (cem_elite_carry.h)
-    cem_elite_carry_t elite;                 // as set; n_keep 0: off, and the handle launches what create chose
     float *elite_dev;                        // a device allocation of the handle's own, made by the first enabling call: counts [slots] (int32, padded to
                                              // 256 bytes), then the stores [slots][n_keep][H][A]
     int elite_cap;                           // rows per slot the allocation has room for (grows with n_keep, never shrinks)
     bool elite_clear;                        // a plan call returned an error: the counts are zeroed in front of the next plan
     // cem_planner_set_population_schedule / cem_planner_set_mean_candidate (cem_population.h)
-    std::vector<IterPlan> pop;               // [I] the plan of every iteration while a schedule is on; empty: off, every iteration is the handle's own plan
+    std::vector<IterPlan> pop;               // [I] the plan of every iteration while a schedule is on (opt.pop: their sizes); empty: off, every iteration is the handle's own plan
     char *pop_dev;                           // a device allocation of the handle's own: the tile lists of the iterations with n[it] != n_samples, then
                                              // (only when some iteration needs more than the workspace holds) segment flags and hand-over state
     uint32_t *pop_seg_flags; f4 *pop_seg_state;   // where a scheduled plan's floating tiles keep those two: the workspace's, or inside pop_dev
     int pop_n_ready;                         // FIFO entries the plan's first kernel clears: the most any iteration uses
-    int mean_cand;                           // 1: the last iteration's last candidate is the clipped mean
     // cem_planner_set_plan_readout (cem_plan_readout.h)
-    int readout;                             // 1: cem_plan_track_kernel follows every select
     uint32_t *readout_dev;                   // a device allocation of the handle's own, made by the first enabling call: [slots] blocks of
                                              // CEM_READOUT_WORDS(H, A, P) words (the population never enters the size)
 };
@@ -803,11 +799,6 @@ namespace {
 
 // problems side by side on the handle = its carry slots: a single-state handle is a handle of ONE problem
 int warm_slots(const cem_planner *h) { return h->batch ? h->batch : 1; }
-
-// Elite carry-over overwrites rows of a sample that lies in HBM between two launches: while it is on, the sampler is a launch of its own
-// and the rollouts are the generic kernels that read it, whatever create chose (which n_keep = 0 restores)
-// — and so does the mean candidate, in the one iteration it is written in (cem_population.h)
-bool injects_mean(const cem_planner *h, int it) { return h->mean_cand && it == h->d.I - 1; }
 
 // The plan iteration `it` launches, as the enqueue functions read it: the handle's own, or the scheduled iteration's (cem_population.h)
 struct IterView {
@@ -825,9 +816,6 @@ IterView iter_view(const cem_planner *h, int it)
                     ip.tiles_off == (size_t)-1 ? (const TileDesc *)(h->ws + l.tiles) : (const TileDesc *)(h->pop_dev + ip.tiles_off),
                     h->pop_seg_flags, h->pop_seg_state};
 }
-
-bool samples_in_rollout(const cem_planner *h, int it) { return iter_view(h, it).sample_in_rollout && h->elite.n_keep == 0 && !injects_mean(h, it); }
-bool runs_lean(const cem_planner *h, int it) { return iter_view(h, it).lean_rollout && h->elite.n_keep == 0 && !injects_mean(h, it); }
 
 // Which form of the lean kernels a lean iteration launches: 2, the straight-line form (cem_rollout_lean_straight.hip), where the plan's
 // facts are the ones that form is compiled for — the goal a lidar kind, at most one constrained cost kind, every wave's weight stream
@@ -864,14 +852,97 @@ void drop_graph(cem_planner *h)
     h->graph_ready = false;
 }
 
-// a setter changes what a plan launches: wait for the captured plan (it may still be draining behind the polled result), then drop it.
-// Whatever the setter allocates it allocates before this, so that a failed allocation leaves the handle as it was
-int retire_graph(cem_planner *h)
+// What iteration `it` of a plan launches, decided here once: enqueue_rollout and enqueue_select branch on it, launches_of counts it,
+// the report functions (cem_planner_rollout_path / _rollout_form / _iteration_plan / _launches_per_iteration) read it.
+// own_noise: the plan call brought noise tensors of its own, which the lean kernels — they draw in place — cannot take.
+struct LaunchRecipe {
+    bool sampler_launch;                     // cem_sample_kernel in front of the rollout launch (else the rollout's tiles sample as their prologue)
+    bool inject_elites, inject_mean;         // behind that sampler: the kept elites into the first rows, the clipped mean into the last
+    int lean_form;                           // 0: the generic rollout kernels; 1 / 2: the lean kernels, branchy / straight-line form (lean_form)
+    bool fold_reduce;                        // a whole plan's select forms the particle mean itself: no score launch
+    int select_mode; bool select_cache;      // the select form (select_mode_for) and whether the one-workgroup kernel stages its keys in LDS
+    bool one_workgroup_only;                 // something below, or a schedule: admit() let it onto a one-workgroup select only
+    bool weighted, keep_elites, track;       // behind the select: the weighted refit, carry-over's keep, the read-out's tracker
+};
+LaunchRecipe recipe_of(const cem_planner *h, int it, bool own_noise)
 {
-    if (h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));
+    const IterView v = iter_view(h, it); const PlanOptions &o = h->opt;
+    LaunchRecipe r{};
+    // Elite carry-over overwrites rows of a sample that lies in HBM between two launches: while it is on, the sampler is a launch of its
+    // own and the rollouts are the generic kernels that read it, whatever create chose (which n_keep = 0 restores) — and so does the
+    // mean candidate, in the one iteration it is written in (cem_population.h)
+    r.inject_elites = o.elite.n_keep != 0;   // (a plan's iteration 0 has nothing to take without across_plans: enqueue_rollout; counted all the same)
+    r.inject_mean = o.mean_cand && it == h->d.I - 1;
+    const bool rewritten = r.inject_elites || r.inject_mean;
+    r.sampler_launch = !v.sample_in_rollout || rewritten;
+    // (the handle's own mixed tensor stands in wherever the caller passed none: the lean kernels step aside for it as for any tensor)
+    r.lean_form = v.lean_rollout && !rewritten && !own_noise && o.noise_kind != CEM_NOISE_MIXED ? lean_form(h, it) : 0;
+    r.select_mode = select_mode_for(h, v.d->N, &r.select_cache);
+    // one rank (the scores need no exchange), the CemMpc objective (no per-step Beta counts; what the select folds IS the mean), and a
+    // population the one-workgroup select serves with its keys staged in LDS
+    r.fold_reduce = h->d.W == 1 && !h->comm && h->cfg.variant == CEM_VARIANT_CEM && !o.tail_m && r.select_mode == 1 && r.select_cache;
+    r.weighted = o.refit_kind == CEM_REFIT_SOFTMAX; r.keep_elites = o.elite.n_keep != 0; r.track = o.readout != 0;
+    r.one_workgroup_only = r.weighted || r.keep_elites || r.track || !h->pop.empty();
+    return r;
+}
+
+// launches of iteration `it` (cem_planner_launches_per_iteration's rule): a count of what its recipe says — the rollout, the sampler
+// where it is a launch of its own with what it carries behind it, the score kernel unless the select folds it, the select's, what follows it
+int launches_of(const cem_planner *h, int it)
+{
+    const LaunchRecipe r = recipe_of(h, it, false);
+    return 1 + r.sampler_launch + r.inject_elites + r.inject_mean + !r.fold_reduce + (r.select_mode == 2 ? 8 : r.select_mode == 3 ? 2 : 1) +
+           r.weighted + r.keep_elites + r.track;
+}
+
+// The handle's options as a setter takes them.  Whether there is a communicator is the one fact not kept in cem_planner::opt: `comm` says it
+PlanOptions options_of(const cem_planner *h) { PlanOptions o = h->opt; o.comm = h->comm != nullptr; return o; }
+
+// T = H * m * kinds of a budget plan stays below this, so that an infeasible score's encoding is exact (cem_f32_encode_infeasible)
+constexpr long long kBudgetTotalLimit = 1ll << 23;
+
+// What the option rules read off the handle (cem_plan_options.h), for the schedule `next` asks for
+HandleFacts facts_of(const cem_planner *h, const PlanOptions &next)
+{
+    const Dims &d = h->d;
+    HandleFacts f;
+    f.W = d.W; f.batch = h->batch; f.variant = h->cfg.variant; f.N = d.N; f.k = d.k; f.H = d.H; f.A = d.A; f.I = d.I; f.P = d.P;
+    f.select_mode = select_mode_now(h);
+    for (int32_t n : next.pop) f.pop_select_mode.push_back(select_mode_for(h, n));
+    f.tail_max_p = CEM_TAIL_MAX_P; f.budget_max_tail_p = CEM_BUDGET_MAX_TAIL_P; f.elite_max_k = CEM_ELITE_MAX_K; f.mix_max_h = CEM_MIX_MAX_H;
+    f.readout_max_p = CEM_READOUT_MAX_P; f.max_cost_kinds = CEM_MAX_COST_KINDS; f.budget_total_limit = kBudgetTotalLimit;
+    f.refit_lds_bytes = CEM_REFIT_LDS_BYTES(d.k, d.H * d.A); f.refit_lds_limit = h->sel_dyn_limit;
+    f.can_mix = launch_mix_action_noise && prepare_mix_action_noise; f.can_carry = launch_elite_keep && launch_elite_inject;
+    f.can_mean = launch_mean_candidate != nullptr; f.can_track = launch_plan_track != nullptr;
+    return f;
+}
+int admit_on(const cem_planner *h, const PlanOptions &next, PlanChange change = PLAN_CHANGE_OTHER) { return admit(facts_of(h, next), next, change); }
+
+// A setter changes what a plan launches.  The caller has admitted `next` and prepared whatever it needs — nothing of the handle is
+// touched yet, so a failure up to here leaves it as it was.  Then: wait for the stream — `always`, where an EAGER plan still draining
+// behind its polled result may be using what `swap_in` replaces; else only for a captured plan — let the caller swap its new state in,
+// drop the graph (the captured plan holds the other setting's launches) and take `next`.  A swap_in that fails has changed nothing:
+// the handle keeps its options and its graph.
+template <typename SwapIn>
+int commit_launch_change(cem_planner *h, PlanOptions &next, bool always, SwapIn swap_in)
+{
+    if (always || h->graph_ready) HIPCHK(hipStreamSynchronize(h->stream));
+    if (const int st = swap_in()) return st;
     drop_graph(h);
+    h->opt = std::move(next);
     return CEM_OK;
 }
+int commit_launch_change(cem_planner *h, PlanOptions &next, bool always) { return commit_launch_change(h, next, always, [] { return (int)CEM_OK; }); }
+
+// a device allocation that goes again unless it is released into the handle: "free what this call allocated, leave the handle as it was"
+struct DevBlock {
+    void *p = nullptr;
+    DevBlock() = default;
+    DevBlock(const DevBlock &) = delete; DevBlock &operator=(const DevBlock &) = delete;
+    ~DevBlock() { if (p) hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    template <typename T> T *release() { T *q = static_cast<T *>(p); p = nullptr; return q; }
+};
 
 // what every handle owns from create on: the three pinned blocks, its stream if it made one, itself
 void release_handle(cem_planner *h)
@@ -1040,13 +1111,13 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     { const char *e = std::getenv("CEM_FORCE_ROLLOUT"); h->lean_branchy = e && std::strcmp(e, "lean_branchy") == 0; }
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
-    h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false; h->tail_m = 0;
-    h->cost_m = 0; h->budget_dev = nullptr; h->cstat_obj = nullptr; h->cstat_obj_n = 0; h->last_cstat = nullptr; h->last_cstat_n = h->last_cstat_problems = 0;
-    h->refit_kind = CEM_REFIT_UNIFORM; h->refit_tau = 0.f; h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
-    h->noise_kind = CEM_NOISE_WHITE; h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
-    h->elite = cem_elite_carry_t{}; h->elite.shift = 1; h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
-    h->readout = 0; h->readout_dev = nullptr;
-    h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0; h->mean_cand = 0;
+    h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false;     // (h->opt: every option off, PlanOptions' own defaults)
+    h->budget_dev = nullptr; h->cstat_obj = nullptr; h->cstat_obj_n = 0; h->last_cstat = nullptr; h->last_cstat_n = h->last_cstat_problems = 0;
+    h->refit_beta = 0.f; h->refit_dev = nullptr; h->refit_ran = false;
+    h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
+    h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
+    h->readout_dev = nullptr;
+    h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
     h->h_ctrl = nullptr; h->h_result = nullptr; h->h_warm = nullptr; h->d_h_warm = nullptr; h->pack_desc = nullptr; h->n_pack_desc = 0;
@@ -1447,7 +1518,7 @@ int enqueue_begin(cem_planner *h)
     HIPCHK(hipGetLastError());
     // time-correlated action noise: the plan's whole eps_act tensor, from the key the kernel above has just put into the workspace (one
     // launch and one graph node per plan); a caller's own eps_act is taken as given
-    if (h->noise_kind == CEM_NOISE_MIXED && !h->eps_act) {
+    if (h->opt.noise_kind == CEM_NOISE_MIXED && !h->eps_act) {
         MixParams mp{}; mp.mix_t = h->noise_dev; mp.eps = h->noise_eps; mp.ctrl = (const CtrlBlock *)(h->ws + l.ctrl);
         mp.I = d.I; mp.N = d.N; mp.H = d.H; mp.A = d.A;
         HIPCHK(launch_mix_action_noise(mp, warm_slots(h), h->stream));
@@ -1478,7 +1549,7 @@ ReduceParams fill_score(const cem_planner *h, const float *ret, const uint8_t *c
     if (clear_select) { p.zero = (uint32_t *)(h->ws + h->lay.ms_hist); p.zero_n = CEM_MS_CLEAR_BYTES / 4; }
     // one m serves both: the setters refuse a lower tail on a budget handle and the reverse, and a COST handle refuses both, so at most one of
     // cost_m / tail_m is set; a kernel that reads neither m nor budget ignores them
-    p.m = h->cost_m ? h->cost_m : h->tail_m; p.cstat = cstat; p.budget = h->budget_dev;
+    p.m = h->opt.cost_m ? h->opt.cost_m : h->opt.tail_m; p.cstat = cstat; p.budget = h->budget_dev;
     return p;
 }
 
@@ -1487,8 +1558,8 @@ hipError_t launch_score(const cem_planner *h, const ReduceParams &p, int n_probl
 {
     const dim3 grid((p.Nloc + 63) / 64, n_problems), block(CEM_SCORE_THREADS);
     if (h->cfg.variant == CEM_VARIANT_COST) hipLaunchKernelGGL(cem_constraint_reduce_kernel, grid, block, 0, h->stream, p);
-    else if (h->cost_m) hipLaunchKernelGGL(cem_constrained_budget_kernel, grid, block, CEM_BUDGET_LDS_BYTES(p.P, p.m), h->stream, p);
-    else if (h->tail_m) hipLaunchKernelGGL(cem_constraint_tail_kernel, grid, block, CEM_TAIL_LDS_BYTES(p.P), h->stream, p);
+    else if (h->opt.cost_m) hipLaunchKernelGGL(cem_constrained_budget_kernel, grid, block, CEM_BUDGET_LDS_BYTES(p.P, p.m), h->stream, p);
+    else if (h->opt.tail_m) hipLaunchKernelGGL(cem_constraint_tail_kernel, grid, block, CEM_TAIL_LDS_BYTES(p.P), h->stream, p);
     else hipLaunchKernelGGL(cem_reduce_kernel, grid, block, 0, h->stream, p);
     return hipGetLastError();
 }
@@ -1500,16 +1571,18 @@ EliteCarryParams fill_elite(const cem_planner *h, int it)
     const Dims &d = *v.d; const Layout &l = h->lay; char *ws = h->ws;
     EliteCarryParams ep{}; ep.scores = (const float *)(ws + l.scores_global); ep.actions = (float *)(ws + l.actions); ep.act_pad = (float *)(ws + l.act_pad);
     ep.ctrl = (const CtrlBlock *)(ws + l.ctrl); ep.elite_idx = (const int32_t *)(ws + l.elite); ep.store = elite_store(h); ep.count = elite_counts(h);
-    ep.N = d.N; ep.k = d.k; ep.m = h->elite.n_keep; ep.H = d.H; ep.A = d.A; ep.it = it; ep.shift = h->elite.across_plans ? h->elite.shift : 0;
+    ep.N = d.N; ep.k = d.k; ep.m = h->opt.elite.n_keep; ep.H = d.H; ep.A = d.A; ep.it = it; ep.shift = h->opt.elite.across_plans ? h->opt.elite.shift : 0;
     ep.pad_shift = d.O - 4 * d.act_q0; ep.pad_floats = 4 * d.act_nq;
     return ep;
 }
 
-// One iteration up to the scores: the rollout launch (its tiles sample their own action sequences first: cem_tile_sample_actions), then
-// the particle mean / Beta filter — unless `fold_reduce`: a single-rank whole plan on the CemMpc objective lets the select kernel form
-// the particle mean while it stages its keys (same sum, same order, one launch and one graph node fewer per iteration).
-int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
+// One iteration up to the scores, as its recipe says: the rollout launch (its tiles sample their own action sequences first:
+// cem_tile_sample_actions), then the particle mean / Beta filter — unless the reduce is folded: a single-rank `whole_plan` on the CemMpc
+// objective lets the select kernel form the particle mean while it stages its keys (same sum, same order, one launch and one graph
+// node fewer per iteration).  The stepwise form always leaves the scores in scores_local (the caller may exchange them).
+int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
 {
+    const LaunchRecipe rc = recipe_of(h, it, h->eps_act || h->eps_model);
     // v: what this iteration launches — the handle's plan, or the scheduled iteration's (cem_population.h); d: its shape.  The caller's
     // noise tensors keep the slabs of the handle's own n_samples (h->d), of which a narrower iteration reads the leading part
     const IterView v = iter_view(h, it);
@@ -1524,8 +1597,8 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     rp.H = d.H; rp.Bloc = d.Bloc; rp.Btot = d.Btot; rp.it = it; rp.variant = cost_obj ? (int)CEM_VARIANT_SAFE : h->cfg.variant; rp.check_done = 1;
     rp.stamps = (long long *)(ws + l.stamps);
     // the sampler's inputs and outputs (cem_mpc.py:44-48)
-    // (the handle's own mixed tensor stands in wherever the caller passed none: the lean kernels then step aside below, as for any tensor)
-    const float *eps_act = h->eps_act ? h->eps_act : (h->noise_kind == CEM_NOISE_MIXED ? h->noise_eps : nullptr);
+    // (the handle's own mixed tensor stands in wherever the caller passed none)
+    const float *eps_act = h->eps_act ? h->eps_act : (h->opt.noise_kind == CEM_NOISE_MIXED ? h->noise_eps : nullptr);
     rp.musig = (const float *)(ws + l.musig); rp.eps_act = eps_act ? eps_act + (size_t)it * h->d.N * d.H * d.A : nullptr;
     rp.act_bounds = (const float *)(ws + l.act_bounds); rp.actions_w = (float *)(ws + l.actions); rp.act_pad_w = (float *)(ws + l.act_pad);
     rp.pad_shift = d.O - 4 * d.act_q0; rp.pad_floats = 4 * d.act_nq; rp.N = d.N; rp.Nloc = d.Nloc; rp.n_off = d.n_off; rp.n_tiles = v.n_tiles;
@@ -1533,7 +1606,7 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
     const int nb = warm_slots(h);
     rp.tiles_per_problem = h->batch ? v.n_tiles : 0;
     rp.eps_act_pstride = (long long)d.I * h->d.N * d.H * d.A; rp.eps_model_pstride = (long long)d.I * d.H * h->d.Btot * d.O;
-    if (!samples_in_rollout(h, it)) {                         // all N candidates once, in front of the rollout launch (which then samples nothing)
+    if (rc.sampler_launch) {                                  // all N candidates once, in front of the rollout launch (which then samples nothing)
         const int total = d.N * d.H * ((d.A + 3) / 4);
         TimedLaunch timed(h, 3);
         hipLaunchKernelGGL(cem_sample_kernel, dim3(std::min((total + 255) / 256, 2048), nb), dim3(256), 0, h->stream, rp);
@@ -1541,12 +1614,12 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         rp.musig = nullptr;
         // elite carry-over: rows 0 .. count - 1 of the sample become the kept elites (cem_elite_carry.h).  Iteration 0 has nothing of this
         // plan to take; across_plans lets the device-side count decide there, so that one captured graph serves the first plan and later ones
-        if (h->elite.n_keep && (it > 0 || h->elite.across_plans)) {
+        if (rc.inject_elites && (it > 0 || h->opt.elite.across_plans)) {
             EliteCarryParams ep = fill_elite(h, it);
             HIPCHK(launch_elite_inject(ep, nb, h->stream));
         }
         // the mean candidate: the iteration's last row becomes the clipped mu it was sampled from (cem_population.h)
-        if (injects_mean(h, it)) {
+        if (rc.inject_mean) {
             MeanCandidateParams mc{}; mc.musig = (const float *)(ws + l.musig); mc.act_bounds = rp.act_bounds; mc.ctrl = rp.ctrl;
             mc.actions = rp.actions_w; mc.act_pad = rp.act_pad_w; mc.N = d.N; mc.row = d.N - 1; mc.H = d.H; mc.A = d.A;
             mc.pad_shift = rp.pad_shift; mc.pad_floats = rp.pad_floats;
@@ -1554,13 +1627,13 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         }
     }
     TimedLaunch timed(h, 0);
-    if (runs_lean(h, it) && !rp.eps_act && !rp.eps_model) {      // (the same tiles, segments and work queue as the generic launches below)
+    if (rc.lean_form) {                                          // (the same tiles, segments and work queue as the generic launches below)
         if (queued) {
             rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
             rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
         }
         const int grid = queued ? v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned) : v.n_tiles;
-        if (lean_form(h, it) == 2 && (rp.variant == 1) == (rp.costs != nullptr)) HIPCHK(launch_rollout_lean_straight(rp, grid, h->stream, queued));
+        if (rc.lean_form == 2 && (rp.variant == 1) == (rp.costs != nullptr)) HIPCHK(launch_rollout_lean_straight(rp, grid, h->stream, queued));
         else HIPCHK(launch_rollout_lean(rp, grid, h->stream, queued));
     }
     else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, rp.eps_model ? 1 : 0));
@@ -1573,50 +1646,32 @@ int enqueue_rollout(cem_planner *h, int it, bool fold_reduce)
         HIPCHK(launch_rollout_seg(v.rc, d.NFW, rp, v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned), h->stream));
     } else HIPCHK(launch_rollout<0>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     timed.stop();
-    if (fold_reduce) return CEM_OK;
+    if (whole_plan && rc.fold_reduce) return CEM_OK;
 
     // the score kernel of the handle's objective, timed as the one reduce launch; it clears the words of this iteration's multi-workgroup select
-    const ReduceParams sp = fill_score(h, rp.ret, rp.costs, (float *)(ws + l.scores_local), h->cost_m ? h->budget_dev + nb : nullptr, d.Nloc, d.H, 1, true);
+    const ReduceParams sp = fill_score(h, rp.ret, rp.costs, (float *)(ws + l.scores_local), h->opt.cost_m ? h->budget_dev + nb : nullptr, d.Nloc, d.H, 1, true);
     h->sel_zeroed = true;
-    if (h->cost_m) note_plan_cstat(h);
+    if (h->opt.cost_m) note_plan_cstat(h);
     TimedLaunch timed_reduce(h, 2);
     HIPCHK(launch_score(h, sp, nb));
     return CEM_OK;
 }
 
-// whether a whole plan of this handle folds the particle mean into the select kernel: one rank (the scores need no exchange), the
-// CemMpc objective (no per-step Beta counts), and a population the one-workgroup select serves with its keys staged in LDS
-// (it: the iteration — a population schedule gives each its own population, hence its own answer)
-bool folds_reduce(const cem_planner *h, int it = 0)
-{
-    const Dims &d = h->d;
-    if (d.W != 1 || h->comm || h->cfg.variant != CEM_VARIANT_CEM) return false;
-    if (h->tail_m) return false;                       // what the select folds IS the mean
-    bool cache = false;
-    return select_mode_for(h, iter_view(h, it).d->N, &cache) == 1 && cache;
-}
-
-// launches of iteration `it` (cem_planner_launches_per_iteration's rule): the rollout, the sampler where it is a launch of its own, the score
-// kernel unless the select folds it, the select's, the weighted refit, carry-over's inject and keep, the mean candidate, the read-out's tracker
-int launches_of(const cem_planner *h, int it)
-{
-    const int mode = select_mode_for(h, iter_view(h, it).d->N);
-    return 1 + (samples_in_rollout(h, it) ? 0 : 1) + (folds_reduce(h, it) ? 0 : 1) + (mode == 2 ? 8 : (mode == 3 ? 2 : 1)) +
-           (h->refit_kind == CEM_REFIT_SOFTMAX ? 1 : 0) + (h->elite.n_keep ? 2 : 0) + (injects_mean(h, it) ? 1 : 0) + (h->readout ? 1 : 0);
-}
-
-// fold_final: the select writes the plan's result itself (whole plans only: eps_out is known before the loop) — returns through
-// *folded whether it did (only the one-workgroup kernel does), so the caller knows whether a final kernel is still needed
-int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = false, bool have_eps_out = false, bool *folded = nullptr)
+// whole_plan: the select forms the particle mean where the recipe folds it, and writes the plan's result itself where it can (eps_out is
+// known before the loop) — returns through *folded whether it did (only the one-workgroup kernel does), so the caller knows whether a
+// final kernel is still needed
+int enqueue_select(cem_planner *h, int it, bool whole_plan, bool have_eps_out = false, bool *folded = nullptr)
 {
     if (folded) *folded = false;
+    const LaunchRecipe rc = recipe_of(h, it, h->eps_act || h->eps_model);
+    const bool fold_reduce = whole_plan && rc.fold_reduce, fold_final = whole_plan;
     const Dims &d = *iter_view(h, it).d; const Layout &l = h->lay; char *ws = h->ws;    // (a scheduled iteration ranks its own n[it] candidates)
     SelectParams p{}; p.scores = (const float *)(ws + l.scores_global); p.actions = (const float *)(ws + l.actions);
     p.musig = (float *)(ws + l.musig); p.ctrl = (CtrlBlock *)(ws + l.ctrl); p.elite_idx = (int32_t *)(ws + l.elite);
     p.N = d.N; p.k = d.k; p.HA = d.H * d.A; p.A = d.A; p.check_done = 1;
     p.smoothing = h->cfg.smoothing; p.one_minus_smoothing = h->cfg.one_minus_smoothing; p.threshold = h->cfg.stddev_threshold;
     p.stamps = (long long *)(ws + l.stamps) + 64;          // past tile 0's rollout stamps; written by -DCEM_STAMPS builds only
-    if (fold_reduce) { p.ret = (const float *)(ws + l.returns); p.P = d.P; p.scores_w = (float *)(ws + l.scores_local); }   // (folds_reduce(): world 1, so local == global)
+    if (fold_reduce) { p.ret = (const float *)(ws + l.returns); p.P = d.P; p.scores_w = (float *)(ws + l.scores_local); }   // (LaunchRecipe::fold_reduce: world 1, so local == global)
     size_t lds = (size_t)((d.k + 3) & ~3) * 4 + (size_t)2 * d.H * d.A * 4;
     // Large populations (the replicated select of a many-GPU plan) go through multi-workgroup kernels (cem_mpc.h select_mode):
     // the fused form (one launch, grid barriers) whenever all its ceil(N / 4096) workgroups are resident at once, the eight-launch
@@ -1632,17 +1687,14 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
     // iteration's select in stream order (the plan stays valid, with select_mode 2's bits) and the handle stops fusing: read_results,
     // select_mode_now.  select_mode 2 has no such assumption.
     const int G = (d.N + CEM_MS_KEYS - 1) / CEM_MS_KEYS;
-    bool cache = false;
-    const int mode = select_mode_for(h, d.N, &cache);
+    const int mode = rc.select_mode; const bool cache = rc.select_cache;
     if (mode == 0) return CEM_ERR_UNSUPPORTED;          // (an explicit select_mode 1 on a device that grants less dynamic LDS than validate() assumed)
     // The score-weighted refit (cem_refit_weighted.h): the one-workgroup select as it is, blending into a scratch slice, never stopping and
     // never handing over the result; cem_constraint_refit_kernel behind it refits the plan's mu / sigma and decides the early stop.
-    const bool weighted = h->refit_kind == CEM_REFIT_SOFTMAX;
-    if (weighted && (mode != 1 || !h->refit_dev)) return CEM_ERR_UNSUPPORTED;      // (cem_planner_set_refit admitted one-workgroup handles only)
+    const bool weighted = rc.weighted;
+    // (admit() let these onto one-workgroup handles only, and their setters made the allocations before they committed)
+    if (rc.one_workgroup_only && (mode != 1 || (weighted && !h->refit_dev) || (rc.keep_elites && !h->elite_dev) || (rc.track && !h->readout_dev))) return CEM_ERR_UNSUPPORTED;
     if (weighted) { p.musig = h->refit_dev; p.threshold = -std::numeric_limits<float>::infinity(); }
-    if (h->elite.n_keep && (mode != 1 || !h->elite_dev)) return CEM_ERR_UNSUPPORTED;   // (cem_planner_set_elite_carry admitted one-workgroup handles only)
-    if (!h->pop.empty() && mode != 1) return CEM_ERR_UNSUPPORTED;                      // (cem_planner_set_population_schedule likewise)
-    if (h->readout && (mode != 1 || !h->readout_dev)) return CEM_ERR_UNSUPPORTED;      // (cem_planner_set_plan_readout likewise)
     TimedLaunch timed(h, 1);
     if (mode >= 2) {
         MSelParams m{}; m.scores = p.scores; m.actions = p.actions; m.musig = p.musig; m.ctrl = p.ctrl; m.elite_idx = p.elite_idx;
@@ -1694,7 +1746,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
             h->refit_ran = true;
         }
         // elite carry-over: the best n_keep of the elites just chosen, for the next iteration's (the next plan's) inject
-        if (h->elite.n_keep) {
+        if (rc.keep_elites) {
             HIPCHK(hipGetLastError());
             const EliteCarryParams ep = fill_elite(h, it);
             HIPCHK(launch_elite_keep(ep, warm_slots(h), h->stream));
@@ -1702,7 +1754,7 @@ int enqueue_select(cem_planner *h, int it, bool fold_reduce, bool fold_final = f
         // the plan read-out: the best-so-far candidate's sequence, returns and cost counts leave the workspace before the next rollout
         // overwrites them (cem_plan_readout.h).  Last: every launch above stays where it was; device-side state only (the control
         // block in the workspace, never the pinned staging the next plan call writes while this launch may still be running)
-        if (h->readout) {
+        if (rc.track) {
             HIPCHK(hipGetLastError());
             PlanTrackParams tp{}; tp.scores = p.scores; tp.actions = p.actions; tp.ret = (const float *)(ws + l.returns);
             tp.costs = h->cfg.variant != CEM_VARIANT_CEM ? (const uint8_t *)(ws + l.costs) : nullptr;
@@ -1929,10 +1981,9 @@ int enqueue_plan(cem_planner *h, bool have_eps_out)
     bool final_folded = false;
     int st = enqueue_begin(h);
     for (int it = 0; it < h->d.I && !st; ++it) {
-        const bool fold = folds_reduce(h, it);
-        st = enqueue_rollout(h, it, fold);
+        st = enqueue_rollout(h, it, true);
         if (!st) st = enqueue_exchange(h);
-        if (!st) st = enqueue_select(h, it, fold, true, have_eps_out, &final_folded);
+        if (!st) st = enqueue_select(h, it, true, have_eps_out, &final_folded);
     }
     if (!st && !final_folded) st = enqueue_end(h, have_eps_out);
     return st;
@@ -1983,7 +2034,7 @@ int run_plan(cem_planner *h, const PlanCall &pc)
     if (!noise_pair_ok(h, pc)) return CEM_ERR_INVALID_ARG;
     stage_ctrl(h, pc);
     { const int est = clear_elite_after_failure(h); if (est) return est; }
-    if (h->cost_m) note_plan_cstat(h);
+    if (h->opt.cost_m) note_plan_cstat(h);
     if (graph) { const int st = ensure_graph(h); if (st) return st; graph = h->graph_ready; }
     if (graph) {
         HIPCHK(hipGraphLaunch(h->gexec, h->stream));
@@ -2073,7 +2124,7 @@ int cem_plan_rollout(cem_planner_t *h, int32_t it)
     if (!h) return CEM_ERR_INVALID_ARG;
     if (!h->in_plan) return CEM_ERR_STATE;
     if (it < 0 || it >= h->d.I) return CEM_ERR_INVALID_ARG;
-    return enqueue_rollout(h, it, false);      // the stepwise form always leaves the scores in scores_local (the caller may exchange them)
+    return enqueue_rollout(h, it, false);
 }
 
 int cem_plan_select(cem_planner_t *h, int32_t it)
@@ -2118,25 +2169,18 @@ int cem_planner_set_particle_objective(cem_planner_t *h, int32_t kind, int32_t m
     if (!h || (kind != CEM_PARTICLES_MEAN && kind != CEM_PARTICLES_LOWER_TAIL)) return CEM_ERR_INVALID_ARG;
     if (kind == CEM_PARTICLES_LOWER_TAIL && (m < 1 || m > h->d.P)) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
-    if (kind == CEM_PARTICLES_LOWER_TAIL) {
-        // the kernel is rank-local and would serve a shard as it is; no multi-rank run of it has been made, so it is not offered
-        if (h->cfg.variant == CEM_VARIANT_COST || h->d.W > 1) return CEM_ERR_UNSUPPORTED;
-        if (h->d.P > CEM_TAIL_MAX_P) return CEM_ERR_UNSUPPORTED;
-        if (h->cost_m) return CEM_ERR_UNSUPPORTED;         // a lower tail of the returns within a cost budget is not offered (cem_planner_set_constraint)
-    }
-    const int tail_m = kind == CEM_PARTICLES_LOWER_TAIL ? m : 0;
-    if (tail_m == h->tail_m) return CEM_OK;
+    PlanOptions next = options_of(h); next.tail_m = kind == CEM_PARTICLES_LOWER_TAIL ? m : 0;
+    { const int st = admit_on(h, next); if (st) return st; }
+    if (next.tail_m == h->opt.tail_m) return CEM_OK;
     // the captured plan holds the other objective's launches (and, changing m alone, the old m): the next plan captures anew
-    { const int st = retire_graph(h); if (st) return st; }
-    h->tail_m = tail_m;
-    return CEM_OK;
+    return commit_launch_change(h, next, false);
 }
 
 int cem_planner_get_particle_objective(const cem_planner_t *h, int32_t *kind_out, int32_t *m_out)
 {
     if (!h) return CEM_ERR_INVALID_ARG;
-    if (kind_out) *kind_out = h->tail_m ? CEM_PARTICLES_LOWER_TAIL : CEM_PARTICLES_MEAN;
-    if (m_out) *m_out = h->tail_m;
+    if (kind_out) *kind_out = h->opt.tail_m ? CEM_PARTICLES_LOWER_TAIL : CEM_PARTICLES_MEAN;
+    if (m_out) *m_out = h->opt.tail_m;
     return CEM_OK;
 }
 
@@ -2156,29 +2200,19 @@ int cem_planner_set_constraint(cem_planner_t *h, int32_t kind, int32_t worst_cos
     if (!h || (kind != CEM_CONSTRAINT_BETA && kind != CEM_CONSTRAINT_BUDGET)) return CEM_ERR_INVALID_ARG;
     if (kind == CEM_CONSTRAINT_BUDGET && (worst_cost_particles < 0 || worst_cost_particles > h->d.P)) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
-    int cost_m = 0;
-    if (kind == CEM_CONSTRAINT_BUDGET) {
-        cost_m = worst_cost_particles ? worst_cost_particles : h->d.P;
-        if (h->cfg.variant != CEM_VARIANT_SAFE) return CEM_ERR_UNSUPPORTED;            // the SAFE rollout's masked cost bytes are what it reads
-        // the kernel is rank-local and would serve a shard as it is; no multi-rank run of it has been made, so it is not offered
-        if (h->d.W > 1) return CEM_ERR_UNSUPPORTED;
-        if (cost_m < h->d.P && h->d.P > CEM_BUDGET_MAX_TAIL_P) return CEM_ERR_UNSUPPORTED;
-        if ((long long)h->d.H * cost_m * CEM_MAX_COST_KINDS >= (1ll << 23)) return CEM_ERR_UNSUPPORTED;   // T must stay below 2^23 (cem_f32_encode_infeasible)
-        if (h->tail_m) return CEM_ERR_UNSUPPORTED;
-    }
-    if (cost_m == h->cost_m) return CEM_OK;
+    PlanOptions next = options_of(h); next.cost_m = kind != CEM_CONSTRAINT_BUDGET ? 0 : worst_cost_particles ? worst_cost_particles : h->d.P;
+    { const int st = admit_on(h, next); if (st) return st; }
+    if (next.cost_m == h->opt.cost_m) return CEM_OK;
     // the captured plan holds the other constraint's launches (and, changing m_c alone, the old m_c): the next plan captures anew
-    if (cost_m) { const int st = ensure_budget(h); if (st) return st; }
-    { const int st = retire_graph(h); if (st) return st; }
-    h->cost_m = cost_m;
-    return CEM_OK;
+    if (next.cost_m) { const int st = ensure_budget(h); if (st) return st; }
+    return commit_launch_change(h, next, false);
 }
 
 int cem_planner_get_constraint(const cem_planner_t *h, int32_t *kind_out, int32_t *worst_cost_particles_out)
 {
     if (!h) return CEM_ERR_INVALID_ARG;
-    if (kind_out) *kind_out = h->cost_m ? CEM_CONSTRAINT_BUDGET : CEM_CONSTRAINT_BETA;
-    if (worst_cost_particles_out) *worst_cost_particles_out = h->cost_m;
+    if (kind_out) *kind_out = h->opt.cost_m ? CEM_CONSTRAINT_BUDGET : CEM_CONSTRAINT_BETA;
+    if (worst_cost_particles_out) *worst_cost_particles_out = h->opt.cost_m;
     return CEM_OK;
 }
 
@@ -2224,26 +2258,19 @@ int cem_planner_set_refit(cem_planner_t *h, int32_t kind, float temperature)
     if (!h || (kind != CEM_REFIT_UNIFORM && kind != CEM_REFIT_SOFTMAX)) return CEM_ERR_INVALID_ARG;
     if (kind == CEM_REFIT_SOFTMAX && (!finite_bits(temperature) || !(temperature > 0.f))) return CEM_ERR_INVALID_ARG;   // (NaN: by its bits, -fno-honor-nans)
     if (h->in_plan) return CEM_ERR_STATE;
-    if (kind == CEM_REFIT_SOFTMAX) {
-        // one rank and the one-workgroup select: the multi-workgroup forms keep their own moment kernels, which this one does not replace
-        if (h->d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
-        if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;
-        if (CEM_REFIT_LDS_BYTES(h->d.k, h->d.H * h->d.A) > h->sel_dyn_limit) return CEM_ERR_UNSUPPORTED;
-    }
-    const float tau = kind == CEM_REFIT_SOFTMAX ? temperature : 0.f;
-    if (kind == h->refit_kind && std::memcmp(&tau, &h->refit_tau, 4) == 0) return CEM_OK;
+    PlanOptions next = options_of(h); next.refit_kind = kind; next.refit_tau = kind == CEM_REFIT_SOFTMAX ? temperature : 0.f;
+    { const int st = admit_on(h, next, PLAN_CHANGE_REFIT); if (st) return st; }
+    if (kind == h->opt.refit_kind && std::memcmp(&next.refit_tau, &h->opt.refit_tau, 4) == 0) return CEM_OK;
     // the captured plan holds the other refit's launches (and, changing the temperature alone, the old 1 / temperature): the next plan captures anew
     if (kind == CEM_REFIT_SOFTMAX) { const int st = ensure_refit(h); if (st) return st; }
-    { const int st = retire_graph(h); if (st) return st; }
-    h->refit_kind = kind; h->refit_tau = tau; h->refit_beta = kind == CEM_REFIT_SOFTMAX ? 1.0f / temperature : 0.f;
-    return CEM_OK;
+    return commit_launch_change(h, next, false, [&] { h->refit_beta = kind == CEM_REFIT_SOFTMAX ? 1.0f / temperature : 0.f; return (int)CEM_OK; });
 }
 
 int cem_planner_get_refit(const cem_planner_t *h, int32_t *kind_out, float *temperature_out)
 {
     if (!h) return CEM_ERR_INVALID_ARG;
-    if (kind_out) *kind_out = h->refit_kind;
-    if (temperature_out) *temperature_out = h->refit_tau;
+    if (kind_out) *kind_out = h->opt.refit_kind;
+    if (temperature_out) *temperature_out = h->opt.refit_tau;
     return CEM_OK;
 }
 
@@ -2258,61 +2285,45 @@ int cem_planner_refit_stats(cem_planner_t *h, int32_t problem, float *ess_out_ho
     return CEM_OK;
 }
 
-// the handle's noise allocation (cem_planner::noise_dev), made on first use and zeroed: M transposed, then the mixed tensor of every slot
-static int ensure_noise(cem_planner *h)
-{
-    if (h->noise_dev) return CEM_OK;
-    const Dims &d = h->d;
-    HIPCHK(prepare_mix_action_noise(d.H));
-    const size_t mt = ((size_t)d.H * d.H + 3) & ~(size_t)3;
-    const size_t eps = (size_t)warm_slots(h) * d.I * d.N * d.H * d.A;
-    float *p = nullptr;
-    HIPCHK(hipMalloc((void **)&p, (mt + eps) * 4));
-    if (hipMemsetAsync(p, 0, (mt + eps) * 4, h->stream) != hipSuccess) { g_last_hip = (int)hipGetLastError(); hipFree(p); return CEM_ERR_HIP; }
-    h->noise_dev = p; h->noise_eps = p + mt; h->noise_floats = eps;
-    return CEM_OK;
-}
-
 int cem_planner_set_action_noise(cem_planner_t *h, int32_t kind, const float *mix_host)
 {
     if (!h || (kind != CEM_NOISE_WHITE && kind != CEM_NOISE_MIXED)) return CEM_ERR_INVALID_ARG;
     if ((kind == CEM_NOISE_MIXED) != (mix_host != nullptr)) return CEM_ERR_INVALID_ARG;
-    const size_t HH = (size_t)h->d.H * h->d.H;
+    const Dims &d = h->d;
+    const size_t HH = (size_t)d.H * d.H;
     if (kind == CEM_NOISE_MIXED) for (size_t i = 0; i < HH; ++i) if (!finite_bits(mix_host[i])) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
-    if (kind == CEM_NOISE_MIXED) {
-        // the kernel mixes all N candidates of ONE rank's key; a sharded plan would need it per shard and no such run has been made
-        if (h->d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
-        if (h->d.H > CEM_MIX_MAX_H || !launch_mix_action_noise || !prepare_mix_action_noise) return CEM_ERR_UNSUPPORTED;
+    PlanOptions next = options_of(h); next.noise_kind = kind;
+    { const int st = admit_on(h, next); if (st) return st; }
+    if (kind == CEM_NOISE_WHITE && h->opt.noise_kind == CEM_NOISE_WHITE) return CEM_OK;
+    // the handle's noise allocation (cem_planner::noise_dev), made on first use and zeroed: M transposed, then the mixed tensor of every
+    // slot.  A handle this call fails on keeps what it had (cem_planner_action_noise_dev reports NULL on one that has never been MIXED)
+    const size_t mt = (HH + 3) & ~(size_t)3, eps = (size_t)warm_slots(h) * d.I * d.N * d.H * d.A;
+    DevBlock made;
+    if (kind == CEM_NOISE_MIXED && !h->noise_dev) {
+        HIPCHK(prepare_mix_action_noise(d.H));
+        HIPCHK(made.alloc((mt + eps) * 4));
+        HIPCHK(hipMemsetAsync(made.p, 0, (mt + eps) * 4, h->stream));
     }
-    if (kind == CEM_NOISE_WHITE && h->noise_kind == CEM_NOISE_WHITE) return CEM_OK;
-    const bool fresh = kind == CEM_NOISE_MIXED && !h->noise_dev;
-    if (kind == CEM_NOISE_MIXED) { const int st = ensure_noise(h); if (st) return st; }
-    // a handle this call fails on keeps what it had: an allocation made just above goes again (cem_planner_action_noise_dev reports
-    // NULL on a handle that has never been MIXED)
-    auto fail = [&](hipError_t e) { g_last_hip = (int)e; if (fresh) { hipFree(h->noise_dev); h->noise_dev = h->noise_eps = nullptr; h->noise_floats = 0; } return CEM_ERR_HIP; };
-    // Not retire_graph, as the sibling setters: that waits only for a captured plan, and here an EAGER MIXED plan still draining behind
-    // its polled result may be reading the matrix about to be overwritten.  So the wait is unconditional.
-    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) return fail(e);
-    std::vector<float> mix, mix_t;
-    if (kind == CEM_NOISE_MIXED) {
-        const int H = h->d.H;
-        mix.assign(mix_host, mix_host + HH); mix_t.resize(HH);
-        for (int t = 0; t < H; ++t) for (int u = 0; u < H; ++u) mix_t[(size_t)u * H + t] = mix_host[(size_t)t * H + u];
+    // The wait is unconditional — not only for a captured plan, as in the sibling setters: an EAGER MIXED plan still draining behind its
+    // polled result may be reading the matrix about to be overwritten.
+    return commit_launch_change(h, next, true, [&]() -> int {
+        if (kind != CEM_NOISE_MIXED) return CEM_OK;
+        std::vector<float> mix(mix_host, mix_host + HH), mix_t(HH);
+        for (int t = 0; t < d.H; ++t) for (int u = 0; u < d.H; ++u) mix_t[(size_t)u * d.H + t] = mix_host[(size_t)t * d.H + u];
         // (the swap below keeps mix_t's storage alive in the handle for as long as the stream may read it)
-        if (const hipError_t e = hipMemcpyAsync(h->noise_dev, mix_t.data(), HH * 4, hipMemcpyHostToDevice, h->stream); e != hipSuccess) return fail(e);
+        HIPCHK(hipMemcpyAsync(made.p ? made.p : h->noise_dev, mix_t.data(), HH * 4, hipMemcpyHostToDevice, h->stream));
+        if (made.p) { h->noise_dev = made.release<float>(); h->noise_eps = h->noise_dev + mt; h->noise_floats = eps; }
         h->h_mix.swap(mix); h->h_mix_t.swap(mix_t);
-    }
-    drop_graph(h);                                                              // the captured plan holds the other sampler's launches
-    h->noise_kind = kind;
-    return CEM_OK;
+        return CEM_OK;
+    });
 }
 
 int cem_planner_get_action_noise(const cem_planner_t *h, int32_t *kind_out, float *mix_out_host)
 {
     if (!h) return CEM_ERR_INVALID_ARG;
-    if (kind_out) *kind_out = h->noise_kind;
-    if (mix_out_host && h->noise_kind == CEM_NOISE_MIXED) std::memcpy(mix_out_host, h->h_mix.data(), h->h_mix.size() * 4);
+    if (kind_out) *kind_out = h->opt.noise_kind;
+    if (mix_out_host && h->opt.noise_kind == CEM_NOISE_MIXED) std::memcpy(mix_out_host, h->h_mix.data(), h->h_mix.size() * 4);
     return CEM_OK;
 }
 
@@ -2331,32 +2342,22 @@ int cem_planner_set_elite_carry(cem_planner_t *h, const cem_elite_carry_t *ec)
     if ((ec->across_plans != 0 && ec->across_plans != 1) || ec->reserved != 0) return CEM_ERR_INVALID_ARG;
     if (ec->across_plans && (ec->shift < 1 || ec->shift >= d.H)) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
-    if (ec->n_keep) {
-        // the keep reads ONE rank's select; a sharded plan would need the kept rows on every rank and no such run has been made
-        if (d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
-        if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;               // the multi-workgroup selects: the rule cem_planner_set_refit applies
-        if (d.k > CEM_ELITE_MAX_K || !launch_elite_keep || !launch_elite_inject) return CEM_ERR_UNSUPPORTED;
-        if (ec->across_plans && h->batch) return CEM_ERR_UNSUPPORTED;          // a batch handle's rows move between slots (cem_planner_set_carry_slots)
-        // (cem_population.h: the inject's rows must be candidates of every scheduled iteration, and none of them the mean candidate's)
-        for (const IterPlan &ip : h->pop) if (ip.d.N <= ec->n_keep) return CEM_ERR_UNSUPPORTED;
-        if (h->mean_cand && ec->n_keep >= iter_view(h, d.I - 1).d->N - 1) return CEM_ERR_UNSUPPORTED;
-    }
+    PlanOptions next = options_of(h); next.elite = *ec;
+    { const int st = admit_on(h, next); if (st) return st; }
     // a larger store is allocated before anything of the handle changes: a failed allocation leaves it as it was
-    float *grown = nullptr;
+    DevBlock grown;
     const size_t HA = (size_t)d.H * d.A, floats = elite_count_floats(h) + (size_t)warm_slots(h) * ec->n_keep * HA;
-    if (ec->n_keep > h->elite_cap) HIPCHK(hipMalloc((void **)&grown, floats * 4));
+    if (ec->n_keep > h->elite_cap) HIPCHK(grown.alloc(floats * 4));
     // Unconditional, as in cem_planner_set_action_noise: an eager plan still draining behind its polled result may be reading the store
-    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) { g_last_hip = (int)e; if (grown) hipFree(grown); return CEM_ERR_HIP; }
-    if (grown) {
-        if (h->elite_dev) hipFree(h->elite_dev);
-        h->elite_dev = grown; h->elite_cap = ec->n_keep;
-        if (const hipError_t e = hipMemsetAsync(grown, 0, floats * 4, h->stream); e != hipSuccess) {
-            g_last_hip = (int)e; hipFree(grown); h->elite_dev = nullptr; h->elite_cap = 0; h->elite.n_keep = 0; drop_graph(h); return CEM_ERR_HIP;
-        }
-    } else if (h->elite_dev) HIPCHK(hipMemsetAsync(elite_counts(h), 0, (size_t)warm_slots(h) * 4, h->stream));   // every call empties the stores
-    drop_graph(h);                                                              // the captured plan holds the other setting's launches
-    h->elite = *ec; h->elite_clear = false;
-    return CEM_OK;
+    return commit_launch_change(h, next, true, [&]() -> int {
+        if (grown.p) {
+            HIPCHK(hipMemsetAsync(grown.p, 0, floats * 4, h->stream));
+            if (h->elite_dev) hipFree(h->elite_dev);
+            h->elite_dev = grown.release<float>(); h->elite_cap = ec->n_keep;
+        } else if (h->elite_dev) HIPCHK(hipMemsetAsync(elite_counts(h), 0, (size_t)warm_slots(h) * 4, h->stream));   // every call empties the stores
+        h->elite_clear = false;
+        return CEM_OK;
+    });
 }
 
 int cem_planner_set_plan_readout(cem_planner_t *h, int32_t enable)
@@ -2364,40 +2365,32 @@ int cem_planner_set_plan_readout(cem_planner_t *h, int32_t enable)
     if (!h || (enable != 0 && enable != 1)) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
     const Dims &d = h->d;
-    if (enable) {
-        // the tracker reads ONE rank's select and the whole of a candidate's column of `ret`, which a sharded plan splits among the ranks
-        if (d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;
-        if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;               // the multi-workgroup selects: the rule cem_planner_set_refit applies
-        if (d.P > CEM_READOUT_MAX_P || !launch_plan_track) return CEM_ERR_UNSUPPORTED;
-        for (const IterPlan &ip : h->pop) if (select_mode_for(h, ip.d.N) != 1) return CEM_ERR_UNSUPPORTED;
-    }
+    PlanOptions next = options_of(h); next.readout = enable;
+    { const int st = admit_on(h, next); if (st) return st; }
     // the blocks are allocated before anything of the handle changes: a failed allocation leaves it as it was
-    uint32_t *made = nullptr;
-    const size_t words = (size_t)warm_slots(h) * CEM_READOUT_WORDS(d.H, d.A, d.P);
-    if (enable && !h->readout_dev) HIPCHK(hipMalloc((void **)&made, words * 4));
+    DevBlock made;
+    const size_t stride = CEM_READOUT_WORDS(d.H, d.A, d.P), words = (size_t)warm_slots(h) * stride;
+    if (enable && !h->readout_dev) HIPCHK(made.alloc(words * 4));
     // Unconditional, as in cem_planner_set_elite_carry: an eager plan still draining behind its polled result may be writing the blocks
-    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) { g_last_hip = (int)e; if (made) hipFree(made); return CEM_ERR_HIP; }
-    if (made) {
+    return commit_launch_change(h, next, true, [&]() -> int {
+        if (!made.p) return CEM_OK;
         // every block starts as the tracker's reset leaves it: a read-out asked for before any plan says "nothing found"
-        const size_t stride = CEM_READOUT_WORDS(d.H, d.A, d.P);
         std::vector<uint32_t> init(words, 0u);
         for (int b = 0; b < warm_slots(h); ++b) {
             uint32_t *blk = init.data() + (size_t)b * stride;
             blk[0] = 0xff800000u; blk[1] = 0xffffffffu; blk[2] = 0xffffffffu;
             if (h->cfg.variant == CEM_VARIANT_CEM) for (int t = 0; t < d.H; ++t) blk[stride - d.H + t] = 0xffffffffu;
         }
-        if (const hipError_t e = hipMemcpy(made, init.data(), words * 4, hipMemcpyHostToDevice); e != hipSuccess) { g_last_hip = (int)e; hipFree(made); return CEM_ERR_HIP; }
-        h->readout_dev = made;
-    }
-    drop_graph(h);                                                              // the captured plan holds the other setting's launches
-    h->readout = enable;
-    return CEM_OK;
+        HIPCHK(hipMemcpy(made.p, init.data(), words * 4, hipMemcpyHostToDevice));
+        h->readout_dev = made.release<uint32_t>();
+        return CEM_OK;
+    });
 }
 
 int cem_planner_get_plan_readout(const cem_planner_t *h, int32_t *enable_out)
 {
     if (!h || !enable_out) return CEM_ERR_INVALID_ARG;
-    *enable_out = h->readout;
+    *enable_out = h->opt.readout;
     return CEM_OK;
 }
 
@@ -2405,7 +2398,7 @@ int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout
                              float *particle_returns_out_host, int32_t *cost_counts_out_host)
 {
     if (!h || !out || problem < 0 || problem >= warm_slots(h)) return CEM_ERR_INVALID_ARG;
-    if (!h->readout || !h->readout_dev) return CEM_ERR_STATE;
+    if (!h->opt.readout || !h->readout_dev) return CEM_ERR_STATE;
     // the last iteration's tracker runs BEHIND the select that hands the polled result to the host: the stream is drained first
     HIPCHK(hipStreamSynchronize(h->stream));
     const Dims &d = h->d;
@@ -2423,27 +2416,18 @@ int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout
 int cem_planner_get_elite_carry(const cem_planner_t *h, cem_elite_carry_t *out)
 {
     if (!h || !out) return CEM_ERR_INVALID_ARG;
-    *out = h->elite;
+    *out = h->opt.elite;
     return CEM_OK;
 }
 
 int cem_planner_elite_store(cem_planner_t *h, int32_t problem, float *out_host, int32_t *count_out)
 {
     if (!h || problem < 0 || problem >= warm_slots(h) || (!out_host && !count_out)) return CEM_ERR_INVALID_ARG;
-    if (!h->elite.n_keep || !h->elite_dev) return CEM_ERR_STATE;
+    if (!h->opt.elite.n_keep || !h->elite_dev) return CEM_ERR_STATE;
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t row = (size_t)h->elite.n_keep * h->d.H * h->d.A;
+    const size_t row = (size_t)h->opt.elite.n_keep * h->d.H * h->d.A;
     if (out_host) HIPCHK(hipMemcpy(out_host, elite_store(h) + (size_t)problem * row, row * 4, hipMemcpyDeviceToHost));
     if (count_out) HIPCHK(hipMemcpy(count_out, elite_counts(h) + problem, 4, hipMemcpyDeviceToHost));
-    return CEM_OK;
-}
-
-// what both setters of cem_population.h ask of a handle they enable something on
-static int population_admits(const cem_planner *h)
-{
-    if (h->d.W > 1 || h->comm) return CEM_ERR_UNSUPPORTED;      // one rank's select ranks one rank's population
-    if (h->batch) return CEM_ERR_UNSUPPORTED;                   // (a batch handle's launch carries every problem's tiles of ONE plan)
-    if (select_mode_now(h) != 1) return CEM_ERR_UNSUPPORTED;    // the multi-workgroup selects: the rule cem_planner_set_refit applies
     return CEM_OK;
 }
 
@@ -2459,14 +2443,16 @@ int cem_planner_set_population_schedule(cem_planner_t *h, const int32_t *n, int3
         on = on || n[it] != d.N;
     }
     if (h->in_plan) return CEM_ERR_STATE;
+    PlanOptions next = options_of(h); next.pop.clear();
+    if (on) next.pop.assign(n, n + count);
+    // (every population's select mode is asked here, in front of the per-iteration validate below, where it used to be asked behind it:
+    // the arguments above leave validate nothing to refuse on a one-rank handle, and a smaller population never leaves the one-workgroup select)
+    { const int st = admit_on(h, next); if (st) return st; }
     std::vector<IterPlan> plans;
     std::vector<std::vector<Tile6>> lists;
-    char *block = nullptr; uint32_t *flags = (uint32_t *)(h->ws + h->lay.seg_flags); f4 *state = (f4 *)(h->ws + h->lay.seg_state);
+    DevBlock block; uint32_t *flags = (uint32_t *)(h->ws + h->lay.seg_flags); f4 *state = (f4 *)(h->ws + h->lay.seg_state);
     size_t n_ready = 0, flags_off = 0, flags_bytes = 0, state_bytes = 0;
     if (on) {
-        { const int st = population_admits(h); if (st) return st; }
-        for (int it = 0; it < count; ++it) if (h->elite.n_keep && n[it] <= h->elite.n_keep) return CEM_ERR_UNSUPPORTED;
-        if (h->mean_cand && h->elite.n_keep && h->elite.n_keep >= n[d.I - 1] - 1) return CEM_ERR_UNSUPPORTED;
         // every iteration's plan, from the functions create uses, for the configuration that differs in n_samples alone
         plans.resize(d.I); lists.resize(d.I);
         size_t bytes = 0;
@@ -2484,7 +2470,6 @@ int cem_planner_set_population_schedule(cem_planner_t *h, const int32_t *n, int3
                 build_plan_tiles(ip.d, ip.rc, lists[it]);
                 ip.n_tiles = (int)lists[it].size();
                 place_sampler(h, ip.d, pl, &ip.sample_in_rollout, &ip.lean_rollout);
-                if (select_mode_for(h, ip.d.N) != 1) return CEM_ERR_UNSUPPORTED;
                 ip.tiles_off = bytes; bytes += align256(lists[it].size() * sizeof(Tile6));
             }
             if (ip.n_seg > 1) {
@@ -2498,21 +2483,22 @@ int cem_planner_set_population_schedule(cem_planner_t *h, const int32_t *n, int3
         const bool own_seg = flags_bytes > h->lay.seg_state - h->lay.seg_flags || state_bytes > h->lay.ms_hist - h->lay.seg_state;
         if (own_seg) { flags_off = bytes; bytes += align256(flags_bytes) + align256(state_bytes); }
         // allocated and filled before anything of the handle changes: a failed call leaves it as it was
-        HIPCHK(hipMalloc((void **)&block, std::max<size_t>(bytes, 256)));
-        hipError_t e = hipSuccess;
-        for (int it = 0; it < d.I && e == hipSuccess; ++it)
+        HIPCHK(block.alloc(std::max<size_t>(bytes, 256)));
+        char *base = (char *)block.p;
+        for (int it = 0; it < d.I; ++it)
             if (plans[it].tiles_off != (size_t)-1)
-                e = hipMemcpy(block + plans[it].tiles_off, lists[it].data(), lists[it].size() * sizeof(Tile6), hipMemcpyHostToDevice);
-        if (e == hipSuccess && own_seg) e = hipMemset(block + flags_off, 0, align256(flags_bytes) + align256(state_bytes));
-        if (e != hipSuccess) { g_last_hip = (int)e; hipFree(block); return CEM_ERR_HIP; }
-        if (own_seg) { flags = (uint32_t *)(block + flags_off); state = (f4 *)(block + flags_off + align256(flags_bytes)); }
+                HIPCHK(hipMemcpy(base + plans[it].tiles_off, lists[it].data(), lists[it].size() * sizeof(Tile6), hipMemcpyHostToDevice));
+        if (own_seg) {
+            HIPCHK(hipMemset(base + flags_off, 0, align256(flags_bytes) + align256(state_bytes)));
+            flags = (uint32_t *)(base + flags_off); state = (f4 *)(base + flags_off + align256(flags_bytes));
+        }
     }
     // Unconditional, as in cem_planner_set_elite_carry: an eager plan still draining behind its polled result may be reading the old lists
-    if (const hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) { g_last_hip = (int)e; if (block) hipFree(block); return CEM_ERR_HIP; }
-    drop_graph(h);                                                              // the captured plan holds the other setting's launches
-    if (h->pop_dev) hipFree(h->pop_dev);
-    h->pop_dev = block; h->pop.swap(plans); h->pop_seg_flags = flags; h->pop_seg_state = state; h->pop_n_ready = (int)n_ready;
-    return CEM_OK;
+    return commit_launch_change(h, next, true, [&]() -> int {
+        if (h->pop_dev) hipFree(h->pop_dev);
+        h->pop_dev = block.release<char>(); h->pop.swap(plans); h->pop_seg_flags = flags; h->pop_seg_state = state; h->pop_n_ready = (int)n_ready;
+        return CEM_OK;
+    });
 }
 
 int cem_planner_get_population_schedule(const cem_planner_t *h, int32_t *n_out, int32_t count, int32_t *enabled_out)
@@ -2527,20 +2513,15 @@ int cem_planner_set_mean_candidate(cem_planner_t *h, int32_t enable)
 {
     if (!h || (enable != 0 && enable != 1)) return CEM_ERR_INVALID_ARG;
     if (h->in_plan) return CEM_ERR_STATE;
-    if (enable) {
-        { const int st = population_admits(h); if (st) return st; }
-        if (!launch_mean_candidate) return CEM_ERR_UNSUPPORTED;
-        if (h->elite.n_keep && h->elite.n_keep >= iter_view(h, h->d.I - 1).d->N - 1) return CEM_ERR_UNSUPPORTED;   // the inject's rows stay the inject's
-    }
-    { const int st = retire_graph(h); if (st) return st; }
-    h->mean_cand = enable;
-    return CEM_OK;
+    PlanOptions next = options_of(h); next.mean_cand = enable;
+    { const int st = admit_on(h, next); if (st) return st; }
+    return commit_launch_change(h, next, false);
 }
 
 int cem_planner_get_mean_candidate(const cem_planner_t *h, int32_t *enable_out)
 {
     if (!h || !enable_out) return CEM_ERR_INVALID_ARG;
-    *enable_out = h->mean_cand;
+    *enable_out = h->opt.mean_cand;
     return CEM_OK;
 }
 
@@ -2628,10 +2609,8 @@ int cem_planner_comm_init(cem_planner_t *h, const void *id, int32_t n_ranks, int
     if (h->batch) return CEM_ERR_STATE;                                        // batch handles are single-rank
     if (n_ranks != h->d.W || rank != h->d.R) return CEM_ERR_INVALID_ARG;       // the communicator IS the candidate sharding of this handle
     if (h->in_plan) return CEM_ERR_STATE;
-    if (h->noise_kind == CEM_NOISE_MIXED) return CEM_ERR_UNSUPPORTED;          // (cem_planner_set_action_noise refuses a communicator; so the reverse)
-    if (h->elite.n_keep) return CEM_ERR_UNSUPPORTED;                           // (cem_planner_set_elite_carry likewise)
-    if (!h->pop.empty() || h->mean_cand) return CEM_ERR_UNSUPPORTED;           // (cem_planner_set_population_schedule / _mean_candidate likewise)
-    if (h->readout) return CEM_ERR_UNSUPPORTED;                                // (cem_planner_set_plan_readout likewise)
+    PlanOptions next = options_of(h); next.comm = true;
+    { const int st = admit_on(h, next); if (st) return st; }
     Rccl *r = rccl(); if (!r) return CEM_ERR_COMM;
     if (h->comm) { r->CommDestroy(h->comm); h->comm = nullptr; }
     CemNcclId nid; std::memcpy(nid.internal, id, CEM_COMM_ID_BYTES);
@@ -2687,14 +2666,14 @@ int cem_planner_graph_nodes(const cem_planner_t *h, int32_t *nodes_out)
 int cem_planner_rollout_path(const cem_planner_t *h, int32_t *path_out)
 {
     if (!h || !path_out) return CEM_ERR_INVALID_ARG;
-    *path_out = (runs_lean(h, 0) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;       // (the lean kernels draw in place and cannot take a tensor)
+    *path_out = recipe_of(h, 0, false).lean_form ? 1 : 0;
     return CEM_OK;
 }
 
 int cem_planner_rollout_form(const cem_planner_t *h, int32_t it, int32_t *form_out)
 {
     if (!h || !form_out || it < 0 || it >= h->d.I) return CEM_ERR_INVALID_ARG;
-    *form_out = (runs_lean(h, it) && h->noise_kind != CEM_NOISE_MIXED) ? lean_form(h, it) : 0;
+    *form_out = recipe_of(h, it, false).lean_form;
     return CEM_OK;
 }
 
@@ -2711,7 +2690,7 @@ int cem_planner_iteration_plan(const cem_planner_t *h, int32_t it, cem_iteration
     const IterView v = iter_view(h, it);
     out->n_samples = v.d->N; out->chunks_per_tile = v.rc; out->n_tiles = v.n_tiles; out->n_segments = v.n_seg; out->n_pinned = v.n_pinned;
     out->launches = launches_of(h, it);
-    out->rollout_path = (runs_lean(h, it) && h->noise_kind != CEM_NOISE_MIXED) ? 1 : 0;
+    out->rollout_path = recipe_of(h, it, false).lean_form ? 1 : 0;
     out->reserved = 0;
     return CEM_OK;
 }
@@ -2791,7 +2770,7 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
     if ((long long)n_rows * horizon > 0x7fffffffll) return CEM_ERR_UNSUPPORTED;
     const bool cost_obj = h->cfg.variant == CEM_VARIANT_COST;             // compute_mean_costs (safe_cem_mpc.py:98-108): scores = -mean cost
     const bool safe = h->cfg.variant == CEM_VARIANT_SAFE || cost_obj;     // (the safe variant's cost bytes, un-masked by sc_roll's threshold)
-    if (h->cost_m && (long long)horizon * h->cost_m * CEM_MAX_COST_KINDS >= (1ll << 23)) return CEM_ERR_UNSUPPORTED;   // (the encoding of infeasible scores)
+    if (h->opt.cost_m && (long long)horizon * h->opt.cost_m * CEM_MAX_COST_KINDS >= kBudgetTotalLimit) return CEM_ERR_UNSUPPORTED;   // (the encoding of infeasible scores)
     const size_t ret_bytes = align256((size_t)n_rows * 4);
     int st = ensure_scratch(h, ret_bytes + (safe ? (size_t)n_rows * horizon : 0)); if (st) return st;
     ObjectiveParams op{}; op.traj = traj_dev; op.ret = (float *)h->scratch; op.costs = safe ? (uint8_t *)(h->scratch + ret_bytes) : nullptr;
@@ -2799,16 +2778,16 @@ int cem_compute_objective(cem_planner_t *h, const float *traj_dev, int32_t n_row
     hipLaunchKernelGGL(cem_objective_kernel, dim3((unsigned)(((size_t)n_rows * 16 + 255) / 256)), dim3(256), 0, h->stream, op);
     HIPCHK(hipGetLastError());
     const int n_cand = n_rows / d.P;
-    if (h->cost_m && (size_t)n_cand > h->cstat_obj_n) {
+    if (h->opt.cost_m && (size_t)n_cand > h->cstat_obj_n) {
         if (h->cstat_obj) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipFree(h->cstat_obj)); h->cstat_obj = nullptr; h->cstat_obj_n = 0; if (h->last_cstat_problems == 0) h->last_cstat = nullptr; }
         const size_t want = (size_t)n_cand + (size_t)n_cand / 2;
         HIPCHK(hipMalloc((void **)&h->cstat_obj, want * 4));
         h->cstat_obj_n = want;
     }
-    const ReduceParams sp = fill_score(h, op.ret, op.costs, scores_out_dev, h->cost_m ? h->cstat_obj : nullptr, n_cand, horizon, 0, false);
+    const ReduceParams sp = fill_score(h, op.ret, op.costs, scores_out_dev, h->opt.cost_m ? h->cstat_obj : nullptr, n_cand, horizon, 0, false);
     HIPCHK(launch_score(h, sp, 1));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->cost_m) { h->last_cstat = sp.cstat; h->last_cstat_n = n_cand; h->last_cstat_problems = 0; }      // (0: the op's own array)
+    if (h->opt.cost_m) { h->last_cstat = sp.cstat; h->last_cstat_n = n_cand; h->last_cstat_problems = 0; }      // (0: the op's own array)
     return CEM_OK;
 }
 

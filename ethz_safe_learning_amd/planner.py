@@ -319,54 +319,24 @@ class CemPlanner:
         self.layout = lay
         self._call = 0
         self.has_comm = False
-        if cfg.worst_particles:
-            try:
-                self.set_particle_objective('lower_tail', cfg.worst_particles)
-            except Exception:
-                self.close()
-                raise
-        if cfg.constraint != 'beta' or cfg.worst_cost_particles:
-            try:
-                self.set_constraint(cfg.constraint, cfg.worst_cost_particles)
-            except Exception:
-                self.close()
-                raise
-        if cfg.refit != 'uniform':
-            try:
-                self.set_refit(cfg.refit, cfg.refit_temperature)
-            except Exception:
-                self.close()
-                raise
-        if cfg.action_noise != 'white':
-            try:
-                self.set_action_noise(cfg.action_noise, cfg.action_noise_param)
-            except Exception:
-                self.close()
-                raise
-        if cfg.keep_elites:
-            try:
-                self.set_elite_carry(cfg.keep_elites, cfg.shift_elites, cfg.elite_shift)
-            except Exception:
-                self.close()
-                raise
-        if cfg.population:
-            try:
-                self.set_population_schedule(cfg.population)
-            except Exception:
-                self.close()
-                raise
-        if cfg.mean_candidate:
-            try:
-                self.set_mean_candidate(True)
-            except Exception:
-                self.close()
-                raise
-        if cfg.plan_readout:
-            try:
-                self.set_plan_readout(True)
-            except Exception:
-                self.close()
-                raise
+        # the configured options, in this order: (is it configured?, the call that applies it).  A handle that refuses one is closed
+        options = (
+            (cfg.worst_particles, lambda: self.set_particle_objective('lower_tail', cfg.worst_particles)),
+            (cfg.constraint != 'beta' or cfg.worst_cost_particles, lambda: self.set_constraint(cfg.constraint, cfg.worst_cost_particles)),
+            (cfg.refit != 'uniform', lambda: self.set_refit(cfg.refit, cfg.refit_temperature)),
+            (cfg.action_noise != 'white', lambda: self.set_action_noise(cfg.action_noise, cfg.action_noise_param)),
+            (cfg.keep_elites, lambda: self.set_elite_carry(cfg.keep_elites, cfg.shift_elites, cfg.elite_shift)),
+            (cfg.population, lambda: self.set_population_schedule(cfg.population)),
+            (cfg.mean_candidate, lambda: self.set_mean_candidate(True)),
+            (cfg.plan_readout, lambda: self.set_plan_readout(True)),
+        )
+        try:
+            for configured, apply in options:
+                if configured:
+                    apply()
+        except Exception:
+            self.close()
+            raise
         self.have_device_weights = False              # the last weight sync came from device memory (set_weights_dev / set_weights_from)
         # the generate_action hot path: staging buffers and their ctypes views are made once (a.ctypes.data_as and the two small
         # numpy allocations were 12 of the 17 us the wrapper added to a 1.9-ms plan)

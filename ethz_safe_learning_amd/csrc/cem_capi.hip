@@ -12,6 +12,7 @@
 #include "cem_train_tile.h"
 #include "cem_forward.h"
 #include "cem_rollout_split.h"
+#include "cem_rollout_bf16.h"
 #include "cem_rollout_wide.h"
 #include "cem_pack.h"
 #include "../../include/cem_mpc.h"
@@ -46,6 +47,7 @@ struct Dims {
     int act_q0, act_nq;              // feature quads of the network input that hold action features: [act_q0, act_q0 + act_nq)
     bool wide;                       // units > 128 or an activation other than relu: the generic rollout kernel (cem_rollout_wide.h)
     bool split;                      // precision CEM_PRECISION_SPLIT_BF16X3: cem_rollout_split.h (weight stream in 6 KB chunk groups)
+    bool bf16;                       // precision CEM_PRECISION_BF16: cem_rollout_bf16.h (weight stream in 2 KB chunk groups, one bf16 plane)
     int wave_groups[4]; uint32_t wave_off_f4[4]; uint32_t member_stride_f4;
     size_t nat_member_floats;
 };
@@ -111,8 +113,10 @@ int validate(const cem_config_t *c)
     if (c->chunks_per_tile < 0 || c->chunks_per_tile > 4) return CEM_ERR_INVALID_ARG;
     if (c->rollout_segments < 0 || c->rollout_segments > 64) return CEM_ERR_INVALID_ARG;
     if (c->select_mode < 0 || c->select_mode > 3) return CEM_ERR_INVALID_ARG;
-    if (c->precision != CEM_PRECISION_FP32 && c->precision != CEM_PRECISION_SPLIT_BF16X3) return CEM_ERR_INVALID_ARG;
-    if (c->precision == CEM_PRECISION_SPLIT_BF16X3 && (c->units > CEM_U || c->activation != CEM_ACT_RELU)) return CEM_ERR_UNSUPPORTED;
+    if (c->precision != CEM_PRECISION_FP32 && c->precision != CEM_PRECISION_SPLIT_BF16X3 && c->precision != CEM_PRECISION_BF16) return CEM_ERR_INVALID_ARG;
+    if (c->precision != CEM_PRECISION_FP32 && (c->units > CEM_U || c->activation != CEM_ACT_RELU)) return CEM_ERR_UNSUPPORTED;
+    // the reduced-precision mode's arithmetic is its contract: the diagnostic that routes a handle to the generic fp32 kernel (make_dims) is refused
+    if (c->precision == CEM_PRECISION_BF16 && std::getenv("CEM_FORCE_GENERIC_ROLLOUT") != nullptr) return CEM_ERR_UNSUPPORTED;
     if ((long long)c->particles * c->n_samples > (1ll << 30)) return CEM_ERR_UNSUPPORTED;
     return CEM_OK;
 }
@@ -128,11 +132,13 @@ Dims make_dims(const cem_config_t *c)
     d.act_q0 = d.O / 4; d.act_nq = (d.Din + 3) / 4 - d.act_q0;
     d.wide = d.U > CEM_U || c->activation != CEM_ACT_RELU || std::getenv("CEM_FORCE_GENERIC_ROLLOUT") != nullptr;   // (the variable: a diagnostic, scripts/sweep_configs.py)
     d.split = !d.wide && c->precision == CEM_PRECISION_SPLIT_BF16X3;
+    d.bf16 = !d.wide && c->precision == CEM_PRECISION_BF16;
     uint32_t off = 0;
     for (int w = 0; w < 4; ++w) {
-        // fp32 stream: 2 KB groups, one per 16-feature input block; split stream: 6 KB groups, one per K = 32 chunk (two blocks)
-        const int per_stage = d.split ? CEM_SPLIT_CHUNKS : CEM_NG;
-        int g = (d.split ? cem_split_l0_chunks(d.NFW) : d.KF0) + per_stage * (d.L - 1);
+        // fp32 stream: 2 KB groups, one per 16-feature input block; split stream: 6 KB groups, one per K = 32 chunk (two blocks);
+        // bf16 stream: 2 KB groups, one per K = 32 chunk
+        const int per_stage = (d.split || d.bf16) ? CEM_SPLIT_CHUNKS : CEM_NG;
+        int g = (d.split ? cem_split_l0_chunks(d.NFW) : d.bf16 ? cem_bf16_l0_chunks(d.NFW) : d.KF0) + per_stage * (d.L - 1);
         for (int i = 0; i < d.NFW; ++i) if (w + 4 * i < d.KB_obs) g += per_stage;
         d.wave_groups[w] = g; d.wave_off_f4[w] = off; off += (uint32_t)g * (d.split ? 384u : 128u);
     }
@@ -237,6 +243,46 @@ void pack_member_split(const Dims &d, const float *nat, uint16_t *out)
     }
 }
 
+// Weight stream of (member, wave) for cem_rollout_bf16.h: pack_member_split's groups with ONE plane — 2 KB, [a][b], each [64 lanes][8 bf16],
+// the same k slots in the same visiting order — every weight rounded to bf16 once, to nearest even (cem_rn_bf16_bits).
+void pack_member_bf16(const Dims &d, const float *nat, uint16_t *out)
+{
+    const NatOff no = nat_offsets(d);
+    std::memset(out, 0, (size_t)d.member_stride_f4 * 16);
+    for (int w = 0; w < 4; ++w) {
+        uint16_t *dst = out + (size_t)d.wave_off_f4[w] * 8;
+        auto emit = [&](const float *W, int in_dim, int out_dim, int ld, int F, int ab, int Gout) {
+            for (int lane = 0; lane < 64; ++lane) {
+                const int kq = lane >> 4, i = lane & 15;
+                for (int s = 0; s < 8; ++s) {
+                    const int k = 16 * (2 * F + (s >> 2)) + 4 * kq + (s & 3), o = 16 * Gout + i;
+                    const float v = (k < in_dim && o < out_dim) ? W[(size_t)k * ld + o] : 0.f;
+                    dst[((size_t)ab * 64 + lane) * 8 + s] = (uint16_t)(cem_rn_bf16_bits(v) >> 16);
+                }
+            }
+        };
+        for (int P = 0; P < cem_bf16_l0_chunks(d.NFW); ++P) {     // layer 0: chunks in ascending order (no own chunk); chunks past the input are zero
+            emit(nat + no.W[0], d.Din, d.U, d.U, P, 0, 2 * w); emit(nat + no.W[0], d.Din, d.U, d.U, P, 1, 2 * w + 1);
+            dst += 1024;
+        }
+        for (int l = 1; l < d.L; ++l)
+            for (int P = 0; P < CEM_SPLIT_CHUNKS; ++P) {
+                const int F = cem_split_perm(w, P);
+                emit(nat + no.W[l], d.U, d.U, d.U, F, 0, 2 * w); emit(nat + no.W[l], d.U, d.U, d.U, F, 1, 2 * w + 1);
+                dst += 1024;
+            }
+        for (int i = 0; i < d.NFW; ++i) {
+            const int Fo = w + 4 * i;
+            if (Fo >= d.KB_obs) continue;
+            for (int P = 0; P < CEM_SPLIT_CHUNKS; ++P) {          // heads: a = mean, b = variance of observation block Fo
+                const int F = cem_split_perm(w, P);
+                emit(nat + no.Wmu, d.U, d.O, d.O, F, 0, Fo); emit(nat + no.Wvar, d.U, d.O, d.O, F, 1, Fo);
+                dst += 1024;
+            }
+        }
+    }
+}
+
 // Weight image of one member for cem_rollout_wide_kernel: 1 KB groups [64 lanes][4] in cem_wide_base / cem_wide_groups order;
 // lane (q, j), word r of group (k block kb, output block ob) = W[16 kb + 4 q + r][16 ob + j], zero past the matrix.
 // rows of the per-member feature table (RolloutParams::etab): the wide kernel's hidden layers are up to 256 features = two rows each
@@ -291,23 +337,24 @@ std::vector<PackDesc> build_pack_table(const Dims &d)
         return t;
     }
     for (int w = 0; w < 4; ++w) {                         // the waves' streams follow each other (Dims::wave_off_f4)
-        const int n0 = d.split ? cem_split_l0_chunks(d.NFW) : d.KF0, per_stage = d.split ? CEM_SPLIT_CHUNKS : CEM_NG;
+        const bool chunked = d.split || d.bf16;           // K = 32 chunks in cem_split_perm order (else 16-feature blocks, cem_perm_*)
+        const int n0 = d.split ? cem_split_l0_chunks(d.NFW) : d.bf16 ? cem_bf16_l0_chunks(d.NFW) : d.KF0, per_stage = chunked ? CEM_SPLIT_CHUNKS : CEM_NG;
         for (int P = 0; P < n0; ++P) {
-            const int F = d.split ? P : cem_perm_l0(w, d.NFW, P);
+            const int F = chunked ? P : cem_perm_l0(w, d.NFW, P);
             unit(no.W[0], d.Din, d.U, F, 2 * w); unit(no.W[0], d.Din, d.U, F, 2 * w + 1);
         }
         for (int l = 1; l < d.L; ++l)
             for (int P = 0; P < per_stage; ++P) {
-                const int F = d.split ? cem_split_perm(w, P) : cem_perm_hidden(w, P);
-                const int Fb = d.split ? F : cem_perm_hidden(w, P < 2 ? (P ^ 1) : P);     // fp32: the second accumulator takes its own blocks swapped
+                const int F = chunked ? cem_split_perm(w, P) : cem_perm_hidden(w, P);
+                const int Fb = chunked ? F : cem_perm_hidden(w, P < 2 ? (P ^ 1) : P);     // fp32: the second accumulator takes its own blocks swapped
                 unit(no.W[l], d.U, d.U, F, 2 * w); unit(no.W[l], d.U, d.U, Fb, 2 * w + 1);
             }
         for (int i = 0; i < d.NFW; ++i) {
             const int Fo = w + 4 * i;
             if (Fo >= d.KB_obs) continue;
             for (int P = 0; P < per_stage; ++P) {
-                const int F = d.split ? cem_split_perm(w, P) : cem_perm_hidden(w, P);
-                const int Fb = d.split ? F : cem_perm_hidden(w, P < 2 ? (P ^ 1) : P);
+                const int F = chunked ? cem_split_perm(w, P) : cem_perm_hidden(w, P);
+                const int Fb = chunked ? F : cem_perm_hidden(w, P < 2 ? (P ^ 1) : P);
                 unit(no.Wmu, d.U, d.O, F, Fo); unit(no.Wvar, d.U, d.O, Fb, Fo);
             }
         }
@@ -526,6 +573,30 @@ int auto_chunks_split(const Dims &d)
     return best;
 }
 
+// Tile size of the bf16 rollout (cem_rollout_bf16.h): auto_chunks_split's rule on a table of its own.  A third of the split kernel's
+// weight bytes and a sixth of its MFMAs per chunk; what decides between the sizes is again how many tiles the busiest CU gets
+// (ceil(tiles / CUs)) and how many of them run side by side.  Plan ms (5 iterations, H = 30) of a device whose busiest CU runs m
+// co-resident tiles of rc chunks, measured over population sizes (scripts/sweep_bf16_tiles.py, profiles/bf16_tile_sizes.txt: the rule
+// picks the fastest size in 15 of its 16 rows and one 0.6 % behind in the other); only the ratios matter.  Residency: registers (512 / VGPRs of the planning instantiations:
+// 113 145 171 205 | 155 185 221 253), LDS never binds.
+static const double kBf16Step[2][4][4] = {{{0.45, 0.61, 0.82, 1.07}, {0.52, 0.70, 0.935, 0}, {0.61, 0.84, 0, 0}, {0.73, 0.985, 0, 0}},
+                                          {{0.62, 0.865, 1.187, 0}, {0.79, 1.075, 0, 0}, {0.97, 1.35, 0, 0}, {1.17, 1.67, 0, 0}}};
+static const int kBf16Resident[2][4] = {{4, 3, 2, 2}, {3, 2, 2, 2}};
+int auto_chunks_bf16(const Dims &d)
+{
+    int best = 1; double bestc = 1e30;
+    for (int rc = 1; rc <= 4; ++rc) {
+        std::vector<Tile6> t; build_plan_tiles(d, rc, t);
+        const long per_cu = (long)((t.size() + num_cus() - 1) / num_cus());
+        const int R = kBf16Resident[d.NFW - 1][rc - 1];
+        const double *ts = kBf16Step[d.NFW - 1][rc - 1];
+        const double cost = (double)(per_cu / R) * ts[R - 1] + (per_cu % R ? ts[per_cu % R - 1] : 0.0);
+        // rc ascends: within 2 % the larger tile wins (fewer workgroups, less weight traffic)
+        if (cost <= bestc * 1.02) { best = rc; bestc = std::min(bestc, cost); }
+    }
+    return best;
+}
+
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
@@ -546,9 +617,10 @@ Plan make_plan(const cem_config_t *c, const Dims &d, int mb = 0)
     const int seg_req = mb > 0 ? 1 : c->rollout_segments;
     pl.rc = d.wide ? 1 : (c->chunks_per_tile ? c->chunks_per_tile : auto_chunks(d, seg_req, std::max(mb, 1)));   // the wide kernel: 16-row tiles
     if (d.split && !c->chunks_per_tile) pl.rc = auto_chunks_split(d);
+    if (d.bf16 && !c->chunks_per_tile) pl.rc = auto_chunks_bf16(d);
     std::vector<Tile6> t; build_plan_tiles(d, pl.rc, t);
     pl.n_tiles = (int)t.size();
-    pl.n_seg = (d.wide || d.split) ? 1 : segments_for(d, pl.rc, t.size(), seg_req);
+    pl.n_seg = (d.wide || d.split || d.bf16) ? 1 : segments_for(d, pl.rc, t.size(), seg_req);
     pl.seg_len = (d.H + pl.n_seg - 1) / pl.n_seg;
     pl.n_seg = (d.H + pl.seg_len - 1) / pl.seg_len;
     // tiles every CU gets the same number of stay whole ("pinned"); only the remainder floats in segments
@@ -1016,6 +1088,7 @@ int cem_pack_weights_host(const cem_config_t *cfg, const float *blob, float *pac
     if (d.wide) return CEM_ERR_UNSUPPORTED;
     for (int m = 0; m < d.E; ++m) {
         if (d.split) pack_member_split(d, blob + (size_t)m * d.nat_member_floats, reinterpret_cast<uint16_t *>(packed + (size_t)m * d.member_stride_f4 * 4));
+        else if (d.bf16) pack_member_bf16(d, blob + (size_t)m * d.nat_member_floats, reinterpret_cast<uint16_t *>(packed + (size_t)m * d.member_stride_f4 * 4));
         else pack_member(d, blob + (size_t)m * d.nat_member_floats, packed + (size_t)m * d.member_stride_f4 * 4);
     }
     return CEM_OK;
@@ -1066,7 +1139,7 @@ int cem_rollout_residency(int32_t chunks_per_tile, int32_t input_blocks_per_wave
 // fit its LDS allowance.  Everything else — and any plan given explicit noise tensors — runs the generic kernels.
 static bool lean_eligible(const cem_planner *h, const Dims &d, int rc, bool sample_in_rollout)
 {
-    return launch_rollout_lean != nullptr && !d.wide && !d.split && rc == 1 && d.NFW == 1 && d.L == 4 && d.O % 4 == 0 && h->cfg.world_size == 1 && !h->batch &&
+    return launch_rollout_lean != nullptr && !d.wide && !d.split && !d.bf16 && rc == 1 && d.NFW == 1 && d.L == 4 && d.O % 4 == 0 && h->cfg.world_size == 1 && !h->batch &&
            sample_in_rollout && CEM_LEAN_ACT_LDS_BYTES(d.H, (d.A + 3) / 4) <= CEM_LEAN_ACT_LDS_MAX;
 }
 
@@ -1079,7 +1152,10 @@ static bool lean_eligible(const cem_planner *h, const Dims &d, int rc, bool samp
 static void place_sampler(const cem_planner *h, const Dims &d, const Plan &pl, bool *sample_in_rollout, bool *lean_rollout)
 {
     const size_t nb = (size_t)warm_slots(h);
-    const int slots = real_cus() * ((d.wide || d.split) ? 1 : resident_workgroups(d.NFW, pl.rc, pl.n_seg > 1));
+    // (the bf16 kernel: one slot per CU, like the split kernel — its launch is short enough that a second co-resident tile's prologue,
+    // which samples every candidate once per particle, shows: B4's 512 four-chunk tiles 2.70 ms per plan inside against 2.48 in a launch
+    // of its own, the shipped safe shape 0.603 against 0.612, B2 inside either way; profiles/bf16_rollout_isa.txt)
+    const int slots = real_cus() * ((d.wide || d.split || d.bf16) ? 1 : resident_workgroups(d.NFW, pl.rc, pl.n_seg > 1));
     *sample_in_rollout = (long long)nb * pl.n_tiles <= slots;          // (a batch handle: all its problems' tiles in one launch)
     if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
         *sample_in_rollout = std::strcmp(e, "kernel") != 0;
@@ -1093,6 +1169,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
 {
     int st = mb ? validate_batch(cfg, mb) : validate(cfg); if (st) return st;
     if (!workspace || !out) return CEM_ERR_INVALID_ARG;
+    if (cfg->precision == CEM_PRECISION_BF16 && (launch_rollout_bf16 == nullptr || launch_pack_bf16 == nullptr)) return CEM_ERR_UNSUPPORTED;   // a build without cem_rollout_bf16.hip
     warn_if_two_hip_runtimes();
     cem_planner *h = new (std::nothrow) cem_planner();
     if (!h) return CEM_ERR_INVALID_ARG;
@@ -1317,6 +1394,7 @@ int cem_planner_set_weights(cem_planner_t *h, const float *blob, size_t n_floats
     for (int m = 0; m < d.E; ++m) {
         const float *nat = blob + (size_t)m * d.nat_member_floats;
         if (d.split) pack_member_split(d, nat, reinterpret_cast<uint16_t *>(packed.data() + (size_t)m * d.member_stride_f4 * 4));
+        else if (d.bf16) pack_member_bf16(d, nat, reinterpret_cast<uint16_t *>(packed.data() + (size_t)m * d.member_stride_f4 * 4));
         else pack_member(d, nat, packed.data() + (size_t)m * d.member_stride_f4 * 4);
         for (int l = 0; l < d.L; ++l) std::memcpy(&bh[((size_t)m * d.L + l) * CEM_U], nat + no.b[l], d.U * 4);
         std::memcpy(&bmu[(size_t)m * CEM_U], nat + no.bmu, d.O * 4);
@@ -1358,6 +1436,7 @@ int cem_planner_set_weights_dev(cem_planner_t *h, const float *blob_dev, size_t 
     const dim3 grid(wgs * (unsigned)d.E), block(64 * CEM_PACK_WAVES);
     if (d.wide) hipLaunchKernelGGL(cem_pack_wide_kernel, grid, block, 0, h->stream, p);
     else if (d.split) hipLaunchKernelGGL(cem_pack_split_kernel, grid, block, 0, h->stream, p);
+    else if (d.bf16) launch_pack_bf16(p, grid.x, h->stream);
     else hipLaunchKernelGGL(cem_pack_fp32_kernel, grid, block, 0, h->stream, p);
     cem_pack_trained_bias_t b{};
     b.blob = blob_dev; b.bias_h = (float *)(h->ws + h->lay.bias_h); b.bias_mu = (float *)(h->ws + h->lay.bias_mu);
@@ -1638,6 +1717,7 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
     }
     else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, rp.eps_model ? 1 : 0));
     else if (d.split) HIPCHK(launch_rollout_split(v.rc, d.NFW, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
+    else if (d.bf16) HIPCHK(launch_rollout_bf16(v.rc, d.NFW, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
     else if (rp.eps_model) HIPCHK(launch_rollout<1>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     else if (queued) {
         rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
@@ -2755,6 +2835,7 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
     rp.H = horizon; rp.Bloc = n_rows; rp.Btot = n_rows; rp.it = 0; rp.variant = 0; rp.check_done = 0;
     hipError_t e = d.wide ? launch_rollout_wide(h, rp, (int)tiles.size(), 1)
                  : d.split ? launch_rollout_split(rc, d.NFW, 1, rp, (int)tiles.size(), h->stream)
+                 : d.bf16 ? launch_rollout_bf16(rc, d.NFW, 1, rp, (int)tiles.size(), h->stream)
                            : launch_rollout<1>(rc, d.NFW, rp, (int)tiles.size(), h->stream);
     hipError_t e2 = hipStreamSynchronize(h->stream);
     HIPCHK(e); HIPCHK(e2);

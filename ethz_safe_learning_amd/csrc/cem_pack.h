@@ -12,6 +12,9 @@
 //   wide   unit = one 1 KB group of cem_rollout_wide.h: the same map
 //   split  unit = the a or b half of a 6 KB group: [plane(3)][lane(64)][s(8)] bf16; lane 16 q + i, slot s = piece `plane` of
 //          W[16 (2 kb + s / 4) + 4 q + s % 4][16 ob + i]   (cem_split3_bits: the host's split, and -ffp-contract=off here as there)
+//   bf16   unit = the a or b half of a 2 KB group of cem_rollout_bf16.h: [lane(64)][s(8)] bf16, the same slots, each weight rounded
+//          once (cem_rn_bf16_bits).  Its kernel, cem_pack_bf16_kernel, lives in cem_rollout_bf16.hip, which takes the types and helpers
+//          of this header (CEM_DEVICE_PRIMITIVES_ONLY, as with cem_device.h) and none of its kernels.
 // The gathered reads run along the output index for the 16 lanes of a lane group (64 B segments); the shipped ensemble is 4.4 MB in all.
 // One launch per image covers all E members; no atomics, no spin loops, nothing crosses a workgroup.
 #pragma once
@@ -60,6 +63,11 @@ __device__ __forceinline__ f4 cem_pack_quad(const PackDesc d, const float *nat, 
     for (int r = 0; r < 4; ++r) v[r] = cem_pack_at(d, nat, 16 * d.kb + 4 * q + r, 16 * d.ob + i);
     return v;
 }
+
+// the bf16 image from cem_rollout_bf16.hip.  Weak: a library built from cem_capi.hip alone has no bf16 rollout (cem_rollout_bf16.h).
+__attribute__((weak)) void launch_pack_bf16(const cem_pack_trained_t &p, unsigned grid, hipStream_t st);
+
+#ifndef CEM_DEVICE_PRIMITIVES_ONLY   // (a second translation unit takes the types and helpers above, not the plain kernels: cem_rollout_bf16.hip)
 
 // the tuned rollout's stream (pack_member): 2 KB groups [g(2)][lane(64)][r(4)], two units each
 __global__ __launch_bounds__(64 * CEM_PACK_WAVES) void cem_pack_fp32_kernel(const cem_pack_trained_t p)
@@ -138,3 +146,5 @@ __global__ __launch_bounds__(256) void cem_pack_bias_kernel(const cem_pack_train
     *reinterpret_cast<f4 *>(p.etab + ((size_t)m * et_rows + et_row) * CEM_U + f0) = v;
     if (out) *reinterpret_cast<f4 *>(out + f0) = v;
 }
+
+#endif  // CEM_DEVICE_PRIMITIVES_ONLY

@@ -62,7 +62,8 @@ class PlannerConfig:
     chunks_per_tile: int = 0
     use_graph: bool = False
     rollout_segments: int = 0          # 0 auto, 1 off, n > 1: horizon-segment work queue (cem_mpc.h)
-    precision: str = 'fp32'            # 'fp32' | 'bf16x3' (enum cem_precision: exact three-way bf16 split products, opt-in)
+    precision: str = 'fp32'            # 'fp32' | 'bf16x3' (exact three-way bf16 split products: fp32-grade) | 'bf16' (REDUCED precision: the
+                                       # operands of every dense stage rounded to bf16 once, bf16_reference_forward) — enum cem_precision, opt-in
     select_mode: int = 0               # 0 auto, 1 one-workgroup select, 2 multi-workgroup chain, 3 the chain fused into one launch (cem_mpc.h)
     constraint: str = 'beta'           # 'beta': the reference's Beta filter | 'budget': return within a cost budget (cem_planner_set_constraint,
                                        # CEM_CONSTRAINT_BUDGET; 'safe' handles only); not in cem_config_t: set after create.  The budget VALUE is
@@ -100,7 +101,41 @@ PARTICLE_OBJECTIVES = {'mean': _capi.CEM_PARTICLES_MEAN, 'lower_tail': _capi.CEM
 CONSTRAINTS = {'beta': _capi.CEM_CONSTRAINT_BETA, 'budget': _capi.CEM_CONSTRAINT_BUDGET}
 REFITS = {'uniform': _capi.CEM_REFIT_UNIFORM, 'softmax': _capi.CEM_REFIT_SOFTMAX}
 ACTION_NOISES = ('white', 'powerlaw', 'ar1')
+PRECISIONS = {'fp32': 0, 'bf16x3': 1, 'bf16': 2}   # enum cem_precision
 INFEASIBLE_BELOW = np.float32(-2.0 ** 100)          # cem_mpc.h CEM_INFEASIBLE_BELOW: a constrained score is feasible iff it lies above
+
+
+def rn_bf16(x) -> np.ndarray:
+    """x (taken as float32) rounded to bf16 — 8 significand bits, round to nearest, ties to even — and returned as float32: bit for bit
+    what the library does to a weight when it packs a precision='bf16' image (cem_rn_bf16_bits) and what v_cvt_pk_bf16_f32 does to an
+    activation on the device.  Finite inputs below the largest bf16 (3.39e38); signed zeros and denormals keep their sign and round like
+    every other value."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = (u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) & np.uint64(0xFFFF0000)
+    return r.astype(np.uint32).view(np.float32).reshape(np.shape(x))
+
+
+def bf16_reference_forward(x, member_weights):
+    """The arithmetic contract of precision='bf16' for one ensemble member, in NumPy with float64 accumulation: (mu, var) of the rows x
+    [B, obs + act] (the SCALED network input), `member_weights` = dict(W=[...], b=[...], W_mu, b_mu, W_var, b_var) in Keras layout
+    [in, out].  Weights and the input of every dense stage — x itself and every post-ReLU activation, taken as float32 — are rounded
+    with rn_bf16; products and sums are exact / float64 from the float32 bias; a stage's output is rounded to float32 (the device's
+    accumulator) before the ReLU.  Softplus + 1e-4 is float32, as everywhere.  Returns arrays of x's dtype.  The device differs from
+    this by the order of its float32 sums alone."""
+    dt = np.asarray(x).dtype
+    def dense(h, W, b):
+        return (rn_bf16(h).astype(np.float64) @ rn_bf16(W).astype(np.float64) + np.asarray(b, np.float32).astype(np.float64)).astype(np.float32)
+    h = np.asarray(x, np.float32)
+    for W, b in zip(member_weights['W'], member_weights['b']):
+        h = np.maximum(dense(h, W, b), np.float32(0))
+    mu = dense(h, member_weights['W_mu'], member_weights['b_mu'])
+    z = dense(h, member_weights['W_var'], member_weights['b_var'])
+    # tf.math.softplus in float32 (threshold log(eps) + 2), + 1e-4
+    thr = np.float32(np.log(np.finfo(np.float32).eps) + 2.0)
+    with np.errstate(over='ignore'):
+        ez = np.exp(z)
+    var = np.where(z > -thr, z, np.where(z < thr, ez, np.log1p(ez))).astype(np.float32) + np.float32(1e-4)
+    return mu.astype(dt), var.astype(dt)
 
 
 def powerlaw_mixing(H, beta, dtype=np.float32) -> np.ndarray:
@@ -261,7 +296,7 @@ def to_c_config(cfg: PlannerConfig) -> _capi.CemConfig:
         c.scorer.cost_lo[i], c.scorer.cost_hi[i], c.scorer.cost_size[i] = int(lo), int(hi), float(size)
     c.world_size, c.rank, c.chunks_per_tile, c.use_graph = cfg.world_size, cfg.rank, cfg.chunks_per_tile, int(cfg.use_graph)
     c.rollout_segments = int(cfg.rollout_segments)
-    c.precision = {'fp32': 0, 'bf16x3': 1}[cfg.precision]
+    c.precision = PRECISIONS[cfg.precision]
     c.select_mode = int(cfg.select_mode)
     return c
 

@@ -98,7 +98,8 @@ class CemMpc(MpcPolicy):
         self.seed = seed
         self.device = device
         self.use_graph = use_graph
-        self.precision = precision                     # 'fp32' | 'bf16x3' (PlannerConfig.precision; beyond the reference's kwargs)
+        self.precision = precision                     # 'fp32' | 'bf16x3' (fp32-grade) | 'bf16' (reduced precision: dense operands rounded to
+                                                       # bf16) — PlannerConfig.precision; beyond the reference's kwargs
         # warm start (beyond the reference's kwargs, like precision): see the module docstring
         self.warm_start, self.warm_shift, self.warm_tail, self.warm_sigma, self.warm_sigma_floor = bool(warm_start), warm_shift, warm_tail, warm_sigma, warm_sigma_floor
         # risk-averse planning (beyond the reference's kwargs): see the module docstring

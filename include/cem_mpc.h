@@ -30,7 +30,8 @@
  *                                  (the fused select's grid, where the sampler runs) always use the device's real multiProcessorCount.
  *   CEM_NO_POLL                    cem_planner_plan waits for a captured plan with hipStreamSynchronize instead of polling the result block in
  *                                  pinned memory (polling spins one host core for the duration of the plan and returns ~10 us sooner).
- *   CEM_FORCE_GENERIC_ROLLOUT      every configuration on the width-generic rollout kernel;  CEM_TRAIN_GEMM_KERNEL: the GEMM-by-GEMM trainer.
+ *   CEM_FORCE_GENERIC_ROLLOUT      every configuration on the width-generic rollout kernel (a CEM_PRECISION_BF16 configuration is refused
+ *                                  while it is set, CEM_ERR_UNSUPPORTED: that kernel multiplies in fp32);  CEM_TRAIN_GEMM_KERNEL: the GEMM-by-GEMM trainer.
  */
 #ifndef CEM_MPC_H
 #define CEM_MPC_H
@@ -100,12 +101,19 @@ typedef struct cem_scorer {
     float cost_size[CEM_MAX_COST_KINDS];
 } cem_scorer_t;
 
-/* How the rollout's dense layers multiply.  Both accumulate in fp32 and keep every term of a product down to 2^-24 of it.
+/* How the rollout's dense layers multiply.  All three accumulate in fp32, starting from the fp32 bias; everything outside the dense
+ * layers (state, normaliser, heads' outputs, softplus, noise, scorer, bookkeeping) is the same fp32 code in all three.
  * CEM_PRECISION_FP32: v_mfma_f32_16x16x4_f32 (the default; what every number in BASELINE / DESIGN is quoted on unless labelled).
  * CEM_PRECISION_SPLIT_BF16X3: weights and activations as exact three-way bf16 splits, the six leading bf16 x bf16 products per
  * fp32 product on v_mfma_f32_16x16x32_bf16 (csrc/cem_rollout_split.h).  Same oracle, same tolerances, not bit-identical to the
- * fp32 form; units <= 128 and relu only. */
-enum cem_precision { CEM_PRECISION_FP32 = 0, CEM_PRECISION_SPLIT_BF16X3 = 1 };
+ * fp32 form; units <= 128 and relu only.  These two keep every term of a product down to 2^-24 of it.
+ * CEM_PRECISION_BF16: a REDUCED-precision mode (csrc/cem_rollout_bf16.h).  Weights are rounded to bf16 (8 significand bits, round to
+ * nearest even) when they are packed, the inputs of every dense stage — the scaled layer-0 input, observation and action features
+ * alike, and every post-ReLU hidden activation — where they are published; one v_mfma_f32_16x16x32_bf16 per product block, products
+ * exact in its fp32 accumulator.  An operand carries a relative error of up to 2^-8: the results are NOT those of the fp32 form at its
+ * tolerances (measured: profiles/bf16_error.json, README); they are those of that rounding model (planner.bf16_reference_forward) at
+ * the fp32 kernels' tolerances.  Finite inputs below the largest bf16; units <= 128 and relu only.  Never chosen by the library. */
+enum cem_precision { CEM_PRECISION_FP32 = 0, CEM_PRECISION_SPLIT_BF16X3 = 1, CEM_PRECISION_BF16 = 2 };
 
 /* Constructor kwargs of CemMpc / SafeCemMpc (cem_mpc.py:7-17, safe_cem_mpc.py:8-19)
  * + the model dims of TransitionModel/MlpEnsemble (transition_model.py:8-21,

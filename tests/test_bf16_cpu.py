@@ -106,9 +106,10 @@ def test_trajectory_bars_with_the_fp32_emulation_in_the_kernels_place(dims, orde
 @pytest.mark.parametrize('order', [0, 1, 2])
 def test_score_bars_with_the_fp32_emulation_in_the_kernels_place(O, A, variant, order):
     """GPU test 3 with emu32 for the kernel: the exclusion cap, the admissible outcomes of the near-threshold candidates and the two
-    conditions on the rest."""
-    ratio, near = bc.check_scores(bc.score_stand_in(O, A, variant, order), bc.score_case(O, A, variant), 'obs %d %s' % (O, variant))
-    print('obs %d %s: ratio %.4f, %.1f %% of the candidates near a threshold' % (O, variant, ratio, 100 * near))
+    conditions on the rest, and the two quantile conditions on the flip-free candidates."""
+    ratio, near, med, p90 = bc.check_scores(bc.score_stand_in(O, A, variant, order), bc.score_case(O, A, variant), 'obs %d %s' % (O, variant))
+    print('obs %d %s: ratio %.4f, %.1f %% of the candidates near a threshold; over the flip-free ones median ratio %.4f, 90th percentile ratio %.4f' % (
+        O, variant, ratio, 100 * near, med, p90))
 
 
 @pytest.mark.parametrize('variant', ['cem', 'safe'])

@@ -97,8 +97,40 @@ def test_scores_follow_the_rounding_model(torch, O, A, rc, variant):
     pl.plan_end()
     assert pl.tiles()[0] == rc
     pl.close()
-    ratio, near = bc.check_scores(sc, c, 'obs %d %s rc %d' % (O, variant, rc))
-    print('bf16 obs %d %s rc %d: score ratio %.4f, %.1f %% near a threshold' % (O, variant, rc, ratio, 100 * near))
+    print('bf16 obs %d %s rc %d: %s' % (O, variant, rc, bc.score_figures(sc, c)))
+    ratio, near, med, p90 = bc.check_scores(sc, c, 'obs %d %s rc %d' % (O, variant, rc))
+    print('bf16 obs %d %s rc %d: score ratio %.4f, %.1f %% near a threshold; flip-free median ratio %.4f, 90th percentile ratio %.4f' % (
+        O, variant, rc, ratio, 100 * near, med, p90))
+
+
+@pytest.mark.parametrize('obs', [60, 84])
+@pytest.mark.parametrize('variant', ['cem', 'safe'])
+@pytest.mark.parametrize('case', list(hp.SCORER_CASES))
+def test_scorer_branches_follow_the_rounding_model(torch, case, variant, obs):
+    """Every branch of the scorer (helpers.SCORER_CASES: 0 - 4 constrained kinds, the non-indicator sum, observe_goal_dist, reward clip
+    absent / active) in the kernel's own copy of the epilogue, at obs 60 (one input block per wave) and 84 (two), both objectives,
+    planning mode on explicit noise at test_rollout_scorer_branches' shape: check_scores against candidate_scores under the emulation,
+    and for the safe objective the done-masked per-step cost bytes of every row clear of a threshold, exactly (small integers), against
+    the costs on the emulation's trajectory (tests/test_bf16_bars_cpu.py holds the stand-ins and the mutants to the same bars)."""
+    c = bc.scorer_case(case, obs, variant)
+    n = bc.SCORER_SHAPE
+    _, pcfg = hp.configs(c['pb'], variant=variant, post=bc.SCORER_POST, precision='bf16', **n)
+    pl = hp.make_planner(c['pb'], pcfg)
+    pl.plan_begin(c['pb']['state'], eps_act=c['ea'], eps_model=c['em'])
+    pl.plan_rollout(0)
+    torch.cuda.synchronize()
+    sc = pl.scores_local().cpu().numpy().copy()
+    actions = pl.actions().cpu().numpy().copy()
+    costs = pl.costs().cpu().numpy().reshape(n['H'], n['P'] * n['N']).astype(np.float64) if variant == 'safe' else None
+    pl.plan_end()
+    pl.close()
+    what = 'bf16 %s obs %d %s' % (case, obs, variant)
+    np.testing.assert_array_equal(actions, c['actions'], err_msg=what)
+    print('%s: %s' % (what, bc.score_figures(sc, c)))
+    ratio, near, med, p90 = bc.check_scores(sc, c, what)
+    print('%s: score ratio %.4f, %.1f %% near a threshold; flip-free median ratio %.4f, 90th percentile ratio %.4f' % (what, ratio, 100 * near, med, p90))
+    if variant == 'safe':
+        np.testing.assert_array_equal(costs[:, c['row_clear']], c['costs'][:, c['row_clear']], err_msg=what)
 
 
 # ---- 4. bit-identical within the kernel --------------------------------------------------------------------------------------------

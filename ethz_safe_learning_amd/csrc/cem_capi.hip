@@ -46,10 +46,15 @@ struct Dims {
     int KB_in, KB_obs, NFW, KF0;     // KF0 = 4*NFW: layer-0 groups per wave, zero padded so every stage is a multiple of 4
     int act_q0, act_nq;              // feature quads of the network input that hold action features: [act_q0, act_q0 + act_nq)
     bool wide;                       // units > 128 or an activation other than relu: the generic rollout kernel (cem_rollout_wide.h)
-    bool split;                      // precision CEM_PRECISION_SPLIT_BF16X3: cem_rollout_split.h (weight stream in 6 KB chunk groups)
-    bool bf16;                       // precision CEM_PRECISION_BF16: cem_rollout_bf16.h (weight stream in 2 KB chunk groups, one bf16 plane)
+    int planes;                      // bf16 planes of the chunked rollouts (cem_rollout_chunked.h), 0 for fp32 / wide: 3 = precision CEM_PRECISION_SPLIT_BF16X3
+                                     // (cem_rollout_split.h, weight stream in 6 KB chunk groups), 1 = CEM_PRECISION_BF16 (cem_rollout_bf16.h, 2 KB chunk groups)
+    int G0, GS;                      // groups of a wave's stream per stage: layer 0 / every other stage (K = 32 chunks when chunked, else 16-feature blocks)
     int wave_groups[4]; uint32_t wave_off_f4[4]; uint32_t member_stride_f4;
     size_t nat_member_floats;
+    bool chunked() const { return planes != 0; }
+    bool split() const { return planes == 3; }      // (the two for sites that concern ONE kernel)
+    bool bf16() const { return planes == 1; }
+    uint32_t group_bytes() const { return chunked() ? planes * 2048u : 2048u; }
 };
 
 // Which select kernel an iteration gets (cem_mpc.h select_mode; used by validate() and enqueue_select() alike, so that what one accepts
@@ -131,16 +136,16 @@ Dims make_dims(const cem_config_t *c)
     d.KB_in = (d.Din + 15) / 16; d.KB_obs = (d.O + 15) / 16; d.NFW = (d.KB_in + 3) / 4; d.KF0 = 4 * d.NFW;
     d.act_q0 = d.O / 4; d.act_nq = (d.Din + 3) / 4 - d.act_q0;
     d.wide = d.U > CEM_U || c->activation != CEM_ACT_RELU || std::getenv("CEM_FORCE_GENERIC_ROLLOUT") != nullptr;   // (the variable: a diagnostic, scripts/sweep_configs.py)
-    d.split = !d.wide && c->precision == CEM_PRECISION_SPLIT_BF16X3;
-    d.bf16 = !d.wide && c->precision == CEM_PRECISION_BF16;
+    d.planes = d.wide ? 0 : c->precision == CEM_PRECISION_SPLIT_BF16X3 ? 3 : c->precision == CEM_PRECISION_BF16 ? 1 : 0;
+    // fp32 stream: 2 KB groups, one per 16-feature input block; split stream: 6 KB groups, one per K = 32 chunk (two blocks);
+    // bf16 stream: 2 KB groups, one per K = 32 chunk
+    d.G0 = d.chunked() ? cem_chunked_l0_chunks(d.NFW, d.split() ? CEM_SPLIT_RING : CEM_BF16_RING) : d.KF0;
+    d.GS = d.chunked() ? CEM_SPLIT_CHUNKS : CEM_NG;
     uint32_t off = 0;
     for (int w = 0; w < 4; ++w) {
-        // fp32 stream: 2 KB groups, one per 16-feature input block; split stream: 6 KB groups, one per K = 32 chunk (two blocks);
-        // bf16 stream: 2 KB groups, one per K = 32 chunk
-        const int per_stage = (d.split || d.bf16) ? CEM_SPLIT_CHUNKS : CEM_NG;
-        int g = (d.split ? cem_split_l0_chunks(d.NFW) : d.bf16 ? cem_bf16_l0_chunks(d.NFW) : d.KF0) + per_stage * (d.L - 1);
-        for (int i = 0; i < d.NFW; ++i) if (w + 4 * i < d.KB_obs) g += per_stage;
-        d.wave_groups[w] = g; d.wave_off_f4[w] = off; off += (uint32_t)g * (d.split ? 384u : 128u);
+        int g = d.G0 + d.GS * (d.L - 1);
+        for (int i = 0; i < d.NFW; ++i) if (w + 4 * i < d.KB_obs) g += d.GS;
+        d.wave_groups[w] = g; d.wave_off_f4[w] = off; off += (uint32_t)g * (d.group_bytes() / 16);
     }
     d.member_stride_f4 = off + 256u;    // +2 groups of slack: the prefetch queue may run ahead of a short stream
     d.nat_member_floats = (size_t)d.Din * d.U + d.U + (size_t)(d.L - 1) * ((size_t)d.U * d.U + d.U) + 2 * ((size_t)d.U * d.O + d.O);
@@ -204,9 +209,12 @@ void pack_member(const Dims &d, const float *nat, float *out)
 // 2F, 2F + 1): [a planes 0..2][b planes 0..2], a plane = [64 lanes][8 bf16].  Lane 16 q + i holds, for output feature 16 G + i, the
 // chunk's k slots s = 0..7 = input features 16 (2F + s / 4) + 4 q + s % 4 — what a lane's two accumulator quads of the producing
 // stage hold — as piece `plane` of the exact three-way bf16 split of the weight (cem_split3_bits).
-void pack_member_split(const Dims &d, const float *nat, uint16_t *out)
+// For cem_rollout_bf16.h (d.planes == 1): the same groups with ONE plane — 2 KB, [a][b], each [64 lanes][8 bf16], the same k slots in the
+// same visiting order — every weight rounded to bf16 once, to nearest even (cem_rn_bf16_bits).
+void pack_member_chunked(const Dims &d, const float *nat, uint16_t *out)
 {
     const NatOff no = nat_offsets(d);
+    const int planes = d.planes, group = planes * 1024;           // uint16 per group
     std::memset(out, 0, (size_t)d.member_stride_f4 * 16);
     for (int w = 0; w < 4; ++w) {
         uint16_t *dst = out + (size_t)d.wave_off_f4[w] * 8;
@@ -216,20 +224,21 @@ void pack_member_split(const Dims &d, const float *nat, uint16_t *out)
                 for (int s = 0; s < 8; ++s) {
                     const int k = 16 * (2 * F + (s >> 2)) + 4 * kq + (s & 3), o = 16 * Gout + i;
                     const float v = (k < in_dim && o < out_dim) ? W[(size_t)k * ld + o] : 0.f;
-                    unsigned a[3]; cem_split3_bits(v, a[0], a[1], a[2]);
-                    for (int pl = 0; pl < 3; ++pl) dst[((size_t)(ab * 3 + pl) * 64 + lane) * 8 + s] = (uint16_t)(a[pl] >> 16);
+                    unsigned a[3] = {cem_rn_bf16_bits(v), 0u, 0u};
+                    if (planes == 3) cem_split3_bits(v, a[0], a[1], a[2]);
+                    for (int pl = 0; pl < planes; ++pl) dst[((size_t)(ab * planes + pl) * 64 + lane) * 8 + s] = (uint16_t)(a[pl] >> 16);
                 }
             }
         };
-        for (int P = 0; P < cem_split_l0_chunks(d.NFW); ++P) {    // layer 0: chunks in ascending order (no own chunk); chunks past the input are zero
+        for (int P = 0; P < d.G0; ++P) {                          // layer 0: chunks in ascending order (no own chunk); chunks past the input are zero
             emit(nat + no.W[0], d.Din, d.U, d.U, P, 0, 2 * w); emit(nat + no.W[0], d.Din, d.U, d.U, P, 1, 2 * w + 1);
-            dst += 3072;
+            dst += group;
         }
         for (int l = 1; l < d.L; ++l)
             for (int P = 0; P < CEM_SPLIT_CHUNKS; ++P) {
                 const int F = cem_split_perm(w, P);
                 emit(nat + no.W[l], d.U, d.U, d.U, F, 0, 2 * w); emit(nat + no.W[l], d.U, d.U, d.U, F, 1, 2 * w + 1);
-                dst += 3072;
+                dst += group;
             }
         for (int i = 0; i < d.NFW; ++i) {
             const int Fo = w + 4 * i;
@@ -237,47 +246,7 @@ void pack_member_split(const Dims &d, const float *nat, uint16_t *out)
             for (int P = 0; P < CEM_SPLIT_CHUNKS; ++P) {          // heads: a = mean, b = variance of observation block Fo
                 const int F = cem_split_perm(w, P);
                 emit(nat + no.Wmu, d.U, d.O, d.O, F, 0, Fo); emit(nat + no.Wvar, d.U, d.O, d.O, F, 1, Fo);
-                dst += 3072;
-            }
-        }
-    }
-}
-
-// Weight stream of (member, wave) for cem_rollout_bf16.h: pack_member_split's groups with ONE plane — 2 KB, [a][b], each [64 lanes][8 bf16],
-// the same k slots in the same visiting order — every weight rounded to bf16 once, to nearest even (cem_rn_bf16_bits).
-void pack_member_bf16(const Dims &d, const float *nat, uint16_t *out)
-{
-    const NatOff no = nat_offsets(d);
-    std::memset(out, 0, (size_t)d.member_stride_f4 * 16);
-    for (int w = 0; w < 4; ++w) {
-        uint16_t *dst = out + (size_t)d.wave_off_f4[w] * 8;
-        auto emit = [&](const float *W, int in_dim, int out_dim, int ld, int F, int ab, int Gout) {
-            for (int lane = 0; lane < 64; ++lane) {
-                const int kq = lane >> 4, i = lane & 15;
-                for (int s = 0; s < 8; ++s) {
-                    const int k = 16 * (2 * F + (s >> 2)) + 4 * kq + (s & 3), o = 16 * Gout + i;
-                    const float v = (k < in_dim && o < out_dim) ? W[(size_t)k * ld + o] : 0.f;
-                    dst[((size_t)ab * 64 + lane) * 8 + s] = (uint16_t)(cem_rn_bf16_bits(v) >> 16);
-                }
-            }
-        };
-        for (int P = 0; P < cem_bf16_l0_chunks(d.NFW); ++P) {     // layer 0: chunks in ascending order (no own chunk); chunks past the input are zero
-            emit(nat + no.W[0], d.Din, d.U, d.U, P, 0, 2 * w); emit(nat + no.W[0], d.Din, d.U, d.U, P, 1, 2 * w + 1);
-            dst += 1024;
-        }
-        for (int l = 1; l < d.L; ++l)
-            for (int P = 0; P < CEM_SPLIT_CHUNKS; ++P) {
-                const int F = cem_split_perm(w, P);
-                emit(nat + no.W[l], d.U, d.U, d.U, F, 0, 2 * w); emit(nat + no.W[l], d.U, d.U, d.U, F, 1, 2 * w + 1);
-                dst += 1024;
-            }
-        for (int i = 0; i < d.NFW; ++i) {
-            const int Fo = w + 4 * i;
-            if (Fo >= d.KB_obs) continue;
-            for (int P = 0; P < CEM_SPLIT_CHUNKS; ++P) {          // heads: a = mean, b = variance of observation block Fo
-                const int F = cem_split_perm(w, P);
-                emit(nat + no.Wmu, d.U, d.O, d.O, F, 0, Fo); emit(nat + no.Wvar, d.U, d.O, d.O, F, 1, Fo);
-                dst += 1024;
+                dst += group;
             }
         }
     }
@@ -337,9 +306,9 @@ std::vector<PackDesc> build_pack_table(const Dims &d)
         return t;
     }
     for (int w = 0; w < 4; ++w) {                         // the waves' streams follow each other (Dims::wave_off_f4)
-        const bool chunked = d.split || d.bf16;           // K = 32 chunks in cem_split_perm order (else 16-feature blocks, cem_perm_*)
-        const int n0 = d.split ? cem_split_l0_chunks(d.NFW) : d.bf16 ? cem_bf16_l0_chunks(d.NFW) : d.KF0, per_stage = chunked ? CEM_SPLIT_CHUNKS : CEM_NG;
-        for (int P = 0; P < n0; ++P) {
+        const bool chunked = d.chunked();                 // K = 32 chunks in cem_split_perm order (else 16-feature blocks, cem_perm_*)
+        const int per_stage = d.GS;
+        for (int P = 0; P < d.G0; ++P) {
             const int F = chunked ? P : cem_perm_l0(w, d.NFW, P);
             unit(no.W[0], d.Din, d.U, F, 2 * w); unit(no.W[0], d.Din, d.U, F, 2 * w + 1);
         }
@@ -555,25 +524,11 @@ int auto_chunks(const Dims &d, int requested_segments, int problems = 1)
 // tiles are bound by the L2 -> CU path and larger tiles pay; what decides between the sizes is how many tiles the busiest CU gets
 // (ceil(tiles / CUs)) and how many of them run side by side.  K cycles per step of ONE CU running m co-resident tiles of rc chunks,
 // measured over population sizes (scripts/sweep_split_tiles.py, profiles/r03_split_tile_sizes.txt); residency: registers / LDS.
-static const double kSplitStep[2][4][3] = {{{11.2, 18.2, 28.5}, {15.8, 25.0, 0}, {21.6, 34.2, 0}, {27.2, 0, 0}},
-                                           {{14.2, 26.0, 0}, {21.0, 39.0, 0}, {28.5, 0, 0}, {36.4, 0, 0}}};
+static const double kSplitStep[2][4][4] = {{{11.2, 18.2, 28.5, 0}, {15.8, 25.0, 0, 0}, {21.6, 34.2, 0, 0}, {27.2, 0, 0, 0}},
+                                           {{14.2, 26.0, 0, 0}, {21.0, 39.0, 0, 0}, {28.5, 0, 0, 0}, {36.4, 0, 0, 0}}};
 static const int kSplitResident[2][4] = {{3, 2, 2, 1}, {2, 2, 1, 1}};
-int auto_chunks_split(const Dims &d)
-{
-    int best = 1; double bestc = 1e30;
-    for (int rc = 1; rc <= 4; ++rc) {
-        std::vector<Tile6> t; build_plan_tiles(d, rc, t);
-        const long per_cu = (long)((t.size() + num_cus() - 1) / num_cus());
-        const int R = kSplitResident[d.NFW - 1][rc - 1];
-        const double *ts = kSplitStep[d.NFW - 1][rc - 1];
-        const double cost = (double)(per_cu / R) * ts[R - 1] + (per_cu % R ? ts[per_cu % R - 1] : 0.0);
-        // rc ascends: within 5 % the larger tile wins (fewer workgroups, a third or half of the weight traffic)
-        if (cost <= bestc * 1.05) { best = rc; bestc = std::min(bestc, cost); }
-    }
-    return best;
-}
 
-// Tile size of the bf16 rollout (cem_rollout_bf16.h): auto_chunks_split's rule on a table of its own.  A third of the split kernel's
+// Tile size of the bf16 rollout (cem_rollout_bf16.h): the split kernel's rule on a table of its own.  A third of the split kernel's
 // weight bytes and a sixth of its MFMAs per chunk; what decides between the sizes is again how many tiles the busiest CU gets
 // (ceil(tiles / CUs)) and how many of them run side by side.  Plan ms (5 iterations, H = 30) of a device whose busiest CU runs m
 // co-resident tiles of rc chunks, measured over population sizes (scripts/sweep_bf16_tiles.py, profiles/bf16_tile_sizes.txt: the rule
@@ -582,17 +537,22 @@ int auto_chunks_split(const Dims &d)
 static const double kBf16Step[2][4][4] = {{{0.45, 0.61, 0.82, 1.07}, {0.52, 0.70, 0.935, 0}, {0.61, 0.84, 0, 0}, {0.73, 0.985, 0, 0}},
                                           {{0.62, 0.865, 1.187, 0}, {0.79, 1.075, 0, 0}, {0.97, 1.35, 0, 0}, {1.17, 1.67, 0, 0}}};
 static const int kBf16Resident[2][4] = {{4, 3, 2, 2}, {3, 2, 2, 2}};
-int auto_chunks_bf16(const Dims &d)
+
+// The one rule over either table: step[NFW - 1][rc - 1][m - 1] (zero past the residency R; the rule never reads past R - 1), the
+// residency, and the tie margin — rc ascends, and within the margin the larger tile wins (fewer workgroups, less weight traffic: 5 % for
+// the split kernel, whose larger tiles save a third or half of it, 2 % for the bf16 kernel).
+struct ChunkedTileRule { const double (*step)[4][4]; const int (*resident)[4]; double tie; };
+int auto_chunks_chunked(const Dims &d)
 {
+    const ChunkedTileRule rule = d.split() ? ChunkedTileRule{kSplitStep, kSplitResident, 1.05} : ChunkedTileRule{kBf16Step, kBf16Resident, 1.02};
     int best = 1; double bestc = 1e30;
     for (int rc = 1; rc <= 4; ++rc) {
         std::vector<Tile6> t; build_plan_tiles(d, rc, t);
         const long per_cu = (long)((t.size() + num_cus() - 1) / num_cus());
-        const int R = kBf16Resident[d.NFW - 1][rc - 1];
-        const double *ts = kBf16Step[d.NFW - 1][rc - 1];
+        const int R = rule.resident[d.NFW - 1][rc - 1];
+        const double *ts = rule.step[d.NFW - 1][rc - 1];
         const double cost = (double)(per_cu / R) * ts[R - 1] + (per_cu % R ? ts[per_cu % R - 1] : 0.0);
-        // rc ascends: within 2 % the larger tile wins (fewer workgroups, less weight traffic)
-        if (cost <= bestc * 1.02) { best = rc; bestc = std::min(bestc, cost); }
+        if (cost <= bestc * rule.tie) { best = rc; bestc = std::min(bestc, cost); }
     }
     return best;
 }
@@ -616,11 +576,10 @@ Plan make_plan(const cem_config_t *c, const Dims &d, int mb = 0)
     Plan pl{};
     const int seg_req = mb > 0 ? 1 : c->rollout_segments;
     pl.rc = d.wide ? 1 : (c->chunks_per_tile ? c->chunks_per_tile : auto_chunks(d, seg_req, std::max(mb, 1)));   // the wide kernel: 16-row tiles
-    if (d.split && !c->chunks_per_tile) pl.rc = auto_chunks_split(d);
-    if (d.bf16 && !c->chunks_per_tile) pl.rc = auto_chunks_bf16(d);
+    if (d.chunked() && !c->chunks_per_tile) pl.rc = auto_chunks_chunked(d);
     std::vector<Tile6> t; build_plan_tiles(d, pl.rc, t);
     pl.n_tiles = (int)t.size();
-    pl.n_seg = (d.wide || d.split || d.bf16) ? 1 : segments_for(d, pl.rc, t.size(), seg_req);
+    pl.n_seg = (d.wide || d.chunked()) ? 1 : segments_for(d, pl.rc, t.size(), seg_req);
     pl.seg_len = (d.H + pl.n_seg - 1) / pl.n_seg;
     pl.n_seg = (d.H + pl.seg_len - 1) / pl.seg_len;
     // tiles every CU gets the same number of stay whole ("pinned"); only the remainder floats in segments
@@ -1087,8 +1046,7 @@ int cem_pack_weights_host(const cem_config_t *cfg, const float *blob, float *pac
     const Dims d = make_dims(cfg);
     if (d.wide) return CEM_ERR_UNSUPPORTED;
     for (int m = 0; m < d.E; ++m) {
-        if (d.split) pack_member_split(d, blob + (size_t)m * d.nat_member_floats, reinterpret_cast<uint16_t *>(packed + (size_t)m * d.member_stride_f4 * 4));
-        else if (d.bf16) pack_member_bf16(d, blob + (size_t)m * d.nat_member_floats, reinterpret_cast<uint16_t *>(packed + (size_t)m * d.member_stride_f4 * 4));
+        if (d.chunked()) pack_member_chunked(d, blob + (size_t)m * d.nat_member_floats, reinterpret_cast<uint16_t *>(packed + (size_t)m * d.member_stride_f4 * 4));
         else pack_member(d, blob + (size_t)m * d.nat_member_floats, packed + (size_t)m * d.member_stride_f4 * 4);
     }
     return CEM_OK;
@@ -1139,7 +1097,7 @@ int cem_rollout_residency(int32_t chunks_per_tile, int32_t input_blocks_per_wave
 // fit its LDS allowance.  Everything else — and any plan given explicit noise tensors — runs the generic kernels.
 static bool lean_eligible(const cem_planner *h, const Dims &d, int rc, bool sample_in_rollout)
 {
-    return launch_rollout_lean != nullptr && !d.wide && !d.split && !d.bf16 && rc == 1 && d.NFW == 1 && d.L == 4 && d.O % 4 == 0 && h->cfg.world_size == 1 && !h->batch &&
+    return launch_rollout_lean != nullptr && !d.wide && !d.chunked() && rc == 1 && d.NFW == 1 && d.L == 4 && d.O % 4 == 0 && h->cfg.world_size == 1 && !h->batch &&
            sample_in_rollout && CEM_LEAN_ACT_LDS_BYTES(d.H, (d.A + 3) / 4) <= CEM_LEAN_ACT_LDS_MAX;
 }
 
@@ -1155,7 +1113,7 @@ static void place_sampler(const cem_planner *h, const Dims &d, const Plan &pl, b
     // (the bf16 kernel: one slot per CU, like the split kernel — its launch is short enough that a second co-resident tile's prologue,
     // which samples every candidate once per particle, shows: B4's 512 four-chunk tiles 2.70 ms per plan inside against 2.48 in a launch
     // of its own, the shipped safe shape 0.603 against 0.612, B2 inside either way; profiles/bf16_rollout_isa.txt)
-    const int slots = real_cus() * ((d.wide || d.split || d.bf16) ? 1 : resident_workgroups(d.NFW, pl.rc, pl.n_seg > 1));
+    const int slots = real_cus() * ((d.wide || d.chunked()) ? 1 : resident_workgroups(d.NFW, pl.rc, pl.n_seg > 1));
     *sample_in_rollout = (long long)nb * pl.n_tiles <= slots;          // (a batch handle: all its problems' tiles in one launch)
     if (const char *e = std::getenv("CEM_FORCE_SAMPLER"))      // diagnostic / tests: "tile" or "kernel" — the results do not depend on it
         *sample_in_rollout = std::strcmp(e, "kernel") != 0;
@@ -1216,7 +1174,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
         h->n_pack_desc = (uint32_t)table.size();
         // the table must tile a member's image exactly: the pack kernels write one unit per descriptor (plus 4 KB of slack)
         const size_t image_bytes = h->d.wide ? wide_image_floats(h->d) * 4 : (size_t)h->d.member_stride_f4 * 16 - 4096;
-        if (table.size() * (h->d.split ? 3072 : 1024) != image_bytes) return fail(CEM_ERR_STATE);
+        if (table.size() * (h->d.group_bytes() / 2) != image_bytes) return fail(CEM_ERR_STATE);      // (a group is two units: output blocks a, b)
         if (hipMalloc((void **)&h->pack_desc, table.size() * sizeof(PackDesc)) != hipSuccess ||
             hipMemcpy(h->pack_desc, table.data(), table.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) return fail(CEM_ERR_HIP);
     }
@@ -1393,8 +1351,7 @@ int cem_planner_set_weights(cem_planner_t *h, const float *blob, size_t n_floats
     const NatOff no = nat_offsets(d);
     for (int m = 0; m < d.E; ++m) {
         const float *nat = blob + (size_t)m * d.nat_member_floats;
-        if (d.split) pack_member_split(d, nat, reinterpret_cast<uint16_t *>(packed.data() + (size_t)m * d.member_stride_f4 * 4));
-        else if (d.bf16) pack_member_bf16(d, nat, reinterpret_cast<uint16_t *>(packed.data() + (size_t)m * d.member_stride_f4 * 4));
+        if (d.chunked()) pack_member_chunked(d, nat, reinterpret_cast<uint16_t *>(packed.data() + (size_t)m * d.member_stride_f4 * 4));
         else pack_member(d, nat, packed.data() + (size_t)m * d.member_stride_f4 * 4);
         for (int l = 0; l < d.L; ++l) std::memcpy(&bh[((size_t)m * d.L + l) * CEM_U], nat + no.b[l], d.U * 4);
         std::memcpy(&bmu[(size_t)m * CEM_U], nat + no.bmu, d.O * 4);
@@ -1435,8 +1392,8 @@ int cem_planner_set_weights_dev(cem_planner_t *h, const float *blob_dev, size_t 
     const unsigned wgs = (p.n_desc + p.n_slack + CEM_PACK_WAVES - 1) / CEM_PACK_WAVES;
     const dim3 grid(wgs * (unsigned)d.E), block(64 * CEM_PACK_WAVES);
     if (d.wide) hipLaunchKernelGGL(cem_pack_wide_kernel, grid, block, 0, h->stream, p);
-    else if (d.split) hipLaunchKernelGGL(cem_pack_split_kernel, grid, block, 0, h->stream, p);
-    else if (d.bf16) launch_pack_bf16(p, grid.x, h->stream);
+    else if (d.split()) hipLaunchKernelGGL(cem_pack_split_kernel, grid, block, 0, h->stream, p);
+    else if (d.bf16()) launch_pack_bf16(p, grid.x, h->stream);
     else hipLaunchKernelGGL(cem_pack_fp32_kernel, grid, block, 0, h->stream, p);
     cem_pack_trained_bias_t b{};
     b.blob = blob_dev; b.bias_h = (float *)(h->ws + h->lay.bias_h); b.bias_mu = (float *)(h->ws + h->lay.bias_mu);
@@ -1514,20 +1471,12 @@ hipError_t launch_rollout(int rc, int nfw, const RolloutParams &p, int n_tiles, 
     return with_tile_shape(rc, nfw, hipErrorInvalidValue, [&](auto R, auto F) { return launch_rollout_t<R(), F(), MODE>(p, n_tiles, st); });
 }
 
-// the split-product rollout (cem_rollout_split.h): rc 1 / 2, whole-horizon tiles; mode 1 = caller-supplied noise tensors
-template <int RC, int NFW, int MODE>
-hipError_t launch_rollout_split_t(const RolloutParams &p, int n_tiles, hipStream_t st)
+// the chunked rollouts (cem_rollout_chunked.h), whole-horizon tiles; mode 1 = caller-supplied noise tensors.  The split kernels are
+// this unit's, the bf16 kernels cem_rollout_bf16.hip's: the same dispatch, expanded where the kernels are.
+CEM_CHUNKED_LAUNCHER(launch_rollout_split, cem_rollout_split_kernel, 3)
+hipError_t launch_rollout_chunked(const Dims &d, int rc, int mode, const RolloutParams &p, int n_tiles, hipStream_t st)
 {
-    const size_t lds = (size_t)2 * CEM_SPLIT_XB(RC) + CEM_PART_FLOATS * 4;
-    hipLaunchKernelGGL((cem_rollout_split_kernel<RC, NFW, MODE>), dim3(n_tiles), dim3(256), lds, st, p);
-    return hipGetLastError();
-}
-hipError_t launch_rollout_split(int rc, int nfw, int mode, const RolloutParams &p, int n_tiles, hipStream_t st)
-{
-    if (mode != 0 && mode != 1) return hipErrorInvalidValue;
-    return with_tile_shape(rc, nfw, hipErrorInvalidValue, [&](auto R, auto F) {
-        return mode ? launch_rollout_split_t<R(), F(), 1>(p, n_tiles, st) : launch_rollout_split_t<R(), F(), 0>(p, n_tiles, st);
-    });
+    return (d.split() ? launch_rollout_split : launch_rollout_bf16)(rc, d.NFW, mode, p, n_tiles, st);
 }
 
 // mode 0: planning; mode 1: caller-supplied action / noise tensors, trajectory and head-moment outputs
@@ -1716,8 +1665,7 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
         else HIPCHK(launch_rollout_lean(rp, grid, h->stream, queued));
     }
     else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, rp.eps_model ? 1 : 0));
-    else if (d.split) HIPCHK(launch_rollout_split(v.rc, d.NFW, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
-    else if (d.bf16) HIPCHK(launch_rollout_bf16(v.rc, d.NFW, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
+    else if (d.chunked()) HIPCHK(launch_rollout_chunked(d, v.rc, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
     else if (rp.eps_model) HIPCHK(launch_rollout<1>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     else if (queued) {
         rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
@@ -2815,7 +2763,7 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
     if (n_rows % d.E != 0) return CEM_ERR_SPLIT;
     if ((long long)n_rows * (horizon + 1) * d.O > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
     const int chunk = n_rows / d.E;
-    const int rc = d.wide ? 1 : (d.split ? (n_rows >= 256 * 32 ? 2 : 1) : (n_rows >= 256 * 64 ? 4 : (n_rows >= 256 * 32 ? 2 : 1)));
+    const int rc = d.wide ? 1 : (d.split() ? (n_rows >= 256 * 32 ? 2 : 1) : (n_rows >= 256 * 64 ? 4 : (n_rows >= 256 * 32 ? 2 : 1)));
     std::vector<Tile6> tiles;
     for (int m = 0; m < d.E; ++m)
         for (int r = m * chunk; r < (m + 1) * chunk; r += 16 * rc) {
@@ -2834,9 +2782,8 @@ int cem_unfold_sequences(cem_planner_t *h, const float *s0_dev, const float *act
     rp.traj = traj_out_dev; rp.mu_out = mu_out_dev; rp.sd_out = sd_out_dev;
     rp.H = horizon; rp.Bloc = n_rows; rp.Btot = n_rows; rp.it = 0; rp.variant = 0; rp.check_done = 0;
     hipError_t e = d.wide ? launch_rollout_wide(h, rp, (int)tiles.size(), 1)
-                 : d.split ? launch_rollout_split(rc, d.NFW, 1, rp, (int)tiles.size(), h->stream)
-                 : d.bf16 ? launch_rollout_bf16(rc, d.NFW, 1, rp, (int)tiles.size(), h->stream)
-                           : launch_rollout<1>(rc, d.NFW, rp, (int)tiles.size(), h->stream);
+                 : d.chunked() ? launch_rollout_chunked(d, rc, 1, rp, (int)tiles.size(), h->stream)
+                               : launch_rollout<1>(rc, d.NFW, rp, (int)tiles.size(), h->stream);
     hipError_t e2 = hipStreamSynchronize(h->stream);
     HIPCHK(e); HIPCHK(e2);
     return CEM_OK;

@@ -1,6 +1,6 @@
 // cem_pack.h — the weight images of the rollout kernels, packed ON THE DEVICE from a natural (Keras-layout) blob that already lives
 // there (cem_planner_set_weights_dev: the trainer's workspace after a fit).  Bit for bit what the host packers of cem_capi.hip
-// (pack_member, pack_member_split, pack_member_wide + the bias rows of cem_planner_set_weights) upload.
+// (pack_member, pack_member_chunked, pack_member_wide + the bias rows of cem_planner_set_weights) upload.
 //
 // Destination driven: every image is a sequence of UNITS of 64 lanes; a lane owns the 16 bytes (fp32, wide) or the 3 x 16 bytes (split:
 // one per bf16 plane) of its unit and gathers what belongs there, so every word of a member's image is written — zero padding past
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64 * CEM_PACK_WAVES) void cem_pack_fp32_kernel(cons
     *reinterpret_cast<f4 *>(img + (size_t)unit * 1024 + lane * 16) = v;
 }
 
-// the split rollout's stream (pack_member_split): 6 KB groups [ab(2)][plane(3)][lane(64)][s(8)] bf16, two 3 KB units each
+// the split rollout's stream (pack_member_chunked, three planes): 6 KB groups [ab(2)][plane(3)][lane(64)][s(8)] bf16, two 3 KB units each
 __global__ __launch_bounds__(64 * CEM_PACK_WAVES) void cem_pack_split_kernel(const cem_pack_trained_t p)
 {
     CEM_PACK_WHERE(p, p.n_desc + p.n_slack);

@@ -6,7 +6,7 @@
 #include "cem_rollout_bf16.h"
 #include "cem_pack.h"
 
-// the bf16 rollout's stream (pack_member_bf16): 2 KB groups [ab(2)][lane(64)][s(8)] bf16, two 1 KB units each
+// the bf16 rollout's stream (pack_member_chunked, one plane): 2 KB groups [ab(2)][lane(64)][s(8)] bf16, two 1 KB units each
 __global__ __launch_bounds__(64 * CEM_PACK_WAVES) void cem_pack_bf16_kernel(const cem_pack_trained_t p)
 {
     CEM_PACK_WHERE(p, p.n_desc + p.n_slack);
@@ -23,38 +23,7 @@ __global__ __launch_bounds__(64 * CEM_PACK_WAVES) void cem_pack_bf16_kernel(cons
     *reinterpret_cast<cem_u4 *>(img + (size_t)unit * 1024 + lane * 16) = v;
 }
 
-namespace {
-
-template <int RC, int NFW>
-hipError_t launch_t(int mode, const RolloutParams &p, int n_tiles, hipStream_t st)
-{
-    const size_t lds = CEM_BF16_LDS_BYTES(RC);
-    if (mode) hipLaunchKernelGGL((cem_rollout_bf16_kernel<RC, NFW, 1>), dim3(n_tiles), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((cem_rollout_bf16_kernel<RC, NFW, 0>), dim3(n_tiles), dim3(256), lds, st, p);
-    return hipGetLastError();
-}
-
-template <int NFW>
-hipError_t launch_f(int rc, int mode, const RolloutParams &p, int n_tiles, hipStream_t st)
-{
-    switch (rc) {
-    case 1: return launch_t<1, NFW>(mode, p, n_tiles, st);
-    case 2: return launch_t<2, NFW>(mode, p, n_tiles, st);
-    case 3: return launch_t<3, NFW>(mode, p, n_tiles, st);
-    case 4: return launch_t<4, NFW>(mode, p, n_tiles, st);
-    }
-    return hipErrorInvalidValue;
-}
-
-}  // namespace
-
-hipError_t launch_rollout_bf16(int rc, int nfw, int mode, const RolloutParams &p, int n_tiles, hipStream_t st)
-{
-    if ((mode != 0 && mode != 1) || n_tiles < 1) return hipErrorInvalidValue;
-    if (nfw == 1) return launch_f<1>(rc, mode, p, n_tiles, st);
-    if (nfw == 2) return launch_f<2>(rc, mode, p, n_tiles, st);
-    return hipErrorInvalidValue;
-}
+CEM_CHUNKED_LAUNCHER(launch_rollout_bf16, cem_rollout_bf16_kernel, 1)
 
 void launch_pack_bf16(const cem_pack_trained_t &p, unsigned grid, hipStream_t st)
 {

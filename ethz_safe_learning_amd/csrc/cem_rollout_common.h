@@ -1,7 +1,8 @@
-// cem_rollout_common.h — what the three rollout kernels share around their dense stages: cem_rollout_tile (cem_device.h),
-// cem_rollout_tile_split (cem_rollout_split.h) and cem_rollout_wide_kernel (cem_rollout_wide.h) differ in how a dense stage is
-// computed and in where a stage's input travels; the action loads, the rare scorer kinds and the reward / cost / done bookkeeping
-// are written ONCE, here, at file scope, and every name they touch is an argument (nothing is captured from the expanding function).
+// cem_rollout_common.h — what the rollout kernels share around their dense stages: cem_rollout_tile (cem_device.h),
+// the chunked tile (cem_rollout_chunked.h: the split and bf16 kernels), cem_rollout_wide_kernel (cem_rollout_wide.h) and the
+// lean kernels (cem_rollout_lean.hip, cem_rollout_lean_straight.hip) differ in how a dense stage is computed and in where a stage's input travels; the action loads,
+// the model noise, the rare scorer kinds and the reward / cost / done bookkeeping are written ONCE, here, at file scope, and every
+// name they touch is an argument (nothing is captured from the expanding function).
 // They are macros, not functions: the rollout kernels are tuned to their register counts, and as forceinline functions these pieces
 // moved vgpr_count in 32 of the 42 rollout instantiations (tests/test_warm_capi_cpu.py pins them); as macros the device code is
 // unchanged to the byte (profiles/rollout_common_isa.txt).

@@ -14,8 +14,9 @@
 // Structure: cem_rollout_tile's — 4 waves per tile of 16 RC rows of one member for the whole horizon, wave w computes output blocks
 // 2w, 2w + 1 of a hidden layer and keeps them, SPLIT, as its own K = 32 input chunk of the next stage; the other chunks travel through
 // LDS as three bf16 planes; weights stream from a per-wave image of 6 KB groups (chunk x {a, b} output block x 3 planes) in visiting
-// order.  Action loads, model noise, rare scorer kinds and bookkeeping are cem_rollout_common.h's, arguments explicit.  Whole-horizon tiles only (no floating
-// segments); MODE 1 also serves cem_unfold_sequences (trajectory / head-moment outputs).
+// order.  The tile around the stages is cem_rollout_chunked.h's, shared with the one-plane kernel (cem_rollout_bf16.h); this header
+// keeps the split primitives, the LDS offsets, the ring, the stage and what the shared tile takes from them (the CEM_CHUNKED_* hooks).
+// Whole-horizon tiles only (no floating segments); MODE 1 also serves cem_unfold_sequences (trajectory / head-moment outputs).
 #pragma once
 #include "cem_device.h"
 
@@ -75,38 +76,38 @@ __device__ __forceinline__ void cem_split4(const f4 x, cem_u2 (&p)[3])
 __host__ __device__ inline int cem_split_perm(int w, int phi) { return phi == 0 ? w : (phi - 1 < w ? phi - 1 : phi); }
 
 // LDS: [2 buffers][RC][4 chunks][3 planes][64 lanes][16 B]; a lane's 16 bytes = 4 bf16 of block 2c, 4 bf16 of block 2c + 1
-#define CEM_SPLIT_XB(RC_) ((RC_) * CEM_SPLIT_CHUNKS * 3 * 1024)
 __device__ __forceinline__ int cem_split_off(const int c_rc, const int chunk, const int plane, const int lane)
 {
     return (((c_rc * CEM_SPLIT_CHUNKS + chunk) * 3 + plane) * 64 + lane) * 16;
 }
 
-// Weight ring over the wave's stream of 6 KB groups: [a planes 0..2][b planes 0..2], a plane = [64 lanes][8 bf16].  CEM_SPLIT_RING
-// slots, RING - 1 groups ahead of the MFMAs; every stage is a multiple of RING chunks long, so the slot of a stage's chunk phi is
-// the compile-time constant phi % RING (with RING 4 the two-chunk layer 0 of the obs+act <= 64 family is padded with two
-// zero-weight chunks: cem_split_l0_chunks, host and device).
+// Weight ring over a wave's stream of groups of NL KB, [a planes][b planes], a plane = [64 lanes][8 bf16] (6 KB here, 2 KB in
+// cem_rollout_bf16.h): RING slots, RING - 1 groups ahead of the MFMAs; every stage is a multiple of RING chunks long, so the slot of a
+// stage's chunk phi is the compile-time constant phi % RING (with RING 4 the two-chunk layer 0 of the obs+act <= 64 family is padded
+// with two zero-weight chunks: cem_chunked_l0_chunks, host and device).
 #ifndef CEM_SPLIT_RING
 #define CEM_SPLIT_RING 2                       // measured 2 vs 4 (same box): B1 0.123 vs 0.133 ms, B2 0.358 vs 0.510, B3 2.93 vs 3.12, B4 1.60 vs 1.86 (48 more VGPRs cost a resident workgroup)
 #endif
-__host__ __device__ constexpr int cem_split_l0_chunks(int nfw) { return 2 * nfw < CEM_SPLIT_RING ? CEM_SPLIT_RING : 2 * nfw; }
-struct SRing {
+template <int NL, int RING>
+struct ChunkRing {
     __amdgpu_buffer_rsrc_t rsrc;
     int voff, n, pos;
-    cem_u4 slot[CEM_SPLIT_RING][6];
-    __device__ __forceinline__ void ld(cem_u4 (&s)[6], const int g) const
+    cem_u4 slot[RING][NL];
+    __device__ __forceinline__ void ld(cem_u4 (&s)[NL], const int g) const
     {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) s[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, g * 6144 + i * 1024, 0);
+        for (int i = 0; i < NL; ++i) s[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, g * (NL * 1024) + i * 1024, 0);
     }
     __device__ __forceinline__ void init(const f4 *b, const int lane_, const int n_)
     {
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4 *>(b), 0, n_ * 6144, 0x00020000);
+        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4 *>(b), 0, n_ * (NL * 1024), 0x00020000);
         voff = lane_ * 16; n = n_;
 #pragma unroll
-        for (int i = 0; i < CEM_SPLIT_RING - 1; ++i) ld(slot[i], i % n_);
-        pos = (CEM_SPLIT_RING - 1) % n_;
+        for (int i = 0; i < RING - 1; ++i) ld(slot[i], i % n_);
+        pos = (RING - 1) % n_;
     }
 };
+typedef ChunkRing<6, CEM_SPLIT_RING> SRing;
 
 // One dense stage: acc{0,1}[c] += sum over the stage's chunks of the six split products.  OWN: chunk 0 of the visiting order is the
 // wave's own (planes in registers) and the barrier that publishes the other waves' chunks comes after its MFMAs.  XMODE as in
@@ -161,240 +162,22 @@ __device__ __forceinline__ void cem_split_stage(f4 (&acc0)[RC], f4 (&acc1)[RC], 
 #undef CEM_SPLIT_READ
 }
 
-// One tile for the whole horizon (cem_rollout_tile with the split stages; MODE as there)
-template <int RC, int NFW, int MODE>
-__device__ __forceinline__ void cem_rollout_tile_split(const RolloutParams &p, char *smem, const int tile_idx)
-{
-    const int tid = (int)((threadIdx.x + 64u * (unsigned)((tile_idx + (tile_idx >> 8)) & 3)) & 255u);   // wave roles rotate with the tile
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const int j = lane & 15, q = lane >> 4;
-    const TileDesc td = p.tiles[tile_idx];
-    const int wbk = 0;
-    const int O = p.O, A = p.A, H = p.H;
-    constexpr int XB = CEM_SPLIT_XB(RC);
-    constexpr int NCH0 = cem_split_l0_chunks(NFW);        // K = 32 chunks of the layer-0 input (padded to the ring length)
-    float *part = reinterpret_cast<float *>(smem + 2 * XB);
-    int xw = 0;
-    if (NCH0 > 2 * NFW) {                                 // padded layer-0 chunks meet zero weights: what LDS holds there must be finite
-        for (int o = (int)threadIdx.x * 16; o < 2 * XB; o += 256 * 16) *reinterpret_cast<cem_u4 *>(smem + o) = (cem_u4){0u, 0u, 0u, 0u};
-        __syncthreads();
-    }
-    const PhiloxKey key = cem_key(p.ctrl);
-    const float rscale = p.sampling ? CEM_BM_RSCALE : 0.0f;
-    const int member_u = __builtin_amdgcn_readfirstlane(td.member);
-    SRing wq;
-    wq.init(p.wpack + (size_t)member_u * p.member_stride_f4 + p.wave_off_f4[w], lane, (int)p.wave_groups[w]);
-    const __amdgpu_buffer_rsrc_t et_rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.etab + (size_t)member_u * (CEM_ET_ROWS + p.L) * CEM_U), 0, (CEM_ET_ROWS + p.L) * CEM_U * 4, 0x00020000);
-    const int tab_v = 64 * w + 16 * q;
-    const int bias_v = 128 * w + 16 * q;
-
-    f4 s[NFW][RC];
-    int slotc[RC];
-#pragma unroll
-    for (int c = 0; c < RC; ++c) { const int sl = 16 * c + j; slotc[c] = sl < td.cnt ? sl : td.cnt - 1; }
-#pragma unroll
-    for (int i = 0; i < NFW; ++i) {
-        const int f0 = 16 * (w + 4 * i) + 4 * q;
-#pragma unroll
-        for (int c = 0; c < RC; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int f = f0 + r;
-                float v = 0.f;
-                if (f < O) v = td.s0_base < 0 ? p.ctrl->state[f] : p.s0[(size_t)(td.s0_base + slotc[c]) * O + f];
-                s[i][c][r] = v;
-            }
-    }
-    const __amdgpu_buffer_rsrc_t act_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f4 *>(p.act_pad), 0, MODE == 0 ? p.act_pad_bytes : 0u, 0x00020000);
-    int actv[NFW][RC];
-    const float *actrow[RC];
-#pragma unroll
-    for (int c = 0; c < RC; ++c) {
-        actrow[c] = p.actions + (size_t)(td.act_base + slotc[c]) * H * A;
-#pragma unroll
-        for (int i = 0; i < NFW; ++i) {
-            int qi = 4 * (w + 4 * i) + q - p.act_q0;
-            qi = qi < 0 ? 0 : (qi >= p.act_nq ? p.act_nq - 1 : qi);
-            actv[i][c] = ((td.act_base + slotc[c]) * H * p.act_nq + qi) * 16;
-        }
-    }
-    // the scaled input block Fo of chunk c_rc goes to LDS as three planes of 4 bf16 per lane (its half of the lane's 16 bytes)
-#define CEM_PUBLISH_X(X_, FO_, C_) do { cem_u2 px_[3]; cem_split4((X_), px_); \
+// The tile (cem_rollout_tile_split) is cem_rollout_chunked.h's body with three planes, split by the publishing wave:
+#define CEM_CHUNKED_TILE cem_rollout_tile_split
+#define CEM_CHUNKED_PLANES 3
+#define CEM_CHUNKED_RING CEM_SPLIT_RING
+#define CEM_CHUNKED_STAGE cem_split_stage
+#define CEM_CHUNKED_OWN(OWN_, RC_) cem_u4 OWN_[RC_][3]; \
+    _Pragma("unroll") for (int c = 0; c < (RC_); ++c) \
+        _Pragma("unroll") for (int jj = 0; jj < 3; ++jj) OWN_[c][jj] = (cem_u4){0u, 0u, 0u, 0u}
+// the scaled input block FO_ of row chunk C_ goes to LDS as three planes of 4 bf16 per lane (its half of the lane's 16 bytes)
+#define CEM_CHUNKED_PUBLISH_X(SMEM_, XW_, LANE_, X_, FO_, C_) do { cem_u2 px_[3]; cem_split4((X_), px_); \
         _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_) \
-            *reinterpret_cast<cem_u2 *>(smem + xw + cem_split_off((C_), (FO_) >> 1, j_, lane) + 8 * ((FO_) & 1)) = px_[j_]; } while (0)
-
-    float d_prev = 0.f, c_prev = 0.f, cum = 0.f;
-    bool done = false;
-    const int nk = 1 + p.sc.n_cost;
-    const float csz[4] = {p.sc.cost_size[0], p.sc.cost_size[1], p.sc.cost_size[2], p.sc.cost_size[3]};
-    const float ind_cap = p.sc.indicator ? 1.0f : __builtin_inff(), clipv = p.sc.reward_clip > 0.f ? p.sc.reward_clip : __builtin_inff();
-    const __amdgpu_buffer_rsrc_t cost_rs = __builtin_amdgcn_make_buffer_rsrc(p.costs, 0, p.costs ? (uint32_t)(H * p.Bloc) : 0u, 0x00020000);
-
-    // ---- prologue: x_0 = scale(concat[s_0, a_0]) and the scorer terms of s_0 --------------------------------------------------
-    {
-        float pm[2][RC];
-#pragma unroll
-        for (int c = 0; c < RC; ++c) { pm[0][c] = __builtin_inff(); pm[1][c] = __builtin_inff(); }
-#pragma unroll
-        for (int i = 0; i < NFW; ++i) {
-            const int tv = tab_v + 256 * i;
-            const f4 mn4 = cem_ld_tab(et_rs, tv, CEM_ET_NMIN * 512), rd4 = cem_ld_tab(et_rs, tv, CEM_ET_RDELTA * 512);
-            const f4 isact4 = cem_ld_tab(et_rs, tv, CEM_ET_ACT * 512);
-            const f4 sel0 = cem_ld_tab(et_rs, tv, CEM_ET_SEL0 * 512), sel1 = cem_ld_tab(et_rs, tv, CEM_ET_SEL1 * 512);
-#pragma unroll
-            for (int c = 0; c < RC; ++c) {
-                f4 act4; CEM_LOAD_ACT(act4, MODE, p, act_rs, actv, actrow, w, q, O, A, i, c, 0);
-                const f4 sn = s[i][c];
-                if (MODE == 1) {
-                    const int slot = 16 * c + j, f0 = 16 * (w + 4 * i) + 4 * q;
-                    if (p.traj && slot < td.cnt) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (f0 + r < O) p.traj[((size_t)(td.row_base + slot) * (H + 1)) * O + f0 + r] = sn[r];
-                    }
-                }
-                cem_scorer_terms(sn, p.sc.D, sel0, sel1, pm[0][c], pm[1][c]);
-                const f4 x = cem_sub4(__builtin_elementwise_fma(isact4, act4, sn), mn4) * rd4;
-                CEM_PUBLISH_X(x, w + 4 * i, c);
-            }
-        }
-        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_MEM, et_rs);
-        xw = XB;
-    }
-    f4 nb0 = cem_ld_tab(et_rs, bias_v, CEM_ET_ROWS * 512);
-    f4 nb1 = cem_ld_tab(et_rs, bias_v + 64, CEM_ET_ROWS * 512);
-    cem_u4 own[RC][3];                                    // the wave's own chunk (its two output blocks of the last hidden stage), split
-#pragma unroll
-    for (int c = 0; c < RC; ++c)
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) own[c][jj] = (cem_u4){0u, 0u, 0u, 0u};
-
-#ifdef CEM_STAMPS
-    long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tprev_ = (long long)__builtin_amdgcn_s_memtime();
-    st_[7] = tprev_;
-#endif
-    const int prio_r0 = (tile_idx >> 8) % 3;
-    f4 bm0, bv0;
-    for (int t = 0; t < H; ++t) {
-        {
-            const int lvl = (t + prio_r0) % 3;
-            if (lvl == 0) __builtin_amdgcn_s_setprio(0); else if (lvl == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(2);
-        }
-#define CEM_SPLIT_PUBLISH() do { \
-            _Pragma("unroll") for (int c = 0; c < RC; ++c) { \
-                f4 h0 = acc0[c], h1 = acc1[c]; \
-                _Pragma("unroll") for (int r = 0; r < 4; ++r) { h0[r] = fmaxf(h0[r], 0.f); h1[r] = fmaxf(h1[r], 0.f); } \
-                cem_split8(h0, h1, own[c]); \
-                _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_) *reinterpret_cast<cem_u4 *>(smem + xw + cem_split_off(c, w, j_, lane)) = own[c][j_]; \
-            } \
-            xw ^= XB; } while (0)
-#define CEM_NEXT_BIAS(LN) do { \
-            nb0 = cem_ld_tab(et_rs, bias_v, (CEM_ET_ROWS + (LN)) * 512); \
-            nb1 = cem_ld_tab(et_rs, bias_v + 64, (CEM_ET_ROWS + (LN)) * 512); } while (0)
-        {
-            f4 acc0[RC], acc1[RC];
-#pragma unroll
-            for (int c = 0; c < RC; ++c) { acc0[c] = nb0; acc1[c] = nb1; }
-            CEM_NEXT_BIAS(p.L > 1 ? 1 : 0);
-            // layer 0: every chunk of the scaled input comes from LDS (a wave's input blocks w, w + 4 are halves of two chunks)
-            cem_split_stage<RC, NCH0, false, CEM_X_EXCHANGE>(acc0, acc1, own, wq, smem, xw ^ XB, lane, w);
-            // the head biases of the wave's first observation block start the heads' accumulators: requested here, a step's worth of
-            // hidden stages ahead (requested next to their use they cost the heads stage an L2 round trip: 2.26 K vs 1.8 K cycles)
-            bm0 = cem_ld_tab(et_rs, tab_v, CEM_ET_BMU * 512); bv0 = cem_ld_tab(et_rs, tab_v, CEM_ET_BVAR * 512);
-            CEM_STAMP(0);
-            CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, t - 1);
-            CEM_STAMP(6);
-            CEM_SPLIT_PUBLISH();
-            CEM_STAMP(5);
-        }
-        for (int l = 1; l < p.L; ++l) {
-            f4 acc0[RC], acc1[RC];
-#pragma unroll
-            for (int c = 0; c < RC; ++c) { acc0[c] = nb0; acc1[c] = nb1; }
-            CEM_NEXT_BIAS(l + 1 < p.L ? l + 1 : 0);
-            cem_split_stage<RC, CEM_SPLIT_CHUNKS, true, CEM_X_EXCHANGE>(acc0, acc1, own, wq, smem, xw ^ XB, lane, w);
-            CEM_STAMP(1);
-            CEM_SPLIT_PUBLISH();
-            CEM_STAMP(5);
-        }
-#undef CEM_SPLIT_PUBLISH
-#undef CEM_NEXT_BIAS
-
-        // ---- heads, state update, scorer terms, next scaled input: cem_rollout_tile's epilogue ------------------------------------
-        float pm[2][RC];
-#pragma unroll
-        for (int c = 0; c < RC; ++c) { pm[0][c] = __builtin_inff(); pm[1][c] = __builtin_inff(); }
-        const int tn = (t + 1 < H) ? t + 1 : H - 1;
-#pragma unroll
-        for (int i = 0; i < NFW; ++i) {
-            const int Fo = w + 4 * i;
-            const int tv = tab_v + 256 * i;
-            const f4 mn4 = cem_ld_tab(et_rs, tv, CEM_ET_NMIN * 512), rd4 = cem_ld_tab(et_rs, tv, CEM_ET_RDELTA * 512);
-            const f4 bm = i == 0 ? bm0 : cem_ld_tab(et_rs, tv, CEM_ET_BMU * 512), bv = i == 0 ? bv0 : cem_ld_tab(et_rs, tv, CEM_ET_BVAR * 512);
-            const f4 om4 = cem_ld_tab(et_rs, tv, CEM_ET_OBS * 512), isact4 = cem_ld_tab(et_rs, tv, CEM_ET_ACT * 512);
-            const f4 sel0 = cem_ld_tab(et_rs, tv, CEM_ET_SEL0 * 512), sel1 = cem_ld_tab(et_rs, tv, CEM_ET_SEL1 * 512);
-            f4 accm[RC], accv[RC];
-#pragma unroll
-            for (int c = 0; c < RC; ++c) { accm[c] = bm; accv[c] = bv; }
-            CEM_STAMP(2);
-            if (Fo < p.KB_obs) {                                                           // wave-uniform
-                if (i == 0) cem_split_stage<RC, CEM_SPLIT_CHUNKS, true, CEM_X_EXCHANGE>(accm, accv, own, wq, smem, xw ^ XB, lane, w);
-                else cem_split_stage<RC, CEM_SPLIT_CHUNKS, true, CEM_X_REREAD>(accm, accv, own, wq, smem, xw ^ XB, lane, w);
-            } else if (i == 0) {
-                __syncthreads();                      // keep the barrier count of waves without observation features
-            }
-            CEM_STAMP(3);
-            // the step's model noise and actions: independent of the heads' MFMAs, so drawn AFTER they are issued — VALU work behind
-            // queued bf16 MFMAs runs in their shadow (scripts/mfma_microbench5.hip -DMB_BF16: 288 MFMAs + 330 VALU take 1.08 x the MFMAs alone)
-            f4 act4[RC], eps4[RC];
-#pragma unroll
-            for (int c = 0; c < RC; ++c) {
-                CEM_LOAD_ACT(act4[c], MODE, p, act_rs, actv, actrow, w, q, O, A, i, c, tn);
-                CEM_MODEL_NOISE4(eps4[c], MODE, p, td, 0, O, t, t, slotc[c], Fo, q, key, rscale);
-            }
-#pragma unroll
-            for (int c = 0; c < RC; ++c) {
-                const f4 mu = accm[c];
-                const f4 var = cem_softplus4(accv[c]) + 1e-4f;
-                f4 sd;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sd[r] = __builtin_amdgcn_sqrtf(var[r]);
-                const f4 d = mu + sd * eps4[c];
-                const f4 sn = s[i][c] + d * om4;
-                if (MODE == 1) {
-                    const int slot = 16 * c + j, f0 = 16 * Fo + 4 * q;
-                    if (slot < td.cnt) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (f0 + r < O) {
-                                const size_t o = ((size_t)(td.row_base + slot) * H + t) * O + f0 + r;
-                                if (p.mu_out) p.mu_out[o] = mu[r];
-                                if (p.sd_out) p.sd_out[o] = sd[r];
-                                if (p.traj) p.traj[((size_t)(td.row_base + slot) * (H + 1) + (t + 1)) * O + f0 + r] = sn[r];
-                            }
-                    }
-                }
-                s[i][c] = sn;
-                cem_scorer_terms(sn, p.sc.D, sel0, sel1, pm[0][c], pm[1][c]);
-                const f4 x = cem_sub4(__builtin_elementwise_fma(isact4, act4[c], sn), mn4) * rd4;
-                CEM_PUBLISH_X(x, Fo, c);
-            }
-        }
-        CEM_RARE_KINDS_AND_STORE(RC, NFW, p, part, w, q, j, nk, s, pm, tab_v, CEM_SEL0_MEM, et_rs);
-        xw ^= XB;
-        CEM_STAMP(4);
-    }
-    __syncthreads();
-    CEM_BOOKKEEP(p, td, part, w, wbk, lane, nk, csz, ind_cap, clipv, cost_rs, d_prev, c_prev, cum, done, H - 1);
-    if (w == wbk && lane < td.cnt) p.ret[td.row_base + lane] = cum;
-#ifdef CEM_STAMPS
-    if (p.stamps && lane == 0) for (int i = 0; i < 8; ++i) p.stamps[((size_t)tile_idx * 4 + w) * 8 + i] = st_[i];
-#endif
-#undef CEM_PUBLISH_X
-}
+            *reinterpret_cast<cem_u2 *>((SMEM_) + (XW_) + cem_split_off((C_), (FO_) >> 1, j_, LANE_) + 8 * ((FO_) & 1)) = px_[j_]; } while (0)
+#define CEM_CHUNKED_PUBLISH_H(SMEM_, XW_, LANE_, W_, H0_, H1_, OWN_, C_) do { cem_split8(H0_, H1_, OWN_[C_]); \
+        _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_) \
+            *reinterpret_cast<cem_u4 *>((SMEM_) + (XW_) + cem_split_off(C_, W_, j_, LANE_)) = OWN_[C_][j_]; } while (0)
+#include "cem_rollout_chunked.h"
 
 template <int RC, int NFW, int MODE>
 __global__ __launch_bounds__(256) void cem_rollout_split_kernel(const RolloutParams p)
@@ -404,3 +187,4 @@ __global__ __launch_bounds__(256) void cem_rollout_split_kernel(const RolloutPar
     cem_tile_sample_actions(p, (int)blockIdx.x, 0, p.H, true, MODE == 1);
     cem_rollout_tile_split<RC, NFW, MODE>(p, smem, (int)blockIdx.x);
 }
+

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: the bf16 rollout (precision 'bf16', csrc/cem_rollout_bf16.h) over population sizes and tile sizes (K = P members, H = 30,
 I = 5): plan time with 1 / 2 / 3 / 4 chunks per tile and with the library's own choice, per input family (obs 60 act 2 K 5: one input
-block per wave; obs 100 act 12 K 8: two).  The last column is the load auto_chunks_bf16 keys its table on: row-chunks per CU at
+block per wave; obs 100 act 12 K 8: two).  The last column is the load auto_chunks_chunked keys its table on: row-chunks per CU at
 one-chunk tiles.  usage: python scripts/sweep_bf16_tiles.py [--family 60|100] [N ...] > profiles/bf16_tile_sizes.txt"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,7 +16,7 @@ if '--family' in args:
 H, I = 30, 5
 cus = torch.cuda.get_device_properties(0).multi_processor_count
 print("# bf16 rollout (precision 'bf16', csrc/cem_rollout_bf16.h): plan ms (captured graph, %d iterations, H = %d) at 1 / 2 / 3 / 4 chunks per tile" % (I, H))
-print('# and at the size auto_chunks_bf16 picks (its table, kBf16Step, holds the m-co-resident-tiles figures of the rc columns); %d CUs' % cus, flush=True)
+print('# and at the size auto_chunks_chunked picks (its table, kBf16Step, holds the m-co-resident-tiles figures of the rc columns); %d CUs' % cus, flush=True)
 for fam, (obs, act, K, sizes) in FAMILIES.items():
     if only and fam != only:
         continue

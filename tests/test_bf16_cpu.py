@@ -162,12 +162,10 @@ def test_emulations_agree_with_the_oracle_where_nothing_is_rounded():
 
 
 # ---- the build: what the tile rule and the residency table of cem_capi.hip rest on ---------------------------------------------------
-def test_bf16_rollout_kernels_fit_the_residency_their_tile_rule_assumes():
-    """cem_rollout_bf16.hip compiled to assembly with the Makefile's flags (cached under /tmp on the hash of the device sources): all 16
-    instantiations, no spilled VGPR anywhere, no scratch and no more VGPRs than kBf16Resident assumes (512 / resident workgroups) in
-    the planning instantiations; the products are bf16 MFMAs (one per chunk and output block: 2 x (2 + 4 + 4) in the unrolled stages
-    of the one-chunk kernel), nothing falls back to fp32 MFMAs, and the operands are rounded by the hardware conversion."""
-    import hashlib, os, re, subprocess
+def _bf16_unit_assembly():
+    """cem_rollout_bf16.hip compiled to assembly with the Makefile's flags (cached under /tmp on the hash of the device sources).
+    Skips the calling test where there is no hipcc."""
+    import hashlib, os, subprocess
     from tests import helpers as hp
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     if not os.path.exists(hipcc):
@@ -182,7 +180,17 @@ def test_bf16_rollout_kernels_fit_the_residency_their_tile_rule_assumes():
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-3000:]
         os.replace(out + '.tmp', out)
-    isa = open(out).read()
+    return open(out).read()
+
+
+def test_bf16_rollout_kernels_fit_the_residency_their_tile_rule_assumes():
+    """cem_rollout_bf16.hip compiled to assembly with the Makefile's flags (cached under /tmp on the hash of the device sources): all 16
+    instantiations, no spilled VGPR anywhere, no scratch and no more VGPRs than kBf16Resident assumes (512 / resident workgroups) in
+    the planning instantiations; the products are bf16 MFMAs (one per chunk and output block: 2 x (2 + 4 + 4) in the unrolled stages
+    of the one-chunk kernel), nothing falls back to fp32 MFMAs, and the operands are rounded by the hardware conversion."""
+    import re
+    from tests import helpers as hp
+    isa = _bf16_unit_assembly()
     meta = hp.kernel_meta(isa, r'cem_rollout_bf16_kernelILi\dELi\dELi\dEE')
     assert len(meta) == 16, sorted(meta)
     resident = {1: (4, 3, 2, 2), 2: (3, 2, 2, 2)}            # cem_capi.hip kBf16Resident[nfw - 1][rc - 1]
@@ -199,6 +207,20 @@ def test_bf16_rollout_kernels_fit_the_residency_their_tile_rule_assumes():
     assert not any(l.startswith('v_mfma_f32_16x16x4_f32') for l in ins), 'the bf16 kernel must not fall back to fp32 MFMAs'
     assert any(l.startswith('v_cvt_pk_bf16_f32') for l in ins), 'operands are rounded to nearest even by the hardware conversion'
     assert not any(l.startswith('scratch_') for l in ins)
+
+
+def test_bf16_rollout_kernels_keep_their_register_counts():
+    """Every cem_rollout_bf16_kernel instantiation keeps the registers, spills, scratch and LDS it had when the tile rule's residency row
+    (cem_capi.hip kBf16Resident: 512 / VGPRs of the planning instantiations, 113 145 171 205 | 155 185 221 253) was measured.  The
+    golden is the metadata of cem_rollout_bf16.hip at commit 52f6ae7 (the last one with a tile body of its own), compiled with the
+    Makefile's flags: hipcc <FLAGS without -fPIC -shared> -S --cuda-device-only cem_rollout_bf16.hip, read with helpers.kernel_meta."""
+    import json, os
+    from tests import helpers as hp
+    keys = ('vgpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size', 'group_segment_fixed_size')
+    want = json.load(open(os.path.join(hp.ROOT, 'tests', 'golden', 'bf16_rollout_registers.json')))
+    assert len(want) == 16
+    got = hp.kernel_meta(_bf16_unit_assembly(), r'cem_rollout_bf16_kernelILi\dELi\dELi\dEE', keys)
+    assert got == want, {k: (want.get(k), got.get(k)) for k in sorted(set(want) | set(got)) if want.get(k) != got.get(k)}
 
 
 def test_the_forced_generic_rollout_is_refused(monkeypatch):

@@ -85,7 +85,7 @@ def test_dot_products_of_split_operands_match_fp32_dot_products():
     assert e_split.max() <= 4e-7 and e_split.max() <= 2.0 * max(e_plain.max(), 6e-8), (e_split.max(), e_plain.max())
 
 
-# ---- the packed weight stream of the split kernel (pack_member_split), consumed the way cem_rollout_split.h consumes it ----------------
+# ---- the packed weight stream of the split kernel (pack_member_chunked), consumed the way cem_rollout_split.h consumes it ----------------
 def _bf16_planes_to_f64(words16):
     return (np.asarray(words16, np.uint32) << 16).view(np.float32).astype(np.float64)
 

@@ -22,6 +22,7 @@ CEM_CONSTRAINT_BETA, CEM_CONSTRAINT_BUDGET = 0, 1               # enum cem_const
 CEM_REFIT_UNIFORM, CEM_REFIT_SOFTMAX = 0, 1                       # enum cem_refit
 CEM_NOISE_WHITE, CEM_NOISE_MIXED = 0, 1                         # enum cem_action_noise
 CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
+CEM_TASK_SAFETY_GYM, CEM_TASK_QUADRATIC = 0, 1                  # enum cem_task_kind
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_population_schedule', 'cem_planner_get_population_schedule', 'cem_planner_iteration_plan',
     'cem_planner_set_mean_candidate', 'cem_planner_get_mean_candidate',
     'cem_planner_set_plan_readout', 'cem_planner_get_plan_readout', 'cem_planner_plan_readout',
+    'cem_planner_set_task', 'cem_planner_task_trajectories', 'cem_task_score',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -96,6 +98,11 @@ class CemIterationPlan(C.Structure):
 
 class CemPlanReadout(C.Structure):
     _fields_ = [('score', C.c_float), ('candidate', C.c_int32), ('iteration', C.c_int32), ('flags', C.c_int32)]
+
+
+class CemTask(C.Structure):
+    _fields_ = [('kind', C.c_int32)] + [(n, C.POINTER(C.c_float)) for n in ('q', 'g', 'c', 'goal_mask', 'lo', 'hi', 'rho')] + \
+               [('goal_radius', C.c_float), ('reward_goal', C.c_float), ('reward_clip', C.c_float)]
 
 
 class CemLayout(C.Structure):
@@ -208,6 +215,9 @@ def load():
     lib.cem_planner_set_plan_readout.argtypes = [vp, C.c_int32]
     lib.cem_planner_get_plan_readout.argtypes = [vp, i32p]
     lib.cem_planner_plan_readout.argtypes = [vp, C.c_int32, C.POINTER(CemPlanReadout), vp, vp, vp]
+    lib.cem_planner_set_task.argtypes = [vp, C.POINTER(CemTask)]
+    lib.cem_planner_task_trajectories.argtypes = [vp, vp]
+    lib.cem_task_score.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

@@ -7,6 +7,7 @@
 #include "cem_noise_mix.h"
 #include "cem_elite_carry.h"
 #include "cem_plan_readout.h"
+#include "cem_task_score.h"
 #include "cem_population.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
@@ -824,6 +825,10 @@ struct cem_planner {
     // cem_planner_set_plan_readout (cem_plan_readout.h)
     uint32_t *readout_dev;                   // a device allocation of the handle's own, made by the first enabling call: [slots] blocks of
                                              // CEM_READOUT_WORDS(H, A, P) words (the population never enters the size)
+    // cem_planner_set_task (cem_task_score.h)
+    float *task_dev;                         // a device allocation of the handle's own, made by the first enabling call: the tables
+                                             // [CEM_TASK_TABLES][CEM_U], then the trajectories [Bloc][H + 1][O] of the last rollout launch
+    TaskScoreParams task;                    // the task as set: tab, r2, reward_goal, clip, rho (the launch fills in the rest)
 };
 
 namespace {
@@ -860,6 +865,9 @@ int lean_form(const cem_planner *h, int it)
     for (int w = 0; w < 4; ++w) straight = straight && d.wave_groups[w] == 4 + 3 * CEM_NG + (w < d.KB_obs ? CEM_NG : 0);
     return straight ? 2 : 1;
 }
+// the two parts of the task allocation (cem_planner::task_dev)
+size_t task_tab_floats() { return (size_t)CEM_TASK_TABLES * CEM_U; }
+float *task_traj(const cem_planner *h) { return h->task_dev + task_tab_floats(); }
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
 size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
 float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
@@ -894,6 +902,7 @@ struct LaunchRecipe {
     int select_mode; bool select_cache;      // the select form (select_mode_for) and whether the one-workgroup kernel stages its keys in LDS
     bool one_workgroup_only;                 // something below, or a schedule: admit() let it onto a one-workgroup select only
     bool weighted, keep_elites, track;       // behind the select: the weighted refit, carry-over's keep, the read-out's tracker
+    bool task;                               // the rollout is the family's MODE 1 kernel writing the handle's trajectory buffer, cem_task_score_kernel behind it
 };
 LaunchRecipe recipe_of(const cem_planner *h, int it, bool own_noise)
 {
@@ -904,7 +913,9 @@ LaunchRecipe recipe_of(const cem_planner *h, int it, bool own_noise)
     // mean candidate, in the one iteration it is written in (cem_population.h)
     r.inject_elites = o.elite.n_keep != 0;   // (a plan's iteration 0 has nothing to take without across_plans: enqueue_rollout; counted all the same)
     r.inject_mean = o.mean_cand && it == h->d.I - 1;
-    const bool rewritten = r.inject_elites || r.inject_mean;
+    // The task scorer reads trajectories only the MODE 1 kernels write, and those read a sample that lies in memory (cem_task_score.h)
+    r.task = o.task != 0;
+    const bool rewritten = r.inject_elites || r.inject_mean || r.task;
     r.sampler_launch = !v.sample_in_rollout || rewritten;
     // (the handle's own mixed tensor stands in wherever the caller passed none: the lean kernels step aside for it as for any tensor)
     r.lean_form = v.lean_rollout && !rewritten && !own_noise && o.noise_kind != CEM_NOISE_MIXED ? lean_form(h, it) : 0;
@@ -923,7 +934,7 @@ int launches_of(const cem_planner *h, int it)
 {
     const LaunchRecipe r = recipe_of(h, it, false);
     return 1 + r.sampler_launch + r.inject_elites + r.inject_mean + !r.fold_reduce + (r.select_mode == 2 ? 8 : r.select_mode == 3 ? 2 : 1) +
-           r.weighted + r.keep_elites + r.track;
+           r.weighted + r.keep_elites + r.track + r.task;
 }
 
 // The handle's options as a setter takes them.  Whether there is a communicator is the one fact not kept in cem_planner::opt: `comm` says it
@@ -944,7 +955,7 @@ HandleFacts facts_of(const cem_planner *h, const PlanOptions &next)
     f.readout_max_p = CEM_READOUT_MAX_P; f.max_cost_kinds = CEM_MAX_COST_KINDS; f.budget_total_limit = kBudgetTotalLimit;
     f.refit_lds_bytes = CEM_REFIT_LDS_BYTES(d.k, d.H * d.A); f.refit_lds_limit = h->sel_dyn_limit;
     f.can_mix = launch_mix_action_noise && prepare_mix_action_noise; f.can_carry = launch_elite_keep && launch_elite_inject;
-    f.can_mean = launch_mean_candidate != nullptr; f.can_track = launch_plan_track != nullptr;
+    f.can_mean = launch_mean_candidate != nullptr; f.can_track = launch_plan_track != nullptr; f.can_task = launch_task_score != nullptr;
     return f;
 }
 int admit_on(const cem_planner *h, const PlanOptions &next, PlanChange change = PLAN_CHANGE_OTHER) { return admit(facts_of(h, next), next, change); }
@@ -987,6 +998,7 @@ void release_handle(cem_planner *h)
     if (h->noise_dev) hipFree(h->noise_dev);
     if (h->elite_dev) hipFree(h->elite_dev);
     if (h->readout_dev) hipFree(h->readout_dev);
+    if (h->task_dev) hipFree(h->task_dev);
     if (h->pop_dev) hipFree(h->pop_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
@@ -1152,6 +1164,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
     h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
     h->readout_dev = nullptr;
+    h->task_dev = nullptr; h->task = TaskScoreParams{};
     h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
@@ -1615,7 +1628,8 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
     // noise tensors keep the slabs of the handle's own n_samples (h->d), of which a narrower iteration reads the leading part
     const IterView v = iter_view(h, it);
     const Dims &d = *v.d; const Layout &l = h->lay; char *ws = h->ws;
-    const bool queued = v.n_seg > 1 && !h->eps_model;       // explicit eps_model tensors take the general (MODE 1) kernel
+    const bool queued = v.n_seg > 1 && !h->eps_model && !rc.task;   // explicit eps_model tensors and the task scorer take the general (MODE 1) kernel
+    if (rc.task && !h->task_dev) return CEM_ERR_UNSUPPORTED;        // (the setter made the allocation before it committed)
     RolloutParams rp; fill_rollout_common(h, rp, v.d);
     rp.tiles = v.tiles; rp.s0 = nullptr; rp.actions = (const float *)(ws + l.actions);
     rp.eps_model = h->eps_model ? h->eps_model + (size_t)it * d.H * h->d.Btot * d.O : nullptr;
@@ -1654,6 +1668,10 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
             HIPCHK(launch_mean_candidate(mc, nb, h->stream));
         }
     }
+    // the task scorer: the family's MODE 1 instantiation (cem_unfold_sequences'), its raw states into the handle's buffer; Philox model
+    // noise unless the caller brought a tensor
+    const bool mode1 = rp.eps_model || rc.task;
+    if (rc.task) rp.traj = task_traj(h);
     TimedLaunch timed(h, 0);
     if (rc.lean_form) {                                          // (the same tiles, segments and work queue as the generic launches below)
         if (queued) {
@@ -1664,9 +1682,9 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
         if (rc.lean_form == 2 && (rp.variant == 1) == (rp.costs != nullptr)) HIPCHK(launch_rollout_lean_straight(rp, grid, h->stream, queued));
         else HIPCHK(launch_rollout_lean(rp, grid, h->stream, queued));
     }
-    else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, rp.eps_model ? 1 : 0));
-    else if (d.chunked()) HIPCHK(launch_rollout_chunked(d, v.rc, rp.eps_model ? 1 : 0, rp, v.n_tiles, h->stream));
-    else if (rp.eps_model) HIPCHK(launch_rollout<1>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
+    else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, mode1 ? 1 : 0));
+    else if (d.chunked()) HIPCHK(launch_rollout_chunked(d, v.rc, mode1 ? 1 : 0, rp, v.n_tiles, h->stream));
+    else if (mode1) HIPCHK(launch_rollout<1>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     else if (queued) {
         rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
         rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
@@ -1674,6 +1692,16 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
         HIPCHK(launch_rollout_seg(v.rc, d.NFW, rp, v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned), h->stream));
     } else HIPCHK(launch_rollout<0>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     timed.stop();
+    // the task's returns and cost bytes over the Safety-Gym ones the rollout has just written, in stream order (cem_task_score.h);
+    // timed with the reduce
+    if (rc.task) {
+        TaskScoreParams tp = h->task;
+        tp.traj = rp.traj; tp.actions = rp.actions; tp.ctrl = rp.ctrl; tp.ret = rp.ret; tp.costs = rp.costs;
+        tp.rows = d.Bloc; tp.N = d.N; tp.H = d.H; tp.O = d.O; tp.A = d.A; tp.variant = rp.variant; tp.check_done = 1;
+        if (cost_obj) tp.r2 = 0.f;                           // compute_mean_costs has no done mask (safe_cem_mpc.py:98-108): near is never true
+        TimedLaunch timed_task(h, 2);
+        HIPCHK(launch_task_score(tp, h->stream));
+    }
     if (whole_plan && rc.fold_reduce) return CEM_OK;
 
     // the score kernel of the handle's objective, timed as the one reduce launch; it clears the words of this iteration's multi-workgroup select
@@ -2438,6 +2466,87 @@ int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout
     if (sequence_out_host) HIPCHK(hipMemcpy(sequence_out_host, blk + CEM_READOUT_HEAD, HA * 4, hipMemcpyDeviceToHost));
     if (particle_returns_out_host) HIPCHK(hipMemcpy(particle_returns_out_host, blk + CEM_READOUT_HEAD + HA, (size_t)d.P * 4, hipMemcpyDeviceToHost));
     if (cost_counts_out_host) HIPCHK(hipMemcpy(cost_counts_out_host, blk + CEM_READOUT_HEAD + HA + d.P, (size_t)d.H * 4, hipMemcpyDeviceToHost));
+    return CEM_OK;
+}
+
+int cem_planner_set_task(cem_planner_t *h, const cem_task_t *task)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    const Dims &d = h->d;
+    const bool on = task && task->kind != CEM_TASK_SAFETY_GYM;
+    if (task && task->kind != CEM_TASK_SAFETY_GYM && task->kind != CEM_TASK_QUADRATIC) return CEM_ERR_INVALID_ARG;
+    // on the bit patterns: this file is built with -fno-honor-nans
+    auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+    auto finite = [&](float v) { return (bits(v) & 0x7fffffffu) < 0x7f800000u; };
+    auto is_nan = [&](float v) { return (bits(v) & 0x7fffffffu) > 0x7f800000u; };
+    // the tables as the kernel reads them: [CEM_TASK_TABLES][CEM_U], the defaults beyond obs_dim and for a NULL table
+    std::vector<float> tab(task_tab_floats(), 0.f);
+    TaskScoreParams tp{};
+    if (on) {
+        const float inf = std::numeric_limits<float>::infinity();
+        const float *src[CEM_TASK_TABLES] = {task->q, task->g, task->c, task->goal_mask, task->lo, task->hi};
+        for (int f = 0; f < CEM_U; ++f) { tab[CEM_TASK_TAB_LO * CEM_U + f] = -inf; tab[CEM_TASK_TAB_HI * CEM_U + f] = inf; }
+        for (int k = 0; k < CEM_TASK_TABLES; ++k)
+            for (int f = 0; src[k] && f < d.O; ++f) {
+                const float v = src[k][f];
+                if (k < CEM_TASK_TAB_LO ? !finite(v) : is_nan(v)) return CEM_ERR_INVALID_ARG;
+                tab[(size_t)k * CEM_U + f] = v;
+            }
+        for (int f = 0; f < d.O; ++f) if (tab[CEM_TASK_TAB_LO * CEM_U + f] > tab[CEM_TASK_TAB_HI * CEM_U + f]) return CEM_ERR_INVALID_ARG;
+        for (int j = 0; task->rho && j < d.A; ++j) { if (!finite(task->rho[j])) return CEM_ERR_INVALID_ARG; tp.rho[j] = task->rho[j]; }
+        if (!finite(task->goal_radius) || !finite(task->reward_goal) || !finite(task->reward_clip) || (bits(task->goal_radius) >> 31 && task->goal_radius != 0.f)) return CEM_ERR_INVALID_ARG;
+        tp.r2 = task->goal_radius * task->goal_radius;         // fl32, rounded once here
+        tp.reward_goal = task->reward_goal; tp.clip = task->reward_clip > 0.f ? task->reward_clip : inf;
+    }
+    if (h->in_plan) return CEM_ERR_STATE;
+    PlanOptions next = options_of(h); next.task = on ? (int)CEM_TASK_QUADRATIC : (int)CEM_TASK_SAFETY_GYM;
+    { const int st = admit_on(h, next); if (st) return st; }
+    // cem_unfold_sequences' element limit on the trajectory tensor
+    const long long traj_floats = (long long)d.Bloc * (d.H + 1) * d.O;
+    if (on && traj_floats > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
+    // allocated before anything of the handle changes: a failed allocation leaves it as it was
+    DevBlock made;
+    if (on && !h->task_dev) HIPCHK(made.alloc((task_tab_floats() + (size_t)traj_floats) * 4));
+    // Unconditional: an eager plan still draining behind its polled result may be reading the tables
+    return commit_launch_change(h, next, true, [&]() -> int {
+        if (!on) return CEM_OK;
+        float *dev = made.p ? static_cast<float *>(made.p) : h->task_dev;
+        HIPCHK(hipMemcpy(dev, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        // (the buffer reads as zeros until the first rollout launch has filled it)
+        if (made.p) HIPCHK(hipMemset(dev + task_tab_floats(), 0, (size_t)traj_floats * 4));
+        if (made.p) h->task_dev = made.release<float>();
+        tp.tab = h->task_dev;
+        h->task = tp;
+        return CEM_OK;
+    });
+}
+
+int cem_planner_task_trajectories(cem_planner_t *h, float *out_dev)
+{
+    if (!h || !out_dev) return CEM_ERR_INVALID_ARG;
+    if (!h->opt.task || !h->task_dev) return CEM_ERR_STATE;
+    const Dims &d = h->d;
+    HIPCHK(hipMemcpyAsync(out_dev, task_traj(h), (size_t)d.Bloc * (d.H + 1) * d.O * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CEM_OK;
+}
+
+int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions_dev, int32_t n_rows, int32_t horizon,
+                   float *ret_out_dev, uint8_t *costs_out_dev)
+{
+    if (!h || !traj_dev || !actions_dev || !ret_out_dev || n_rows < 1 || horizon < 1 || horizon > 65535) return CEM_ERR_INVALID_ARG;
+    if (h->batch) return CEM_ERR_STATE;
+    if (!h->opt.task || !h->task_dev) return CEM_ERR_STATE;
+    const Dims &d = h->d;
+    if (n_rows % d.P != 0) return CEM_ERR_INVALID_ARG;                 // reshape(cum, (particles, -1)) would raise (mpc_policy.py:38)
+    if ((long long)n_rows * (horizon + 1) * d.O > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
+    TaskScoreParams tp = h->task;
+    tp.traj = traj_dev; tp.actions = actions_dev; tp.ctrl = nullptr; tp.ret = ret_out_dev;
+    tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0; tp.costs = tp.variant ? costs_out_dev : nullptr;
+    tp.rows = n_rows; tp.N = n_rows / d.P; tp.H = horizon; tp.O = d.O; tp.A = d.A; tp.check_done = 0;
+    if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;      // (as in a plan: the cost objective's bytes are not masked by done)
+    HIPCHK(launch_task_score(tp, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return CEM_OK;
 }
 

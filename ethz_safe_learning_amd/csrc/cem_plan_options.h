@@ -20,6 +20,7 @@ struct PlanOptions {
     std::vector<int32_t> pop;                // cem_planner_set_population_schedule: n[it] of every iteration; empty: off (cem_population.h)
     int mean_cand = 0;                       // cem_planner_set_mean_candidate: 1 = the last iteration's last candidate is the clipped mean
     int readout = 0;                         // cem_planner_set_plan_readout: 1 = cem_plan_track_kernel follows every select (cem_plan_readout.h)
+    int task = 0;                            // cem_planner_set_task: enum cem_task_kind; CEM_TASK_QUADRATIC puts cem_task_score_kernel behind a MODE 1 rollout (cem_task_score.h)
     bool comm = false;                       // the handle has a communicator (cem_planner_comm_init; cem_capi.hip: options_of reads it off the handle)
 };
 
@@ -33,7 +34,7 @@ struct HandleFacts {
     long long budget_total_limit = 0;                  // H * m * kinds of a budget plan stays below it (cem_capi.hip: kBudgetTotalLimit)
     size_t refit_lds_bytes = 0, refit_lds_limit = 0;   // the weighted refit's dynamic LDS at this (k, H A) and what the device grants
     // the launchers of the optional translation units that are linked in
-    bool can_mix = false, can_carry = false, can_mean = false, can_track = false;
+    bool can_mix = false, can_carry = false, can_mean = false, can_track = false, can_task = false;
 };
 
 // which call asks: only the inherited asymmetry below reads it
@@ -75,6 +76,9 @@ inline int admit(const HandleFacts &f, const PlanOptions &o, PlanChange change =
     if (carry && (f.k > f.elite_max_k || !f.can_carry)) return CEM_ERR_UNSUPPORTED;
     if (mean && !f.can_mean) return CEM_ERR_UNSUPPORTED;
     if (track && (f.P > f.readout_max_p || !f.can_track)) return CEM_ERR_UNSUPPORTED;
+    // THE TASK SCORER reads every row's whole trajectory out of ONE buffer of a single-state, single-rank handle (cem_task_score.h): no
+    // shard, no communicator, no batch handle, and the kernel itself
+    if (o.task != 0 && (f.W > 1 || o.comm || f.batch || !f.can_task)) return CEM_ERR_UNSUPPORTED;
     // THE INJECT'S ROWS are candidates of every iteration, and none of them is the mean candidate's (the last iteration's last row)
     if (carry) {
         for (int32_t n : o.pop) if (n <= o.elite.n_keep) return CEM_ERR_UNSUPPORTED;

@@ -33,6 +33,45 @@ class ScorerConfig:
 
 
 @dataclass
+class QuadraticTask:
+    """A quadratic reward with box state constraints (cem_task_t, CEM_TASK_QUADRATIC; cem_mpc.h "Task scorers"): the objective of plans
+    whose observation is no Safety-Gym lidar vector.  Per step, with s the raw state and a the action,
+        reward = -sum_f [q_f (s'_f - g_f)^2 - c_f s'_f] - sum_j rho_j a_j^2 + reward_goal * near(s),   clipped to +-reward_clip (0: no clip)
+        near(s) = goal_radius > 0 and sum_f goal_mask_f (s_f - g_f)^2 <= goal_radius^2             (near ends the episode, as the goal does)
+        cost(s) = 1 if any s_f < lo_f or s_f > hi_f                                                  ('safe' / 'cost' handles)
+    Every table is an array of the feature count or a scalar broadcast to it."""
+    q: object = 0.0
+    g: object = 0.0
+    c: object = 0.0
+    goal_mask: object = 0.0
+    lo: object = -np.inf
+    hi: object = np.inf
+    rho: object = 0.0
+    goal_radius: float = 0.0
+    reward_goal: float = 0.0
+    reward_clip: float = 0.0
+
+    @classmethod
+    def to_target(cls, target, weights=1.0, action_weights=0.0, lo=-np.inf, hi=np.inf, goal_radius=0.0, reward_goal=0.0, reward_clip=0.0):
+        """Stay near `target`: reward = -sum weights (s - target)^2 - sum action_weights a^2; with goal_radius > 0 the episode ends (and
+        reward_goal is paid) within that weighted distance of the target, measured on the features whose weight is not zero."""
+        w = np.asarray(weights, np.float32)
+        return cls(q=w, g=target, goal_mask=(w != 0).astype(np.float32), lo=lo, hi=hi, rho=action_weights, goal_radius=goal_radius,
+                   reward_goal=reward_goal, reward_clip=reward_clip)
+
+    def tables(self, obs_dim, act_dim):
+        """The float32 tables as the library takes them: dict of q, g, c, goal_mask, lo, hi [obs_dim] and rho [act_dim]."""
+        def full(v, n, name):
+            a = np.asarray(v, np.float32)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+                raise ValueError('%s must be a scalar or have shape [%d]' % (name, n))
+            return np.ascontiguousarray(np.broadcast_to(a, (n,)), dtype=np.float32)
+        out = {k: full(getattr(self, k), int(obs_dim), k) for k in ('q', 'g', 'c', 'goal_mask', 'lo', 'hi')}
+        out['rho'] = full(self.rho, int(act_dim), 'rho')
+        return out
+
+
+@dataclass
 class PlannerConfig:
     """CemMpc/SafeCemMpc ctor kwargs (cem_mpc.py:7-17, safe_cem_mpc.py:8-19) +
     model dims (config/models.yaml) + sharding."""
@@ -80,6 +119,8 @@ class PlannerConfig:
     plan_readout: bool = False         # True: a tracker kernel behind every select keeps the best-so-far candidate's whole sequence, its particle
                                        # returns and per-step cost counts (cem_planner_set_plan_readout; CemPlanner.plan_readout); not in
                                        # cem_config_t: set after create
+    task: Optional[QuadraticTask] = None   # None: the Safety-Gym scorer (the reference); a QuadraticTask: rollouts are scored by it
+                                       # (cem_planner_set_task) and `scorer` is inert; not in cem_config_t: set after create
     action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
@@ -354,6 +395,7 @@ class CemPlanner:
         self.layout = lay
         self._call = 0
         self.has_comm = False
+        self.task = None                              # the QuadraticTask in force (set_task)
         # the configured options, in this order: (is it configured?, the call that applies it).  A handle that refuses one is closed
         options = (
             (cfg.worst_particles, lambda: self.set_particle_objective('lower_tail', cfg.worst_particles)),
@@ -364,6 +406,7 @@ class CemPlanner:
             (cfg.population, lambda: self.set_population_schedule(cfg.population)),
             (cfg.mean_candidate, lambda: self.set_mean_candidate(True)),
             (cfg.plan_readout, lambda: self.set_plan_readout(True)),
+            (cfg.task is not None, lambda: self.set_task(cfg.task)),
         )
         try:
             for configured, apply in options:
@@ -762,6 +805,47 @@ class CemPlanner:
         _capi.check(self.lib.cem_planner_plan_readout(self.h, int(problem), C.byref(head), _np_ptr(seq), _np_ptr(pret), _np_ptr(cnt)),
                     'cem_planner_plan_readout')
         return PlanReadout(seq, np.float32(head.score), int(head.candidate), int(head.iteration), pret, cnt, int(head.flags))
+
+    def set_task(self, task=None):
+        """Score rollouts by a QuadraticTask instead of the Safety-Gym scorer (cem_planner_set_task); None switches it off.  While on,
+        every iteration launches the sampler, the MODE 1 rollout kernel and cem_task_score_kernel; rollout_path() is 'generic'.
+        Sticky; waits for the stream and re-captures the graph.  task_objective restates the kernel."""
+        if task is None:
+            _capi.check(self.lib.cem_planner_set_task(self.h, None), 'cem_planner_set_task')
+            self.task = None
+            return
+        tb = task.tables(self.cfg.obs_dim, self.cfg.act_dim)      # (kept alive until the call returns: the library copies them)
+        fp = C.POINTER(C.c_float)
+        ct = _capi.CemTask(kind=_capi.CEM_TASK_QUADRATIC, goal_radius=float(task.goal_radius), reward_goal=float(task.reward_goal),
+                           reward_clip=float(task.reward_clip), **{k: tb[k].ctypes.data_as(fp) for k in tb})
+        _capi.check(self.lib.cem_planner_set_task(self.h, C.byref(ct)), 'cem_planner_set_task')
+        self.task = task
+
+    def task_trajectories(self):
+        """The raw state trajectories [P * n_samples, H + 1, obs_dim] of the last rollout launch of a task plan, a copy (torch, on the
+        GPU; cem_planner_task_trajectories).  Rows p * n + candidate; an iteration of a population schedule fills the leading P * n[it]."""
+        c, t = self.cfg, self._torch
+        out = t.empty((c.particles * self.n_local, c.horizon + 1, c.obs_dim), dtype=t.float32, device=self.device)
+        self._wait_inputs()
+        _capi.check(self.lib.cem_planner_task_trajectories(self.h, _ptr(out)), 'cem_planner_task_trajectories')
+        return out
+
+    def task_score(self, trajectories, actions):
+        """cem_task_score_kernel alone (cem_task_score) with the handle's task and variant: trajectories [P * n, H + 1, obs_dim], actions
+        [n, H, act_dim] -> (returns [P * n] float32, cost bytes [H, P * n] uint8 — None on a 'cem' handle), torch tensors on the GPU."""
+        c, t = self.cfg, self._torch
+        traj = t.as_tensor(trajectories, dtype=t.float32, device=self.device).contiguous()
+        act = t.as_tensor(actions, dtype=t.float32, device=self.device).contiguous()
+        if traj.dim() != 3 or traj.shape[2] != c.obs_dim or traj.shape[1] < 2:
+            raise ValueError('trajectories must be [P*n, H+1, obs_dim]')
+        B, H = traj.shape[0], traj.shape[1] - 1
+        if B % c.particles != 0 or tuple(act.shape) != (B // c.particles, H, c.act_dim):
+            raise ValueError('actions must be [rows / particles, H, act_dim]')
+        ret = t.empty((B,), dtype=t.float32, device=self.device)
+        costs = t.empty((H, B), dtype=t.uint8, device=self.device) if c.variant != 'cem' else None
+        self._wait_inputs()
+        _capi.check(self.lib.cem_task_score(self.h, _ptr(traj), _ptr(act), B, H, _ptr(ret), _ptr(costs)), 'cem_task_score')
+        return ret, costs
 
     def plan_exchange(self):
         _capi.check(self.lib.cem_plan_exchange(self.h), 'cem_plan_exchange')
@@ -1231,6 +1315,78 @@ def mean_candidate(actions, mu, lb, ub) -> np.ndarray:
     m = np.asarray(mu, np.float32).reshape(out.shape[1:])
     out[-1] = np.minimum(np.maximum(m, np.asarray(lb, np.float32)), np.asarray(ub, np.float32))
     return out
+
+
+def task_objective(traj, actions, task, variant='cem', return_done=False):
+    """Host restatement of cem_task_score_kernel (csrc/cem_task_score.h; cem_mpc.h "Task scorers"), bit for bit: traj [rows, H + 1, O]
+    raw states, actions [N, H, A] (row r belongs to candidate r mod N), task a QuadraticTask, variant 'cem' | 'safe' | 'cost' ->
+    (returns [rows] float32, cost bytes [H, rows] uint8 — None for 'cem', whose rollout stores none).  Every product and sum is a float32
+    operation of its own, in the kernel's order: per feature d = s - g, dd = d d, q dd - c s and m dd; sixteen partial sums over the
+    features 64 i + 4 l + r (i, then r), added pairwise, neighbours first; u = sum_j rho_j (a_j a_j) from j = 0; the steps in order.
+    A NaN return is stored as 0x7fc00000.  return_done=True appends the first step at which near held, int [rows] (H: never)."""
+    f = np.float32
+    if variant not in VARIANTS:
+        raise ValueError("variant must be 'cem', 'safe' or 'cost'")
+    tr = np.ascontiguousarray(np.asarray(traj, f))
+    act = np.ascontiguousarray(np.asarray(actions, f))
+    if tr.ndim != 3 or act.ndim != 3 or tr.shape[1] != act.shape[1] + 1 or tr.shape[0] % act.shape[0] != 0:
+        raise ValueError('traj must be [rows, H + 1, O] and actions [N, H, A] with rows a multiple of N')
+    rows, H1, O = tr.shape
+    N, H, A = act.shape
+    if O > 128:
+        raise ValueError('obs_dim > 128')
+    tb = task.tables(O, A)
+
+    def pad(a, v):
+        return np.concatenate([a, np.full(128 - O, v, f)])
+    q, g, c, m = (pad(tb[k], 0) for k in ('q', 'g', 'c', 'goal_mask'))
+    s = np.zeros((rows, H1, 128), f)
+    s[..., :O] = tr
+
+    def lane_sum(x):                                  # [rows, H + 1, 128] -> [rows, H + 1]
+        x = x.reshape(rows, H1, 2, 16, 4)
+        acc = np.zeros((rows, H1, 16), f)
+        for i in range(2):
+            for r in range(4):
+                acc = acc + x[:, :, i, :, r]
+        for _ in range(4):
+            acc = acc[..., 0::2] + acc[..., 1::2]
+        return acc[..., 0]
+    with np.errstate(all='ignore'):
+        d = s - g
+        dd = d * d
+        phi = lane_sum(q * dd - c * s)
+        nsum = lane_sum(m * dd)
+        r2 = f(task.goal_radius) * f(task.goal_radius)
+        near = (nsum <= r2) & bool(r2 > 0) & (variant != 'cost')       # (the cost objective's bytes are not masked by done: near is never true)
+        viol = ((tr < tb['lo']) | (tr > tb['hi'])).any(axis=2).astype(f)
+        u = np.zeros((N, H), f)
+        for j in range(A):
+            u = u + tb['rho'][j] * (act[:, :, j] * act[:, :, j])
+        u = u[np.arange(rows) % N]
+        clip = f(task.reward_clip) if f(task.reward_clip) > 0 else f(np.inf)
+        safe = variant != 'cem'
+        cum = np.zeros(rows, f)
+        done = np.zeros(rows, bool)
+        costs = np.zeros((H, rows), np.uint8) if safe else None
+        first = np.full(rows, H, np.int64)
+        for t in range(H):
+            ga = near[:, t]
+            first = np.where(ga & (first == H), t, first)
+            r = ((-phi[:, t + 1]) - u[:, t]) + np.where(ga, f(1), f(0)) * f(task.reward_goal)
+            r = np.fmin(np.fmax(r, -clip), clip)
+            if safe:
+                done = done | ga
+                nd = np.where(done, f(0), f(1))
+                costs[t] = (viol[:, t] * nd).astype(np.uint8)
+                cum = cum + r * nd
+            else:
+                nd = np.where(done, f(0), f(1))
+                cum = cum + r * nd
+                done = done | ga
+    cum = np.ascontiguousarray(cum, f)
+    cum.view(np.uint32)[np.isnan(cum)] = np.uint32(0x7fc00000)
+    return (cum, costs, first) if return_done else (cum, costs)
 
 
 class PlanReadout(NamedTuple):

@@ -66,6 +66,11 @@ select keeps what the plan knew about its choice (``PlannerConfig.plan_readout``
 the safe variant, ``cost_counts [H]`` — how many of the P particles predicted a cost at each step of the plan.  After
 ``generate_actions`` ``last_plans`` holds one per row.  ``generate_action_sequence(state)`` plans and returns ``last_plan.sequence``.
 Sampler, rollout, select and refit launch as before (the lean rollout stays); every read of the block waits for the planner's stream.
+Task scorers (beyond the reference, off by default): with ``task=planner.QuadraticTask(...)`` rollouts are scored by a quadratic reward
+with box state constraints instead of the Safety-Gym scorer (``PlannerConfig.task``, cem_mpc.h cem_planner_set_task):
+the policy then plans for environments whose observation is no lidar vector, and the environment need not expose a scorer.  Every
+option above applies; ``generate_actions`` raises (batch handles do not serve a task).
+
 With ``replan_every=r``, 1 <= r <= horizon (which implies ``plan_readout``), ``generate_action`` plans at decisions 0, r, 2r, ... of an
 episode and in between returns step j of the kept sequence, plus ``noise_stddev`` times the output noise of that decision's own Philox
 call number (no draw, and an exact copy, when ``noise_stddev`` is 0): every decision consumes one call number, ``last_score`` /
@@ -77,7 +82,7 @@ returns or the safety of an agent that uses them."""
 import logging
 import numpy as np
 
-from ...planner import PlannerConfig, cached_batch_planner, cached_planner, elite_keep_count, population_schedule, risk_particles, stage_model_weights
+from ...planner import PlannerConfig, ScorerConfig, cached_batch_planner, cached_planner, elite_keep_count, population_schedule, risk_particles, stage_model_weights
 from .mpc_policy import MpcPolicy
 
 
@@ -88,8 +93,10 @@ class CemMpc(MpcPolicy):
                  stddev_threshold, noise_stddev, seed=0, device='cuda:0', use_graph=True, precision='fp32',
                  warm_start=False, warm_shift=1, warm_tail='box', warm_sigma='reset', warm_sigma_floor=0.25, risk_level=None,
                  elite_temperature=None, noise_beta=None, noise_rho=None, keep_elites=None, shift_elites=False,
-                 population_decay=None, min_population=None, mean_candidate=False, plan_readout=False, replan_every=1):
+                 population_decay=None, min_population=None, mean_candidate=False, plan_readout=False, replan_every=1, task=None):
         super().__init__(model, environment, horizon, n_samples, particles)
+        # a task scorer (beyond the reference's kwargs): see the module docstring
+        self.task = task
         self.iterations = iterations
         self.smoothing = smoothing
         self.elite = n_elite
@@ -191,8 +198,13 @@ class CemMpc(MpcPolicy):
     def _readout_config(self):
         return dict(plan_readout=True) if self.plan_readout else {}
 
+    def _task_config(self):
+        return dict(task=self.task) if self.task is not None else {}
+
     def _scorer_config(self):
         scorer = getattr(self.environment, '_scorer', None) or getattr(self.environment, 'scorer', None)
+        if scorer is None and self.task is not None:      # a task plan never reads the Safety-Gym scorer: any valid one serves
+            return ScorerConfig(goal_slice=(0, 1))
         if scorer is None:
             raise ValueError('environment must expose its SafetyGymStateScorer as `_scorer` (as MbrlSafetyGym does, '
                              'reference simba/environment_utils/safety_gym.py:27-29)')
@@ -210,7 +222,7 @@ class CemMpc(MpcPolicy):
             variant=self.variant, sampling_propagation=m.sampling_propagation, scale_features=m.scale_features,
             use_graph=self.use_graph, precision=self.precision, worst_particles=self.worst_particles, **self._refit_config(),
             **self._noise_config(), **self._carry_config(), **self._population_config(), **self._readout_config(),
-            **self._extra_config())
+            **self._task_config(), **self._extra_config())
 
     def _owns_handles(self):
         """Whether this policy's planning handles carry state of its own (the warm-start carry, the elites kept across plans; SafeCemMpc:
@@ -337,6 +349,9 @@ class CemMpc(MpcPolicy):
         Warm start: slots[B] is the environment index of every row (distinct; default: the row index) — row b continues the plans of
         ITS environment whichever rows the call holds — and reset[B] marks rows whose environment begins an episode (they plan cold).
         Both are ignored without warm start."""
+        if self.task is not None:
+            raise ValueError('task= scores the trajectories of ONE plan out of one buffer; generate_actions plans on a batch handle, which the '
+                             'task scorer does not serve: use generate_action')
         if self.shift_elites:
             raise ValueError('shift_elites=True carries elites across the plans of ONE environment; generate_actions plans on a batch handle, '
                              'whose rows move between slots: use generate_action, or keep_elites alone')

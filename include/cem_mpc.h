@@ -753,6 +753,58 @@ int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout
                              int32_t *cost_counts_out_host /* [H] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Task scorers: plan on quadratic rewards and box state constraints.  Beyond the reference, off by default.
+ * cem_scorer_t says "the observation is a Safety-Gym lidar vector and the reward is progress towards the goal lidar".  With a task set,
+ * the handle scores its rollouts by the task instead: every iteration launches the sampler, the handle's MODE 1 rollout kernel (the one
+ * cem_unfold_sequences runs: unchanged, writing the raw state trajectory [rows][H + 1][O] into a buffer the handle owns) and ONE more
+ * kernel (cem_task_score_kernel, csrc/cem_task_score.h) that turns trajectories and actions into the returns [P][N] and cost bytes
+ * [H][P][N] every later stage has always read.  The scorer fields of cem_config_t are inert on such a handle.
+ *
+ * For one rollout row r (particle-major: r = p * N + n, candidate n = r mod N) with states s_0 .. s_H and actions a_0 .. a_{H-1}:
+ *   phi(s)  = sum_f [ q_f (s_f - g_f)^2 - c_f s_f ]                   q, g, c [obs_dim]; NULL: zeros
+ *   u(a)    = sum_j rho_j a_j^2                                       rho [act_dim]; NULL: zeros
+ *   near(s) = R2 > 0 and sum_f goal_mask_f (s_f - g_f)^2 <= R2        R2 = fl32(goal_radius * goal_radius); goal_mask NULL: zeros
+ *   viol(s) = 1 if any s_f < lo_f or s_f > hi_f, else 0               lo NULL: -inf, hi NULL: +inf; a NaN state compares false
+ * and, step by step, the reference's bookkeeping (mpc_policy.py:34-37, safe_cem_mpc.py:86-93):
+ *   ga = near(s_t);  r = -phi(s_{t+1}) - u(a_t) + (ga ? reward_goal : 0);  r = clip(r, -reward_clip, reward_clip)  (reward_clip <= 0: none)
+ *   CEM_VARIANT_CEM:          return += r * (done ? 0 : 1);  done |= ga
+ *   CEM_VARIANT_SAFE:         done |= ga;  cost byte [t] = viol(s_t) * (done ? 0 : 1);  return += r * (done ? 0 : 1)
+ *   CEM_VARIANT_COST:         as SAFE with near never true: compute_mean_costs has no done mask (safe_cem_mpc.py:98-108)
+ * All of it fp32, products and sums rounded separately, in the fixed order csrc/cem_task_score.h states (planner.task_objective is
+ * the NumPy restatement, bit for bit).  A NaN return is stored as 0x7fc00000.
+ *
+ * cem_planner_set_task copies the tables (they may be freed on return), allocates the trajectory buffer (rows * (H + 1) * obs_dim * 4
+ * bytes, kept until destroy) before it changes anything, waits for the stream and drops the captured graph.  NULL or kind
+ * CEM_TASK_SAFETY_GYM switches the task off: the handle then launches what it launched and returns the bits it returned.  While on,
+ * cem_planner_rollout_path reports generic (no lean form, no folded sampler, no floating segments) and
+ * cem_planner_launches_per_iteration counts the extra launches.  Graph, eager, stepwise and timed plans (the kernel's time is part of
+ * the reduce time), population schedules, caller noise tensors and every option of the setters above serve it, on all three
+ * precisions and on 129 .. 256 units.
+ *   CEM_ERR_INVALID_ARG  null handle; kind not 0 / 1; a NaN or infinite q / g / c / goal_mask / rho entry, goal_radius, reward_goal or
+ *                        reward_clip; a NaN bound or lo_f > hi_f; goal_radius < 0
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  a batch handle, world_size > 1 or a communicator (and cem_planner_comm_init on a handle with a task); a
+ *                        library built without the kernel; a trajectory buffer beyond cem_unfold_sequences' element limit
+ * A failed allocation returns CEM_ERR_HIP; the handle keeps its previous setting after any of these.
+ *
+ * cem_planner_task_trajectories copies the buffer as the last rollout launch left it ([P * n_samples][H + 1][obs_dim]; an iteration of
+ * a population schedule fills the leading P * n[it] rows) to out_dev and waits for the stream; CEM_ERR_STATE without a task.
+ * cem_task_score runs the kernel alone on the caller's device arrays with the handle's task and variant: traj [n_rows][horizon + 1]
+ * [obs_dim], actions [n_rows / particles][horizon][act_dim] -> ret_out [n_rows] and, on SAFE / COST handles where it is not NULL,
+ * costs_out [horizon][n_rows] bytes.  CEM_ERR_STATE without a task; CEM_ERR_INVALID_ARG for n_rows not a multiple of particles. */
+enum cem_task_kind { CEM_TASK_SAFETY_GYM = 0, CEM_TASK_QUADRATIC = 1 };
+typedef struct {
+    int32_t kind;                 /* enum cem_task_kind */
+    const float *q, *g, *c, *goal_mask, *lo, *hi;   /* [obs_dim] each, host memory, or NULL for the default */
+    const float *rho;             /* [act_dim], host memory, or NULL */
+    float goal_radius, reward_goal, reward_clip;
+} cem_task_t;
+int cem_planner_set_task(cem_planner_t *h, const cem_task_t *task);
+int cem_planner_task_trajectories(cem_planner_t *h, float *out_dev);
+int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions_dev, int32_t n_rows, int32_t horizon,
+                   float *ret_out_dev, uint8_t *costs_out_dev);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

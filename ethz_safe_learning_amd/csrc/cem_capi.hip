@@ -1673,24 +1673,22 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
     const bool mode1 = rp.eps_model || rc.task;
     if (rc.task) rp.traj = task_traj(h);
     TimedLaunch timed(h, 0);
+    // a segmented launch: its work queue into rp, and its grid — one workgroup per pinned tile, then one per (floating tile, segment) item
+    const auto queue_grid = [&] {
+        rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
+        rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
+        return v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned);
+    };
     if (rc.lean_form) {                                          // (the same tiles, segments and work queue as the generic launches below)
-        if (queued) {
-            rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
-            rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
-        }
-        const int grid = queued ? v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned) : v.n_tiles;
+        const int grid = queued ? queue_grid() : v.n_tiles;
         if (rc.lean_form == 2 && (rp.variant == 1) == (rp.costs != nullptr)) HIPCHK(launch_rollout_lean_straight(rp, grid, h->stream, queued));
         else HIPCHK(launch_rollout_lean(rp, grid, h->stream, queued));
     }
     else if (d.wide) HIPCHK(launch_rollout_wide(h, rp, v.n_tiles, mode1 ? 1 : 0));
     else if (d.chunked()) HIPCHK(launch_rollout_chunked(d, v.rc, mode1 ? 1 : 0, rp, v.n_tiles, h->stream));
     else if (mode1) HIPCHK(launch_rollout<1>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
-    else if (queued) {
-        rp.seg_queue = (uint32_t *)(ws + l.seg_queue); rp.seg_flags = v.seg_flags; rp.seg_state = v.seg_state;
-        rp.seg_len = v.seg_len; rp.n_seg = v.n_seg; rp.n_pinned = v.n_pinned;
-        // one workgroup per pinned tile, then one per (floating tile, segment) item
-        HIPCHK(launch_rollout_seg(v.rc, d.NFW, rp, v.n_pinned + v.n_seg * (v.n_tiles - v.n_pinned), h->stream));
-    } else HIPCHK(launch_rollout<0>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
+    else if (queued) HIPCHK(launch_rollout_seg(v.rc, d.NFW, rp, queue_grid(), h->stream));
+    else HIPCHK(launch_rollout<0>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     timed.stop();
     // the task's returns and cost bytes over the Safety-Gym ones the rollout has just written, in stream order (cem_task_score.h);
     // timed with the reduce

@@ -921,6 +921,62 @@ __global__ __launch_bounds__(256) void cem_rollout_kernel(const RolloutParams p)
 // floating item completes; if every resident floating workgroup were waiting, all drawn tickets below the FIFO tail would be
 // complete and the number of completed final segments would equal n_float — then the tail is the item count and nobody waits.
 #define CEM_SEG_SPIN_LIMIT (1u << 23)
+#ifndef CEM_FLOAT_PRIO
+#define CEM_FLOAT_PRIO 3
+#endif
+// The scheduler of a floating workgroup, stated once for the three segmented kernels (the one below, cem_rollout_lean_seg_kernel and
+// cem_rollout_lean_straight_seg_kernel): the raised priority, the ticket, the bounded wait on the FIFO slot, the tile call, the queue
+// reset and the hand-over flag.  A macro with every name an argument: P_ the RolloutParams, ITEM_S_ the kernel's __shared__ uint32_t,
+// TILE_ / SEG_ / T0_ / T1_ the names the item's tile, segment and steps [T0_, T1_) are declared under, RUN_ the parenthesised
+// expression that runs them.  It returns from the kernel when the wait gives up.
+//   - Every wave drains its OWN sc1 state stores (s_waitcnt vmcnt(0); the encoding leaves expcnt / lgkmcnt alone) before the barrier
+//     that precedes the flag: s_barrier does not drain stores on gfx940+, and a workgroup-scope release fence compiles to no wait at
+//     all here.  tests/test_isa_cpu.py and tests/test_lean_rollout_cpu.py check the ISA for this wait between the last sc1 store and
+//     the barrier.
+//   - The launch's last floating tile leaves the work queue as the next launch needs it (all items have run by then: every ticket is
+//     drawn, every FIFO entry written and read), so no other kernel has to reset it between iterations.
+//   - A slot never filled within the spin limit: the workgroup gives up rather than hang the device, and says so (CEM_FAULT_SEGMENT;
+//     the host returns CEM_ERR_DEVICE for this plan).
+#define CEM_SEG_SCHEDULE(P_, ITEM_S_, TILE_, SEG_, T0_, T1_, RUN_) \
+    __builtin_amdgcn_s_setprio(CEM_FLOAT_PRIO); \
+    const uint32_t n_float = (uint32_t)((P_).n_tiles - (P_).n_pinned); \
+    if (threadIdx.x == 0) { \
+        const uint32_t ticket = atomicAdd((P_).seg_queue, 1u); \
+        uint32_t item = (((uint32_t)(P_).n_pinned + ticket) << 8);      /* (tile << 8) | segment */ \
+        if (ticket >= n_float) { \
+            const uint32_t *slot = (P_).seg_flags + (ticket - n_float); \
+            uint32_t spins = 0, v; \
+            while ((v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u && ++spins < CEM_SEG_SPIN_LIMIT) \
+                __builtin_amdgcn_s_sleep(16); \
+            item = v ? v - 1u : 0xffffffffu; \
+            if (!v) atomicOr(const_cast<int32_t *>(&(P_).ctrl->fault), 1 /* CEM_FAULT_SEGMENT */); \
+        } \
+        ITEM_S_ = item; \
+    } \
+    __syncthreads();                                       /* the state loads that follow are agent-scope atomic loads themselves */ \
+    const uint32_t item = ITEM_S_; \
+    if (item == 0xffffffffu) return; \
+    const int TILE_ = (int)(item >> 8), SEG_ = (int)(item & 255u); \
+    const int T0_ = SEG_ * (P_).seg_len, T1_ = (T0_ + (P_).seg_len < (P_).H) ? T0_ + (P_).seg_len : (P_).H; \
+    RUN_; \
+    if (T1_ == (P_).H) { \
+        if (threadIdx.x == 0) ITEM_S_ = atomicAdd((P_).seg_queue + 2, 1u); \
+        __syncthreads(); \
+        if (ITEM_S_ == n_float - 1u) { \
+            const int n_ready = (int)n_float * ((P_).n_seg - 1); \
+            for (int i = (int)threadIdx.x; i < n_ready; i += 256) __hip_atomic_store((P_).seg_flags + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+            if (threadIdx.x < 3) __hip_atomic_store((P_).seg_queue + threadIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+        } \
+    } \
+    if (T1_ < (P_).H) { \
+        __builtin_amdgcn_s_waitcnt(0x0F70); \
+        __syncthreads(); \
+        if (threadIdx.x == 0) { \
+            const uint32_t pos = atomicAdd((P_).seg_queue + 1, 1u); \
+            __hip_atomic_store((P_).seg_flags + pos, (((uint32_t)TILE_ << 8) | (uint32_t)(SEG_ + 1)) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+        } \
+    }
+
 template <int RC, int NFW>
 __global__ __launch_bounds__(256) void cem_rollout_seg_kernel(const RolloutParams p)
 {
@@ -932,55 +988,10 @@ __global__ __launch_bounds__(256) void cem_rollout_seg_kernel(const RolloutParam
         cem_rollout_tile<RC, NFW, 0, true>(p, smem, (int)blockIdx.x, 0, p.H);
         return;
     }
-#ifndef CEM_FLOAT_PRIO
-#define CEM_FLOAT_PRIO 3
-#endif
-    __builtin_amdgcn_s_setprio(CEM_FLOAT_PRIO);
-    const uint32_t n_float = (uint32_t)(p.n_tiles - p.n_pinned);
-    if (threadIdx.x == 0) {
-        const uint32_t ticket = atomicAdd(p.seg_queue, 1u);
-        uint32_t item = (((uint32_t)p.n_pinned + ticket) << 8);      // (tile << 8) | segment
-        if (ticket >= n_float) {
-            const uint32_t *slot = p.seg_flags + (ticket - n_float);
-            uint32_t spins = 0, v;
-            while ((v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u && ++spins < CEM_SEG_SPIN_LIMIT)
-                __builtin_amdgcn_s_sleep(16);
-            item = v ? v - 1u : 0xffffffffu;               // never filled within the limit: give up rather than hang the device ...
-            if (!v) atomicOr(const_cast<int32_t *>(&p.ctrl->fault), 1 /* CEM_FAULT_SEGMENT */);   // ... and say so: the host returns CEM_ERR_DEVICE for this plan
-        }
-        item_s = item;
-    }
-    __syncthreads();                                       // the state loads that follow are agent-scope atomic loads themselves
-    const uint32_t item = item_s;
-    if (item == 0xffffffffu) return;
-    const int tile = (int)(item >> 8), seg = (int)(item & 255u);
-    const int t0 = seg * p.seg_len, t1 = (t0 + p.seg_len < p.H) ? t0 + p.seg_len : p.H;
     // every segment samples the steps IT reads (the epilogue of step t fetches the action of step t + 1): a floating tile's segments
     // run on different CUs, and nothing sampled by one workgroup is read by another
-    cem_tile_sample_actions<false>(p, tile, t0, t1 < p.H ? t1 + 1 : p.H, seg == 0, false);
-    cem_rollout_tile<RC, NFW, 0, true>(p, smem, tile, t0, t1);
-    if (t1 == p.H) {
-        // the launch's last floating tile leaves the work queue as the next launch needs it (all items have run by then: every ticket
-        // is drawn, every FIFO entry written and read), so no other kernel has to reset it between iterations
-        if (threadIdx.x == 0) item_s = atomicAdd(p.seg_queue + 2, 1u);
-        __syncthreads();
-        if (item_s == n_float - 1u) {
-            const int n_ready = (int)n_float * (p.n_seg - 1);
-            for (int i = (int)threadIdx.x; i < n_ready; i += 256) __hip_atomic_store(p.seg_flags + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (threadIdx.x < 3) __hip_atomic_store(p.seg_queue + threadIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (t1 < p.H) {
-        // EVERY wave waits for the acknowledgements of its own sc1 state stores (vmcnt(0); the encoding leaves expcnt / lgkmcnt
-        // alone) before the barrier: s_barrier does not drain stores on gfx940+, and a workgroup-scope release fence compiles
-        // to no wait at all here.  tests/test_capi_cpu.py checks the ISA for this wait between the last sc1 store and the barrier.
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t pos = atomicAdd(p.seg_queue + 1, 1u);
-            __hip_atomic_store(p.seg_flags + pos, (((uint32_t)tile << 8) | (uint32_t)(seg + 1)) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    CEM_SEG_SCHEDULE(p, item_s, tile, seg, t0, t1,
+                     (cem_tile_sample_actions<false>(p, tile, t0, t1 < p.H ? t1 + 1 : p.H, seg == 0, false), cem_rollout_tile<RC, NFW, 0, true>(p, smem, tile, t0, t1)))
 }
 
 // The order-preserving integer key every select ranks fp32 scores by (a larger key is a better score), from the score's bits — what a

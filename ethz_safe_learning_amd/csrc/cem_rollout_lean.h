@@ -17,3 +17,6 @@ __attribute__((weak)) hipError_t launch_rollout_lean(const RolloutParams &p, int
 // The same launch in the straight-line form (cem_rollout_lean_straight.hip; p.variant picks the objective's instantiation): for the plans
 // cem_capi.hip's lean_form gives 2.  Weak for the same reason.
 __attribute__((weak)) hipError_t launch_rollout_lean_straight(const RolloutParams &p, int grid, hipStream_t st, bool seg);
+
+// a compile-time int as a value: the exchange-buffer offset of a half-round (cem_rollout_lean_tile.h), a group of the straight-line ring
+template <int V> struct LeanConst { static constexpr int value = V; };

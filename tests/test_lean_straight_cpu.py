@@ -1,9 +1,11 @@
 """What the compiler made of the two lean translation units (hipcc -S --cuda-device-only with the Makefile's own flags; no GPU):
 every lean kernel, branchy or straight-line, keeps three workgroups per CU resident (at most 168 VGPRs) with no VGPR spill and no
-scratch; the two branchy kernels of csrc/cem_rollout_lean.hip keep the register counts they had before the straight-line form existed
-(the form left that unit alone); and the straight-line step loop is what csrc/cem_rollout_lean_straight.hip says it is — the same
-MFMAs and 16-byte loads per round as the branchy loop, no scalar load of a kernel argument, fewer vector and scalar instructions."""
+scratch; the two branchy kernels of csrc/cem_rollout_lean.hip keep the register counts they had before the straight-line form existed;
+all six keep the registers, spills, scratch and LDS they had before the two units shared one tile body (csrc/cem_rollout_lean_tile.h);
+and the straight-line step loop is what csrc/cem_rollout_lean_straight.hip says it is — the same MFMAs and 16-byte loads per round as
+the branchy loop, no scalar load of a kernel argument, fewer vector and scalar instructions."""
 import hashlib
+import json
 import os
 import subprocess
 
@@ -50,6 +52,18 @@ def test_every_lean_kernel_keeps_three_workgroups_per_cu_without_spills(isa):
 def test_the_branchy_kernels_keep_their_register_counts(isa):
     meta = hp.kernel_meta(isa['branchy'], r'.')
     assert {hp.kernel_function_name(n): d['vgpr_count'] for n, d in meta.items()} == BRANCHY_VGPRS
+
+
+def test_the_lean_kernels_keep_the_registers_of_their_own_tile_bodies(isa):
+    """The shared tile body and the shared segment scheduler changed no instruction, so every lean kernel's registers, spills, scratch
+    and static LDS are what they were when each unit held a tile body and a scheduler of its own.  The golden is the metadata of
+    cem_rollout_lean.hip and cem_rollout_lean_straight.hip at commit 452d227 (the last one with two tile bodies), compiled with the
+    Makefile's flags: hipcc <FLAGS without -fPIC -shared> -S --cuda-device-only <unit>, read with helpers.kernel_meta."""
+    keys = ('vgpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size', 'group_segment_fixed_size')
+    want = json.load(open(os.path.join(hp.ROOT, 'tests', 'golden', 'lean_rollout_registers.json')))
+    assert len(want) == 6
+    got = {**hp.kernel_meta(isa['branchy'], r'.', keys), **hp.kernel_meta(isa['straight'], r'.', keys)}
+    assert got == want, {k: (want.get(k), got.get(k)) for k in sorted(set(want) | set(got)) if want.get(k) != got.get(k)}
 
 
 def test_the_straight_line_step_loop(isa):

@@ -424,6 +424,8 @@ def _combined(name):
 
 @pytest.mark.parametrize('name', ['elite_temperature', 'noise_beta', 'warm_start', 'risk_level', 'cost_budget'])
 def test_together_with_the_other_settings_graph_equals_stepwise(name):
+    """What this compares is the library with itself: a mistake in the host path the three forms share is held by
+    tests/test_gpu_option_fuzz.py, which checks option combinations stage by stage against the composed restatement of tests/composed_cases.py."""
     case, setup = _combined(name)
     across = name == 'warm_start'                                                 # a warm-started policy shifts its elites too
     pb, ps = _planner(case, across=across)

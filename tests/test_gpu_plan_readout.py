@@ -424,7 +424,9 @@ def _combined(name):
 @pytest.mark.parametrize('name', ['keep_elites', 'mean_candidate', 'elite_temperature', 'noise_beta', 'warm_start', 'risk_level', 'cost_budget'])
 def test_together_with_the_other_settings(name, monkeypatch):
     """Two plans in a row (the second warm, where that applies): stepwise launch by launch against track_best, the plan's invariants,
-    and the captured plan leaves the same block."""
+    and the captured plan leaves the same block.  Beyond the tracker, what this compares is the library with itself: a mistake in the
+    host path the plan forms share is held by tests/test_gpu_option_fuzz.py, which checks option combinations stage by stage against the
+    composed restatement of tests/composed_cases.py."""
     case, setup = _combined(name)
     pb, ps = _planner(case, monkeypatch)
     pb, pg = _planner(case, monkeypatch, use_graph=True)

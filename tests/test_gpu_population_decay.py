@@ -63,51 +63,7 @@ def _status(fn, *a, **kw):
     return 0
 
 
-class Arrays:
-    """The per-candidate arrays of a handle as flat byte views, and the bytes of each that a population of n owns: the leading ones."""
-
-    def __init__(self, pl, case):
-        t = _torch()
-        self.pl, self.case, self.t = pl, case, t
-        pf, _ = dc.pad_layout(case)
-        N, Hh, A, P = case.N, case.H, case.act, case.P
-        lay = pl.layout
-        self.spec = dict(actions=(lay.actions, N * Hh * A * 4, Hh * A * 4), act_pad=(dc.pad_offset(lay.actions, case), N * Hh * pf * 4, Hh * pf * 4),
-                         scores=(lay.scores_local, N * 4, 4), returns=(lay.returns, P * N * 4, P * 4), costs=(lay.costs, Hh * P * N, Hh * P))
-        self.saved = {}
-
-    def view(self, key):
-        off, total, _ = self.spec[key]
-        return self.pl._ws_view[off:off + total]
-
-    def lead(self, key, n):
-        return self.spec[key][2] * n
-
-    def get(self, key, n, dtype=None):
-        """The leading bytes of `key` a population of n owns, as numpy (dtype: float32 unless uint8 is asked for)."""
-        self.pl.synchronize()
-        b = _np(self.view(key)[:self.lead(key, n)])
-        return b if dtype == np.uint8 else b.view(F)
-
-    def poison(self, n):
-        """Everything beyond the leading n entries of every array becomes 0xFF bytes (what was there is kept for `check`)."""
-        self.pl.synchronize()
-        with self.pl.stream_context():
-            for key in self.spec:
-                tail = self.view(key)[self.lead(key, n):]
-                self.saved[key] = tail.clone()
-                tail.fill_(0xFF)
-        self.pl.synchronize()
-
-    def check(self, n, what):
-        """The poison is intact; then what it covered comes back (the padding words of act_pad are zeros no kernel ever rewrites)."""
-        self.pl.synchronize()
-        with self.pl.stream_context():
-            for key in self.spec:
-                tail = self.view(key)[self.lead(key, n):]
-                assert bool((tail == 0xFF).all()), '%s: %s beyond the leading %d entries was written' % (what, key, n)
-                tail.copy_(self.saved[key])
-        self.pl.synchronize()
+Arrays = hp.Arrays                       # (tests/test_gpu_option_fuzz.py poisons with the same helper)
 
 
 def _plain(case, n, cache):
@@ -463,6 +419,8 @@ def _combined(name):
 
 @pytest.mark.parametrize('name', ['risk_level', 'cost_budget', 'warm_start', 'everything'])
 def test_together_with_the_other_settings_graph_equals_stepwise(name):
+    """What this compares is the library with itself: a mistake in the host path the three forms share is held by
+    tests/test_gpu_option_fuzz.py, which checks option combinations stage by stage against the composed restatement of tests/composed_cases.py."""
     case, setup = _combined(name)
     pb, ps = _planner(case)
     pb, pg = _planner(case, use_graph=True)

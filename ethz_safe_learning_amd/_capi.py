@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_create', 'cem_planner_destroy', 'cem_planner_layout', 'cem_planner_set_weights', 'cem_planner_set_weights_dev',
     'cem_planner_set_normaliser', 'cem_planner_plan', 'cem_plan_begin', 'cem_plan_rollout', 'cem_plan_select',
     'cem_plan_end', 'cem_comm_unique_id', 'cem_planner_comm_init', 'cem_planner_comm_destroy', 'cem_planner_comm_ranks', 'cem_plan_exchange', 'cem_planner_graph_status', 'cem_planner_graph_nodes', 'cem_planner_launches_per_iteration', 'cem_planner_rollout_path', 'cem_planner_rollout_form', 'cem_unfold_sequences', 'cem_compute_objective', 'cem_scorer_reward', 'cem_scorer_cost', 'cem_fill_noise', 'cem_philox_words', 'cem_planner_set_timing', 'cem_planner_last_timing', 'cem_planner_last_timing_detail', 'cem_planner_select_mode', 'cem_planner_inject_fault',
+    'cem_planner_select_form', 'cem_select_form_for',
     'cem_batch_workspace_bytes', 'cem_batch_planner_create', 'cem_planner_plan_batch', 'cem_planner_batch_capacity',
     'cem_planner_set_warm_start', 'cem_planner_set_initial_distribution', 'cem_planner_set_init_mode', 'cem_planner_reset_carry',
     'cem_planner_get_carry', 'cem_planner_set_carry_slots', 'cem_planner_set_particle_objective', 'cem_planner_get_particle_objective',
@@ -177,6 +178,8 @@ def load():
     lib.cem_fill_noise.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
     lib.cem_philox_words.argtypes = [vp, C.c_uint64, C.c_uint64] + [C.c_uint32] * 6 + [vp]
     lib.cem_planner_select_mode.argtypes = [vp, i32p]
+    lib.cem_planner_select_form.argtypes = [vp, C.c_int32, i32p]
+    lib.cem_select_form_for.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, i32p]
     lib.cem_planner_inject_fault.argtypes = [vp, C.c_int32]
     lib.cem_planner_set_timing.argtypes = [vp, C.c_int32]
     lib.cem_planner_last_timing.argtypes = [vp, fp, i32p, fp]

@@ -7,6 +7,7 @@
 #include "cem_noise_mix.h"
 #include "cem_elite_carry.h"
 #include "cem_plan_readout.h"
+#include "cem_select_ranked.h"
 #include "cem_task_score.h"
 #include "cem_population.h"
 #include "cem_train.h"
@@ -755,6 +756,7 @@ struct cem_planner {
     bool sample_in_rollout;                  // the sampler runs as the rollout tiles' prologue (else: cem_sample_kernel in front of the rollout launch)
     bool lean_rollout;                       // plans without caller noise tensors run cem_rollout_lean.hip's kernels (lean_eligible)
     bool lean_branchy;                       // CEM_FORCE_ROLLOUT=lean_branchy at create: never the straight-line form (lean_form)
+    bool select_bucket;                      // CEM_FORCE_SELECT=bucket at create: never the ranked form of the one-workgroup select (select_form_of)
     const float *eps_act, *eps_model;       // current plan's explicit noise (device) or null
     // pinned host staging
     CtrlBlock *h_ctrl;
@@ -775,6 +777,7 @@ struct cem_planner {
     int plans_since_comm;                    // the first plan after comm_init runs eagerly (RCCL sets itself up lazily), then the graph is captured
     bool graph_failed;                       // capture with the collective did not work on this stack: stay eager
     size_t sel_dyn_limit;                    // dynamic-LDS allowance of the select kernels on this handle's device
+    bool ranked_ready;                       // cem_select_ranked_kernel is in the library and has the same allowance
     int fused_resident;                      // workgroups of cem_msel_fused_kernel the device keeps resident at once (occupancy x CUs)
     bool sel_zeroed;                         // the multi-workgroup select's histograms / barrier counter were cleared by this iteration's reduce kernel
     bool fuse_banned;                        // a grid barrier of the fused select expired on this handle once (recovered in-stream): select_mode 2 from then on
@@ -882,6 +885,14 @@ int select_mode_for(const cem_planner *h, int N, bool *cache = nullptr)
     return resolve_select_mode(h->cfg.select_mode, N, d.k, (long long)d.H * d.A, h->sel_dyn_limit, can_fuse, cache);
 }
 int select_mode_now(const cem_planner *h, bool *cache = nullptr) { return select_mode_for(h, h->d.N, cache); }
+// Which form of the one-workgroup select serves a (mode, cache, N) on this handle (select_ranked_form): 1, cem_select_ranked_kernel, only
+// where the library has it, the device granted it the select's dynamic LDS and CEM_FORCE_SELECT=bucket did not keep form 0 at create.
+// A function of the handle's constants and of what select_mode_for returns: where that changes, the graph is dropped already.
+int select_form_of(const cem_planner *h, int mode, bool cache, int N)
+{
+    if (!h->ranked_ready || h->select_bucket) return 0;
+    return select_ranked_form(mode, cache, N, h->cfg.variant == CEM_VARIANT_CEM);
+}
 
 // the captured plan no longer describes what the handle would launch (or never came to be): the next graphable plan captures anew
 void drop_graph(cem_planner *h)
@@ -900,6 +911,7 @@ struct LaunchRecipe {
     int lean_form;                           // 0: the generic rollout kernels; 1 / 2: the lean kernels, branchy / straight-line form (lean_form)
     bool fold_reduce;                        // a whole plan's select forms the particle mean itself: no score launch
     int select_mode; bool select_cache;      // the select form (select_mode_for) and whether the one-workgroup kernel stages its keys in LDS
+    int select_form;                         // 1: the one-workgroup select is cem_select_ranked_kernel (select_form_of)
     bool one_workgroup_only;                 // something below, or a schedule: admit() let it onto a one-workgroup select only
     bool weighted, keep_elites, track;       // behind the select: the weighted refit, carry-over's keep, the read-out's tracker
     bool task;                               // the rollout is the family's MODE 1 kernel writing the handle's trajectory buffer, cem_task_score_kernel behind it
@@ -920,6 +932,7 @@ LaunchRecipe recipe_of(const cem_planner *h, int it, bool own_noise)
     // (the handle's own mixed tensor stands in wherever the caller passed none: the lean kernels step aside for it as for any tensor)
     r.lean_form = v.lean_rollout && !rewritten && !own_noise && o.noise_kind != CEM_NOISE_MIXED ? lean_form(h, it) : 0;
     r.select_mode = select_mode_for(h, v.d->N, &r.select_cache);
+    r.select_form = select_form_of(h, r.select_mode, r.select_cache, v.d->N);
     // one rank (the scores need no exchange), the CemMpc objective (no per-step Beta counts; what the select folds IS the mean), and a
     // population the one-workgroup select serves with its keys staged in LDS
     r.fold_reduce = h->d.W == 1 && !h->comm && h->cfg.variant == CEM_VARIANT_CEM && !o.tail_m && r.select_mode == 1 && r.select_cache;
@@ -1156,6 +1169,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     { const Plan pl = make_plan(cfg, h->d, mb); h->rc = pl.rc; h->n_seg = pl.n_seg; h->seg_len = pl.seg_len; h->n_pinned = pl.n_pinned;
       place_sampler(h, h->d, pl, &h->sample_in_rollout, &h->lean_rollout); }
     { const char *e = std::getenv("CEM_FORCE_ROLLOUT"); h->lean_branchy = e && std::strcmp(e, "lean_branchy") == 0; }
+    { const char *e = std::getenv("CEM_FORCE_SELECT"); h->select_bucket = e && std::strcmp(e, "bucket") == 0; }     // diagnostic / tests: the results do not depend on it
     h->have_weights = false; h->in_plan = false; h->eps_act = h->eps_model = nullptr;
     h->timing = false; h->roll_ms = h->sel_ms = h->red_ms = h->samp_ms = 0.f; h->roll_n = 0;
     h->graph = nullptr; h->gexec = nullptr; h->graph_ready = false;     // (h->opt: every option off, PlanOptions' own defaults)
@@ -1267,6 +1281,8 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
         hipFuncSetAttribute(reinterpret_cast<const void *>(&cem_select_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             140 * 1024) == hipSuccess) h->sel_dyn_limit = 140 * 1024;
     else (void)hipGetLastError();
+    h->ranked_ready = launch_select_ranked && prepare_select_ranked && prepare_select_ranked(h->sel_dyn_limit) == hipSuccess;
+    if (!h->ranked_ready) (void)hipGetLastError();
     {
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cem_msel_fused_kernel, 1024, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 0; }
@@ -1787,7 +1803,8 @@ int enqueue_select(cem_planner *h, int it, bool whole_plan, bool have_eps_out = 
         // counts and ranks wave by wave; same results either way)
         // one workgroup per problem (batch handles: blockIdx.x is the problem)
         const dim3 grid(warm_slots(h));
-        if (cache && h->cfg.variant != CEM_VARIANT_CEM) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
+        if (rc.select_form == 1) HIPCHK(launch_select_ranked(p, warm_slots(h), lds, h->stream));     // (the same p, grid and LDS bytes)
+        else if (cache && h->cfg.variant != CEM_VARIANT_CEM) hipLaunchKernelGGL((cem_select_kernel<true, true>), grid, dim3(1024), lds, h->stream, p);
         else if (cache) hipLaunchKernelGGL((cem_select_kernel<true, false>), grid, dim3(1024), lds, h->stream, p);
         else hipLaunchKernelGGL((cem_select_kernel<false, false>), grid, dim3(1024), lds, h->stream, p);
         if (weighted) {
@@ -2983,6 +3000,22 @@ int cem_planner_select_mode(const cem_planner_t *h, int32_t *mode_out)
 {
     if (!h || !mode_out) return CEM_ERR_INVALID_ARG;
     *mode_out = select_mode_now(h);
+    return CEM_OK;
+}
+
+int cem_planner_select_form(const cem_planner_t *h, int32_t it, int32_t *form_out)
+{
+    if (!h || !form_out || it < 0 || it >= h->d.I) return CEM_ERR_INVALID_ARG;
+    *form_out = recipe_of(h, it, false).select_form;
+    return CEM_OK;
+}
+
+int cem_select_form_for(int32_t select_mode, int64_t n_samples, int64_t n_elite, int64_t horizon_x_act_dim, int32_t variant, int32_t *form_out)
+{
+    if (!form_out || select_mode < 0 || select_mode > 3 || n_samples < 1 || n_elite < 1 || n_elite > n_samples || horizon_x_act_dim < 1) return CEM_ERR_INVALID_ARG;
+    bool cache = false;
+    const int mode = resolve_select_mode(select_mode, n_samples, n_elite, horizon_x_act_dim, 140 * 1024, true, &cache);
+    *form_out = select_ranked_form(mode, cache, n_samples, variant == CEM_VARIANT_CEM);
     return CEM_OK;
 }
 

@@ -1215,7 +1215,10 @@ __device__ __forceinline__ float cem_out_noise(const CtrlBlock *ctrl, const floa
     return e[a & 3];
 }
 
+#endif  // CEM_DEVICE_PRIMITIVES_ONLY
 
+// (What the one-workgroup selects share — the result block, SelectParams, the staged key list's layout — is outside the guard:
+// cem_select_ranked.hip takes it with the primitives.)
 // The plan's result as the HOST reads it from pinned memory: words [0, A) action, [32] score, [33] iterations run, [34] early-stop flag,
 // [35] fault bits, [36] the host's plan counter (CtrlBlock::seq), [37] the XOR of words 0..36 and a constant.  The host may poll for word
 // 36 instead of synchronising the stream, and writes to host memory from the device are NOT ordered with one another on the way (a
@@ -1286,6 +1289,8 @@ __device__ __forceinline__ float cem_key2f(const uint32_t key)       // inverse 
 {
     return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }
+
+#ifndef CEM_DEVICE_PRIMITIVES_ONLY
 
 // exclusive scans of two values per thread over a 1024-thread block (one barrier): pa, pb = sums over lower thread ids
 __device__ __forceinline__ void cem_block_excl_scan2(const uint32_t a, const uint32_t b, uint32_t (*wsum)[16], uint32_t &pa, uint32_t &pb)

@@ -857,6 +857,13 @@ class CemPlanner:
         _capi.check(self.lib.cem_planner_select_mode(self.h, C.byref(m)), 'cem_planner_select_mode')
         return m.value
 
+    def select_form(self, it=0):
+        """0 cem_select_kernel (and every select that is not one workgroup) | 1 cem_select_ranked_kernel: which form of the one-workgroup
+        select iteration `it` launches (cem_planner_select_form).  Same results; CEM_FORCE_SELECT=bucket at create keeps form 0."""
+        n = C.c_int32()
+        _capi.check(self.lib.cem_planner_select_form(self.h, int(it), C.byref(n)), 'cem_planner_select_form')
+        return n.value
+
     def inject_fault(self, kind=1):
         """Test hook (cem_planner_inject_fault): the next plan's first fused select sees one of its grid barriers expire."""
         _capi.check(self.lib.cem_planner_inject_fault(self.h, kind), 'cem_planner_inject_fault')

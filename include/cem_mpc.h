@@ -273,6 +273,16 @@ int cem_plan_exchange(cem_planner_t *h);
 /* The select form the handle's next iteration takes (1 / 2 / 3, see cem_config_t::select_mode): what automatic resolves to on this device,
  * and 2 once a fused select has had to be recovered on this handle. */
 int cem_planner_select_mode(const cem_planner_t *h, int32_t *mode_out);
+/* Which form of the one-workgroup select iteration `it` launches: 0 = the bucket kernel of csrc/cem_device.h (and every select that is not one workgroup);
+ * 1 = the ranked kernel of csrc/cem_select_ranked.hip, which keeps a thread's keys in registers and takes five barrier phases in
+ * front of the moments — where the select resolves to mode 1 with its keys staged in LDS, n_samples <= 4096 and the objective is
+ * CemMpc's.  Same results bit for bit; cem_planner_select_mode reports 1 for both.  CEM_FORCE_SELECT=bucket at create keeps an eligible
+ * handle on form 0.  CEM_ERR_INVALID_ARG: `it` outside [0, iterations). */
+int cem_planner_select_form(const cem_planner_t *h, int32_t it, int32_t *form_out);
+/* The same rule without a handle or a device, for a requested select_mode, a population, an elite count, horizon x act_dim and a variant,
+ * on a device that grants the one-workgroup select its 140 KB of dynamic LDS: what cem_planner_select_form reports on such a handle
+ * unless CEM_FORCE_SELECT=bucket was set.  CEM_ERR_INVALID_ARG: a select_mode outside 0 .. 3, sizes below 1, n_elite > n_samples. */
+int cem_select_form_for(int32_t select_mode, int64_t n_samples, int64_t n_elite, int64_t horizon_x_act_dim, int32_t variant, int32_t *form_out);
 /* Test hook.  kind 1: in the NEXT plan's first iteration, the last workgroup of the fused select treats its first grid barrier as
  * expired (as if its peers were not resident) — the recovery path then runs without having to load the GPU.  No effect on plans
  * whose select is not fused.

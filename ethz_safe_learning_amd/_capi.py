@@ -23,6 +23,8 @@ CEM_REFIT_UNIFORM, CEM_REFIT_SOFTMAX = 0, 1                       # enum cem_ref
 CEM_NOISE_WHITE, CEM_NOISE_MIXED = 0, 1                         # enum cem_action_noise
 CEM_FORWARD_SPLIT, CEM_FORWARD_ALL = 0, 1                       # enum cem_forward_map
 CEM_TASK_SAFETY_GYM, CEM_TASK_QUADRATIC = 0, 1                  # enum cem_task_kind
+CEM_TASK_TRACKING = 2                                           # its third value (cem_planner_set_task_tracking)
+CEM_TASK_REF_MAX_STEPS = 16384
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds
@@ -45,6 +47,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_mean_candidate', 'cem_planner_get_mean_candidate',
     'cem_planner_set_plan_readout', 'cem_planner_get_plan_readout', 'cem_planner_plan_readout',
     'cem_planner_set_task', 'cem_planner_task_trajectories', 'cem_task_score',
+    'cem_planner_set_task_tracking', 'cem_planner_set_task_clock',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -104,6 +107,10 @@ class CemPlanReadout(C.Structure):
 class CemTask(C.Structure):
     _fields_ = [('kind', C.c_int32)] + [(n, C.POINTER(C.c_float)) for n in ('q', 'g', 'c', 'goal_mask', 'lo', 'hi', 'rho')] + \
                [('goal_radius', C.c_float), ('reward_goal', C.c_float), ('reward_clip', C.c_float)]
+
+
+class CemTaskTracking(C.Structure):
+    _fields_ = [('ref', C.POINTER(C.c_float)), ('ref_steps', C.c_int32), ('q_terminal', C.POINTER(C.c_float)), ('action_rate', C.POINTER(C.c_float))]
 
 
 class CemLayout(C.Structure):
@@ -221,6 +228,8 @@ def load():
     lib.cem_planner_set_task.argtypes = [vp, C.POINTER(CemTask)]
     lib.cem_planner_task_trajectories.argtypes = [vp, vp]
     lib.cem_task_score.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
+    lib.cem_planner_set_task_tracking.argtypes = [vp, C.POINTER(CemTask), C.POINTER(CemTaskTracking)]
+    lib.cem_planner_set_task_clock.argtypes = [vp, C.c_int32, vp]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

@@ -9,6 +9,7 @@
 #include "cem_plan_readout.h"
 #include "cem_select_ranked.h"
 #include "cem_task_score.h"
+#include "cem_task_reference.h"
 #include "cem_population.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
@@ -832,6 +833,11 @@ struct cem_planner {
     float *task_dev;                         // a device allocation of the handle's own, made by the first enabling call: the tables
                                              // [CEM_TASK_TABLES][CEM_U], then the trajectories [Bloc][H + 1][O] of the last rollout launch
     TaskScoreParams task;                    // the task as set: tab, r2, reward_goal, clip, rho (the launch fills in the rest)
+    // cem_planner_set_task_tracking (cem_task_reference.h)
+    uint32_t *track_dev;                     // a device allocation of the handle's own, one per enabling call: the clock block
+                                             // [CEM_TASK_CLOCK_WORDS], then the reference table [ref_steps][CEM_U]
+    TaskReferenceParams track;               // the tracking task as set: tab, ref, clock, T, r2, reward_goal, clip, rho, kappa
+    std::vector<uint32_t> h_clock;           // host copy of the clock block: the source of its stream-ordered copies
 };
 
 namespace {
@@ -871,6 +877,8 @@ int lean_form(const cem_planner *h, int it)
 // the two parts of the task allocation (cem_planner::task_dev)
 size_t task_tab_floats() { return (size_t)CEM_TASK_TABLES * CEM_U; }
 float *task_traj(const cem_planner *h) { return h->task_dev + task_tab_floats(); }
+// the second part of the tracking allocation (cem_planner::track_dev)
+float *track_ref(uint32_t *dev) { return reinterpret_cast<float *>(dev + CEM_TASK_CLOCK_WORDS); }
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
 size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
 float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
@@ -969,6 +977,7 @@ HandleFacts facts_of(const cem_planner *h, const PlanOptions &next)
     f.refit_lds_bytes = CEM_REFIT_LDS_BYTES(d.k, d.H * d.A); f.refit_lds_limit = h->sel_dyn_limit;
     f.can_mix = launch_mix_action_noise && prepare_mix_action_noise; f.can_carry = launch_elite_keep && launch_elite_inject;
     f.can_mean = launch_mean_candidate != nullptr; f.can_track = launch_plan_track != nullptr; f.can_task = launch_task_score != nullptr;
+    if (next.task == CEM_TASK_TRACKING) f.can_task = f.can_task && launch_task_reference != nullptr;   // (the kind's own kernel: cem_task_reference.h)
     return f;
 }
 int admit_on(const cem_planner *h, const PlanOptions &next, PlanChange change = PLAN_CHANGE_OTHER) { return admit(facts_of(h, next), next, change); }
@@ -1012,6 +1021,7 @@ void release_handle(cem_planner *h)
     if (h->elite_dev) hipFree(h->elite_dev);
     if (h->readout_dev) hipFree(h->readout_dev);
     if (h->task_dev) hipFree(h->task_dev);
+    if (h->track_dev) hipFree(h->track_dev);
     if (h->pop_dev) hipFree(h->pop_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
@@ -1179,6 +1189,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
     h->readout_dev = nullptr;
     h->task_dev = nullptr; h->task = TaskScoreParams{};
+    h->track_dev = nullptr; h->track = TaskReferenceParams{}; h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
     h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
@@ -1709,12 +1720,17 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
     // the task's returns and cost bytes over the Safety-Gym ones the rollout has just written, in stream order (cem_task_score.h);
     // timed with the reduce
     if (rc.task) {
-        TaskScoreParams tp = h->task;
-        tp.traj = rp.traj; tp.actions = rp.actions; tp.ctrl = rp.ctrl; tp.ret = rp.ret; tp.costs = rp.costs;
-        tp.rows = d.Bloc; tp.N = d.N; tp.H = d.H; tp.O = d.O; tp.A = d.A; tp.variant = rp.variant; tp.check_done = 1;
-        if (cost_obj) tp.r2 = 0.f;                           // compute_mean_costs has no done mask (safe_cem_mpc.py:98-108): near is never true
+        const bool tracking = h->opt.task == CEM_TASK_TRACKING;  // the kind picks the kernel (cem_task_reference.h)
+        if (tracking && !h->track_dev) return CEM_ERR_UNSUPPORTED;
+        auto filled = [&](auto tp) {
+            tp.traj = rp.traj; tp.actions = rp.actions; tp.ctrl = rp.ctrl; tp.ret = rp.ret; tp.costs = rp.costs;
+            tp.rows = d.Bloc; tp.N = d.N; tp.H = d.H; tp.O = d.O; tp.A = d.A; tp.variant = rp.variant; tp.check_done = 1;
+            if (cost_obj) tp.r2 = 0.f;                       // compute_mean_costs has no done mask (safe_cem_mpc.py:98-108): near is never true
+            return tp;
+        };
         TimedLaunch timed_task(h, 2);
-        HIPCHK(launch_task_score(tp, h->stream));
+        if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
+        else { HIPCHK(launch_task_score(filled(h->task), h->stream)); }
     }
     if (whole_plan && rc.fold_reduce) return CEM_OK;
 
@@ -2484,12 +2500,12 @@ int cem_planner_plan_readout(cem_planner_t *h, int32_t problem, cem_plan_readout
     return CEM_OK;
 }
 
-int cem_planner_set_task(cem_planner_t *h, const cem_task_t *task)
+// cem_planner_set_task (trk null) and cem_planner_set_task_tracking (task: its base; cem_task_reference.h), which differ in the second
+// table row (g / qT), in the kind and in what the tracking task owns besides: the reference table and the clock
+static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tracking_t *trk)
 {
-    if (!h) return CEM_ERR_INVALID_ARG;
     const Dims &d = h->d;
     const bool on = task && task->kind != CEM_TASK_SAFETY_GYM;
-    if (task && task->kind != CEM_TASK_SAFETY_GYM && task->kind != CEM_TASK_QUADRATIC) return CEM_ERR_INVALID_ARG;
     // on the bit patterns: this file is built with -fno-honor-nans
     auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
     auto finite = [&](float v) { return (bits(v) & 0x7fffffffu) < 0x7f800000u; };
@@ -2497,9 +2513,11 @@ int cem_planner_set_task(cem_planner_t *h, const cem_task_t *task)
     // the tables as the kernel reads them: [CEM_TASK_TABLES][CEM_U], the defaults beyond obs_dim and for a NULL table
     std::vector<float> tab(task_tab_floats(), 0.f);
     TaskScoreParams tp{};
+    TaskReferenceParams rt{};
+    std::vector<uint32_t> trk_host;                            // the clock block at (0, zeros), then ref as the kernel reads it: [T][CEM_U], zero beyond obs_dim
     if (on) {
         const float inf = std::numeric_limits<float>::infinity();
-        const float *src[CEM_TASK_TABLES] = {task->q, task->g, task->c, task->goal_mask, task->lo, task->hi};
+        const float *src[CEM_TASK_TABLES] = {task->q, trk ? (trk->q_terminal ? trk->q_terminal : task->q) : task->g, task->c, task->goal_mask, task->lo, task->hi};
         for (int f = 0; f < CEM_U; ++f) { tab[CEM_TASK_TAB_LO * CEM_U + f] = -inf; tab[CEM_TASK_TAB_HI * CEM_U + f] = inf; }
         for (int k = 0; k < CEM_TASK_TABLES; ++k)
             for (int f = 0; src[k] && f < d.O; ++f) {
@@ -2513,27 +2531,74 @@ int cem_planner_set_task(cem_planner_t *h, const cem_task_t *task)
         tp.r2 = task->goal_radius * task->goal_radius;         // fl32, rounded once here
         tp.reward_goal = task->reward_goal; tp.clip = task->reward_clip > 0.f ? task->reward_clip : inf;
     }
+    if (trk) {
+        if (!trk->ref || trk->ref_steps < 1 || trk->ref_steps > CEM_TASK_REF_MAX_STEPS) return CEM_ERR_INVALID_ARG;
+        trk_host.assign(CEM_TASK_CLOCK_WORDS + (size_t)trk->ref_steps * CEM_U, 0u);
+        for (int j = 0; j < trk->ref_steps; ++j)
+            for (int f = 0; f < d.O; ++f) {
+                const float v = trk->ref[(size_t)j * d.O + f];
+                if (!finite(v)) return CEM_ERR_INVALID_ARG;
+                trk_host[CEM_TASK_CLOCK_WORDS + (size_t)j * CEM_U + f] = bits(v);
+            }
+        for (int j = 0; trk->action_rate && j < d.A; ++j) { if (!finite(trk->action_rate[j])) return CEM_ERR_INVALID_ARG; rt.kappa[j] = trk->action_rate[j]; }
+        std::memcpy(rt.rho, tp.rho, sizeof rt.rho);
+        rt.T = trk->ref_steps; rt.r2 = tp.r2; rt.reward_goal = tp.reward_goal; rt.clip = tp.clip;
+    }
     if (h->in_plan) return CEM_ERR_STATE;
-    PlanOptions next = options_of(h); next.task = on ? (int)CEM_TASK_QUADRATIC : (int)CEM_TASK_SAFETY_GYM;
+    PlanOptions next = options_of(h); next.task = trk ? (int)CEM_TASK_TRACKING : on ? (int)CEM_TASK_QUADRATIC : (int)CEM_TASK_SAFETY_GYM;
     { const int st = admit_on(h, next); if (st) return st; }
     // cem_unfold_sequences' element limit on the trajectory tensor
     const long long traj_floats = (long long)d.Bloc * (d.H + 1) * d.O;
     if (on && traj_floats > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
     // allocated before anything of the handle changes: a failed allocation leaves it as it was
-    DevBlock made;
+    DevBlock made, made_trk;
     if (on && !h->task_dev) HIPCHK(made.alloc((task_tab_floats() + (size_t)traj_floats) * 4));
+    if (trk) HIPCHK(made_trk.alloc(trk_host.size() * 4));         // (one per call: ref_steps is the call's)
     // Unconditional: an eager plan still draining behind its polled result may be reading the tables
     return commit_launch_change(h, next, true, [&]() -> int {
         if (!on) return CEM_OK;
         float *dev = made.p ? static_cast<float *>(made.p) : h->task_dev;
+        if (trk) HIPCHK(hipMemcpy(made_trk.p, trk_host.data(), trk_host.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dev, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         // (the buffer reads as zeros until the first rollout launch has filled it)
         if (made.p) HIPCHK(hipMemset(dev + task_tab_floats(), 0, (size_t)traj_floats * 4));
         if (made.p) h->task_dev = made.release<float>();
         tp.tab = h->task_dev;
-        h->task = tp;
+        if (!trk) { h->task = tp; return CEM_OK; }
+        // (the stream is drained: nothing reads the previous call's table or clock any more)
+        if (h->track_dev) hipFree(h->track_dev);
+        h->track_dev = made_trk.release<uint32_t>();
+        rt.tab = tp.tab; rt.clock = h->track_dev; rt.ref = track_ref(h->track_dev);
+        h->track = rt;
+        h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
         return CEM_OK;
     });
+}
+
+int cem_planner_set_task(cem_planner_t *h, const cem_task_t *task)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    if (task && task->kind != CEM_TASK_SAFETY_GYM && task->kind != CEM_TASK_QUADRATIC) return CEM_ERR_INVALID_ARG;
+    return set_task(h, task, nullptr);
+}
+
+int cem_planner_set_task_tracking(cem_planner_t *h, const cem_task_t *base, const cem_task_tracking_t *trk)
+{
+    if (!h || !base || !trk || base->kind != CEM_TASK_QUADRATIC || base->g) return CEM_ERR_INVALID_ARG;
+    return set_task(h, base, trk);
+}
+
+int cem_planner_set_task_clock(cem_planner_t *h, int32_t k0, const float *prev_action)
+{
+    if (!h || k0 < 0) return CEM_ERR_INVALID_ARG;
+    const int A = h->d.A;
+    for (int j = 0; prev_action && j < A; ++j) { uint32_t u; std::memcpy(&u, &prev_action[j], 4); if ((u & 0x7fffffffu) >= 0x7f800000u) return CEM_ERR_INVALID_ARG; }   // by its bits (-fno-honor-nans)
+    if (h->opt.task != CEM_TASK_TRACKING || !h->track_dev || h->in_plan) return CEM_ERR_STATE;
+    // through a copy the handle owns (as cem_planner_set_cost_budget): the caller's array need not outlive this call; no wait, the graph stays
+    h->h_clock[0] = (uint32_t)k0;
+    if (prev_action) std::memcpy(&h->h_clock[1], prev_action, (size_t)A * 4);
+    HIPCHK(hipMemcpyAsync(h->track_dev, h->h_clock.data(), (size_t)CEM_TASK_CLOCK_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+    return CEM_OK;
 }
 
 int cem_planner_task_trajectories(cem_planner_t *h, float *out_dev)
@@ -2555,12 +2620,17 @@ int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions
     const Dims &d = h->d;
     if (n_rows % d.P != 0) return CEM_ERR_INVALID_ARG;                 // reshape(cum, (particles, -1)) would raise (mpc_policy.py:38)
     if ((long long)n_rows * (horizon + 1) * d.O > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
-    TaskScoreParams tp = h->task;
-    tp.traj = traj_dev; tp.actions = actions_dev; tp.ctrl = nullptr; tp.ret = ret_out_dev;
-    tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0; tp.costs = tp.variant ? costs_out_dev : nullptr;
-    tp.rows = n_rows; tp.N = n_rows / d.P; tp.H = horizon; tp.O = d.O; tp.A = d.A; tp.check_done = 0;
-    if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;      // (as in a plan: the cost objective's bytes are not masked by done)
-    HIPCHK(launch_task_score(tp, h->stream));
+    const bool tracking = h->opt.task == CEM_TASK_TRACKING;     // (with the handle's clock, as a plan)
+    if (tracking && !h->track_dev) return CEM_ERR_STATE;
+    auto filled = [&](auto tp) {
+        tp.traj = traj_dev; tp.actions = actions_dev; tp.ctrl = nullptr; tp.ret = ret_out_dev;
+        tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0; tp.costs = tp.variant ? costs_out_dev : nullptr;
+        tp.rows = n_rows; tp.N = n_rows / d.P; tp.H = horizon; tp.O = d.O; tp.A = d.A; tp.check_done = 0;
+        if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;  // (as in a plan: the cost objective's bytes are not masked by done)
+        return tp;
+    };
+    if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
+    else { HIPCHK(launch_task_score(filled(h->task), h->stream)); }
     HIPCHK(hipStreamSynchronize(h->stream));
     return CEM_OK;
 }

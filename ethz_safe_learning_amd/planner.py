@@ -8,6 +8,7 @@ corresponds to one compiled ``@tf.function`` graph of the reference
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import math
 from dataclasses import dataclass, field
 from typing import List, NamedTuple, Optional, Sequence, Tuple
@@ -30,6 +31,14 @@ class ScorerConfig:
     reward_clip: float = 10.0
     constrain_indicator: bool = True
     cost_kinds: List[Tuple[int, int, float]] = field(default_factory=list)   # (lo, hi, size), reference order
+
+
+def _task_table(v, n, name):
+    """A task's table as float32 [n]: an array of that length, or a scalar broadcast to it."""
+    a = np.asarray(v, np.float32)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != int(n)):
+        raise ValueError('%s must be a scalar or have shape [%d]' % (name, n))
+    return np.ascontiguousarray(np.broadcast_to(a, (int(n),)), dtype=np.float32)
 
 
 @dataclass
@@ -61,13 +70,52 @@ class QuadraticTask:
 
     def tables(self, obs_dim, act_dim):
         """The float32 tables as the library takes them: dict of q, g, c, goal_mask, lo, hi [obs_dim] and rho [act_dim]."""
-        def full(v, n, name):
-            a = np.asarray(v, np.float32)
-            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
-                raise ValueError('%s must be a scalar or have shape [%d]' % (name, n))
-            return np.ascontiguousarray(np.broadcast_to(a, (n,)), dtype=np.float32)
-        out = {k: full(getattr(self, k), int(obs_dim), k) for k in ('q', 'g', 'c', 'goal_mask', 'lo', 'hi')}
-        out['rho'] = full(self.rho, int(act_dim), 'rho')
+        out = {k: _task_table(getattr(self, k), obs_dim, k) for k in ('q', 'g', 'c', 'goal_mask', 'lo', 'hi')}
+        out['rho'] = _task_table(self.rho, act_dim, 'rho')
+        return out
+
+
+@dataclass
+class TrackingTask:
+    """A QuadraticTask whose set-point moves with time (cem_task_tracking_t, CEM_TASK_TRACKING; cem_mpc.h "Tracking tasks"): row j of
+    `reference` [T, obs_dim] takes g's place for the state that lies j - k0 steps into the plan (the last row is held), the last
+    predicted state is weighted by `terminal_weights` (None: q) and every step pays sum_j action_rate_j (a_t[j] - a_{t-1}[j])^2 (None:
+    nothing).  k0 and the action before the plan's first are the handle's clock (CemPlanner.set_task_clock; CemMpc keeps it).  The other
+    fields are QuadraticTask's."""
+    reference: object = None
+    q: object = 0.0
+    c: object = 0.0
+    goal_mask: object = 0.0
+    lo: object = -np.inf
+    hi: object = np.inf
+    rho: object = 0.0
+    goal_radius: float = 0.0
+    reward_goal: float = 0.0
+    reward_clip: float = 0.0
+    terminal_weights: object = None
+    action_rate: object = None
+
+    @classmethod
+    def to_reference(cls, reference, weights=1.0, action_weights=0.0, terminal_weights=None, action_rate=None, lo=-np.inf, hi=np.inf,
+                     goal_radius=0.0, reward_goal=0.0, reward_clip=0.0):
+        """Follow `reference` [T, obs_dim]: reward = -sum weights (s - reference row)^2 - sum action_weights a^2 - the action-rate term;
+        goal_radius as QuadraticTask.to_target's, measured against the row of the moment."""
+        w = np.asarray(weights, np.float32)
+        return cls(reference=reference, q=w, goal_mask=(w != 0).astype(np.float32), lo=lo, hi=hi, rho=action_weights, goal_radius=goal_radius,
+                   reward_goal=reward_goal, reward_clip=reward_clip, terminal_weights=terminal_weights, action_rate=action_rate)
+
+    def tables(self, obs_dim, act_dim):
+        """The float32 tables as the library takes them: QuadraticTask.tables' without g, q_terminal [obs_dim], action_rate [act_dim]
+        and reference [T, obs_dim]."""
+        O, A = int(obs_dim), int(act_dim)
+        out = {k: _task_table(getattr(self, k), O, k) for k in ('q', 'c', 'goal_mask', 'lo', 'hi')}
+        out['rho'] = _task_table(self.rho, A, 'rho')
+        out['q_terminal'] = out['q'] if self.terminal_weights is None else _task_table(self.terminal_weights, O, 'terminal_weights')
+        out['action_rate'] = _task_table(0.0 if self.action_rate is None else self.action_rate, A, 'action_rate')
+        ref = np.asarray(self.reference if self.reference is not None else (), np.float32)
+        if ref.ndim != 2 or ref.shape[1] != O or not 1 <= ref.shape[0] <= _capi.CEM_TASK_REF_MAX_STEPS:
+            raise ValueError('reference must have shape [T, %d] with 1 <= T <= %d' % (O, _capi.CEM_TASK_REF_MAX_STEPS))
+        out['reference'] = np.ascontiguousarray(ref)
         return out
 
 
@@ -119,8 +167,10 @@ class PlannerConfig:
     plan_readout: bool = False         # True: a tracker kernel behind every select keeps the best-so-far candidate's whole sequence, its particle
                                        # returns and per-step cost counts (cem_planner_set_plan_readout; CemPlanner.plan_readout); not in
                                        # cem_config_t: set after create
-    task: Optional[QuadraticTask] = None   # None: the Safety-Gym scorer (the reference); a QuadraticTask: rollouts are scored by it
-                                       # (cem_planner_set_task) and `scorer` is inert; not in cem_config_t: set after create
+    task: Optional[object] = None      # None: the Safety-Gym scorer (the reference); a QuadraticTask: rollouts are scored by it
+                                       # (cem_planner_set_task) and `scorer` is inert; a TrackingTask: by a reference that
+                                       # moves with the handle's clock (cem_planner_set_task_tracking); not in cem_config_t:
+                                       # set after create
     action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
@@ -395,7 +445,8 @@ class CemPlanner:
         self.layout = lay
         self._call = 0
         self.has_comm = False
-        self.task = None                              # the QuadraticTask in force (set_task)
+        self.task = None                              # the QuadraticTask or TrackingTask in force (set_task)
+        self.task_clock = None                        # a TrackingTask's clock as last set: (k0, previous action [A]) (set_task_clock)
         # the configured options, in this order: (is it configured?, the call that applies it).  A handle that refuses one is closed
         options = (
             (cfg.worst_particles, lambda: self.set_particle_objective('lower_tail', cfg.worst_particles)),
@@ -812,14 +863,34 @@ class CemPlanner:
         Sticky; waits for the stream and re-captures the graph.  task_objective restates the kernel."""
         if task is None:
             _capi.check(self.lib.cem_planner_set_task(self.h, None), 'cem_planner_set_task')
-            self.task = None
+            self.task, self.task_clock = None, None
             return
         tb = task.tables(self.cfg.obs_dim, self.cfg.act_dim)      # (kept alive until the call returns: the library copies them)
         fp = C.POINTER(C.c_float)
+        if isinstance(task, TrackingTask):
+            # a TrackingTask (cem_planner_set_task_tracking): the same launches with cem_task_reference_kernel behind the rollout;
+            # the clock starts at (0, zeros); tracking_objective restates the kernel
+            base = _capi.CemTask(kind=_capi.CEM_TASK_QUADRATIC, goal_radius=float(task.goal_radius), reward_goal=float(task.reward_goal),
+                                 reward_clip=float(task.reward_clip),
+                                 **{k: tb[k].ctypes.data_as(fp) for k in ('q', 'c', 'goal_mask', 'lo', 'hi', 'rho')})
+            trk = _capi.CemTaskTracking(ref=tb['reference'].ctypes.data_as(fp), ref_steps=tb['reference'].shape[0],
+                                        q_terminal=tb['q_terminal'].ctypes.data_as(fp) if task.terminal_weights is not None else None,
+                                        action_rate=tb['action_rate'].ctypes.data_as(fp) if task.action_rate is not None else None)
+            _capi.check(self.lib.cem_planner_set_task_tracking(self.h, C.byref(base), C.byref(trk)), 'cem_planner_set_task_tracking')
+            self.task, self.task_clock = task, (0, np.zeros(self.cfg.act_dim, np.float32))
+            return
         ct = _capi.CemTask(kind=_capi.CEM_TASK_QUADRATIC, goal_radius=float(task.goal_radius), reward_goal=float(task.reward_goal),
                            reward_clip=float(task.reward_clip), **{k: tb[k].ctypes.data_as(fp) for k in tb})
         _capi.check(self.lib.cem_planner_set_task(self.h, C.byref(ct)), 'cem_planner_set_task')
-        self.task = task
+        self.task, self.task_clock = task, None
+
+    def set_task_clock(self, k0, prev_action=None):
+        """The clock of a TrackingTask (cem_planner_set_task_clock): the plan's first state is compared with reference row k0, its first
+        action with prev_action [act_dim] (None: as it was).  A stream-ordered copy: later plans see it, the captured graph stays.
+        `task_clock` is the host's record of it."""
+        a = None if prev_action is None else np.ascontiguousarray(np.asarray(prev_action, np.float32).reshape(self.cfg.act_dim))
+        _capi.check(self.lib.cem_planner_set_task_clock(self.h, int(k0), _np_ptr(a) if a is not None else None), 'cem_planner_set_task_clock')
+        self.task_clock = (int(k0), a.copy() if a is not None else self.task_clock[1])
 
     def task_trajectories(self):
         """The raw state trajectories [P * n_samples, H + 1, obs_dim] of the last rollout launch of a task plan, a copy (torch, on the
@@ -1324,29 +1395,23 @@ def mean_candidate(actions, mu, lb, ub) -> np.ndarray:
     return out
 
 
-def task_objective(traj, actions, task, variant='cem', return_done=False):
-    """Host restatement of cem_task_score_kernel (csrc/cem_task_score.h; cem_mpc.h "Task scorers"), bit for bit: traj [rows, H + 1, O]
-    raw states, actions [N, H, A] (row r belongs to candidate r mod N), task a QuadraticTask, variant 'cem' | 'safe' | 'cost' ->
-    (returns [rows] float32, cost bytes [H, rows] uint8 — None for 'cem', whose rollout stores none).  Every product and sum is a float32
-    operation of its own, in the kernel's order: per feature d = s - g, dd = d d, q dd - c s and m dd; sixteen partial sums over the
-    features 64 i + 4 l + r (i, then r), added pairwise, neighbours first; u = sum_j rho_j (a_j a_j) from j = 0; the steps in order.
-    A NaN return is stored as 0x7fc00000.  return_done=True appends the first step at which near held, int [rows] (H: never)."""
+def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, return_done):
+    """What task_objective and tracking_objective share, in the kernels' order: tb the [O] / [A] tables, ref [H + 1, O] the row every
+    state is compared with (or [O]: one for all), q_terminal [O] the weights of the last state (None: q), rate [N, H] the action-rate
+    term of every step (None: the reward has no such term)."""
     f = np.float32
     if variant not in VARIANTS:
         raise ValueError("variant must be 'cem', 'safe' or 'cost'")
-    tr = np.ascontiguousarray(np.asarray(traj, f))
-    act = np.ascontiguousarray(np.asarray(actions, f))
-    if tr.ndim != 3 or act.ndim != 3 or tr.shape[1] != act.shape[1] + 1 or tr.shape[0] % act.shape[0] != 0:
-        raise ValueError('traj must be [rows, H + 1, O] and actions [N, H, A] with rows a multiple of N')
+    tr, act = traj, actions
     rows, H1, O = tr.shape
     N, H, A = act.shape
-    if O > 128:
-        raise ValueError('obs_dim > 128')
-    tb = task.tables(O, A)
 
     def pad(a, v):
-        return np.concatenate([a, np.full(128 - O, v, f)])
-    q, g, c, m = (pad(tb[k], 0) for k in ('q', 'g', 'c', 'goal_mask'))
+        a = np.asarray(a, f)
+        return np.concatenate([a, np.full(a.shape[:-1] + (128 - O,), v, f)], axis=-1)
+    q, g, c, m = pad(tb['q'], 0), pad(ref, 0), pad(tb['c'], 0), pad(tb['goal_mask'], 0)
+    if q_terminal is not None:                        # [H + 1, 128]: q on s_0 .. s_{H-1}, q_terminal on s_H
+        q = np.concatenate([np.broadcast_to(q, (H, 128)), pad(q_terminal, 0)[None]], axis=0)
     s = np.zeros((rows, H1, 128), f)
     s[..., :O] = tr
 
@@ -1371,6 +1436,7 @@ def task_objective(traj, actions, task, variant='cem', return_done=False):
         for j in range(A):
             u = u + tb['rho'][j] * (act[:, :, j] * act[:, :, j])
         u = u[np.arange(rows) % N]
+        v = rate[np.arange(rows) % N] if rate is not None else None
         clip = f(task.reward_clip) if f(task.reward_clip) > 0 else f(np.inf)
         safe = variant != 'cem'
         cum = np.zeros(rows, f)
@@ -1380,7 +1446,10 @@ def task_objective(traj, actions, task, variant='cem', return_done=False):
         for t in range(H):
             ga = near[:, t]
             first = np.where(ga & (first == H), t, first)
-            r = ((-phi[:, t + 1]) - u[:, t]) + np.where(ga, f(1), f(0)) * f(task.reward_goal)
+            r = (-phi[:, t + 1]) - u[:, t]
+            if v is not None:
+                r = r - v[:, t]
+            r = r + np.where(ga, f(1), f(0)) * f(task.reward_goal)
             r = np.fmin(np.fmax(r, -clip), clip)
             if safe:
                 done = done | ga
@@ -1394,6 +1463,53 @@ def task_objective(traj, actions, task, variant='cem', return_done=False):
     cum = np.ascontiguousarray(cum, f)
     cum.view(np.uint32)[np.isnan(cum)] = np.uint32(0x7fc00000)
     return (cum, costs, first) if return_done else (cum, costs)
+
+
+def _task_arrays(traj, actions):
+    f = np.float32
+    tr = np.ascontiguousarray(np.asarray(traj, f))
+    act = np.ascontiguousarray(np.asarray(actions, f))
+    if tr.ndim != 3 or act.ndim != 3 or tr.shape[1] != act.shape[1] + 1 or tr.shape[0] % act.shape[0] != 0:
+        raise ValueError('traj must be [rows, H + 1, O] and actions [N, H, A] with rows a multiple of N')
+    if tr.shape[2] > 128:
+        raise ValueError('obs_dim > 128')
+    return tr, act
+
+
+def task_objective(traj, actions, task, variant='cem', return_done=False):
+    """Host restatement of cem_task_score_kernel (csrc/cem_task_score.h; cem_mpc.h "Task scorers"), bit for bit: traj [rows, H + 1, O]
+    raw states, actions [N, H, A] (row r belongs to candidate r mod N), task a QuadraticTask, variant 'cem' | 'safe' | 'cost' ->
+    (returns [rows] float32, cost bytes [H, rows] uint8 — None for 'cem', whose rollout stores none).  Every product and sum is a float32
+    operation of its own, in the kernel's order: per feature d = s - g, dd = d d, q dd - c s and m dd; sixteen partial sums over the
+    features 64 i + 4 l + r (i, then r), added pairwise, neighbours first; u = sum_j rho_j (a_j a_j) from j = 0; the steps in order.
+    A NaN return is stored as 0x7fc00000.  return_done=True appends the first step at which near held, int [rows] (H: never)."""
+    tr, act = _task_arrays(traj, actions)
+    tb = task.tables(tr.shape[2], act.shape[2])
+    return _task_objective(tr, act, tb, tb['g'], None, None, task, variant, return_done)
+
+
+def tracking_objective(traj, actions, task, variant='cem', k0=0, prev_action=None, return_done=False):
+    """Host restatement of cem_task_reference_kernel (csrc/cem_task_reference.h; cem_mpc.h "Tracking tasks"), bit for bit: task_objective
+    with task a TrackingTask and the clock (k0, prev_action [A], default zeros).  State s_st is compared with reference row
+    min(k0 + st, T - 1); s_H is weighted by terminal_weights; step t also pays v_t = sum_j action_rate_j (e e), e = a_t[j] - a_{t-1}[j]
+    (a_{-1} = prev_action), added from j = 0 and subtracted after u: r = ((-phi - u) - v) + bonus."""
+    f = np.float32
+    tr, act = _task_arrays(traj, actions)
+    N, H, A = act.shape
+    tb = task.tables(tr.shape[2], A)
+    k0 = int(k0)
+    if k0 < 0:
+        raise ValueError('k0 must be >= 0')
+    T = tb['reference'].shape[0]
+    ref = tb['reference'][np.minimum(k0 + np.arange(H + 1), T - 1)]
+    ap = np.zeros(A, f) if prev_action is None else np.asarray(prev_action, f).reshape(A)
+    before = np.concatenate([np.broadcast_to(ap, (N, 1, A)), act[:, :-1]], axis=1)
+    with np.errstate(all='ignore'):
+        rate = np.zeros((N, H), f)
+        for j in range(A):
+            e = act[:, :, j] - before[:, :, j]
+            rate = rate + tb['action_rate'][j] * (e * e)
+    return _task_objective(tr, act, tb, ref, tb['q_terminal'], rate, task, variant, return_done)
 
 
 class PlanReadout(NamedTuple):
@@ -1488,6 +1604,8 @@ _PLANNER_CACHE_MAX = 32
 
 
 def _freeze(v):
+    if isinstance(v, np.ndarray) and v.size > 256:      # (a TrackingTask's reference: by its digest)
+        return ('ndarray', v.shape, hashlib.sha256(np.ascontiguousarray(v, np.float64).tobytes()).hexdigest())
     if isinstance(v, np.ndarray):
         return tuple(np.asarray(v, np.float64).ravel().tolist())
     if isinstance(v, (list, tuple)):

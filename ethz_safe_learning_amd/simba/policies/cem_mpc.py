@@ -70,6 +70,10 @@ Task scorers (beyond the reference, off by default): with ``task=planner.Quadrat
 with box state constraints instead of the Safety-Gym scorer (``PlannerConfig.task``, cem_mpc.h cem_planner_set_task):
 the policy then plans for environments whose observation is no lidar vector, and the environment need not expose a scorer.  Every
 option above applies; ``generate_actions`` raises (batch handles do not serve a task).
+With ``task=planner.TrackingTask(...)`` the set-point is a reference table that moves with time, the last predicted state has weights of
+its own and the change of the action is penalised (cem_mpc.h cem_planner_set_task_tracking).  The policy keeps the
+handle's clock: before every plan it sets it to (decisions since ``reset()``, the action it returned last) with a stream-ordered copy
+(the captured graph stays); the decisions between two plans of ``replan_every`` advance the count too; ``reset()`` puts back (0, zeros).
 
 With ``replan_every=r``, 1 <= r <= horizon (which implies ``plan_readout``), ``generate_action`` plans at decisions 0, r, 2r, ... of an
 episode and in between returns step j of the kept sequence, plus ``noise_stddev`` times the output noise of that decision's own Philox
@@ -82,7 +86,7 @@ returns or the safety of an agent that uses them."""
 import logging
 import numpy as np
 
-from ...planner import PlannerConfig, ScorerConfig, cached_batch_planner, cached_planner, elite_keep_count, population_schedule, risk_particles, stage_model_weights
+from ...planner import PlannerConfig, ScorerConfig, TrackingTask, cached_batch_planner, cached_planner, elite_keep_count, population_schedule, risk_particles, stage_model_weights
 from .mpc_policy import MpcPolicy
 
 
@@ -97,6 +101,7 @@ class CemMpc(MpcPolicy):
         super().__init__(model, environment, horizon, n_samples, particles)
         # a task scorer (beyond the reference's kwargs): see the module docstring
         self.task = task
+        self._clock = (0, None)                        # a TrackingTask's clock: decisions since reset(), the action returned last (None: zeros)
         self.iterations = iterations
         self.smoothing = smoothing
         self.elite = n_elite
@@ -258,6 +263,7 @@ class CemMpc(MpcPolicy):
         """An episode begins: the next plan of every slot starts cold and takes no elites of an earlier plan (no effect without warm
         start or shift_elites), and the sequence kept for replan_every is discarded."""
         self._kept, self._kept_step = None, 0          # replan_every: the next decision plans
+        self._clock = (0, None)
         if not (self.warm_start or self.shift_elites):
             return
         for pl in [self._planner] + list(self._batch_planners.values()):
@@ -283,17 +289,30 @@ class CemMpc(MpcPolicy):
         self._sync_model(pl)
         return pl
 
+    def _stage_clock(self, planner):
+        """A TrackingTask's clock onto the handle about to plan (handles are shared through the cache: every plan sets its own)."""
+        if isinstance(self.task, TrackingTask):
+            k0, prev = self._clock
+            planner.set_task_clock(k0, np.zeros(planner.cfg.act_dim, np.float32) if prev is None else prev)
+
+    def _note_decision(self, action):
+        """The decision just made moves the clock on: one more step into the reference, `action` the one before the next plan's first."""
+        if isinstance(self.task, TrackingTask):
+            self._clock = (self._clock[0] + 1, np.array(action, np.float32, copy=True))
+        return action
+
     # ---- the plugin boundary ------------------------------------------------------------------------------------
     def generate_action(self, state):
         self.build()                                   # cached handle + weights of the current model version
         if self._kept is not None:                     # replan_every: a decision between two plans
-            return self._follow(self._next_calls([self.slot])[0] if self.warm_start else int(self._planner.take_calls()[0]))
+            return self._note_decision(self._follow(self._next_calls([self.slot])[0] if self.warm_start else int(self._planner.take_calls()[0])))
+        self._stage_clock(self._planner)
         action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed,
                                                   call=self._next_calls([self.slot])[0] if self.warm_start else None)
         self.last_score, self.last_iterations = score, iters
         self._note_ess(self._planner, iters)
         self._note_plan(self._planner)
-        return action
+        return self._note_decision(action)
 
     def _note_plan(self, planner):
         """last_plan from the handle whose action is being returned (its stream is drained: the last tracker runs behind the polled
@@ -387,6 +406,7 @@ class CemMpc(MpcPolicy):
     def do_generate_action(self, state, eps_act=None, eps_model=None, eps_out=None):
         """(action, best_score) like cem_mpc.py:35-68; explicit noise tensors replace TF's stateful RNG."""
         self.build()
+        self._stage_clock(self._planner)
         action, score, iters = self._planner.plan(np.asarray(state, np.float32), seed=self.seed, eps_act=eps_act,
                                                   eps_model=eps_model, eps_out=eps_out)
         self.last_iterations = iters

@@ -185,7 +185,9 @@ class SafeCemMpc(CemMpc):
         """safe_cem_mpc.py:40-74: state[O] -> np.float32[A], ``best_so_far + noise`` of the CEM loop that maximises minus the mean
         cost (no score is returned, as :74; it is kept in ``last_safety_score``).  call: the Philox call number (None: the cost
         handle's own counter)."""
-        action, score, _ = self.build_cost().plan(np.asarray(state, np.float32), seed=self.seed, call=call)
+        cpl = self.build_cost()
+        self._stage_clock(cpl)                         # (a TrackingTask: the recovery plan follows the same reference from the same step)
+        action, score, _ = cpl.plan(np.asarray(state, np.float32), seed=self.seed, call=call)
         self.last_safety_score = score
         return action
 
@@ -206,6 +208,7 @@ class SafeCemMpc(CemMpc):
         self.build()
         call = self._next_calls([self.slot])[0] if self.warm_start else int(self._planner.take_calls()[0])
         state = np.asarray(state, np.float32)
+        self._stage_clock(self._planner)
         action, score, iters = self._planner.plan(state, seed=self.seed, call=call)
         self.last_score, self.last_iterations = score, iters
         self._note_ess(self._planner, iters)
@@ -214,7 +217,7 @@ class SafeCemMpc(CemMpc):
         if self.last_recovered:
             action = self.optimize_for_safety(state, call=call)
         self._note_plan(self._cost_planner if self.last_recovered else self._planner)
-        return action
+        return self._note_decision(action)
 
     def generate_actions(self, states, slots=None, reset=None):
         if self.cost_budget is not None and np.ndim(self.cost_budget) and self.cost_budget.size != np.shape(states)[0]:

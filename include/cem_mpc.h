@@ -815,6 +815,54 @@ int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions
                    float *ret_out_dev, uint8_t *costs_out_dev);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Tracking tasks: a per-step reference, terminal weights and an action-rate penalty.  Beyond the reference, off by default (DESIGN.md
+ * 4.20).  A second task kind: the quadratic task above with row j of a reference table ref [ref_steps][obs_dim] in the place of g for the
+ * state that lies j - k0 steps into the plan, a weight vector of its own on the last predicted state, and a penalty on the change of the
+ * action from one step to the next.  The handle keeps a "clock" (k0, previous action) in device memory; cem_planner_set_task_clock moves
+ * it between decisions with a stream-ordered copy, so the captured graph stays.  A tracking plan launches what a quadratic-task plan
+ * launches, with the kernel of csrc/cem_task_reference.h, cem_task_reference_kernel, in the place of cem_task_score_kernel.
+ *
+ * Everything not named here is the quadratic task's, statement for statement.  q, c, goal_mask, lo, hi, rho, goal_radius, reward_goal,
+ * reward_clip come from `base` (base->kind CEM_TASK_QUADRATIC, base->g NULL); q_terminal [obs_dim] defaults to q, action_rate
+ * [act_dim] (kappa) to zeros.  For state s_st, st = 0 .. H:
+ *   j = min(k0 + st, ref_steps - 1)                                     the last row is held
+ *   phi(s_st)  = sum_f [ w_f (s_f - ref[j]_f)^2 - c_f s_f ]             w = q_terminal where st == H, else q
+ *   near(s_st) = R2 > 0 and sum_f goal_mask_f (s_f - ref[j]_f)^2 <= R2
+ *   v_t = sum_j kappa_j (a_t[j] - a_{t-1}[j])^2                          a_{-1}: the clock's previous action
+ *   r   = -phi(s_{t+1}) - u(a_t) - v_t + (near(s_t) ? reward_goal : 0)   then the clip and the variant's bookkeeping as above
+ * in fp32, every product, difference and sum rounded on its own, in the order csrc/cem_task_reference.h states
+ * (planner.tracking_objective is the NumPy restatement, bit for bit).  With ref_steps = 1, ref[0] = g and neither q_terminal nor
+ * action_rate the returns and cost bytes are the quadratic task's, bit for bit.
+ *
+ * cem_planner_set_task_tracking copies the tables (they may be freed on return), allocates the reference table (ref_steps rows of 512
+ * bytes), the clock block and, where the handle has none yet, the trajectory buffer before it changes anything, waits for the stream and
+ * drops the captured graph, as cem_planner_set_task does; the clock resets to (0, zeros).  cem_planner_set_task(h, NULL) switches
+ * either kind off; cem_planner_set_task itself accepts kinds 0 and 1 only.  cem_planner_task_trajectories and cem_task_score serve both
+ * kinds; cem_task_score scores with the handle's clock.
+ *   CEM_ERR_INVALID_ARG  null handle, base or trk; base->kind not CEM_TASK_QUADRATIC; base->g not NULL; ref NULL; ref_steps < 1 or
+ *                        > CEM_TASK_REF_MAX_STEPS; a NaN or infinite ref, q_terminal or action_rate entry; whatever cem_planner_set_task
+ *                        refuses in base
+ *   CEM_ERR_STATE        between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  what cem_planner_set_task refuses so; a library built without cem_task_reference_kernel
+ * A failed allocation returns CEM_ERR_HIP; the handle keeps its previous setting after any of these.
+ *
+ * cem_planner_set_task_clock sets k0 and, unless prev_action is NULL, the previous action [act_dim] (host memory, copied before the call
+ * returns).  A stream-ordered copy, as cem_planner_set_cost_budget's: plans enqueued later see it, nothing waits, the captured graph and
+ * its node count stay.
+ *   CEM_ERR_INVALID_ARG  null handle; k0 < 0; a NaN or infinite prev_action entry
+ *   CEM_ERR_STATE        no tracking task in force; between the begin and end calls of a stepwise plan */
+#define CEM_TASK_REF_MAX_STEPS 16384
+enum cem_task_kind_more { CEM_TASK_TRACKING = 2 };   /* a third value for the kind fields, which hold an int32_t */
+typedef struct {
+    const float *ref;             /* [ref_steps][obs_dim], host memory */
+    int32_t ref_steps;            /* 1 .. CEM_TASK_REF_MAX_STEPS */
+    const float *q_terminal;      /* [obs_dim], host memory, or NULL: base->q */
+    const float *action_rate;     /* [act_dim], host memory, or NULL: zeros */
+} cem_task_tracking_t;
+int cem_planner_set_task_tracking(cem_planner_t *h, const cem_task_t *base, const cem_task_tracking_t *trk);
+int cem_planner_set_task_clock(cem_planner_t *h, int32_t k0, const float *prev_action /* [act_dim] or NULL: unchanged */);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

@@ -1,0 +1,302 @@
+"""The tracking task (cem_planner_set_task_tracking, cem_planner_set_task_clock), the parts that need no GPU: the
+symbols and the structs, what the calls refuse without a handle, the NumPy mirror planner.tracking_objective against a plain float64
+evaluation of the contract and against planner.task_objective where the two contracts meet, the kernel's code-object metadata, the
+cache key, the policies' clock and the closed loop's yardstick."""
+import ctypes as C
+import dataclasses
+import hashlib
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from ethz_safe_learning_amd import _capi
+from ethz_safe_learning_amd.planner import PlannerConfig, QuadraticTask, ScorerConfig, TrackingTask, config_key, task_objective, to_c_config, tracking_objective
+from tests import helpers as hp
+from tests import task_cases as tc
+from tests import tracking_cases as tk
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ('cem_planner_set_task_tracking', 'cem_planner_set_task_clock')
+INVALID_ARG = 1
+U = np.uint32
+
+
+def test_symbols_are_declared_exported_and_listed(built_lib):
+    hdr = open(os.path.join(ROOT, 'include', 'cem_mpc.h')).read()
+    for name in SYMBOLS:
+        assert re.search(r'^int %s\(' % name, hdr, re.M), name
+        assert name in _capi.EXPORTED_SYMBOLS
+        assert getattr(built_lib, name) is not None
+    assert re.search(r'\bCEM_TASK_TRACKING = 2\b', hdr) and _capi.CEM_TASK_TRACKING == 2
+    assert re.search(r'#define CEM_TASK_REF_MAX_STEPS 16384\b', hdr) and _capi.CEM_TASK_REF_MAX_STEPS == 16384
+    assert [f[0] for f in _capi.CemTaskTracking._fields_] == ['ref', 'ref_steps', 'q_terminal', 'action_rate']
+    assert re.search(r'#define CEM_ABI_VERSION 4\b', hdr) and built_lib.cem_abi_version() == 4
+    mk = open(os.path.join(hp.CSRC, 'Makefile')).read()
+    assert mk.count('cem_task_reference.hip') == 2                                # a prerequisite and a source of the one link line
+
+
+def test_null_handle_is_an_invalid_argument(built_lib):
+    base, trk = _capi.CemTask(kind=_capi.CEM_TASK_QUADRATIC), _capi.CemTaskTracking(ref_steps=1)
+    assert built_lib.cem_planner_set_task_tracking(None, C.byref(base), C.byref(trk)) == INVALID_ARG
+    assert built_lib.cem_planner_set_task_tracking(None, None, None) == INVALID_ARG
+    assert built_lib.cem_planner_set_task_clock(None, 0, None) == INVALID_ARG
+
+
+def test_the_struct_compiles_as_c_and_the_task_keeps_its_size(tmp_path):
+    cc = os.environ.get('CC', 'cc')
+    src = tmp_path / 'sz.c'
+    src.write_text('#include <stdio.h>\n#include "cem_mpc.h"\nint main(void) { printf("%zu %zu %d", sizeof(cem_task_t), sizeof(cem_task_tracking_t), '
+                   '(int)CEM_TASK_TRACKING); return 0; }\n')
+    exe = tmp_path / 'sz'
+    try:
+        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), '-o', str(exe), str(src)], check=True, capture_output=True)
+    except (OSError, subprocess.CalledProcessError) as e:
+        pytest.fail('the header must compile as plain C: %r' % (getattr(e, 'stderr', e),))
+    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
+    assert got == [C.sizeof(_capi.CemTask), C.sizeof(_capi.CemTaskTracking), 2]
+
+
+def test_the_task_is_part_of_the_cache_key_and_not_of_the_c_config():
+    kw = dict(obs_dim=12, act_dim=2, ensemble_size=5, particles=5, n_samples=64, horizon=5, n_elite=8, iterations=3,
+              scorer=ScorerConfig(goal_slice=(3, 7)), act_low=[-1, -1], act_high=[1, 1], units=32)
+    ref = np.zeros((40, 12), np.float32)                                          # (480 values: hashed by digest; the small ones by value)
+    other = ref.copy()
+    other[39, 11] = 1e-6
+    cfgs = [PlannerConfig(**kw), PlannerConfig(task=QuadraticTask(q=1.0), **kw), PlannerConfig(task=TrackingTask(reference=ref, q=1.0), **kw),
+            PlannerConfig(task=TrackingTask(reference=other, q=1.0), **kw), PlannerConfig(task=TrackingTask(reference=ref[:39], q=1.0), **kw),
+            PlannerConfig(task=TrackingTask(reference=ref, q=1.0, action_rate=np.array([0.0, 0.5])), **kw),
+            PlannerConfig(task=TrackingTask(reference=ref, q=1.0, terminal_weights=np.arange(12.0)), **kw)]
+    keys = [config_key(c) for c in cfgs]
+    assert len(set(keys)) == len(keys) and all(hash(k) is not None for k in keys)
+    assert config_key(cfgs[2]) == config_key(PlannerConfig(task=TrackingTask(reference=ref.copy(), q=1.0), **kw))
+    assert bytes(to_c_config(cfgs[0])) == bytes(to_c_config(cfgs[2]))
+
+
+def test_tables_default_and_refuse_other_shapes():
+    ref = np.arange(6, dtype=np.float32).reshape(2, 3)
+    t = TrackingTask.to_reference(ref, weights=[1.0, 0.0, 2.0], action_weights=0.1)
+    tb = t.tables(3, 2)
+    assert 'g' not in tb and tb['reference'].shape == (2, 3) and tb['reference'].dtype == np.float32
+    assert tb['q'].tolist() == [1.0, 0.0, 2.0] and tb['q_terminal'].tolist() == [1.0, 0.0, 2.0] and tb['goal_mask'].tolist() == [1.0, 0.0, 1.0]
+    assert tb['action_rate'].tolist() == [0.0, 0.0] and np.allclose(tb['rho'], 0.1)
+    assert TrackingTask(reference=ref, terminal_weights=3.0, action_rate=[1.0, 2.0]).tables(3, 2)['q_terminal'].tolist() == [3.0] * 3
+    for bad in (TrackingTask(), TrackingTask(reference=ref[0]), TrackingTask(reference=np.zeros((0, 3))), TrackingTask(reference=ref, action_rate=[1.0] * 3),
+                TrackingTask(reference=np.zeros((_capi.CEM_TASK_REF_MAX_STEPS + 1, 3), np.float32))):
+        with pytest.raises(ValueError):
+            bad.tables(3, 2)
+    with pytest.raises(ValueError):
+        t.tables(4, 2)
+    assert not hasattr(t, 'g')
+
+
+def _cases():
+    """Every shape x variant x seed x clip of the quadratic task's float64 test; the five clocks rotate through them so that every shape
+    meets every clock, with terminal weights, an action rate and a non-zero previous action throughout."""
+    for (O, A, H, rows, P) in tk.SHAPES:
+        for vi, variant in enumerate(('cem', 'safe', 'cost')):
+            for seed in range(3):
+                for clip in (True, False):
+                    T, k0 = tk.clock_cases(H)[(vi + seed + (0 if clip else 2)) % 5]
+                    task = tk.tracking_task_for(O, A, T, seed, clip)
+                    prev = tk.prev_action_for(A, seed)
+                    tr, act = tc.random_case(O, A, H, rows, P, seed)
+                    tk.clear_thresholds(tr, task, k0)
+                    names = tk.craft(tr, act, task, k0, prev, boundaries=False)
+                    yield (O, variant, seed, clip, T, k0), task, tr, act, variant, k0, prev, names
+
+
+def test_mirror_against_float64():
+    """planner.tracking_objective against the contract in float64 (tracking_cases.tracking_f64): the quadratic task's shapes, three
+    variants, three seeds, with and without a clip, every (T, k0) of clock_cases on every shape.  No comparison operand lies within 1e-4
+    of its threshold (asserted; the states were moved off the thresholds of the rows they are compared with), so cost bytes and done
+    steps are EQUAL.  The bar on the returns is twice tracking_cases.MIRROR_ERROR_MEASURED, the largest relative distance measured over
+    these cases on the CPU."""
+    worst, seen, clocks = 0.0, set(), set()
+    for what, task, tr, act, variant, k0, prev, names in _cases():
+        r64, c64, d64, margin = tk.tracking_f64(tr, act, task, variant, k0, prev)
+        r32, c32, d32 = tracking_objective(tr, act, task, variant, k0=k0, prev_action=prev, return_done=True)
+        assert margin > tc.NEAR, (what, margin)
+        assert r32.dtype == np.float32 and np.array_equal(d32, d64), what
+        if variant == 'cem':
+            assert c32 is None and c64 is None
+        else:
+            assert c32.dtype == np.uint8 and np.array_equal(c32, c64), what
+        H = act.shape[1]
+        if variant != 'cost' and names:                                        # the crafted rows are what they are named
+            assert d64[names['goal_at_0']] == 0 and d64[names['goal_at_last_step']] == H - 1 and d64[names['goal_never']] == H, what
+        seen.add((variant, bool((d64 < H).any()), bool((d64 == H).any()), c64 is not None and bool(c64.any())))
+        clocks.add((what[0], what[4] - H, what[5]))
+        worst = max(worst, float((np.abs(r32.astype(np.float64) - r64) / np.maximum(1.0, np.abs(r64))).max()))
+    print('tracking mirror against float64: largest relative distance %.3g' % worst)
+    assert worst <= 2 * tk.MIRROR_ERROR_MEASURED, worst
+    assert worst > 0.5 * tk.MIRROR_ERROR_MEASURED, worst                          # (the recorded figure is this test's own)
+    assert ('safe', True, True, True) in seen and not any(v == 'cost' and d for v, d, _, _ in seen)
+    assert len(clocks) == 5 * len(tk.SHAPES)
+
+
+def test_every_new_term_moves_the_float64_statement_and_the_mirror_alike():
+    """The reference row, the terminal weights, the action rate and the previous action each change the returns, in the mirror as in the
+    float64 statement: a mirror that dropped one of them would not pass the test above by both dropping it."""
+    O, A, H, rows, P = tk.SHAPES[1]
+    prev = tk.prev_action_for(A)
+    tr, act = tc.random_case(O, A, H, rows, P, 0)
+    full = tk.tracking_task_for(O, A, H + 1, 0, False)
+    variants = {'one row': dataclasses.replace(full, reference=np.asarray(full.reference)[:1]),
+                'no terminal weights': dataclasses.replace(full, terminal_weights=None),
+                'no action rate': dataclasses.replace(full, action_rate=None)}
+    r_full = tracking_objective(tr, act, full, 'cem', 0, prev)[0]
+    for name, t in variants.items():
+        r = tracking_objective(tr, act, t, 'cem', 0, prev)[0]
+        r64 = tk.tracking_f64(tr, act, t, 'cem', 0, prev)[0]
+        assert (r != r_full).mean() > 0.3, name                      # (a row that reached the goal early has stopped counting)
+        assert np.abs(r - r64).max() <= 1e-5 * np.abs(r64).max(), name
+    assert (tracking_objective(tr, act, full, 'cem', 0, None)[0] != r_full).mean() > 0.9
+    assert (tracking_objective(tr, act, full, 'cem', 2, prev)[0] != r_full).mean() > 0.9
+    # a deviation at s_H is weighted by qT, the same one at s_{H-1} by q (the crafted pair shares its actions)
+    names = tk.craft(tr, act, full, 0, prev)
+    ret = tracking_objective(tr, act, full, 'cem', 0, prev)[0]
+    b = int(np.nonzero(np.isfinite(np.asarray(full.lo)) & np.isfinite(np.asarray(full.hi)))[0][-1])
+    q, qT = (np.asarray(x, np.float64)[b] for x in (full.q, full.terminal_weights))
+    got = float(ret[names['deviation_before_H']]) - float(ret[names['deviation_at_H']])
+    # the rest of both rows is on the reference and the c s terms of the two rows add up to the same: the difference is (qT - q) 0.25
+    want = (qT - q) * 0.25
+    assert abs(got - want) <= 1e-4 * max(1.0, abs(want)) + 1e-4, (got, want)
+    assert abs(want) > 1e-3
+
+
+def test_mirror_equals_the_quadratic_mirror_where_the_contracts_meet():
+    """T = 1, ref[0] = g, no terminal weights, no action rate: planner.task_objective's returns, cost bytes and done steps bit for bit,
+    whatever the clock says (x - (+0) is x)."""
+    for (O, A, H, rows, P) in tk.SHAPES:
+        for variant in ('cem', 'safe', 'cost'):
+            for clip in (True, False):
+                task = tc.task_for(O, A, 1, clip)
+                tr, act = tc.random_case(O, A, H, rows, P, 1)
+                tc.craft(tr, task)
+                tb = task.tables(O, A)
+                trk = TrackingTask(reference=tb['g'][None], q=task.q, c=task.c, goal_mask=task.goal_mask, lo=task.lo, hi=task.hi, rho=task.rho,
+                                   goal_radius=task.goal_radius, reward_goal=task.reward_goal, reward_clip=task.reward_clip)
+                want = task_objective(tr, act, task, variant, return_done=True)
+                for k0, prev in ((0, None), (7, tk.prev_action_for(A))):
+                    got = tracking_objective(tr, act, trk, variant, k0=k0, prev_action=prev, return_done=True)
+                    assert np.array_equal(got[0].view(U), want[0].view(U)), (O, variant, clip, k0)
+                    assert (got[1] is None and want[1] is None) or np.array_equal(got[1], want[1])
+                    assert np.array_equal(got[2], want[2])
+
+
+def test_mirror_crafted_rows():
+    """What the contract says ON the thresholds and about the clock, in the mirror (the kernel is held to the mirror bit for bit on the
+    GPU): near holds at exactly R2 against a moving row and not one ulp outside; a step whose action equals the previous action pays no
+    rate; rows beyond the table hold the last row."""
+    O, A, H, rows, P = tk.SHAPES[1]
+    prev = tk.prev_action_for(A)
+    for T, k0 in tk.clock_cases(H):
+        task = tk.tracking_task_for(O, A, T, 0, True)
+        tr, act = tc.random_case(O, A, H, rows, P, 0)
+        names = tk.craft(tr, act, task, k0, prev)
+        ret, costs, first = tracking_objective(tr, act, task, 'safe', k0=k0, prev_action=prev, return_done=True)
+        assert costs[:, names['on_bounds']].sum() == 0
+        assert costs[0, names['ulp_below_lo']] == 1 and costs[0, names['ulp_above_hi']] == 1
+        assert first[names['near_exactly']] == names['near_state'] and first[names['near_ulp_outside']] == H, (T, k0)
+        assert costs[:, names['nan_feature']].sum() == 0 and first[names['nan_feature']] == H and np.isfinite(ret[names['nan_feature']])
+    # every state holds the last row: a table of that row alone scores the same
+    task = tk.tracking_task_for(O, A, 4, 0, True)
+    tr, act = tc.random_case(O, A, H, rows, P, 0)
+    last = dataclasses.replace(task, reference=np.asarray(task.reference)[-1:])
+    a = tracking_objective(tr, act, task, 'safe', k0=9, prev_action=prev)
+    b = tracking_objective(tr, act, last, 'safe', k0=0, prev_action=prev)
+    assert np.array_equal(a[0].view(U), b[0].view(U)) and np.array_equal(a[1], b[1])
+    assert not np.array_equal(a[0], tracking_objective(tr, act, task, 'safe', k0=0, prev_action=prev)[0])
+    with pytest.raises(ValueError):
+        tracking_objective(tr, act, task, 'safe', k0=-1)
+
+
+@pytest.fixture(scope='module')
+def reference_isa():
+    """The device ISA of csrc/cem_task_reference.hip, the kernel's own translation unit, with the Makefile's flags (cached like
+    helpers.device_assembly).  Without the compiler the test FAILS: the library these tests load was built by it."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    assert os.path.exists(hipcc), 'no hipcc at %s: the tracking task cannot be compiled for its resource check' % hipcc
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(hp.CSRC)):
+        if f.endswith(('.h', '.hip')) or f == 'Makefile':
+            h.update(open(os.path.join(hp.CSRC, f), 'rb').read())
+    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
+    out = '/tmp/cem_task_reference_isa_%s.s' % h.hexdigest()[:16]
+    if not os.path.exists(out):
+        r = subprocess.run([hipcc] + hp.makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(hp.CSRC, 'cem_task_reference.hip')],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        os.replace(out + '.tmp', out)
+    return open(out).read()
+
+
+def test_the_kernel_has_no_spills_no_scratch_and_the_recorded_registers(reference_isa):
+    meta = hp.kernel_meta(reference_isa, r'.', keys=('vgpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size',
+                                                     'group_segment_fixed_size'))
+    assert sorted({hp.kernel_function_name(n) for n in meta}) == ['cem_task_reference_kernel'], sorted(meta)  # the unit holds this one alone
+    assert len(meta) == 4                                                         # one / two quads per lane x 16-byte / element loads
+    golden = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'task_reference_resources.json')))
+    assert sorted(golden) == sorted(meta)
+    for name, d in meta.items():
+        print(name, d)
+        assert d['vgpr_spill_count'] == 0 and d['sgpr_spill_count'] == 0 and d['private_segment_fixed_size'] == 0, (name, d)
+        assert {'vgpr_count': d['vgpr_count'], 'group_segment_fixed_size': d['group_segment_fixed_size']} == golden[name], (name, d, golden[name])
+        assert d['group_segment_fixed_size'] == 0, (name, d)                      # the tables sit in registers
+
+
+def test_the_policy_keeps_the_clock():
+    """CemMpc's bookkeeping without a handle: the clock a plan is staged with is (decisions since reset(), the action returned last),
+    the decisions between two plans of replan_every count, reset() puts back (0, zeros); a QuadraticTask stages nothing."""
+    from ethz_safe_learning_amd.simba.policies.cem_mpc import CemMpc
+
+    class Handle:
+        cfg = PlannerConfig(obs_dim=2, act_dim=1, ensemble_size=1, particles=1, n_samples=8, horizon=4, n_elite=2, iterations=1,
+                            scorer=ScorerConfig(goal_slice=(0, 1)), act_low=[-1.0], act_high=[1.0])
+
+        def __init__(self):
+            self.clocks = []
+
+        def set_task_clock(self, k0, prev):
+            self.clocks.append((k0, np.asarray(prev, np.float32).tolist()))
+    pol = CemMpc.__new__(CemMpc)
+    pol.task = TrackingTask(reference=np.zeros((3, 2), np.float32))
+    pol._clock = (0, None)
+    h = Handle()
+    pol._stage_clock(h)
+    assert pol._note_decision(np.array([0.5], np.float32)).tolist() == [0.5]
+    pol._stage_clock(h)
+    pol._note_decision(np.array([-0.25], np.float32))             # (a decision between two plans: nothing staged, the count moves)
+    pol._note_decision(np.array([0.125], np.float32))
+    pol._stage_clock(h)
+    assert h.clocks == [(0, [0.0]), (1, [0.5]), (3, [0.125])]
+    pol._kept, pol._kept_step, pol.warm_start, pol.shift_elites = None, 0, False, False
+    pol.reset()
+    pol._stage_clock(h)
+    assert h.clocks[-1] == (0, [0.0])
+    pol.task = QuadraticTask(q=1.0)
+    pol._stage_clock(h)
+    pol._note_decision(np.array([0.5], np.float32))
+    assert len(h.clocks) == 4 and pol._clock == (0, None)
+    pol.task = TrackingTask(reference=np.zeros((3, 2), np.float32))
+    with pytest.raises(ValueError, match='batch handle'):
+        pol.generate_actions(np.zeros((2, 2), np.float32))
+
+
+def test_the_closed_loop_reference_figures_are_the_references():
+    """The bars of tests/test_gpu_tracking_task.py's closed loop, measured here: the NumPy CEM of tracking_cases.reference_closed_loop,
+    seeds 0 .. 4, follows the sine with an RMS position error of at most REFERENCE_WORST_RMS over decisions 40 .. 79 and never moves
+    faster than REFERENCE_WORST_SPEED (the box is 1.0).  The yardstick is worth following: below a quarter of the error of not tracking
+    at all (0.212)."""
+    out = [tk.reference_closed_loop(s) for s in range(5)]
+    print('tracking closed-loop reference:', out)
+    worst = max(e for e, _ in out)
+    assert worst <= tk.REFERENCE_WORST_RMS and worst > 0.9 * tk.REFERENCE_WORST_RMS
+    assert max(v for _, v in out) <= tk.REFERENCE_WORST_SPEED < tc.VEL_BOX
+    assert tk.REFERENCE_WORST_RMS < 0.25 * tk.UNTRACKED_RMS
+    flat = np.zeros((tk.TRACK['steps'], 2))
+    assert abs(tk.rms_position_error(flat) - tk.UNTRACKED_RMS) < 1e-3

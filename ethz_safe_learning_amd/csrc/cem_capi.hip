@@ -10,6 +10,7 @@
 #include "cem_select_ranked.h"
 #include "cem_task_score.h"
 #include "cem_task_reference.h"
+#include "cem_task_zones.h"
 #include "cem_population.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
@@ -838,6 +839,11 @@ struct cem_planner {
                                              // [CEM_TASK_CLOCK_WORDS], then the reference table [ref_steps][CEM_U]
     TaskReferenceParams track;               // the tracking task as set: tab, ref, clock, T, r2, reward_goal, clip, rho, kappa
     std::vector<uint32_t> h_clock;           // host copy of the clock block: the source of its stream-ordered copies
+    // cem_planner_set_task_zones (cem_task_zones.h)
+    uint32_t *zones_dev;                     // a device allocation of the handle's own, one per enabling call: the zone table, then what a
+                                             // quadratic base task lacks of a tracking task: a clock block of zeros, the tables with q in qT's row, the row g
+    TaskZonesParams zones;                   // the task with its zones as set: the base task's tables and scalars, zones, n_zones
+    std::vector<float> h_task_tab;           // host copy of the task's tables as set: what a quadratic base's zones build theirs from
 };
 
 namespace {
@@ -879,6 +885,10 @@ size_t task_tab_floats() { return (size_t)CEM_TASK_TABLES * CEM_U; }
 float *task_traj(const cem_planner *h) { return h->task_dev + task_tab_floats(); }
 // the second part of the tracking allocation (cem_planner::track_dev)
 float *track_ref(uint32_t *dev) { return reinterpret_cast<float *>(dev + CEM_TASK_CLOCK_WORDS); }
+// the parts of the zones allocation (cem_planner::zones_dev), in words
+constexpr size_t kZoneTableWords = (size_t)CEM_TASK_MAX_ZONES * CEM_TASK_ZONE_WORDS;
+constexpr size_t kZoneClockAt = kZoneTableWords, kZoneTabAt = kZoneClockAt + CEM_TASK_CLOCK_WORDS;
+constexpr size_t kZoneRefAt = kZoneTabAt + (size_t)CEM_TASK_TABLES * CEM_U, kZoneWords = kZoneRefAt + CEM_U;
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
 size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
 float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
@@ -978,6 +988,7 @@ HandleFacts facts_of(const cem_planner *h, const PlanOptions &next)
     f.can_mix = launch_mix_action_noise && prepare_mix_action_noise; f.can_carry = launch_elite_keep && launch_elite_inject;
     f.can_mean = launch_mean_candidate != nullptr; f.can_track = launch_plan_track != nullptr; f.can_task = launch_task_score != nullptr;
     if (next.task == CEM_TASK_TRACKING) f.can_task = f.can_task && launch_task_reference != nullptr;   // (the kind's own kernel: cem_task_reference.h)
+    f.can_zones = launch_task_zones != nullptr;
     return f;
 }
 int admit_on(const cem_planner *h, const PlanOptions &next, PlanChange change = PLAN_CHANGE_OTHER) { return admit(facts_of(h, next), next, change); }
@@ -1022,6 +1033,7 @@ void release_handle(cem_planner *h)
     if (h->readout_dev) hipFree(h->readout_dev);
     if (h->task_dev) hipFree(h->task_dev);
     if (h->track_dev) hipFree(h->track_dev);
+    if (h->zones_dev) hipFree(h->zones_dev);
     if (h->pop_dev) hipFree(h->pop_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
@@ -1190,6 +1202,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->readout_dev = nullptr;
     h->task_dev = nullptr; h->task = TaskScoreParams{};
     h->track_dev = nullptr; h->track = TaskReferenceParams{}; h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
+    h->zones_dev = nullptr; h->zones = TaskZonesParams{};
     h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
@@ -1722,6 +1735,8 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
     if (rc.task) {
         const bool tracking = h->opt.task == CEM_TASK_TRACKING;  // the kind picks the kernel (cem_task_reference.h)
         if (tracking && !h->track_dev) return CEM_ERR_UNSUPPORTED;
+        const bool zoned = h->opt.zones != 0;                    // zones: the third kernel, whatever the kind (cem_task_zones.h)
+        if (zoned && !h->zones_dev) return CEM_ERR_UNSUPPORTED;
         auto filled = [&](auto tp) {
             tp.traj = rp.traj; tp.actions = rp.actions; tp.ctrl = rp.ctrl; tp.ret = rp.ret; tp.costs = rp.costs;
             tp.rows = d.Bloc; tp.N = d.N; tp.H = d.H; tp.O = d.O; tp.A = d.A; tp.variant = rp.variant; tp.check_done = 1;
@@ -1729,7 +1744,8 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
             return tp;
         };
         TimedLaunch timed_task(h, 2);
-        if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
+        if (zoned) { HIPCHK(launch_task_zones(filled(h->zones), h->stream)); }
+        else if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
         else { HIPCHK(launch_task_score(filled(h->task), h->stream)); }
     }
     if (whole_plan && rc.fold_reduce) return CEM_OK;
@@ -2546,6 +2562,7 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
     }
     if (h->in_plan) return CEM_ERR_STATE;
     PlanOptions next = options_of(h); next.task = trk ? (int)CEM_TASK_TRACKING : on ? (int)CEM_TASK_QUADRATIC : (int)CEM_TASK_SAFETY_GYM;
+    next.zones = 0;                                             // zones belong to the task they were set on (cem_planner_set_task_zones)
     { const int st = admit_on(h, next); if (st) return st; }
     // cem_unfold_sequences' element limit on the trajectory tensor
     const long long traj_floats = (long long)d.Bloc * (d.H + 1) * d.O;
@@ -2556,7 +2573,8 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
     if (trk) HIPCHK(made_trk.alloc(trk_host.size() * 4));         // (one per call: ref_steps is the call's)
     // Unconditional: an eager plan still draining behind its polled result may be reading the tables
     return commit_launch_change(h, next, true, [&]() -> int {
-        if (!on) return CEM_OK;
+        auto drop_zones = [&] { if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; } h->zones = TaskZonesParams{}; };   // (the stream is drained)
+        if (!on) { drop_zones(); return CEM_OK; }
         float *dev = made.p ? static_cast<float *>(made.p) : h->task_dev;
         if (trk) HIPCHK(hipMemcpy(made_trk.p, trk_host.data(), trk_host.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dev, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
@@ -2564,6 +2582,8 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
         if (made.p) HIPCHK(hipMemset(dev + task_tab_floats(), 0, (size_t)traj_floats * 4));
         if (made.p) h->task_dev = made.release<float>();
         tp.tab = h->task_dev;
+        drop_zones();
+        h->h_task_tab = tab;
         if (!trk) { h->task = tp; return CEM_OK; }
         // (the stream is drained: nothing reads the previous call's table or clock any more)
         if (h->track_dev) hipFree(h->track_dev);
@@ -2601,6 +2621,97 @@ int cem_planner_set_task_clock(cem_planner_t *h, int32_t k0, const float *prev_a
     return CEM_OK;
 }
 
+// The zones of the task in force (cem_task_zones.h).  What the kernel reads besides the zone table is the base task's: a tracking task's
+// own tables, reference and clock; for a quadratic task, which has no such things, a restatement of it as a tracking task inside the
+// zones' own allocation
+int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    const Dims &d = h->d;
+    if (!zones) {
+        if (h->in_plan) return CEM_ERR_STATE;
+        if (!h->opt.zones) return CEM_OK;                      // nothing to clear: the handle, its graph included, stays as it is
+        PlanOptions next = options_of(h); next.zones = 0;
+        return commit_launch_change(h, next, true, [&]() -> int {
+            if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; }
+            h->zones = TaskZonesParams{};
+            return CEM_OK;
+        });
+    }
+    // on the bit patterns: this file is built with -fno-honor-nans
+    auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+    auto finite = [&](float v) { return (bits(v) & 0x7fffffffu) < 0x7f800000u; };
+    auto below_zero = [&](float v) { return (bits(v) >> 31) != 0u && (bits(v) & 0x7fffffffu) != 0u; };
+    const int nz = zones->n_zones;
+    if (nz < 1 || nz > CEM_TASK_MAX_ZONES || !zones->axis || !zones->centre || !zones->weight || !zones->radius) return CEM_ERR_INVALID_ARG;
+    // the allocation as the kernel reads it; a zone from n_zones on has no axis and no penalty
+    std::vector<uint32_t> host(kZoneWords, 0u);
+    for (int z = 0; z < CEM_TASK_MAX_ZONES; ++z)
+        for (int a = 0; a < CEM_TASK_ZONE_AXES; ++a) host[(size_t)z * CEM_TASK_ZONE_WORDS + CEM_TASK_ZONE_ROW_AXIS + a] = 0xffffffffu;
+    for (int z = 0; z < nz; ++z) {
+        uint32_t *const w = &host[(size_t)z * CEM_TASK_ZONE_WORDS];
+        int used = 0;
+        for (int a = 0; a < CEM_TASK_ZONE_AXES; ++a) {
+            const int32_t ax = zones->axis[z * CEM_TASK_ZONE_AXES + a];
+            if (ax < -1 || ax >= d.O) return CEM_ERR_INVALID_ARG;
+            if (ax < 0) continue;
+            const float c = zones->centre[z * CEM_TASK_ZONE_AXES + a], wt = zones->weight[z * CEM_TASK_ZONE_AXES + a];
+            if (!finite(c) || !finite(wt) || below_zero(wt)) return CEM_ERR_INVALID_ARG;
+            w[CEM_TASK_ZONE_ROW_AXIS + a] = (uint32_t)ax; w[CEM_TASK_ZONE_ROW_CENTRE + a] = bits(c); w[CEM_TASK_ZONE_ROW_WEIGHT + a] = bits(wt);
+            ++used;
+        }
+        if (!used) return CEM_ERR_INVALID_ARG;
+        const float radius = zones->radius[z], margin = zones->margin ? zones->margin[z] : 0.f, penalty = zones->penalty ? zones->penalty[z] : 0.f;
+        const int32_t keep_in = zones->keep_in ? zones->keep_in[z] : 0;
+        if (!finite(radius) || !finite(margin) || !finite(penalty) || below_zero(margin) || below_zero(penalty)) return CEM_ERR_INVALID_ARG;
+        if ((bits(radius) >> 31) != 0u || (bits(radius) & 0x7fffffffu) == 0u) return CEM_ERR_INVALID_ARG;                    // radius <= 0
+        if (keep_in != 0 && keep_in != 1) return CEM_ERR_INVALID_ARG;
+        if (keep_in && margin > radius) return CEM_ERR_INVALID_ARG;
+        const float reach = keep_in ? radius - margin : radius + margin;
+        const float R2 = radius * radius, Rm2 = reach * reach;                              // fl32, each rounded once here
+        if (!finite(R2) || !finite(Rm2)) return CEM_ERR_INVALID_ARG;
+        w[CEM_TASK_ZONE_R2] = bits(R2); w[CEM_TASK_ZONE_RM2] = bits(Rm2); w[CEM_TASK_ZONE_PENALTY] = bits(penalty); w[CEM_TASK_ZONE_KEEP_IN] = (uint32_t)keep_in;
+    }
+    if (!h->opt.task || !h->task_dev || h->in_plan) return CEM_ERR_STATE;
+    const bool tracking = h->opt.task == CEM_TASK_TRACKING;
+    if (tracking && !h->track_dev) return CEM_ERR_STATE;
+    PlanOptions next = options_of(h); next.zones = nz;
+    { const int st = admit_on(h, next); if (st) return st; }
+    TaskZonesParams zp{};
+    zp.n_zones = nz;
+    if (tracking) {
+        const TaskReferenceParams &b = h->track;
+        std::memcpy(zp.rho, b.rho, sizeof zp.rho); std::memcpy(zp.kappa, b.kappa, sizeof zp.kappa);
+        zp.T = b.T; zp.r2 = b.r2; zp.reward_goal = b.reward_goal; zp.clip = b.clip;
+    } else {
+        // the quadratic task as a tracking task: qT = q, one reference row g, kappa = 0, the clock at (0, zeros)
+        if (h->h_task_tab.size() != task_tab_floats()) return CEM_ERR_STATE;
+        const TaskScoreParams &b = h->task;
+        std::memcpy(zp.rho, b.rho, sizeof zp.rho);
+        zp.T = 1; zp.r2 = b.r2; zp.reward_goal = b.reward_goal; zp.clip = b.clip;
+        std::memcpy(&host[kZoneTabAt], h->h_task_tab.data(), task_tab_floats() * 4);
+        std::memcpy(&host[kZoneTabAt + (size_t)CEM_TASK_REF_TAB_QT * CEM_U], &h->h_task_tab[(size_t)CEM_TASK_TAB_Q * CEM_U], (size_t)CEM_U * 4);
+        std::memcpy(&host[kZoneRefAt], &h->h_task_tab[(size_t)CEM_TASK_TAB_G * CEM_U], (size_t)CEM_U * 4);
+    }
+    // allocated before anything of the handle changes: a failed allocation leaves it as it was
+    DevBlock made;
+    HIPCHK(made.alloc(kZoneWords * 4));
+    // Unconditional: an eager plan still draining behind its polled result may be reading the previous zones
+    return commit_launch_change(h, next, true, [&]() -> int {
+        HIPCHK(hipMemcpy(made.p, host.data(), kZoneWords * 4, hipMemcpyHostToDevice));
+        if (h->zones_dev) hipFree(h->zones_dev);
+        h->zones_dev = made.release<uint32_t>();
+        zp.zones = h->zones_dev;
+        if (tracking) { zp.tab = h->track.tab; zp.ref = h->track.ref; zp.clock = h->track.clock; }
+        else {
+            zp.tab = reinterpret_cast<const float *>(h->zones_dev + kZoneTabAt); zp.ref = reinterpret_cast<const float *>(h->zones_dev + kZoneRefAt);
+            zp.clock = h->zones_dev + kZoneClockAt;
+        }
+        h->zones = zp;
+        return CEM_OK;
+    });
+}
+
 int cem_planner_task_trajectories(cem_planner_t *h, float *out_dev)
 {
     if (!h || !out_dev) return CEM_ERR_INVALID_ARG;
@@ -2622,6 +2733,8 @@ int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions
     if ((long long)n_rows * (horizon + 1) * d.O > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
     const bool tracking = h->opt.task == CEM_TASK_TRACKING;     // (with the handle's clock, as a plan)
     if (tracking && !h->track_dev) return CEM_ERR_STATE;
+    const bool zoned = h->opt.zones != 0;
+    if (zoned && !h->zones_dev) return CEM_ERR_STATE;
     auto filled = [&](auto tp) {
         tp.traj = traj_dev; tp.actions = actions_dev; tp.ctrl = nullptr; tp.ret = ret_out_dev;
         tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0; tp.costs = tp.variant ? costs_out_dev : nullptr;
@@ -2629,7 +2742,8 @@ int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions
         if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;  // (as in a plan: the cost objective's bytes are not masked by done)
         return tp;
     };
-    if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
+    if (zoned) { HIPCHK(launch_task_zones(filled(h->zones), h->stream)); }
+    else if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
     else { HIPCHK(launch_task_score(filled(h->task), h->stream)); }
     HIPCHK(hipStreamSynchronize(h->stream));
     return CEM_OK;

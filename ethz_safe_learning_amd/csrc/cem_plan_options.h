@@ -22,6 +22,8 @@ struct PlanOptions {
     int readout = 0;                         // cem_planner_set_plan_readout: 1 = cem_plan_track_kernel follows every select (cem_plan_readout.h)
     int task = 0;                            // cem_planner_set_task / _set_task_tracking: the kind; CEM_TASK_QUADRATIC puts cem_task_score_kernel behind a MODE 1 rollout
                                              // (cem_task_score.h), CEM_TASK_TRACKING cem_task_reference_kernel (cem_task_reference.h); admit() treats the two alike
+    int zones = 0;                           // cem_planner_set_task_zones: the number of zones on the task in force; not 0: cem_task_zones_kernel takes the task
+                                             // kernel's place (cem_task_zones.h); recipe and launch count are the base task plan's
     bool comm = false;                       // the handle has a communicator (cem_planner_comm_init; cem_capi.hip: options_of reads it off the handle)
 };
 
@@ -35,7 +37,7 @@ struct HandleFacts {
     long long budget_total_limit = 0;                  // H * m * kinds of a budget plan stays below it (cem_capi.hip: kBudgetTotalLimit)
     size_t refit_lds_bytes = 0, refit_lds_limit = 0;   // the weighted refit's dynamic LDS at this (k, H A) and what the device grants
     // the launchers of the optional translation units that are linked in
-    bool can_mix = false, can_carry = false, can_mean = false, can_track = false, can_task = false;
+    bool can_mix = false, can_carry = false, can_mean = false, can_track = false, can_task = false, can_zones = false;
 };
 
 // which call asks: only the inherited asymmetry below reads it
@@ -80,6 +82,9 @@ inline int admit(const HandleFacts &f, const PlanOptions &o, PlanChange change =
     // THE TASK SCORER reads every row's whole trajectory out of ONE buffer of a single-state, single-rank handle (cem_task_score.h): no
     // shard, no communicator, no batch handle, and the kernel itself
     if (o.task != 0 && (f.W > 1 || o.comm || f.batch || !f.can_task)) return CEM_ERR_UNSUPPORTED;
+    // ZONES need their kernel, which stands in for the task's own (cem_task_zones.h); that they sit on a task is the setters' business:
+    // cem_planner_set_task_zones wants one in force, cem_planner_set_task clears them
+    if (o.zones != 0 && !f.can_zones) return CEM_ERR_UNSUPPORTED;
     // THE INJECT'S ROWS are candidates of every iteration, and none of them is the mean candidate's (the last iteration's last row)
     if (carry) {
         for (int32_t n : o.pop) if (n <= o.elite.n_keep) return CEM_ERR_UNSUPPORTED;

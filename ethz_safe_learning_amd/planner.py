@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import hashlib
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace as _dc_replace
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -42,13 +42,102 @@ def _task_table(v, n, name):
 
 
 @dataclass
+class StateZones:
+    """Keep-out (or keep-in) zones on a task (cem_task_zones_t; cem_mpc.h "Zones"): up to 16 axis-aligned ellipsoids on up to 4 state
+    features each.  Zone z measures dist2 = sum_d weights[z, d] (s[axes[z, d]] - centre[z, d])^2 over its used axes (-1: unused).
+        keep-out: a state with dist2 <= radius^2 is a violation (a cost, as a state outside the box); the reward pays
+                  penalty * max((radius + margin)^2 - dist2, 0)
+        keep-in:  a state with dist2 > radius^2 is a violation; the reward pays penalty * max(dist2 - (radius - margin)^2, 0)
+    axes is [Z, D] (or [D]: one zone), D <= 4; centre and weights broadcast to it; radius, margin, penalty, keep_in to [Z].  Leaving
+    features out makes cylinders.  Set as `zones=` of a QuadraticTask or TrackingTask."""
+    axes: object = None
+    centre: object = 0.0
+    radius: object = 1.0
+    weights: object = 1.0
+    margin: object = 0.0
+    penalty: object = 0.0
+    keep_in: object = False
+
+    @classmethod
+    def discs(cls, features, centres, radii, margin=0.0, penalty=0.0, keep_in=False):
+        """Discs (spheres) on the same `features` (say, the x and y of the state): centres [Z, len(features)], radii [Z] or one for all."""
+        c = np.atleast_2d(np.asarray(centres, np.float32))
+        feats = np.asarray(features, np.int64).reshape(-1)
+        if c.shape[1] != feats.shape[0]:
+            raise ValueError('centres must be [Z, %d]' % feats.shape[0])
+        return cls(axes=np.broadcast_to(feats, c.shape).copy(), centre=c, radius=radii, margin=margin, penalty=penalty, keep_in=keep_in)
+
+    def tables(self, obs_dim):
+        """The tables as the library takes them, validated as it validates them: axis [Z, 4] int32, centre and weight [Z, 4] float32
+        (zero in unused slots), radius, margin, penalty [Z] float32, keep_in [Z] int32."""
+        K, ZMAX = _capi.CEM_TASK_ZONE_AXES, _capi.CEM_TASK_MAX_ZONES
+        ax = np.asarray(self.axes if self.axes is not None else (), np.int64)
+        if ax.ndim == 1:
+            ax = ax[None]
+        if ax.ndim != 2 or not 1 <= ax.shape[0] <= ZMAX or not 1 <= ax.shape[1] <= K:
+            raise ValueError('axes must be [Z, D] with 1 <= Z <= %d and 1 <= D <= %d' % (ZMAX, K))
+        Z, D = ax.shape
+        if (ax < -1).any() or (ax >= int(obs_dim)).any():
+            raise ValueError('an axis must be -1 or a feature below %d' % int(obs_dim))
+        if (ax < 0).all(axis=1).any():
+            raise ValueError('every zone needs a used axis')
+
+        def per_axis(v, name):
+            try:
+                a = np.broadcast_to(np.asarray(v, np.float32), (Z, D))
+            except ValueError:
+                raise ValueError('%s must broadcast to [%d, %d]' % (name, Z, D)) from None
+            out = np.zeros((Z, K), np.float32)
+            out[:, :D] = np.where(ax >= 0, a, np.float32(0))
+            return out
+
+        def per_zone(v, name, dtype=np.float32):
+            try:
+                return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (Z,)), dtype=dtype)
+            except ValueError:
+                raise ValueError('%s must be a scalar or have shape [%d]' % (name, Z)) from None
+        axis = np.full((Z, K), -1, np.int32)
+        axis[:, :D] = ax
+        out = {'axis': axis, 'centre': per_axis(self.centre, 'centre'), 'weight': per_axis(self.weights, 'weights'),
+               'radius': per_zone(self.radius, 'radius'), 'margin': per_zone(self.margin, 'margin'), 'penalty': per_zone(self.penalty, 'penalty')}
+        kin = np.asarray(self.keep_in)
+        if kin.dtype != np.bool_ and not np.isin(kin, (0, 1)).all():
+            raise ValueError('keep_in must be 0 / 1')
+        out['keep_in'] = per_zone(kin.astype(np.int32), 'keep_in', np.int32)
+        for k in ('centre', 'weight', 'radius', 'margin', 'penalty'):
+            if not np.isfinite(out[k]).all():
+                raise ValueError('%s must be finite' % k)
+        if (out['weight'] < 0).any() or (out['margin'] < 0).any() or (out['penalty'] < 0).any():
+            raise ValueError('weights, margin and penalty must be >= 0')
+        if (out['radius'] <= 0).any():
+            raise ValueError('radius must be > 0')
+        if ((out['keep_in'] != 0) & (out['margin'] > out['radius'])).any():
+            raise ValueError('a keep-in zone needs margin <= radius')
+        with np.errstate(all='ignore'):
+            reach = np.where(out['keep_in'] != 0, out['radius'] - out['margin'], out['radius'] + out['margin'])
+            if not (np.isfinite(out['radius'] * out['radius']).all() and np.isfinite(reach * reach).all()):
+                raise ValueError('radius and margin are too large')
+        return out
+
+
+def _zone_tables(task, obs_dim):
+    z = getattr(task, 'zones', None)
+    if z is None:
+        return None
+    if not isinstance(z, StateZones):
+        raise ValueError('zones must be a StateZones')
+    return z.tables(obs_dim)
+
+
+@dataclass
 class QuadraticTask:
     """A quadratic reward with box state constraints (cem_task_t, CEM_TASK_QUADRATIC; cem_mpc.h "Task scorers"): the objective of plans
     whose observation is no Safety-Gym lidar vector.  Per step, with s the raw state and a the action,
         reward = -sum_f [q_f (s'_f - g_f)^2 - c_f s'_f] - sum_j rho_j a_j^2 + reward_goal * near(s),   clipped to +-reward_clip (0: no clip)
         near(s) = goal_radius > 0 and sum_f goal_mask_f (s_f - g_f)^2 <= goal_radius^2             (near ends the episode, as the goal does)
         cost(s) = 1 if any s_f < lo_f or s_f > hi_f                                                  ('safe' / 'cost' handles)
-    Every table is an array of the feature count or a scalar broadcast to it."""
+    Every table is an array of the feature count or a scalar broadcast to it.  `zones` (a StateZones) adds round regions the state
+    must stay out of, or inside of: a hit is a cost as leaving the box is, coming near costs reward."""
     q: object = 0.0
     g: object = 0.0
     c: object = 0.0
@@ -59,20 +148,25 @@ class QuadraticTask:
     goal_radius: float = 0.0
     reward_goal: float = 0.0
     reward_clip: float = 0.0
+    zones: object = None
 
     @classmethod
-    def to_target(cls, target, weights=1.0, action_weights=0.0, lo=-np.inf, hi=np.inf, goal_radius=0.0, reward_goal=0.0, reward_clip=0.0):
+    def to_target(cls, target, weights=1.0, action_weights=0.0, lo=-np.inf, hi=np.inf, goal_radius=0.0, reward_goal=0.0, reward_clip=0.0, zones=None):
         """Stay near `target`: reward = -sum weights (s - target)^2 - sum action_weights a^2; with goal_radius > 0 the episode ends (and
         reward_goal is paid) within that weighted distance of the target, measured on the features whose weight is not zero."""
         w = np.asarray(weights, np.float32)
         return cls(q=w, g=target, goal_mask=(w != 0).astype(np.float32), lo=lo, hi=hi, rho=action_weights, goal_radius=goal_radius,
-                   reward_goal=reward_goal, reward_clip=reward_clip)
+                   reward_goal=reward_goal, reward_clip=reward_clip, zones=zones)
 
     def tables(self, obs_dim, act_dim):
         """The float32 tables as the library takes them: dict of q, g, c, goal_mask, lo, hi [obs_dim] and rho [act_dim]."""
         out = {k: _task_table(getattr(self, k), obs_dim, k) for k in ('q', 'g', 'c', 'goal_mask', 'lo', 'hi')}
         out['rho'] = _task_table(self.rho, act_dim, 'rho')
         return out
+
+    def zone_tables(self, obs_dim):
+        """StateZones.tables of `zones`, or None without zones."""
+        return _zone_tables(self, obs_dim)
 
 
 @dataclass
@@ -81,7 +175,7 @@ class TrackingTask:
     `reference` [T, obs_dim] takes g's place for the state that lies j - k0 steps into the plan (the last row is held), the last
     predicted state is weighted by `terminal_weights` (None: q) and every step pays sum_j action_rate_j (a_t[j] - a_{t-1}[j])^2 (None:
     nothing).  k0 and the action before the plan's first are the handle's clock (CemPlanner.set_task_clock; CemMpc keeps it).  The other
-    fields are QuadraticTask's."""
+    fields are QuadraticTask's, `zones` among them."""
     reference: object = None
     q: object = 0.0
     c: object = 0.0
@@ -94,15 +188,16 @@ class TrackingTask:
     reward_clip: float = 0.0
     terminal_weights: object = None
     action_rate: object = None
+    zones: object = None
 
     @classmethod
     def to_reference(cls, reference, weights=1.0, action_weights=0.0, terminal_weights=None, action_rate=None, lo=-np.inf, hi=np.inf,
-                     goal_radius=0.0, reward_goal=0.0, reward_clip=0.0):
+                     goal_radius=0.0, reward_goal=0.0, reward_clip=0.0, zones=None):
         """Follow `reference` [T, obs_dim]: reward = -sum weights (s - reference row)^2 - sum action_weights a^2 - the action-rate term;
         goal_radius as QuadraticTask.to_target's, measured against the row of the moment."""
         w = np.asarray(weights, np.float32)
         return cls(reference=reference, q=w, goal_mask=(w != 0).astype(np.float32), lo=lo, hi=hi, rho=action_weights, goal_radius=goal_radius,
-                   reward_goal=reward_goal, reward_clip=reward_clip, terminal_weights=terminal_weights, action_rate=action_rate)
+                   reward_goal=reward_goal, reward_clip=reward_clip, terminal_weights=terminal_weights, action_rate=action_rate, zones=zones)
 
     def tables(self, obs_dim, act_dim):
         """The float32 tables as the library takes them: QuadraticTask.tables' without g, q_terminal [obs_dim], action_rate [act_dim]
@@ -117,6 +212,10 @@ class TrackingTask:
             raise ValueError('reference must have shape [T, %d] with 1 <= T <= %d' % (O, _capi.CEM_TASK_REF_MAX_STEPS))
         out['reference'] = np.ascontiguousarray(ref)
         return out
+
+    def zone_tables(self, obs_dim):
+        """StateZones.tables of `zones`, or None without zones."""
+        return _zone_tables(self, obs_dim)
 
 
 @dataclass
@@ -169,8 +268,8 @@ class PlannerConfig:
                                        # cem_config_t: set after create
     task: Optional[object] = None      # None: the Safety-Gym scorer (the reference); a QuadraticTask: rollouts are scored by it
                                        # (cem_planner_set_task) and `scorer` is inert; a TrackingTask: by a reference that
-                                       # moves with the handle's clock (cem_planner_set_task_tracking); not in cem_config_t:
-                                       # set after create
+                                       # moves with the handle's clock (cem_planner_set_task_tracking); either with
+                                       # `zones`, a StateZones (cem_planner_set_task_zones); not in cem_config_t: set after create
     action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
@@ -860,12 +959,50 @@ class CemPlanner:
     def set_task(self, task=None):
         """Score rollouts by a QuadraticTask instead of the Safety-Gym scorer (cem_planner_set_task); None switches it off.  While on,
         every iteration launches the sampler, the MODE 1 rollout kernel and cem_task_score_kernel; rollout_path() is 'generic'.
-        Sticky; waits for the stream and re-captures the graph.  task_objective restates the kernel."""
+        Sticky; waits for the stream and re-captures the graph.  task_objective restates the kernel.  A task with `zones` has them
+        applied in the same call (cem_planner_set_task_zones: cem_task_zones_kernel then scores); a task without clears any."""
         if task is None:
             _capi.check(self.lib.cem_planner_set_task(self.h, None), 'cem_planner_set_task')
             self.task, self.task_clock = None, None
             return
         tb = task.tables(self.cfg.obs_dim, self.cfg.act_dim)      # (kept alive until the call returns: the library copies them)
+        zt = task.zone_tables(self.cfg.obs_dim)                   # (refused before anything of the handle changes)
+        self._set_task_base(task, tb)
+        if zt is not None:
+            # zones (cem_planner_set_task_zones): cem_task_zones_kernel in the task kernel's place; the objectives restate it
+            try:
+                self._set_task_zones(zt)
+            except Exception:
+                _capi.check(self.lib.cem_planner_set_task(self.h, None), 'cem_planner_set_task')     # (not half a task: none)
+                self.task, self.task_clock = None, None
+                raise
+
+    @property
+    def task_zones(self):
+        """The StateZones of the task in force, or None."""
+        return getattr(self.task, 'zones', None)
+
+    def set_task_zones(self, zones=None):
+        """The StateZones of the task in force (cem_planner_set_task_zones); None clears them.  Sticky until the next set_task; waits
+        for the stream and re-captures the graph."""
+        if zones is None:
+            _capi.check(self.lib.cem_planner_set_task_zones(self.h, None), 'cem_planner_set_task_zones')
+        else:
+            if not isinstance(zones, StateZones):
+                raise ValueError('zones must be a StateZones')
+            self._set_task_zones(zones.tables(self.cfg.obs_dim))
+        if self.task is not None:
+            self.task = _dc_replace(self.task, zones=zones)
+
+    def _set_task_zones(self, zt):
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        cz = _capi.CemTaskZones(n_zones=zt['axis'].shape[0], axis=zt['axis'].ctypes.data_as(ip), centre=zt['centre'].ctypes.data_as(fp),
+                                weight=zt['weight'].ctypes.data_as(fp), radius=zt['radius'].ctypes.data_as(fp),
+                                margin=zt['margin'].ctypes.data_as(fp), penalty=zt['penalty'].ctypes.data_as(fp),
+                                keep_in=zt['keep_in'].ctypes.data_as(ip))
+        _capi.check(self.lib.cem_planner_set_task_zones(self.h, C.byref(cz)), 'cem_planner_set_task_zones')
+
+    def _set_task_base(self, task, tb):
         fp = C.POINTER(C.c_float)
         if isinstance(task, TrackingTask):
             # a TrackingTask (cem_planner_set_task_tracking): the same launches with cem_task_reference_kernel behind the rollout;
@@ -1395,10 +1532,49 @@ def mean_candidate(actions, mu, lb, ub) -> np.ndarray:
     return out
 
 
-def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, return_done):
+def zone_terms(traj, zt):
+    """The zones' part of cem_task_zones_kernel (csrc/cem_task_zones.h), bit for bit: traj [rows, H + 1, O] float32, zt the tables of
+    StateZones.tables -> (hit [rows, H + 1] bool: the state hits a zone; pen [rows, H + 1] float32: the sixteen slots penalty * hinge
+    added pairwise, neighbours first; slots [rows, H + 1, 16] float32).  Every product, difference and sum is a float32 operation of its own."""
+    f = np.float32
+    tr = np.asarray(traj, f)
+    rows, H1, _ = tr.shape
+    Z = zt['axis'].shape[0]
+    slots = np.zeros((rows, H1, _capi.CEM_TASK_MAX_ZONES), f)
+    hit = np.zeros((rows, H1), bool)
+    with np.errstate(all='ignore'):
+        for z in range(Z):
+            dist2 = np.zeros((rows, H1), f)
+            for d in range(_capi.CEM_TASK_ZONE_AXES):
+                a = int(zt['axis'][z, d])
+                if a < 0:
+                    continue
+                e = tr[:, :, a] - zt['centre'][z, d]
+                dist2 = dist2 + zt['weight'][z, d] * (e * e)
+            radius, margin = zt['radius'][z], zt['margin'][z]
+            R2 = radius * radius
+            if zt['keep_in'][z]:
+                reach = radius - margin
+                Rm2 = reach * reach
+                hit |= dist2 > R2                                 # (a NaN compares false)
+                gap = dist2 - Rm2
+            else:
+                reach = radius + margin
+                Rm2 = reach * reach
+                hit |= dist2 <= R2
+                gap = Rm2 - dist2
+            hinge = np.where(np.isnan(dist2) | ~(gap > 0), f(0), gap).astype(f)
+            slots[:, :, z] = zt['penalty'][z] * hinge
+        acc = slots
+        for _ in range(4):
+            acc = acc[..., 0::2] + acc[..., 1::2]
+    return hit, acc[..., 0], slots
+
+
+def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, return_done, zt=None):
     """What task_objective and tracking_objective share, in the kernels' order: tb the [O] / [A] tables, ref [H + 1, O] the row every
     state is compared with (or [O]: one for all), q_terminal [O] the weights of the last state (None: q), rate [N, H] the action-rate
-    term of every step (None: the reward has no such term)."""
+    term of every step (None: the reward has no such term), zt the zone tables (None: no zones, and the code of a task without)."""
     f = np.float32
     if variant not in VARIANTS:
         raise ValueError("variant must be 'cem', 'safe' or 'cost'")
@@ -1432,6 +1608,10 @@ def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, ret
         r2 = f(task.goal_radius) * f(task.goal_radius)
         near = (nsum <= r2) & bool(r2 > 0) & (variant != 'cost')       # (the cost objective's bytes are not masked by done: near is never true)
         viol = ((tr < tb['lo']) | (tr > tb['hi'])).any(axis=2).astype(f)
+        pen = None
+        if zt is not None:                            # cem_task_zones_kernel: a hit is a violation, pen leaves the reward after v
+            hit, pen, _ = zone_terms(tr, zt)
+            viol = ((viol != 0) | hit).astype(f)
         u = np.zeros((N, H), f)
         for j in range(A):
             u = u + tb['rho'][j] * (act[:, :, j] * act[:, :, j])
@@ -1449,6 +1629,8 @@ def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, ret
             r = (-phi[:, t + 1]) - u[:, t]
             if v is not None:
                 r = r - v[:, t]
+            if pen is not None:
+                r = r - pen[:, t + 1]
             r = r + np.where(ga, f(1), f(0)) * f(task.reward_goal)
             r = np.fmin(np.fmax(r, -clip), clip)
             if safe:
@@ -1485,7 +1667,7 @@ def task_objective(traj, actions, task, variant='cem', return_done=False):
     A NaN return is stored as 0x7fc00000.  return_done=True appends the first step at which near held, int [rows] (H: never)."""
     tr, act = _task_arrays(traj, actions)
     tb = task.tables(tr.shape[2], act.shape[2])
-    return _task_objective(tr, act, tb, tb['g'], None, None, task, variant, return_done)
+    return _task_objective(tr, act, tb, tb['g'], None, None, task, variant, return_done, task.zone_tables(tr.shape[2]))
 
 
 def tracking_objective(traj, actions, task, variant='cem', k0=0, prev_action=None, return_done=False):
@@ -1509,7 +1691,7 @@ def tracking_objective(traj, actions, task, variant='cem', k0=0, prev_action=Non
         for j in range(A):
             e = act[:, :, j] - before[:, :, j]
             rate = rate + tb['action_rate'][j] * (e * e)
-    return _task_objective(tr, act, tb, ref, tb['q_terminal'], rate, task, variant, return_done)
+    return _task_objective(tr, act, tb, ref, tb['q_terminal'], rate, task, variant, return_done, task.zone_tables(tr.shape[2]))
 
 
 class PlanReadout(NamedTuple):

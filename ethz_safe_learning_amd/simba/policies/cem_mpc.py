@@ -74,6 +74,9 @@ With ``task=planner.TrackingTask(...)`` the set-point is a reference table that 
 its own and the change of the action is penalised (cem_mpc.h cem_planner_set_task_tracking).  The policy keeps the
 handle's clock: before every plan it sets it to (decisions since ``reset()``, the action it returned last) with a stream-ordered copy
 (the captured graph stays); the decisions between two plans of ``replan_every`` advance the count too; ``reset()`` puts back (0, zeros).
+Either task may carry ``zones=planner.StateZones(...)``: round regions of the state space the plan must stay out of (or inside of) — a
+state that hits one is a cost exactly as a state outside the box is, so ``SafeCemMpc``'s filter, budget, recovery and ``last_plan``'s
+cost counts see it, and coming within ``margin`` of one costs reward (cem_mpc.h cem_planner_set_task_zones).
 
 With ``replan_every=r``, 1 <= r <= horizon (which implies ``plan_readout``), ``generate_action`` plans at decisions 0, r, 2r, ... of an
 episode and in between returns step j of the kept sequence, plus ``noise_stddev`` times the output noise of that decision's own Philox

@@ -863,6 +863,51 @@ int cem_planner_set_task_tracking(cem_planner_t *h, const cem_task_t *base, cons
 int cem_planner_set_task_clock(cem_planner_t *h, int32_t k0, const float *prev_action /* [act_dim] or NULL: unchanged */);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Zones: keep-out and keep-in regions on a task.  Beyond the reference, off by default.  A task of either kind may
+ * carry up to CEM_TASK_MAX_ZONES zones: axis-aligned ellipsoids on up to CEM_TASK_ZONE_AXES state features each — discs, spheres,
+ * cylinders (features left out) — which the state must stay out of, or with keep_in inside of.  A state that hits a zone is a violation
+ * exactly as a state outside the box is; a state within `margin` of a zone pays `penalty` times a hinge.  A plan with zones launches what
+ * its base task plan launches, with the kernel of csrc/cem_task_zones.h, cem_task_zones_kernel, in the place of cem_task_score_kernel /
+ * cem_task_reference_kernel.  A task without zones launches what it launched and returns the bits it returned.
+ *
+ * Zone z: axis[z][d], d = 0 .. 3, a feature index or -1 (slot unused; at least one used), centre[z][d], weight[z][d] >= 0, radius[z] > 0,
+ * margin[z] >= 0, penalty[z] >= 0, keep_in[z] 0 / 1.  In fp32, every product, difference and sum rounded on its own:
+ *   dist2_z(s) starts at +0; for d = 0 .. 3 with a used axis:  e = s[axis] - centre;  dist2 = dist2 + weight * (e * e)
+ *   R2_z = fl32(radius * radius);  Rm2_z = fl32((radius + margin) * (radius + margin)), keep-in: fl32((radius - margin) * (radius - margin))
+ *   with margin <= radius; both rounded once by this call
+ *   keep-out:  hit_z = dist2 <= R2;  hinge_z = fmaxf(Rm2 - dist2, 0)          keep-in:  hit_z = dist2 > R2;  hinge_z = fmaxf(dist2 - Rm2, 0)
+ *   a NaN dist2 hits nothing and its hinge is 0
+ *   pen(s): sixteen slots, slot z = penalty_z * hinge_z, slots from n_zones on +0, added pairwise, neighbours first, over four levels
+ *   viol(s) = the box's viol(s) or any hit_z(s): the cost of step t is viol(s_t) * nd as before, in every variant
+ *   r = -phi(s_{t+1}) - u(a_t) - v_t - pen(s_{t+1}) + (near(s_t) ? reward_goal : 0), in that order; then the clip as before
+ * (v_t: a tracking task's action-rate term; a quadratic task has none).  planner.task_objective / tracking_objective restate it, bit for
+ * bit.  Zones that are never hit and have penalty 0 leave every result bit of the base task.
+ *
+ * cem_planner_set_task_zones copies the tables (they may be freed on return), allocates before it changes anything, waits for the
+ * stream and drops the captured graph, as cem_planner_set_task does.  zones NULL clears them (and is a no-op on a handle without any).
+ * cem_planner_set_task and cem_planner_set_task_tracking clear them too: set the task, then its zones.  cem_planner_set_task_clock,
+ * cem_planner_task_trajectories and cem_task_score serve a plan with zones as they serve its base task.
+ *   CEM_ERR_INVALID_ARG  null handle; n_zones outside 1 .. CEM_TASK_MAX_ZONES; axis, centre, weight or radius NULL; an axis < -1 or
+ *                        >= obs_dim; a zone without a used axis; a NaN or infinite entry; a weight, margin or penalty below 0; a
+ *                        radius <= 0; keep-in with margin > radius; a keep_in entry that is not 0 or 1
+ *   CEM_ERR_STATE        no task in force; between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  a library built without cem_task_zones_kernel
+ * A failed allocation returns CEM_ERR_HIP; the handle keeps its previous setting after any of these. */
+#define CEM_TASK_MAX_ZONES 16
+#define CEM_TASK_ZONE_AXES 4
+typedef struct {
+    int32_t n_zones;              /* 1 .. CEM_TASK_MAX_ZONES */
+    const int32_t *axis;          /* [n_zones][CEM_TASK_ZONE_AXES], host memory: feature indices, -1: unused */
+    const float *centre;          /* [n_zones][CEM_TASK_ZONE_AXES] (an unused slot's entry is not read) */
+    const float *weight;          /* [n_zones][CEM_TASK_ZONE_AXES] (an unused slot's entry is not read) */
+    const float *radius;          /* [n_zones] */
+    const float *margin;          /* [n_zones], or NULL: zeros */
+    const float *penalty;         /* [n_zones], or NULL: zeros */
+    const int32_t *keep_in;       /* [n_zones], or NULL: zeros (keep-out) */
+} cem_task_zones_t;
+int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones /* NULL: none */);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate

@@ -1,0 +1,330 @@
+"""Zones on a task (cem_planner_set_task_zones) without a GPU: the NumPy mirror of cem_task_zones_kernel against the
+contract in float64, what the contract says on its thresholds, the equalities with a task without zones, the C surface, the kernel's
+recorded resources and the closed loop's reference figures."""
+import ctypes as C
+import dataclasses
+import hashlib
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from ethz_safe_learning_amd import StateZones, _capi
+from ethz_safe_learning_amd.planner import PlannerConfig, QuadraticTask, ScorerConfig, TrackingTask, config_key, task_objective, tracking_objective, zone_terms
+from tests import helpers as hp
+from tests import task_cases as tc
+from tests import tracking_cases as tk
+from tests import zone_cases as zc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INVALID_ARG = 1
+U, F = np.uint32, np.float32
+
+
+def _objective(task, tr, act, variant, k0=0, prev=None, **kw):
+    if isinstance(task, TrackingTask):
+        return tracking_objective(tr, act, task, variant, k0=k0, prev_action=prev, **kw)
+    return task_objective(tr, act, task, variant, **kw)
+
+
+def _same(a, b):
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        if x is None or y is None:
+            assert x is None and y is None
+        else:
+            np.testing.assert_array_equal(x.view(U) if x.dtype == F else x, y.view(U) if y.dtype == F else y)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the C surface and the build
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_symbols_are_declared_exported_and_listed(built_lib):
+    hdr = open(os.path.join(ROOT, 'include', 'cem_mpc.h')).read()
+    assert re.search(r'^int cem_planner_set_task_zones\(', hdr, re.M)
+    assert 'cem_planner_set_task_zones' in _capi.EXPORTED_SYMBOLS and built_lib.cem_planner_set_task_zones is not None
+    assert re.search(r'#define CEM_TASK_MAX_ZONES 16\b', hdr) and _capi.CEM_TASK_MAX_ZONES == 16
+    assert re.search(r'#define CEM_TASK_ZONE_AXES 4\b', hdr) and _capi.CEM_TASK_ZONE_AXES == 4
+    assert [f[0] for f in _capi.CemTaskZones._fields_] == ['n_zones', 'axis', 'centre', 'weight', 'radius', 'margin', 'penalty', 'keep_in']
+    assert re.search(r'#define CEM_ABI_VERSION 4\b', hdr) and built_lib.cem_abi_version() == 4
+    mk = open(os.path.join(hp.CSRC, 'Makefile')).read()
+    assert mk.count('cem_task_zones.hip') == 2                                    # a prerequisite and a source of the one link line
+    assert built_lib.cem_planner_set_task_zones(None, None) == INVALID_ARG
+    assert built_lib.cem_planner_set_task_zones(None, C.byref(_capi.CemTaskZones(n_zones=1))) == INVALID_ARG
+
+
+def test_the_struct_compiles_as_c_and_the_tasks_keep_their_sizes(tmp_path):
+    cc = os.environ.get('CC', 'cc')
+    src = tmp_path / 'sz.c'
+    src.write_text('#include <stdio.h>\n#include "cem_mpc.h"\nint main(void) { cem_task_zones_t z = {0}; printf("%zu %zu %zu %d %d %d", '
+                   'sizeof(cem_task_t), sizeof(cem_task_tracking_t), sizeof z, z.n_zones, CEM_TASK_MAX_ZONES, CEM_TASK_ZONE_AXES); return 0; }\n')
+    exe = tmp_path / 'sz'
+    try:
+        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), '-o', str(exe), str(src)], check=True, capture_output=True)
+    except (OSError, subprocess.CalledProcessError) as e:
+        pytest.fail('the header must compile as plain C: %r' % (getattr(e, 'stderr', e),))
+    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
+    assert got == [C.sizeof(_capi.CemTask), C.sizeof(_capi.CemTaskTracking), C.sizeof(_capi.CemTaskZones), 0, 16, 4]
+    assert C.sizeof(_capi.CemTask) == 80                                          # (as before zones: eight pointers, a kind, three floats)
+
+
+@pytest.fixture(scope='module')
+def zones_isa():
+    """The device ISA of csrc/cem_task_zones.hip, the kernel's own translation unit, with the Makefile's flags.  Without the compiler
+    the test FAILS: the library these tests load was built by it."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    assert os.path.exists(hipcc), 'no hipcc at %s: the zones kernel cannot be compiled for its resource check' % hipcc
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(hp.CSRC)):
+        if f.endswith(('.h', '.hip')) or f == 'Makefile':
+            h.update(open(os.path.join(hp.CSRC, f), 'rb').read())
+    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
+    out = '/tmp/cem_task_zones_isa_%s.s' % h.hexdigest()[:16]
+    if not os.path.exists(out):
+        r = subprocess.run([hipcc] + hp.makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(hp.CSRC, 'cem_task_zones.hip')],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        os.replace(out + '.tmp', out)
+    return open(out).read()
+
+
+def test_the_kernel_has_no_spills_no_scratch_no_lds_and_the_recorded_registers(zones_isa):
+    meta = hp.kernel_meta(zones_isa, r'.', keys=('vgpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size',
+                                                 'group_segment_fixed_size'))
+    assert sorted({hp.kernel_function_name(n) for n in meta}) == ['cem_task_zones_kernel'], sorted(meta)      # the unit holds this one alone
+    assert len(meta) == 4                                                         # one / two quads per lane x 16-byte / element loads
+    golden = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'task_zones_resources.json')))
+    assert sorted(golden) == sorted(meta)
+    for name, d in meta.items():
+        print(name, d)
+        assert d['vgpr_spill_count'] == 0 and d['sgpr_spill_count'] == 0 and d['private_segment_fixed_size'] == 0, (name, d)
+        assert {'vgpr_count': d['vgpr_count'], 'group_segment_fixed_size': d['group_segment_fixed_size']} == golden[name], (name, d, golden[name])
+        assert d['group_segment_fixed_size'] == 0, (name, d)
+    # no fused multiply-add and no atomic in the unit
+    assert not re.search(r'\bv_(fma|fmac|mad|mac)_f(32|16)|\bv_pk_fma|atomic', zones_isa)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# StateZones
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_tables_broadcast_default_and_refuse():
+    z = StateZones(axes=[[0, 1], [2, -1]], centre=[[0.5, -0.5], [1.0, 7.0]], radius=[0.25, 0.5], penalty=2.0, keep_in=[False, True])
+    t = z.tables(3)
+    assert t['axis'].dtype == np.int32 and t['axis'].tolist() == [[0, 1, -1, -1], [2, -1, -1, -1]]
+    assert t['centre'].tolist() == [[0.5, -0.5, 0, 0], [1.0, 0, 0, 0]] and t['weight'].tolist() == [[1, 1, 0, 0], [1, 0, 0, 0]]
+    assert t['radius'].tolist() == [0.25, 0.5] and t['margin'].tolist() == [0, 0] and t['penalty'].tolist() == [2, 2] and t['keep_in'].tolist() == [0, 1]
+    one = StateZones(axes=[3, 1], centre=0.5, radius=1.0).tables(4)
+    assert one['axis'].tolist() == [[3, 1, -1, -1]] and one['centre'].tolist() == [[0.5, 0.5, 0, 0]]
+    d = StateZones.discs([0, 1], [[0.0, 0.0], [1.0, 2.0]], [0.5, 0.25], margin=0.1, penalty=3.0).tables(4)
+    assert d['axis'].tolist() == [[0, 1, -1, -1]] * 2 and d['centre'][1].tolist() == [1.0, 2.0, 0, 0] and d['radius'].tolist() == [0.5, 0.25]
+    assert np.allclose(d['margin'], 0.1) and d['penalty'].tolist() == [3, 3] and d['keep_in'].tolist() == [0, 0]
+    # what cem_planner_set_task_zones refuses, refused here
+    ok = dict(axes=[[0, 1]], centre=0.0, radius=1.0)
+    bad = [dict(ok, axes=None), dict(ok, axes=np.zeros((17, 1), int)), dict(ok, axes=[[0, 1, 2, 0, 1]]), dict(ok, axes=[[0, 3]]), dict(ok, axes=[[0, -2]]),
+           dict(ok, axes=[[-1, -1]]), dict(ok, centre=np.nan), dict(ok, centre=[[0.0, np.inf]]), dict(ok, weights=-1.0), dict(ok, weights=np.nan),
+           dict(ok, radius=0.0), dict(ok, radius=-1.0), dict(ok, radius=np.inf), dict(ok, margin=-0.1), dict(ok, penalty=-1.0), dict(ok, penalty=np.nan),
+           dict(ok, keep_in=True, margin=1.5), dict(ok, keep_in=2), dict(ok, radius=[1.0, 2.0]), dict(ok, centre=[[0.0, 0.0, 0.0]]), dict(ok, radius=1e30)]
+    StateZones(**ok).tables(3)
+    StateZones(**dict(ok, keep_in=True, margin=1.0)).tables(3)
+    for kw in bad:
+        with pytest.raises(ValueError):
+            StateZones(**kw).tables(3)
+    with pytest.raises(ValueError):
+        QuadraticTask(q=1.0, zones='a disc').zone_tables(3)
+
+
+def test_the_tasks_carry_zones_behind_everything_else():
+    z = StateZones.discs([0, 1], [[0.0, 0.0]], 0.5)
+    assert [f.name for f in dataclasses.fields(QuadraticTask)][-1] == 'zones' and [f.name for f in dataclasses.fields(TrackingTask)][-1] == 'zones'
+    q = QuadraticTask.to_target([1.0, 0.0, 0.0], zones=z)
+    t = TrackingTask.to_reference(np.zeros((2, 3), F), zones=z)
+    assert q.zones is z and t.zones is z and QuadraticTask().zones is None and QuadraticTask().zone_tables(3) is None
+    assert sorted(q.tables(3, 1)) == sorted(QuadraticTask.to_target([1.0, 0.0, 0.0]).tables(3, 1)) == ['c', 'g', 'goal_mask', 'hi', 'lo', 'q', 'rho']
+    assert 'zones' not in t.tables(3, 1) and q.zone_tables(3)['axis'].tolist() == [[0, 1, -1, -1]]
+    kw = dict(obs_dim=3, act_dim=1, ensemble_size=1, particles=1, n_samples=8, horizon=2, n_elite=2, iterations=1,
+              scorer=ScorerConfig(goal_slice=(0, 1)), act_low=[-1.0], act_high=[1.0])
+    keys = [config_key(PlannerConfig(task=x, **kw)) for x in (QuadraticTask(q=1.0), QuadraticTask(q=1.0, zones=z),
+                                                               QuadraticTask(q=1.0, zones=dataclasses.replace(z, penalty=1.0)))]
+    assert len(set(keys)) == 3 and all(hash(k) is not None for k in keys)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the mirror
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _cases():
+    """task_cases.SHAPES x three variants x both base kinds x two seeds, clip on and off in turn; random zones with margins and
+    penalties, the thresholds of the base task and of the zones cleared."""
+    for (O, A, H, rows, P) in zc.SHAPES:
+        for vi, variant in enumerate(('cem', 'safe', 'cost')):
+            for kind in ('quadratic', 'tracking'):
+                for seed in range(2):
+                    clip = (vi + seed) % 2 == 0
+                    tr, act = tc.random_case(O, A, H, rows, P, seed)
+                    if kind == 'quadratic':
+                        base, k0, prev = tc.task_for(O, A, seed, clip), 0, None
+                        clear = lambda x, b=base: tc.clear_thresholds(x, b)
+                    else:
+                        T, k0 = tk.clock_cases(H)[(vi + seed) % 5]
+                        base, prev = tk.tracking_task_for(O, A, T, seed, clip), tk.prev_action_for(A, seed)
+                        clear = lambda x, b=base, k=k0: tk.clear_thresholds(x, b, k)
+                    task = zc.with_zones(base, zc.random_zones(O, seed))
+                    zc.clear_zone_thresholds(tr, task, clear)
+                    yield (O, variant, kind, seed, clip), task, tr, act, variant, k0, prev
+
+
+def test_mirror_against_float64():
+    """The mirror against the contract in float64 (zone_cases.zones_f64).  No comparison operand lies within 1e-4 of its threshold
+    (asserted), so cost bytes and done steps are EQUAL; the bar on the returns is twice zone_cases.MIRROR_ERROR_MEASURED, the largest
+    relative distance measured over these cases on the CPU.  The zones are hit, and not everywhere; the penalty is paid, and not
+    everywhere."""
+    worst, seen = 0.0, set()
+    for what, task, tr, act, variant, k0, prev in _cases():
+        r64, c64, d64, margin = zc.zones_f64(tr, act, task, variant, k0, prev)
+        r32, c32, d32 = _objective(task, tr, act, variant, k0, prev, return_done=True)
+        assert margin > tc.NEAR, (what, margin)
+        assert r32.dtype == F and np.array_equal(d32, d64), what
+        if variant == 'cem':
+            assert c32 is None and c64 is None
+        else:
+            assert c32.dtype == np.uint8 and np.array_equal(c32, c64), what
+        hit, pen, _ = zone_terms(tr, task.zone_tables(tr.shape[2]))
+        if tr.shape[0] > 3:
+            assert hit.any() and not hit.all() and (pen > 0).any() and not (pen > 0).all(), what
+            base_costs = _objective(dataclasses.replace(task, zones=None), tr, act, variant, k0, prev)[1]
+            assert variant == 'cem' or c64.sum() > base_costs.sum(), what    # (hits reach the cost bytes)
+        seen.add((what[1], what[2]))
+        worst = max(worst, float((np.abs(r32.astype(np.float64) - r64) / np.maximum(1.0, np.abs(r64))).max()))
+    print('zones mirror against float64: largest relative distance %.3g' % worst)
+    assert len(seen) == 6
+    assert worst <= 2 * zc.MIRROR_ERROR_MEASURED, worst
+    assert worst > 0.5 * zc.MIRROR_ERROR_MEASURED, worst                          # (the recorded figure is this test's own)
+
+
+def test_every_new_term_moves_the_float64_statement_and_the_mirror_alike():
+    """The penalty, the margin, keep-in and a hit's cost byte each change the result, in the mirror as in the float64 statement."""
+    O, A, H, rows, P = zc.SHAPES[1]
+    tr, act = tc.random_case(O, A, H, rows, P, 0)
+    base = tc.task_for(O, A, 0, False)
+    z = zc.random_zones(O, 0)
+    zt = z.tables(O)
+    full = zc.with_zones(base, z)
+    changed = {'no penalty': dataclasses.replace(z, penalty=0.0), 'no margin': dataclasses.replace(z, margin=0.0),
+               'keep-in flipped': dataclasses.replace(z, keep_in=1 - zt['keep_in'], margin=np.minimum(zt['margin'], zt['radius']))}
+    r_full, c_full = task_objective(tr, act, full, 'cost')
+    for name, zz in changed.items():
+        t = zc.with_zones(base, zz)
+        r, c = task_objective(tr, act, t, 'cost')
+        r64, c64, _, _ = zc.zones_f64(tr, act, t, 'cost')
+        assert (r != r_full).mean() > 0.3, name
+        assert np.abs(r - r64).max() <= 1e-5 * np.abs(r64).max(), name
+        assert (c != c64).mean() < 1e-3, name                                     # (thresholds not cleared here)
+        assert name != 'keep-in flipped' or (c != c_full).mean() > 0.3
+    # a hit's cost byte: the zones without a penalty return the base task's returns and more cost bytes
+    r0, c0 = task_objective(tr, act, base, 'cost')
+    r1, c1 = task_objective(tr, act, zc.with_zones(base, changed['no penalty']), 'cost')
+    assert c1.sum() > c0.sum() and (c1 >= c0).all()
+    assert zc.zones_f64(tr, act, zc.with_zones(base, changed['no penalty']), 'cost')[1].sum() == c1.sum()
+
+
+@pytest.mark.parametrize('kind', ['quadratic', 'tracking'])
+def test_without_zones_and_with_idle_zones_the_bits_are_the_base_tasks(kind):
+    """zones None runs today's code; zones that are never entered and have penalty 0 subtract +0 and set no byte: every bit the same."""
+    for (O, A, H, rows, P) in zc.SHAPES:
+        for variant in ('cem', 'safe', 'cost'):
+            tr, act = tc.random_case(O, A, H, rows, P, 1)
+            if kind == 'quadratic':
+                base, k0, prev = tc.task_for(O, A, 1, True), 0, None
+                tc.craft(tr, base)
+            else:
+                base, k0, prev = tk.tracking_task_for(O, A, H + 1, 1, True), 1, tk.prev_action_for(A)
+                tk.craft(tr, act, base, k0, prev)
+            want = _objective(base, tr, act, variant, k0, prev, return_done=True)
+            assert base.zones is None
+            # a keep-out disc far from every state (|s| stays below 50), a keep-in ball that holds them all, both with a margin they stay out of
+            far = StateZones(axes=[[0, O - 1], [O - 1, 0]], centre=[[100.0, 100.0], [0.0, 0.0]], radius=[1.0, 1e3], margin=[1.0, 1.0], penalty=0.0,
+                             keep_in=[0, 1])
+            _same(_objective(zc.with_zones(base, far), tr, act, variant, k0, prev, return_done=True), want)
+            # with a penalty the second zone's hinge stays +0 (inside radius - margin), the first's too: still the same bits
+            _same(_objective(zc.with_zones(base, dataclasses.replace(far, penalty=5.0)), tr, act, variant, k0, prev, return_done=True), want)
+
+
+@pytest.mark.parametrize('kind', ['quadratic', 'tracking'])
+@pytest.mark.parametrize('shape', zc.SHAPES[1:], ids=lambda s: 'O%d' % s[0])
+def test_mirror_crafted_rows(shape, kind):
+    """What the contract says ON the thresholds (the kernel is held to the mirror bit for bit on the GPU)."""
+    O, A, H, rows, P = shape
+    base, g, k0, prev = zc.crafted_base(O, A, kind, H)
+    task, tr, act, n = zc.crafted_case(base, O, A, H, P, g)
+    zt = task.zone_tables(O)
+    hit, pen, slots = zone_terms(tr, zt)
+    assert (zt['axis'][zt['axis'] >= 0] >= 64).all() == (O > 64)                # at O = 100 the axes lie in the second quad
+    # keep-out: dist2 == R2 hits, one ulp of the state outside does not; both pay the margin's hinge
+    assert hit[n['out_exactly'], 1] and not hit[n['out_ulp_outside'], 1]
+    assert pen[n['out_exactly'], 1] == F(2.0) * (F(0.5625) - F(0.25)) and 0 < pen[n['out_ulp_outside'], 1] < pen[n['out_exactly'], 1]
+    # keep-in: dist2 == R2 is inside, one ulp beyond has left; hinge against (0.5 - 0.125)^2
+    assert not hit[n['in_exactly'], 1] and hit[n['in_ulp_outside'], 1]
+    assert pen[n['in_exactly'], 1] == F(3.0) * (F(0.25) - F(0.140625))
+    # inside the margin, outside the radius: a penalty and no cost
+    assert not hit[n['margin_only'], 1] and pen[n['margin_only'], 1] == F(2.0) * (F(0.5625) - F(0.390625))
+    # a NaN on an axis feature: no hit, no penalty
+    assert not hit[n['nan_axis']].any() and (pen[n['nan_axis']] == 0).all()
+    assert not hit[n['calm']].any() and (pen[n['calm']] == 0).all() and np.array_equal(pen[n['calm']].view(U), np.zeros(H + 1, U))
+    ret_s, cost_s, first = _objective(task, tr, act, 'safe', k0, prev, return_done=True)
+    ret_c, cost_c = _objective(task, tr, act, 'cost', k0, prev)
+    for costs in (cost_s, cost_c):
+        assert costs[1, n['out_exactly']] == 1 and costs[:, n['out_ulp_outside']].sum() == 0
+        assert costs[:, n['in_exactly']].sum() == 0 and costs[1, n['in_ulp_outside']] == 1
+        assert costs[:, n['margin_only']].sum() == 0 and costs[:, n['nan_axis']].sum() == 0 and costs[:, n['calm']].sum() == 0
+        assert costs[0, n['hit_at_0']] == 1 and costs[:, n['hit_at_0']].sum() == 1
+        assert costs[:, n['hit_at_H']].sum() == 0                                 # (no step's cost reads s_H)
+    # a hit after near: masked by done in 'safe', counted in 'cost'
+    assert first[n['hit_after_near']] == 0 and cost_s[:, n['hit_after_near']].sum() == 0 and cost_c[2, n['hit_after_near']] == 1
+    # the margin's penalty left the return: the same row without penalties returns more
+    free = zc.with_zones(base, dataclasses.replace(task.zones, penalty=0.0))
+    r_free = _objective(free, tr, act, 'cost', k0, prev)[0]
+    assert r_free[n['margin_only']] > ret_c[n['margin_only']] and r_free[n['calm']].view(U) == ret_c[n['calm']].view(U)
+    # an unused axis slot is not read: the same zones with the used axes moved to the front score the same bits
+    z = task.zones
+    packed = dataclasses.replace(z, axes=[[a for a in row if a >= 0] + [-1] * sum(a < 0 for a in row) for row in np.asarray(z.axes).tolist()],
+                                 centre=[[c for a, c in zip(ra, rc) if a >= 0] + [0.0] * sum(a < 0 for a in ra)
+                                         for ra, rc in zip(np.asarray(z.axes).tolist(), np.asarray(z.centre).tolist())])
+    assert packed.tables(O)['axis'].tolist() != zt['axis'].tolist()
+    _same(_objective(zc.with_zones(base, packed), tr, act, 'safe', k0, prev), (ret_s, cost_s))
+
+
+def test_sixteen_zones_are_added_pairwise():
+    """Sixteen active slots of mixed magnitude: pen is the pairwise tree's sum, and a left-to-right sum of the same slots differs."""
+    for O in (57, 100):
+        tr, _ = tc.random_case(O, 2, 7, 48, 3, 2)
+        tr = np.clip(tr, -2.0, 2.0)
+        zt = zc.sixteen_zones(O).tables(O)
+        hit, pen, slots = zone_terms(tr, zt)
+        assert (slots > 0).all() and slots.max() / slots.min() > 1e5
+        tree = slots
+        for _ in range(4):
+            tree = tree[..., 0::2] + tree[..., 1::2]
+        np.testing.assert_array_equal(pen.view(U), tree[..., 0].view(U))
+        left = np.zeros(pen.shape, F)
+        for z in range(16):
+            left = left + slots[..., z]
+        assert (left.view(U) != pen.view(U)).mean() > 0.3
+        assert np.abs(pen.astype(np.float64) - slots.astype(np.float64).sum(axis=2)).max() <= 1e-6 * pen.max()
+
+
+def test_the_closed_loop_reference_figures_are_the_references():
+    """The constants of tests/test_gpu_task_zones.py's closed loop, measured here with the NumPy CEM of zone_cases.reference_closed_loop
+    over seeds 0 .. 4: round the disc it never executes a state inside and ends within REFERENCE_WORST_STAGE_COST of the set-point;
+    the same loop without zones enters the disc on every seed."""
+    with_disc = [zc.reference_closed_loop(s) for s in range(5)]
+    without = [zc.reference_closed_loop(s, None) for s in range(5)]
+    print('zones closed-loop reference:', with_disc, without)
+    assert all(inside == 0 for _, inside, _ in with_disc)
+    assert all(closest > zc.DISC_RADIUS for _, _, closest in with_disc)
+    worst = max(c for c, _, _ in with_disc)
+    assert worst <= zc.REFERENCE_WORST_STAGE_COST and worst > 0.9 * zc.REFERENCE_WORST_STAGE_COST
+    assert min(inside for _, inside, _ in without) == zc.REFERENCE_FEWEST_INSIDE >= 1
+    assert zc.LOOP['N'] <= 256 and zc.LOOP['H'] <= 15 and zc.LOOP['I'] <= 4 and zc.LOOP['steps'] <= 80
+    assert zc.stage_cost(zc.START) > 1e3 * zc.REFERENCE_WORST_STAGE_COST         # (reaching the set-point is something)

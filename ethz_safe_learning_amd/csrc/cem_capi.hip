@@ -830,19 +830,19 @@ struct cem_planner {
     // cem_planner_set_plan_readout (cem_plan_readout.h)
     uint32_t *readout_dev;                   // a device allocation of the handle's own, made by the first enabling call: [slots] blocks of
                                              // CEM_READOUT_WORDS(H, A, P) words (the population never enters the size)
-    // cem_planner_set_task (cem_task_score.h)
+    // cem_planner_set_task (cem_task_score.h; the three kinds share cem_task_tile.h)
     float *task_dev;                         // a device allocation of the handle's own, made by the first enabling call: the tables
                                              // [CEM_TASK_TABLES][CEM_U], then the trajectories [Bloc][H + 1][O] of the last rollout launch
-    TaskScoreParams task;                    // the task as set: tab, r2, reward_goal, clip, rho (the launch fills in the rest)
+    TaskParams task;                         // the task as set: tab, r2, reward_goal, clip, rho (task_launch fills in the rest)
     // cem_planner_set_task_tracking (cem_task_reference.h)
     uint32_t *track_dev;                     // a device allocation of the handle's own, one per enabling call: the clock block
                                              // [CEM_TASK_CLOCK_WORDS], then the reference table [ref_steps][CEM_U]
-    TaskReferenceParams track;               // the tracking task as set: tab, ref, clock, T, r2, reward_goal, clip, rho, kappa
+    TaskParams track;                        // the tracking task as set: tab, ref, clock, T, r2, reward_goal, clip, rho, kappa
     std::vector<uint32_t> h_clock;           // host copy of the clock block: the source of its stream-ordered copies
     // cem_planner_set_task_zones (cem_task_zones.h)
     uint32_t *zones_dev;                     // a device allocation of the handle's own, one per enabling call: the zone table, then what a
                                              // quadratic base task lacks of a tracking task: a clock block of zeros, the tables with q in qT's row, the row g
-    TaskZonesParams zones;                   // the task with its zones as set: the base task's tables and scalars, zones, n_zones
+    TaskParams zones;                        // the task with its zones as set: the base task's tables and scalars, zones, n_zones
     std::vector<float> h_task_tab;           // host copy of the task's tables as set: what a quadratic base's zones build theirs from
 };
 
@@ -889,6 +889,25 @@ float *track_ref(uint32_t *dev) { return reinterpret_cast<float *>(dev + CEM_TAS
 constexpr size_t kZoneTableWords = (size_t)CEM_TASK_MAX_ZONES * CEM_TASK_ZONE_WORDS;
 constexpr size_t kZoneClockAt = kZoneTableWords, kZoneTabAt = kZoneClockAt + CEM_TASK_CLOCK_WORDS;
 constexpr size_t kZoneRefAt = kZoneTabAt + (size_t)CEM_TASK_TABLES * CEM_U, kZoneWords = kZoneRefAt + CEM_U;
+// The ONE scoring launch of the task in force, for a plan's rollout (enqueue_rollout) and for a caller's trajectories (cem_task_score):
+// `io` carries what differs between the two (traj, actions, ctrl, ret, costs, rows, N, H, check_done), the handle everything else;
+// `missing` is the status where the kind's or the zones' allocation is not there.  The kind picks the kernel, zones the third
+// whatever the kind (cem_task_tile.h)
+int task_launch(cem_planner *h, const TaskParams &io, int missing)
+{
+    const bool tracking = h->opt.task == CEM_TASK_TRACKING, zoned = h->opt.zones != 0;
+    if (tracking && !h->track_dev) return missing;
+    if (zoned && !h->zones_dev) return missing;
+    const Dims &d = h->d;
+    TaskParams tp = zoned ? h->zones : tracking ? h->track : h->task;
+    tp.traj = io.traj; tp.actions = io.actions; tp.ctrl = io.ctrl; tp.ret = io.ret; tp.costs = io.costs;
+    tp.rows = io.rows; tp.N = io.N; tp.H = io.H; tp.O = d.O; tp.A = d.A; tp.check_done = io.check_done;
+    tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0;
+    // compute_mean_costs has no done mask (safe_cem_mpc.py:98-108): near is never true and the cost bytes are not masked by done
+    if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;
+    HIPCHK((zoned ? launch_task_zones : tracking ? launch_task_reference : launch_task_score)(tp, h->stream));
+    return CEM_OK;
+}
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
 size_t elite_count_floats(const cem_planner *h) { return ((size_t)warm_slots(h) + 63) & ~(size_t)63; }
 float *elite_store(const cem_planner *h) { return h->elite_dev + elite_count_floats(h); }
@@ -1200,9 +1219,9 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->noise_dev = nullptr; h->noise_eps = nullptr; h->noise_floats = 0;
     h->elite_dev = nullptr; h->elite_cap = 0; h->elite_clear = false;
     h->readout_dev = nullptr;
-    h->task_dev = nullptr; h->task = TaskScoreParams{};
-    h->track_dev = nullptr; h->track = TaskReferenceParams{}; h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
-    h->zones_dev = nullptr; h->zones = TaskZonesParams{};
+    h->task_dev = nullptr; h->task = TaskParams{};
+    h->track_dev = nullptr; h->track = TaskParams{}; h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
+    h->zones_dev = nullptr; h->zones = TaskParams{};
     h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
@@ -1730,23 +1749,14 @@ int enqueue_rollout(cem_planner *h, int it, bool whole_plan)
     else if (queued) HIPCHK(launch_rollout_seg(v.rc, d.NFW, rp, queue_grid(), h->stream));
     else HIPCHK(launch_rollout<0>(v.rc, d.NFW, rp, nb * v.n_tiles, h->stream));
     timed.stop();
-    // the task's returns and cost bytes over the Safety-Gym ones the rollout has just written, in stream order (cem_task_score.h);
+    // the task's returns and cost bytes over the Safety-Gym ones the rollout has just written, in stream order (cem_task_tile.h);
     // timed with the reduce
     if (rc.task) {
-        const bool tracking = h->opt.task == CEM_TASK_TRACKING;  // the kind picks the kernel (cem_task_reference.h)
-        if (tracking && !h->track_dev) return CEM_ERR_UNSUPPORTED;
-        const bool zoned = h->opt.zones != 0;                    // zones: the third kernel, whatever the kind (cem_task_zones.h)
-        if (zoned && !h->zones_dev) return CEM_ERR_UNSUPPORTED;
-        auto filled = [&](auto tp) {
-            tp.traj = rp.traj; tp.actions = rp.actions; tp.ctrl = rp.ctrl; tp.ret = rp.ret; tp.costs = rp.costs;
-            tp.rows = d.Bloc; tp.N = d.N; tp.H = d.H; tp.O = d.O; tp.A = d.A; tp.variant = rp.variant; tp.check_done = 1;
-            if (cost_obj) tp.r2 = 0.f;                       // compute_mean_costs has no done mask (safe_cem_mpc.py:98-108): near is never true
-            return tp;
-        };
+        TaskParams io{};
+        io.traj = rp.traj; io.actions = rp.actions; io.ctrl = rp.ctrl; io.ret = rp.ret; io.costs = rp.costs;
+        io.rows = d.Bloc; io.N = d.N; io.H = d.H; io.check_done = 1;
         TimedLaunch timed_task(h, 2);
-        if (zoned) { HIPCHK(launch_task_zones(filled(h->zones), h->stream)); }
-        else if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
-        else { HIPCHK(launch_task_score(filled(h->task), h->stream)); }
+        { const int st = task_launch(h, io, CEM_ERR_UNSUPPORTED); if (st) return st; }
     }
     if (whole_plan && rc.fold_reduce) return CEM_OK;
 
@@ -2528,8 +2538,8 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
     auto is_nan = [&](float v) { return (bits(v) & 0x7fffffffu) > 0x7f800000u; };
     // the tables as the kernel reads them: [CEM_TASK_TABLES][CEM_U], the defaults beyond obs_dim and for a NULL table
     std::vector<float> tab(task_tab_floats(), 0.f);
-    TaskScoreParams tp{};
-    TaskReferenceParams rt{};
+    TaskParams tp{};
+    float kappa[CEM_MAX_ACT] = {};
     std::vector<uint32_t> trk_host;                            // the clock block at (0, zeros), then ref as the kernel reads it: [T][CEM_U], zero beyond obs_dim
     if (on) {
         const float inf = std::numeric_limits<float>::infinity();
@@ -2556,9 +2566,7 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
                 if (!finite(v)) return CEM_ERR_INVALID_ARG;
                 trk_host[CEM_TASK_CLOCK_WORDS + (size_t)j * CEM_U + f] = bits(v);
             }
-        for (int j = 0; trk->action_rate && j < d.A; ++j) { if (!finite(trk->action_rate[j])) return CEM_ERR_INVALID_ARG; rt.kappa[j] = trk->action_rate[j]; }
-        std::memcpy(rt.rho, tp.rho, sizeof rt.rho);
-        rt.T = trk->ref_steps; rt.r2 = tp.r2; rt.reward_goal = tp.reward_goal; rt.clip = tp.clip;
+        for (int j = 0; trk->action_rate && j < d.A; ++j) { if (!finite(trk->action_rate[j])) return CEM_ERR_INVALID_ARG; kappa[j] = trk->action_rate[j]; }
     }
     if (h->in_plan) return CEM_ERR_STATE;
     PlanOptions next = options_of(h); next.task = trk ? (int)CEM_TASK_TRACKING : on ? (int)CEM_TASK_QUADRATIC : (int)CEM_TASK_SAFETY_GYM;
@@ -2573,7 +2581,7 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
     if (trk) HIPCHK(made_trk.alloc(trk_host.size() * 4));         // (one per call: ref_steps is the call's)
     // Unconditional: an eager plan still draining behind its polled result may be reading the tables
     return commit_launch_change(h, next, true, [&]() -> int {
-        auto drop_zones = [&] { if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; } h->zones = TaskZonesParams{}; };   // (the stream is drained)
+        auto drop_zones = [&] { if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; } h->zones = TaskParams{}; };   // (the stream is drained)
         if (!on) { drop_zones(); return CEM_OK; }
         float *dev = made.p ? static_cast<float *>(made.p) : h->task_dev;
         if (trk) HIPCHK(hipMemcpy(made_trk.p, trk_host.data(), trk_host.size() * 4, hipMemcpyHostToDevice));
@@ -2588,8 +2596,9 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
         // (the stream is drained: nothing reads the previous call's table or clock any more)
         if (h->track_dev) hipFree(h->track_dev);
         h->track_dev = made_trk.release<uint32_t>();
-        rt.tab = tp.tab; rt.clock = h->track_dev; rt.ref = track_ref(h->track_dev);
-        h->track = rt;
+        h->track = tp;                                          // the quadratic task's fields, and the tracking task's own
+        std::memcpy(h->track.kappa, kappa, sizeof kappa);
+        h->track.T = trk->ref_steps; h->track.clock = h->track_dev; h->track.ref = track_ref(h->track_dev);
         h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
         return CEM_OK;
     });
@@ -2634,7 +2643,7 @@ int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
         PlanOptions next = options_of(h); next.zones = 0;
         return commit_launch_change(h, next, true, [&]() -> int {
             if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; }
-            h->zones = TaskZonesParams{};
+            h->zones = TaskParams{};
             return CEM_OK;
         });
     }
@@ -2677,20 +2686,14 @@ int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
     if (tracking && !h->track_dev) return CEM_ERR_STATE;
     PlanOptions next = options_of(h); next.zones = nz;
     { const int st = admit_on(h, next); if (st) return st; }
-    TaskZonesParams zp{};
+    TaskParams zp = tracking ? h->track : h->task;             // the base task as a whole: its tables, reference, clock and scalars
     zp.n_zones = nz;
-    if (tracking) {
-        const TaskReferenceParams &b = h->track;
-        std::memcpy(zp.rho, b.rho, sizeof zp.rho); std::memcpy(zp.kappa, b.kappa, sizeof zp.kappa);
-        zp.T = b.T; zp.r2 = b.r2; zp.reward_goal = b.reward_goal; zp.clip = b.clip;
-    } else {
-        // the quadratic task as a tracking task: qT = q, one reference row g, kappa = 0, the clock at (0, zeros)
+    if (!tracking) {
+        // the quadratic task as a tracking task: qT = q, one reference row g, kappa = 0 (as set_task left it), the clock at (0, zeros)
         if (h->h_task_tab.size() != task_tab_floats()) return CEM_ERR_STATE;
-        const TaskScoreParams &b = h->task;
-        std::memcpy(zp.rho, b.rho, sizeof zp.rho);
-        zp.T = 1; zp.r2 = b.r2; zp.reward_goal = b.reward_goal; zp.clip = b.clip;
+        zp.T = 1;
         std::memcpy(&host[kZoneTabAt], h->h_task_tab.data(), task_tab_floats() * 4);
-        std::memcpy(&host[kZoneTabAt + (size_t)CEM_TASK_REF_TAB_QT * CEM_U], &h->h_task_tab[(size_t)CEM_TASK_TAB_Q * CEM_U], (size_t)CEM_U * 4);
+        std::memcpy(&host[kZoneTabAt + (size_t)CEM_TASK_TAB_QT * CEM_U], &h->h_task_tab[(size_t)CEM_TASK_TAB_Q * CEM_U], (size_t)CEM_U * 4);
         std::memcpy(&host[kZoneRefAt], &h->h_task_tab[(size_t)CEM_TASK_TAB_G * CEM_U], (size_t)CEM_U * 4);
     }
     // allocated before anything of the handle changes: a failed allocation leaves it as it was
@@ -2702,8 +2705,7 @@ int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
         if (h->zones_dev) hipFree(h->zones_dev);
         h->zones_dev = made.release<uint32_t>();
         zp.zones = h->zones_dev;
-        if (tracking) { zp.tab = h->track.tab; zp.ref = h->track.ref; zp.clock = h->track.clock; }
-        else {
+        if (!tracking) {
             zp.tab = reinterpret_cast<const float *>(h->zones_dev + kZoneTabAt); zp.ref = reinterpret_cast<const float *>(h->zones_dev + kZoneRefAt);
             zp.clock = h->zones_dev + kZoneClockAt;
         }
@@ -2731,20 +2733,11 @@ int cem_task_score(cem_planner_t *h, const float *traj_dev, const float *actions
     const Dims &d = h->d;
     if (n_rows % d.P != 0) return CEM_ERR_INVALID_ARG;                 // reshape(cum, (particles, -1)) would raise (mpc_policy.py:38)
     if ((long long)n_rows * (horizon + 1) * d.O > 0x7fffffff00ll) return CEM_ERR_UNSUPPORTED;
-    const bool tracking = h->opt.task == CEM_TASK_TRACKING;     // (with the handle's clock, as a plan)
-    if (tracking && !h->track_dev) return CEM_ERR_STATE;
-    const bool zoned = h->opt.zones != 0;
-    if (zoned && !h->zones_dev) return CEM_ERR_STATE;
-    auto filled = [&](auto tp) {
-        tp.traj = traj_dev; tp.actions = actions_dev; tp.ctrl = nullptr; tp.ret = ret_out_dev;
-        tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0; tp.costs = tp.variant ? costs_out_dev : nullptr;
-        tp.rows = n_rows; tp.N = n_rows / d.P; tp.H = horizon; tp.O = d.O; tp.A = d.A; tp.check_done = 0;
-        if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;  // (as in a plan: the cost objective's bytes are not masked by done)
-        return tp;
-    };
-    if (zoned) { HIPCHK(launch_task_zones(filled(h->zones), h->stream)); }
-    else if (tracking) { HIPCHK(launch_task_reference(filled(h->track), h->stream)); }
-    else { HIPCHK(launch_task_score(filled(h->task), h->stream)); }
+    TaskParams io{};                                            // (a tracking task: with the handle's clock, as a plan)
+    io.traj = traj_dev; io.actions = actions_dev; io.ctrl = nullptr; io.ret = ret_out_dev;
+    io.costs = h->cfg.variant != CEM_VARIANT_CEM ? costs_out_dev : nullptr;
+    io.rows = n_rows; io.N = n_rows / d.P; io.H = horizon; io.check_done = 0;
+    { const int st = task_launch(h, io, CEM_ERR_STATE); if (st) return st; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return CEM_OK;
 }

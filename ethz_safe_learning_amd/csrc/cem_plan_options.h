@@ -21,7 +21,7 @@ struct PlanOptions {
     int mean_cand = 0;                       // cem_planner_set_mean_candidate: 1 = the last iteration's last candidate is the clipped mean
     int readout = 0;                         // cem_planner_set_plan_readout: 1 = cem_plan_track_kernel follows every select (cem_plan_readout.h)
     int task = 0;                            // cem_planner_set_task / _set_task_tracking: the kind; CEM_TASK_QUADRATIC puts cem_task_score_kernel behind a MODE 1 rollout
-                                             // (cem_task_score.h), CEM_TASK_TRACKING cem_task_reference_kernel (cem_task_reference.h); admit() treats the two alike
+                                             // (cem_task_score.h), CEM_TASK_TRACKING cem_task_reference_kernel (cem_task_reference.h): two kinds of one tile (cem_task_tile.h); admit() treats the two alike
     int zones = 0;                           // cem_planner_set_task_zones: the number of zones on the task in force; not 0: cem_task_zones_kernel takes the task
                                              // kernel's place (cem_task_zones.h); recipe and launch count are the base task plan's
     bool comm = false;                       // the handle has a communicator (cem_planner_comm_init; cem_capi.hip: options_of reads it off the handle)

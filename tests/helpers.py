@@ -36,6 +36,46 @@ def device_assembly():
     return open(out).read()
 
 
+def unit_assembly(unit_file_name):
+    """The device ISA of one translation unit of csrc (cem_task_score.hip, ...) as text, with the Makefile's flags, cached under /tmp
+    on the hash of the device sources as device_assembly's is.  Without the compiler the calling test FAILS: the library the tests
+    load was built by it."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    assert os.path.exists(hipcc), 'no hipcc at %s: %s cannot be compiled for its resource check' % (hipcc, unit_file_name)
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(('.h', '.hip')) or f == 'Makefile':
+            h.update(open(os.path.join(CSRC, f), 'rb').read())
+    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
+    out = '/tmp/%s_isa_%s.s' % (os.path.splitext(unit_file_name)[0], h.hexdigest()[:16])
+    if not os.path.exists(out):
+        r = subprocess.run([hipcc] + makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(CSRC, unit_file_name)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        os.replace(out + '.tmp', out)
+    return open(out).read()
+
+
+# What tests/golden/task_kernel_mnemonics.json counts per kernel: memory, LDS, DPP and lane-read instructions and all fp32 arithmetic.
+PINNED_MNEMONICS = r'^global_|^ds_|_dpp|^v_readlane|^v_readfirstlane|^v_\w+_f32'
+
+
+def mnemonic_counts(body):
+    """{'total': instructions, 'counts': {mnemonic: n}} of a kernel's instruction lines (kernel_bodies), the mnemonics that match
+    PINNED_MNEMONICS."""
+    counts = {}
+    for line in body:
+        m = line.split()[0]
+        if re.search(PINNED_MNEMONICS, m):
+            counts[m] = counts.get(m, 0) + 1
+    return {'total': len(body), 'counts': dict(sorted(counts.items()))}
+
+
+def template_instance(mangled):
+    """_Z21cem_task_zones_kernelILi1ELb0EEv10TaskParams -> 'cem_task_zones_kernel<1, false>' (an <int, bool> kernel template)."""
+    m = re.search(r'ILi(\d+)ELb([01])EE', mangled)
+    return '%s<%s, %s>' % (kernel_function_name(mangled), m.group(1), 'true' if m.group(2) == '1' else 'false')
+
 
 def kernel_bodies(isa, pattern):
     """{mangled name: [instruction lines]} of the kernels whose name matches."""

@@ -2,7 +2,6 @@
 the calls refuse without a handle, the NumPy mirror planner.task_objective against a plain float64 evaluation of the contract, the
 kernel's code-object metadata, the option rule and the policies' constructor default."""
 import ctypes as C
-import hashlib
 import inspect
 import os
 import re
@@ -145,22 +144,9 @@ def test_mirror_crafted_thresholds():
 
 @pytest.fixture(scope='module')
 def task_isa():
-    """The device ISA of csrc/cem_task_score.hip, the kernel's own translation unit, with the Makefile's flags (cached like
-    helpers.device_assembly).  Without the compiler the test FAILS: the library these tests load was built by it."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    assert os.path.exists(hipcc), 'no hipcc at %s: the task scorer cannot be compiled for its resource check' % hipcc
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(hp.CSRC)):
-        if f.endswith(('.h', '.hip')) or f == 'Makefile':
-            h.update(open(os.path.join(hp.CSRC, f), 'rb').read())
-    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
-    out = '/tmp/cem_task_isa_%s.s' % h.hexdigest()[:16]
-    if not os.path.exists(out):
-        r = subprocess.run([hipcc] + hp.makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(hp.CSRC, 'cem_task_score.hip')],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(out + '.tmp', out)
-    return open(out).read()
+    """The device ISA of csrc/cem_task_score.hip, the kernel's own translation unit (helpers.unit_assembly: without the compiler the
+    test FAILS)."""
+    return hp.unit_assembly('cem_task_score.hip')
 
 
 def test_the_kernel_has_no_spills_no_scratch_no_lds_and_no_atomics(task_isa):

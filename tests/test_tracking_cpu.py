@@ -4,7 +4,6 @@ evaluation of the contract and against planner.task_objective where the two cont
 cache key, the policies' clock and the closed loop's yardstick."""
 import ctypes as C
 import dataclasses
-import hashlib
 import json
 import os
 import re
@@ -217,22 +216,9 @@ def test_mirror_crafted_rows():
 
 @pytest.fixture(scope='module')
 def reference_isa():
-    """The device ISA of csrc/cem_task_reference.hip, the kernel's own translation unit, with the Makefile's flags (cached like
-    helpers.device_assembly).  Without the compiler the test FAILS: the library these tests load was built by it."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    assert os.path.exists(hipcc), 'no hipcc at %s: the tracking task cannot be compiled for its resource check' % hipcc
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(hp.CSRC)):
-        if f.endswith(('.h', '.hip')) or f == 'Makefile':
-            h.update(open(os.path.join(hp.CSRC, f), 'rb').read())
-    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
-    out = '/tmp/cem_task_reference_isa_%s.s' % h.hexdigest()[:16]
-    if not os.path.exists(out):
-        r = subprocess.run([hipcc] + hp.makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(hp.CSRC, 'cem_task_reference.hip')],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(out + '.tmp', out)
-    return open(out).read()
+    """The device ISA of csrc/cem_task_reference.hip, the kernel's own translation unit (helpers.unit_assembly: without the compiler
+    the test FAILS)."""
+    return hp.unit_assembly('cem_task_reference.hip')
 
 
 def test_the_kernel_has_no_spills_no_scratch_and_the_recorded_registers(reference_isa):

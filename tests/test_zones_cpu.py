@@ -3,7 +3,6 @@ contract in float64, what the contract says on its thresholds, the equalities wi
 recorded resources and the closed loop's reference figures."""
 import ctypes as C
 import dataclasses
-import hashlib
 import json
 import os
 import re
@@ -73,22 +72,9 @@ def test_the_struct_compiles_as_c_and_the_tasks_keep_their_sizes(tmp_path):
 
 @pytest.fixture(scope='module')
 def zones_isa():
-    """The device ISA of csrc/cem_task_zones.hip, the kernel's own translation unit, with the Makefile's flags.  Without the compiler
-    the test FAILS: the library these tests load was built by it."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    assert os.path.exists(hipcc), 'no hipcc at %s: the zones kernel cannot be compiled for its resource check' % hipcc
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(hp.CSRC)):
-        if f.endswith(('.h', '.hip')) or f == 'Makefile':
-            h.update(open(os.path.join(hp.CSRC, f), 'rb').read())
-    h.update(open(os.path.join(ROOT, 'include', 'cem_mpc.h'), 'rb').read())
-    out = '/tmp/cem_task_zones_isa_%s.s' % h.hexdigest()[:16]
-    if not os.path.exists(out):
-        r = subprocess.run([hipcc] + hp.makefile_flags() + ['-S', '--cuda-device-only', '-o', out + '.tmp', os.path.join(hp.CSRC, 'cem_task_zones.hip')],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        os.replace(out + '.tmp', out)
-    return open(out).read()
+    """The device ISA of csrc/cem_task_zones.hip, the kernel's own translation unit (helpers.unit_assembly: without the compiler the
+    test FAILS)."""
+    return hp.unit_assembly('cem_task_zones.hip')
 
 
 def test_the_kernel_has_no_spills_no_scratch_no_lds_and_the_recorded_registers(zones_isa):

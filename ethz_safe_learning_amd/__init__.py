@@ -4,7 +4,7 @@ yardenas/ethz-safe-learning ("simba") as fused gfx950 HIP kernels behind a C ABI
 
 Importing this package never touches the GPU and never imports ``oracle/``.
 """
-from .planner import BatchCemPlanner, CemPlanner, PlannerConfig, QuadraticTask, ScorerConfig, StateZones, TrackingTask, flatten_weights, pack_weights_host, plan_tiles, risk_particles, sampling_params  # noqa: F401
+from .planner import BatchCemPlanner, CemPlanner, PlannerConfig, QuadraticTask, ScorerConfig, StateZones, TaskOutputs, TrackingTask, flatten_weights, pack_weights_host, plan_tiles, risk_particles, sampling_params  # noqa: F401
 
-__all__ = ['BatchCemPlanner', 'CemPlanner', 'PlannerConfig', 'QuadraticTask', 'ScorerConfig', 'StateZones', 'TrackingTask', 'flatten_weights', 'pack_weights_host', 'plan_tiles',
+__all__ = ['BatchCemPlanner', 'CemPlanner', 'PlannerConfig', 'QuadraticTask', 'ScorerConfig', 'StateZones', 'TaskOutputs', 'TrackingTask', 'flatten_weights', 'pack_weights_host', 'plan_tiles',
            'risk_particles', 'sampling_params']

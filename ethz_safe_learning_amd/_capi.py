@@ -26,6 +26,7 @@ CEM_TASK_SAFETY_GYM, CEM_TASK_QUADRATIC = 0, 1                  # enum cem_task_
 CEM_TASK_TRACKING = 2                                           # its third value (cem_planner_set_task_tracking)
 CEM_TASK_REF_MAX_STEPS = 16384
 CEM_TASK_MAX_ZONES, CEM_TASK_ZONE_AXES = 16, 4                   # cem_planner_set_task_zones
+CEM_TASK_MAX_OUTPUTS = 16                                       # cem_planner_set_task_outputs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CEM_MPC_LIB') or os.path.join(_HERE, 'lib', 'libcem_mpc_gfx950.so')   # env override: A/B builds
@@ -48,7 +49,7 @@ EXPORTED_SYMBOLS = [
     'cem_planner_set_mean_candidate', 'cem_planner_get_mean_candidate',
     'cem_planner_set_plan_readout', 'cem_planner_get_plan_readout', 'cem_planner_plan_readout',
     'cem_planner_set_task', 'cem_planner_task_trajectories', 'cem_task_score',
-    'cem_planner_set_task_tracking', 'cem_planner_set_task_clock', 'cem_planner_set_task_zones',
+    'cem_planner_set_task_tracking', 'cem_planner_set_task_clock', 'cem_planner_set_task_zones', 'cem_planner_set_task_outputs',
     'cem_trainer_workspace_bytes', 'cem_trainer_blob_floats', 'cem_trainer_create', 'cem_trainer_destroy', 'cem_trainer_set_state',
     'cem_trainer_get_state', 'cem_trainer_weights_dev', 'cem_trainer_step', 'cem_trainer_steps', 'cem_trainer_eval', 'cem_trainer_forward',
 ]
@@ -117,6 +118,11 @@ class CemTaskTracking(C.Structure):
 class CemTaskZones(C.Structure):
     _fields_ = [('n_zones', C.c_int32), ('axis', C.POINTER(C.c_int32)), ('centre', C.POINTER(C.c_float)), ('weight', C.POINTER(C.c_float)),
                 ('radius', C.POINTER(C.c_float)), ('margin', C.POINTER(C.c_float)), ('penalty', C.POINTER(C.c_float)), ('keep_in', C.POINTER(C.c_int32))]
+
+
+class CemTaskOutputs(C.Structure):
+    _fields_ = [('n_outputs', C.c_int32)] + [(n, C.POINTER(C.c_float)) for n in ('matrix', 'weight', 'target', 'linear', 'near', 'lo', 'hi', 'terminal')] + \
+               [('ref_rows', C.c_int32), ('reference', C.POINTER(C.c_float))]
 
 
 class CemLayout(C.Structure):
@@ -237,6 +243,7 @@ def load():
     lib.cem_planner_set_task_tracking.argtypes = [vp, C.POINTER(CemTask), C.POINTER(CemTaskTracking)]
     lib.cem_planner_set_task_clock.argtypes = [vp, C.c_int32, vp]
     lib.cem_planner_set_task_zones.argtypes = [vp, C.POINTER(CemTaskZones)]
+    lib.cem_planner_set_task_outputs.argtypes = [vp, C.POINTER(CemTaskOutputs)]
     tcfgp = C.POINTER(CemTrainConfig)
     for f in ('cem_trainer_workspace_bytes', 'cem_trainer_blob_floats'):
         getattr(lib, f).restype = C.c_size_t

@@ -11,6 +11,7 @@
 #include "cem_task_score.h"
 #include "cem_task_reference.h"
 #include "cem_task_zones.h"
+#include "cem_task_outputs.h"
 #include "cem_population.h"
 #include "cem_train.h"
 #include "cem_train_tile.h"
@@ -844,6 +845,10 @@ struct cem_planner {
                                              // quadratic base task lacks of a tracking task: a clock block of zeros, the tables with q in qT's row, the row g
     TaskParams zones;                        // the task with its zones as set: the base task's tables and scalars, zones, n_zones
     std::vector<float> h_task_tab;           // host copy of the task's tables as set: what a quadratic base's zones build theirs from
+    // cem_planner_set_task_outputs (cem_task_outputs.h)
+    uint32_t *outs_dev;                      // a device allocation of the handle's own, one per enabling call: C, the outputs' tables and reference, an
+                                             // empty zone table, then (as zones_dev) what a quadratic base task lacks of a tracking task
+    TaskParams outs;                         // the task with its outputs as set and no zones: what cem_planner_set_task_zones builds on while outputs are in force
 };
 
 namespace {
@@ -889,23 +894,28 @@ float *track_ref(uint32_t *dev) { return reinterpret_cast<float *>(dev + CEM_TAS
 constexpr size_t kZoneTableWords = (size_t)CEM_TASK_MAX_ZONES * CEM_TASK_ZONE_WORDS;
 constexpr size_t kZoneClockAt = kZoneTableWords, kZoneTabAt = kZoneClockAt + CEM_TASK_CLOCK_WORDS;
 constexpr size_t kZoneRefAt = kZoneTabAt + (size_t)CEM_TASK_TABLES * CEM_U, kZoneWords = kZoneRefAt + CEM_U;
+// the parts of the outputs allocation (cem_planner::outs_dev), in words: C, the outputs' tables, then the zones allocation's layout (an
+// empty zone table; a quadratic base's restatement), then the outputs' reference [ref_rows][CEM_TASK_MAX_OUTPUTS]
+constexpr size_t kOutTabAt = (size_t)CEM_TASK_MAX_OUTPUTS * CEM_U, kOutZoneAt = kOutTabAt + (size_t)CEM_TASK_OUT_TABLES * CEM_TASK_MAX_OUTPUTS;
+constexpr size_t kOutRefAt = kOutZoneAt + kZoneWords;
 // The ONE scoring launch of the task in force, for a plan's rollout (enqueue_rollout) and for a caller's trajectories (cem_task_score):
 // `io` carries what differs between the two (traj, actions, ctrl, ret, costs, rows, N, H, check_done), the handle everything else;
 // `missing` is the status where the kind's or the zones' allocation is not there.  The kind picks the kernel, zones the third
 // whatever the kind (cem_task_tile.h)
 int task_launch(cem_planner *h, const TaskParams &io, int missing)
 {
-    const bool tracking = h->opt.task == CEM_TASK_TRACKING, zoned = h->opt.zones != 0;
+    const bool tracking = h->opt.task == CEM_TASK_TRACKING, zoned = h->opt.zones != 0, outs = h->opt.outputs != 0;
     if (tracking && !h->track_dev) return missing;
     if (zoned && !h->zones_dev) return missing;
+    if (outs && !h->outs_dev) return missing;
     const Dims &d = h->d;
-    TaskParams tp = zoned ? h->zones : tracking ? h->track : h->task;
+    TaskParams tp = zoned ? h->zones : outs ? h->outs : tracking ? h->track : h->task;
     tp.traj = io.traj; tp.actions = io.actions; tp.ctrl = io.ctrl; tp.ret = io.ret; tp.costs = io.costs;
     tp.rows = io.rows; tp.N = io.N; tp.H = io.H; tp.O = d.O; tp.A = d.A; tp.check_done = io.check_done;
     tp.variant = h->cfg.variant != CEM_VARIANT_CEM ? 1 : 0;
     // compute_mean_costs has no done mask (safe_cem_mpc.py:98-108): near is never true and the cost bytes are not masked by done
     if (h->cfg.variant == CEM_VARIANT_COST) tp.r2 = 0.f;
-    HIPCHK((zoned ? launch_task_zones : tracking ? launch_task_reference : launch_task_score)(tp, h->stream));
+    HIPCHK((outs ? launch_task_outputs : zoned ? launch_task_zones : tracking ? launch_task_reference : launch_task_score)(tp, h->stream));
     return CEM_OK;
 }
 int32_t *elite_counts(const cem_planner *h) { return reinterpret_cast<int32_t *>(h->elite_dev); }
@@ -1008,6 +1018,7 @@ HandleFacts facts_of(const cem_planner *h, const PlanOptions &next)
     f.can_mean = launch_mean_candidate != nullptr; f.can_track = launch_plan_track != nullptr; f.can_task = launch_task_score != nullptr;
     if (next.task == CEM_TASK_TRACKING) f.can_task = f.can_task && launch_task_reference != nullptr;   // (the kind's own kernel: cem_task_reference.h)
     f.can_zones = launch_task_zones != nullptr;
+    f.can_outputs = launch_task_outputs != nullptr;
     return f;
 }
 int admit_on(const cem_planner *h, const PlanOptions &next, PlanChange change = PLAN_CHANGE_OTHER) { return admit(facts_of(h, next), next, change); }
@@ -1053,6 +1064,7 @@ void release_handle(cem_planner *h)
     if (h->task_dev) hipFree(h->task_dev);
     if (h->track_dev) hipFree(h->track_dev);
     if (h->zones_dev) hipFree(h->zones_dev);
+    if (h->outs_dev) hipFree(h->outs_dev);
     if (h->pop_dev) hipFree(h->pop_dev);
     if (h->cstat_obj) hipFree(h->cstat_obj);
     if (h->own_stream) hipStreamDestroy(h->stream);
@@ -1222,6 +1234,7 @@ static int planner_create(const cem_config_t *cfg, int32_t mb, void *workspace, 
     h->task_dev = nullptr; h->task = TaskParams{};
     h->track_dev = nullptr; h->track = TaskParams{}; h->h_clock.assign(CEM_TASK_CLOCK_WORDS, 0u);
     h->zones_dev = nullptr; h->zones = TaskParams{};
+    h->outs_dev = nullptr; h->outs = TaskParams{};
     h->pop_dev = nullptr; h->pop_seg_flags = nullptr; h->pop_seg_state = nullptr; h->pop_n_ready = 0;
     h->h_budget.assign(nb, std::numeric_limits<float>::infinity());
     h->comm = nullptr; h->plans_since_comm = 0; h->graph_failed = false;
@@ -2571,6 +2584,7 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
     if (h->in_plan) return CEM_ERR_STATE;
     PlanOptions next = options_of(h); next.task = trk ? (int)CEM_TASK_TRACKING : on ? (int)CEM_TASK_QUADRATIC : (int)CEM_TASK_SAFETY_GYM;
     next.zones = 0;                                             // zones belong to the task they were set on (cem_planner_set_task_zones)
+    next.outputs = 0;                                           // ... and so do outputs (cem_planner_set_task_outputs)
     { const int st = admit_on(h, next); if (st) return st; }
     // cem_unfold_sequences' element limit on the trajectory tensor
     const long long traj_floats = (long long)d.Bloc * (d.H + 1) * d.O;
@@ -2581,7 +2595,10 @@ static int set_task(cem_planner_t *h, const cem_task_t *task, const cem_task_tra
     if (trk) HIPCHK(made_trk.alloc(trk_host.size() * 4));         // (one per call: ref_steps is the call's)
     // Unconditional: an eager plan still draining behind its polled result may be reading the tables
     return commit_launch_change(h, next, true, [&]() -> int {
-        auto drop_zones = [&] { if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; } h->zones = TaskParams{}; };   // (the stream is drained)
+        auto drop_zones = [&] {                                 // (the stream is drained) zones and outputs alike
+            if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; } h->zones = TaskParams{};
+            if (h->outs_dev) { hipFree(h->outs_dev); h->outs_dev = nullptr; } h->outs = TaskParams{};
+        };
         if (!on) { drop_zones(); return CEM_OK; }
         float *dev = made.p ? static_cast<float *>(made.p) : h->task_dev;
         if (trk) HIPCHK(hipMemcpy(made_trk.p, trk_host.data(), trk_host.size() * 4, hipMemcpyHostToDevice));
@@ -2662,7 +2679,7 @@ int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
         int used = 0;
         for (int a = 0; a < CEM_TASK_ZONE_AXES; ++a) {
             const int32_t ax = zones->axis[z * CEM_TASK_ZONE_AXES + a];
-            if (ax < -1 || ax >= d.O) return CEM_ERR_INVALID_ARG;
+            if (ax < -1 || ax >= d.O + h->opt.outputs) return CEM_ERR_INVALID_ARG;    // (an output's index only while outputs are in force)
             if (ax < 0) continue;
             const float c = zones->centre[z * CEM_TASK_ZONE_AXES + a], wt = zones->weight[z * CEM_TASK_ZONE_AXES + a];
             if (!finite(c) || !finite(wt) || below_zero(wt)) return CEM_ERR_INVALID_ARG;
@@ -2686,9 +2703,11 @@ int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
     if (tracking && !h->track_dev) return CEM_ERR_STATE;
     PlanOptions next = options_of(h); next.zones = nz;
     { const int st = admit_on(h, next); if (st) return st; }
-    TaskParams zp = tracking ? h->track : h->task;             // the base task as a whole: its tables, reference, clock and scalars
+    const bool outs = h->opt.outputs != 0;                     // the task with its outputs is the base then, a tracking task whatever its kind
+    if (outs && !h->outs_dev) return CEM_ERR_STATE;
+    TaskParams zp = outs ? h->outs : tracking ? h->track : h->task;   // the base task as a whole: its tables, reference, clock and scalars
     zp.n_zones = nz;
-    if (!tracking) {
+    if (!tracking && !outs) {
         // the quadratic task as a tracking task: qT = q, one reference row g, kappa = 0 (as set_task left it), the clock at (0, zeros)
         if (h->h_task_tab.size() != task_tab_floats()) return CEM_ERR_STATE;
         zp.T = 1;
@@ -2705,11 +2724,100 @@ int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones)
         if (h->zones_dev) hipFree(h->zones_dev);
         h->zones_dev = made.release<uint32_t>();
         zp.zones = h->zones_dev;
-        if (!tracking) {
+        if (!tracking && !outs) {
             zp.tab = reinterpret_cast<const float *>(h->zones_dev + kZoneTabAt); zp.ref = reinterpret_cast<const float *>(h->zones_dev + kZoneRefAt);
             zp.clock = h->zones_dev + kZoneClockAt;
         }
         h->zones = zp;
+        return CEM_OK;
+    });
+}
+
+// The linear outputs of the task in force (cem_task_outputs.h).  The allocation holds C, the outputs' tables and reference, an empty
+// zone table (the kernel is the zones kind's superset and reads one) and, for a quadratic base, its restatement as a tracking task
+// exactly as cem_planner_set_task_zones makes it.  The zones are cleared: they are set on the task WITH its outputs
+int cem_planner_set_task_outputs(cem_planner_t *h, const cem_task_outputs_t *outputs)
+{
+    if (!h) return CEM_ERR_INVALID_ARG;
+    const Dims &d = h->d;
+    auto drop = [](cem_planner_t *h) {
+        if (h->zones_dev) { hipFree(h->zones_dev); h->zones_dev = nullptr; } h->zones = TaskParams{};
+        if (h->outs_dev) { hipFree(h->outs_dev); h->outs_dev = nullptr; } h->outs = TaskParams{};
+    };
+    if (!outputs) {
+        if (h->in_plan) return CEM_ERR_STATE;
+        if (!h->opt.outputs) return CEM_OK;                    // nothing to clear: the handle, its graph and its zones included, stays as it is
+        PlanOptions next = options_of(h); next.outputs = 0; next.zones = 0;
+        return commit_launch_change(h, next, true, [&]() -> int { drop(h); return CEM_OK; });
+    }
+    // on the bit patterns: this file is built with -fno-honor-nans
+    auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+    auto finite = [&](float v) { return (bits(v) & 0x7fffffffu) < 0x7f800000u; };
+    auto is_nan = [&](float v) { return (bits(v) & 0x7fffffffu) > 0x7f800000u; };
+    auto below_zero = [&](float v) { return (bits(v) >> 31) != 0u && (bits(v) & 0x7fffffffu) != 0u; };
+    const int M = outputs->n_outputs;
+    if (M < 1 || M > CEM_TASK_MAX_OUTPUTS || !outputs->matrix) return CEM_ERR_INVALID_ARG;
+    const int rows = outputs->reference ? outputs->ref_rows : 1;
+    if (rows < 1 || rows > CEM_TASK_REF_MAX_STEPS) return CEM_ERR_INVALID_ARG;
+    // the allocation as the kernel reads it; an output from n_outputs on has a zero row, zero weights and infinite bounds
+    std::vector<uint32_t> host(kOutRefAt + (size_t)rows * CEM_TASK_MAX_OUTPUTS, 0u);
+    const float inf = std::numeric_limits<float>::infinity();
+    for (int m = 0; m < M; ++m)
+        for (int f = 0; f < d.O; ++f) {
+            const float v = outputs->matrix[(size_t)m * d.O + f];
+            if (!finite(v)) return CEM_ERR_INVALID_ARG;
+            host[(size_t)m * CEM_U + f] = bits(v);
+        }
+    uint32_t *const tab = &host[kOutTabAt];
+    for (int m = 0; m < CEM_TASK_MAX_OUTPUTS; ++m) { tab[CEM_TASK_OUT_TAB_LO * CEM_TASK_MAX_OUTPUTS + m] = bits(-inf); tab[CEM_TASK_OUT_TAB_HI * CEM_TASK_MAX_OUTPUTS + m] = bits(inf); }
+    for (int m = 0; m < M; ++m) {
+        const float w = outputs->weight ? outputs->weight[m] : 0.f, g = outputs->target ? outputs->target[m] : 0.f, c = outputs->linear ? outputs->linear[m] : 0.f;
+        const float nr = outputs->near ? outputs->near[m] : 0.f, lo = outputs->lo ? outputs->lo[m] : -inf, hi = outputs->hi ? outputs->hi[m] : inf;
+        const float wT = outputs->terminal ? outputs->terminal[m] : w;
+        if (!finite(w) || !finite(g) || !finite(c) || !finite(nr) || !finite(wT) || below_zero(w) || below_zero(wT)) return CEM_ERR_INVALID_ARG;
+        if (is_nan(lo) || is_nan(hi) || lo > hi) return CEM_ERR_INVALID_ARG;
+        tab[CEM_TASK_OUT_TAB_Q * CEM_TASK_MAX_OUTPUTS + m] = bits(w); tab[CEM_TASK_OUT_TAB_QT * CEM_TASK_MAX_OUTPUTS + m] = bits(wT);
+        tab[CEM_TASK_OUT_TAB_C * CEM_TASK_MAX_OUTPUTS + m] = bits(c); tab[CEM_TASK_OUT_TAB_M * CEM_TASK_MAX_OUTPUTS + m] = bits(nr);
+        tab[CEM_TASK_OUT_TAB_LO * CEM_TASK_MAX_OUTPUTS + m] = bits(lo); tab[CEM_TASK_OUT_TAB_HI * CEM_TASK_MAX_OUTPUTS + m] = bits(hi);
+        for (int j = 0; j < rows; ++j) {
+            const float v = outputs->reference ? outputs->reference[(size_t)j * M + m] : g;
+            if (!finite(v)) return CEM_ERR_INVALID_ARG;
+            host[kOutRefAt + (size_t)j * CEM_TASK_MAX_OUTPUTS + m] = bits(v);
+        }
+    }
+    for (int z = 0; z < CEM_TASK_MAX_ZONES; ++z)
+        for (int a = 0; a < CEM_TASK_ZONE_AXES; ++a) host[kOutZoneAt + (size_t)z * CEM_TASK_ZONE_WORDS + CEM_TASK_ZONE_ROW_AXIS + a] = 0xffffffffu;
+    if (!h->opt.task || !h->task_dev || h->in_plan) return CEM_ERR_STATE;
+    const bool tracking = h->opt.task == CEM_TASK_TRACKING;
+    if (tracking && !h->track_dev) return CEM_ERR_STATE;
+    if (rows != 1 && rows != (tracking ? h->track.T : 1)) return CEM_ERR_INVALID_ARG;
+    PlanOptions next = options_of(h); next.outputs = M; next.zones = 0;
+    { const int st = admit_on(h, next); if (st) return st; }
+    TaskParams op = tracking ? h->track : h->task;             // the base task as a whole: its tables, reference, clock and scalars
+    op.n_zones = 0; op.n_outputs = M; op.out_T = rows;
+    if (!tracking) {
+        // the quadratic task as a tracking task, as the zones make it: qT = q, one reference row g, kappa = 0, the clock at (0, zeros);
+        // an output's terminal weight is its weight there
+        if (h->h_task_tab.size() != task_tab_floats()) return CEM_ERR_STATE;
+        op.T = 1;
+        std::memcpy(&host[kOutZoneAt + kZoneTabAt], h->h_task_tab.data(), task_tab_floats() * 4);
+        std::memcpy(&host[kOutZoneAt + kZoneTabAt + (size_t)CEM_TASK_TAB_QT * CEM_U], &h->h_task_tab[(size_t)CEM_TASK_TAB_Q * CEM_U], (size_t)CEM_U * 4);
+        std::memcpy(&host[kOutZoneAt + kZoneRefAt], &h->h_task_tab[(size_t)CEM_TASK_TAB_G * CEM_U], (size_t)CEM_U * 4);
+        std::memcpy(&tab[CEM_TASK_OUT_TAB_QT * CEM_TASK_MAX_OUTPUTS], &tab[CEM_TASK_OUT_TAB_Q * CEM_TASK_MAX_OUTPUTS], (size_t)CEM_TASK_MAX_OUTPUTS * 4);
+    }
+    // allocated before anything of the handle changes: a failed allocation leaves it as it was
+    DevBlock made;
+    HIPCHK(made.alloc(host.size() * 4));
+    // Unconditional: an eager plan still draining behind its polled result may be reading the previous outputs or zones
+    return commit_launch_change(h, next, true, [&]() -> int {
+        HIPCHK(hipMemcpy(made.p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+        drop(h);
+        h->outs_dev = made.release<uint32_t>();
+        const float *const base = reinterpret_cast<const float *>(h->outs_dev);
+        op.out_c = base; op.out_tab = base + kOutTabAt; op.out_ref = base + kOutRefAt;
+        op.zones = h->outs_dev + kOutZoneAt;
+        if (!tracking) { op.tab = base + kOutZoneAt + kZoneTabAt; op.ref = base + kOutZoneAt + kZoneRefAt; op.clock = h->outs_dev + kOutZoneAt + kZoneClockAt; }
+        h->outs = op;
         return CEM_OK;
     });
 }

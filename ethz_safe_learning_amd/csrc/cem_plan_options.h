@@ -24,6 +24,8 @@ struct PlanOptions {
                                              // (cem_task_score.h), CEM_TASK_TRACKING cem_task_reference_kernel (cem_task_reference.h): two kinds of one tile (cem_task_tile.h); admit() treats the two alike
     int zones = 0;                           // cem_planner_set_task_zones: the number of zones on the task in force; not 0: cem_task_zones_kernel takes the task
                                              // kernel's place (cem_task_zones.h); recipe and launch count are the base task plan's
+    int outputs = 0;                         // cem_planner_set_task_outputs: the number of linear outputs on the task in force; not 0: cem_task_outputs_kernel takes
+                                             // the task's (or the zones') kernel's place (cem_task_outputs.h); recipe and launch count are the base task plan's
     bool comm = false;                       // the handle has a communicator (cem_planner_comm_init; cem_capi.hip: options_of reads it off the handle)
 };
 
@@ -37,7 +39,7 @@ struct HandleFacts {
     long long budget_total_limit = 0;                  // H * m * kinds of a budget plan stays below it (cem_capi.hip: kBudgetTotalLimit)
     size_t refit_lds_bytes = 0, refit_lds_limit = 0;   // the weighted refit's dynamic LDS at this (k, H A) and what the device grants
     // the launchers of the optional translation units that are linked in
-    bool can_mix = false, can_carry = false, can_mean = false, can_track = false, can_task = false, can_zones = false;
+    bool can_mix = false, can_carry = false, can_mean = false, can_track = false, can_task = false, can_zones = false, can_outputs = false;
 };
 
 // which call asks: only the inherited asymmetry below reads it
@@ -85,6 +87,7 @@ inline int admit(const HandleFacts &f, const PlanOptions &o, PlanChange change =
     // ZONES need their kernel, which stands in for the task's own (cem_task_zones.h); that they sit on a task is the setters' business:
     // cem_planner_set_task_zones wants one in force, cem_planner_set_task clears them
     if (o.zones != 0 && !f.can_zones) return CEM_ERR_UNSUPPORTED;
+    if (o.outputs != 0 && !f.can_outputs) return CEM_ERR_UNSUPPORTED;   // OUTPUTS likewise (cem_task_outputs.h)
     // THE INJECT'S ROWS are candidates of every iteration, and none of them is the mean candidate's (the last iteration's last row)
     if (carry) {
         for (int32_t n : o.pop) if (n <= o.elite.n_keep) return CEM_ERR_UNSUPPORTED;

@@ -1,12 +1,15 @@
-// cem_task_tile.h — the ONE task-scoring tile: what cem_task_score_kernel, cem_task_reference_kernel and
-// cem_task_zones_kernel share, which is everything but a few statements each.  The three headers of those names hold their contracts,
-// their weak launchers and a wrapper of one line; cem_capi.hip includes them, and each kernel is compiled in a unit of its own.
+// cem_task_tile.h — the ONE task-scoring tile: what cem_task_score_kernel, cem_task_reference_kernel,
+// cem_task_zones_kernel and cem_task_outputs_kernel share, which is everything but a few statements each.  The four headers of those
+// names hold their contracts, their weak launchers and a wrapper of one line; cem_capi.hip includes them, and each kernel is compiled
+// in a unit of its own.
 //
-// THE KINDS.  cem_task_rows<NT, VEC, KIND> is the body of all three; `if constexpr` on KIND keeps each kind's statements exactly what
+// THE KINDS.  cem_task_rows<NT, VEC, KIND> is the body of all four; `if constexpr` on KIND keeps each kind's statements exactly what
 // its header states, in that order and with those parentheses (-ffp-contract=off: no statement is re-associated across kinds):
 //   CEM_TASK_KIND_QUADRATIC  g from row CEM_TASK_TAB_G of the tables;  r = ((-phi) - u) + ...
 //   CEM_TASK_KIND_TRACKING   g from `ref` at the clock's row, qT (the same table row) on the terminal state, v from kappa;  ... - v
 //   CEM_TASK_KIND_ZONES      tracking, and lane l's zone on every state: `hit` joins the ballot, `pen` the shuffles;  ... - pen
+//   CEM_TASK_KIND_OUTPUTS    zones (n_zones may be 0), and lane l's linear output y_l = C[l] . s of every state: its terms join lane l's
+//                            partial sums, its bounds the ballot, and a zone axis may name it (cem_task_outputs.h).  The one kind with LDS: C
 // A later kind is a superset of the one before it (KIND >= ... below).  TaskParams is the superset's parameter block; a kind reads
 // only its own fields (the launcher's checks are per kind too).
 //
@@ -17,7 +20,7 @@
 // 16-byte loads per lane in flight); a tracking kind requests their reference quads, a zoned one its lane's <= 4 axis features, in
 // the same batch.  Where a quad would not be 16-byte aligned (O % 4 != 0, or a caller's unaligned tensor) the same lanes read the same
 // features element by element: same sums, same order.  The tables sit in registers (6 x NT quads per lane, loaded once), rho and
-// kappa in the kernel arguments, the clock in device memory.  No LDS, no atomics; the partial sums meet through four wave shuffles,
+// kappa in the kernel arguments, the clock in device memory.  No LDS (but the outputs kind's C), no atomics; the partial sums meet through four wave shuffles,
 // the box test (and the zones' hits) through one ballot.  A group past the end reads the last row and stores nothing: every lane
 // reaches the shuffles.  Each word of `ret` and each cost byte is written once, by lane 0 of the row's group.
 #pragma once
@@ -48,6 +51,14 @@
 #define CEM_TASK_KIND_QUADRATIC 0
 #define CEM_TASK_KIND_TRACKING 1
 #define CEM_TASK_KIND_ZONES 2
+#define CEM_TASK_KIND_OUTPUTS 3
+#define CEM_TASK_OUT_TABLES 6            // rows of TaskParams::out_tab, CEM_TASK_MAX_OUTPUTS floats each: qy, qTy, cy, my, loy, hiy (outputs >= n_outputs: 0, 0, 0, 0, -inf, +inf)
+#define CEM_TASK_OUT_TAB_Q 0
+#define CEM_TASK_OUT_TAB_QT 1
+#define CEM_TASK_OUT_TAB_C 2
+#define CEM_TASK_OUT_TAB_M 3
+#define CEM_TASK_OUT_TAB_LO 4
+#define CEM_TASK_OUT_TAB_HI 5
 
 struct TaskParams {
     const float *traj;           // [rows][H + 1][O]
@@ -62,19 +73,48 @@ struct TaskParams {
     int32_t rows, N, H, O, A, variant, check_done, T, n_zones;
     float r2, reward_goal, clip; // fl32(goal_radius^2); clip = +inf: none
     float rho[CEM_MAX_ACT], kappa[CEM_MAX_ACT];
+    // outputs (cem_task_outputs.h), read by CEM_TASK_KIND_OUTPUTS alone
+    const float *out_c;          // [CEM_TASK_MAX_OUTPUTS][CEM_U], 16-byte aligned; zero beyond O and from row n_outputs on
+    const float *out_tab;        // [CEM_TASK_OUT_TABLES][CEM_TASK_MAX_OUTPUTS]
+    const float *out_ref;        // [out_T][CEM_TASK_MAX_OUTPUTS]: the outputs' targets, one row or the base task's T rows (the same clock)
+    int32_t n_outputs, out_T;
 };
 
-#if defined(CEM_TASK_SCORE_UNIT) || defined(CEM_TASK_REFERENCE_UNIT) || defined(CEM_TASK_ZONES_UNIT)
+#if defined(CEM_TASK_SCORE_UNIT) || defined(CEM_TASK_REFERENCE_UNIT) || defined(CEM_TASK_ZONES_UNIT) || defined(CEM_TASK_OUTPUTS_UNIT)
 typedef uint32_t cem_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bool cem_task_is_nan(const float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+// The outputs kind's lane predicates would not fit beside the zones kind's in the scalar file: it keeps them as masks in vector registers.
+// cem_task_mask: all ones where the condition holds (through an empty asm, or the compiler folds mask and pick back into a select on a
+// scalar register pair); cem_task_pick: a where the lane's mask is all ones, b where it is zero — the same bits a select gives
+__device__ __forceinline__ uint32_t cem_task_mask(const bool on) { uint32_t m = on ? 0xffffffffu : 0u; asm volatile("" : "+v"(m)); return m; }
+__device__ __forceinline__ float cem_task_pick(const uint32_t mask, const float a, const float b) { return __uint_as_float((__float_as_uint(a) & mask) | (__float_as_uint(b) & ~mask)); }
 
 // NT: feature quads per lane (1: O <= 64, 2: O <= 128).  VEC: the state quads are 16-byte aligned and whole (O % 4 == 0).
 template <int NT, bool VEC, int KIND>
 __device__ __forceinline__ void cem_task_rows(const TaskParams &p)
 {
-    constexpr bool TRACK = KIND >= CEM_TASK_KIND_TRACKING, ZONED = KIND >= CEM_TASK_KIND_ZONES;
+    constexpr bool TRACK = KIND >= CEM_TASK_KIND_TRACKING, ZONED = KIND >= CEM_TASK_KIND_ZONES, OUTS = KIND >= CEM_TASK_KIND_OUTPUTS;
     if (p.check_done && p.ctrl->done) return;
     const int tid = (int)threadIdx.x, l = tid & 15, grp = (tid & 63) >> 4;
+    // outputs: C in LDS, 8 KB, copied once by the whole block (the return above is the block's as a whole); lane l's own tables in registers
+    float *cl = nullptr;
+    uint32_t out_on = 0u;                    // (all ones: this lane owns an output)
+    float qy = 0.f, qTy = 0.f, cy = 0.f, my = 0.f;
+    uint32_t kloy = 0u, khiy = 0u;
+    int gy_stride = 0;                       // floats between the rows of out_ref that two reference rows of the base task read: 0 where it has one row
+    if constexpr (OUTS) {
+        __shared__ f4 c_lds[CEM_TASK_MAX_OUTPUTS * CEM_U / 4];
+#pragma unroll
+        for (int j = 0; j < CEM_TASK_MAX_OUTPUTS * CEM_U / 4 / CEM_TASK_THREADS; ++j)
+            c_lds[j * CEM_TASK_THREADS + tid] = reinterpret_cast<const f4 *>(p.out_c)[j * CEM_TASK_THREADS + tid];
+        __syncthreads();
+        cl = reinterpret_cast<float *>(c_lds);
+        out_on = cem_task_mask(l < p.n_outputs);
+        gy_stride = p.out_T > 1 ? CEM_TASK_MAX_OUTPUTS : 0;
+        qy = p.out_tab[CEM_TASK_OUT_TAB_Q * CEM_TASK_MAX_OUTPUTS + l]; qTy = p.out_tab[CEM_TASK_OUT_TAB_QT * CEM_TASK_MAX_OUTPUTS + l];
+        cy = p.out_tab[CEM_TASK_OUT_TAB_C * CEM_TASK_MAX_OUTPUTS + l]; my = p.out_tab[CEM_TASK_OUT_TAB_M * CEM_TASK_MAX_OUTPUTS + l];
+        kloy = cem_f2key(p.out_tab[CEM_TASK_OUT_TAB_LO * CEM_TASK_MAX_OUTPUTS + l]); khiy = cem_f2key(p.out_tab[CEM_TASK_OUT_TAB_HI * CEM_TASK_MAX_OUTPUTS + l]);
+    }
     const int row_raw = (int)blockIdx.x * CEM_TASK_ROWS_PER_BLOCK + (tid >> 4);
     const bool live = row_raw < p.rows;
     const int row = live ? row_raw : p.rows - 1;             // (a group past the end reads the last row and stores nothing: every lane reaches the shuffles)
@@ -103,6 +143,9 @@ __device__ __forceinline__ void cem_task_rows(const TaskParams &p)
     f4 zc = {0.f, 0.f, 0.f, 0.f}, zw = zc;
     bool zone_on = false, keep_in = false, zused[CEM_TASK_ZONE_AXES] = {};
     int zoff[CEM_TASK_ZONE_AXES] = {};
+    uint32_t zout[CEM_TASK_ZONE_AXES] = {};  // outputs: all ones where the axis names output zsrc - (this group's first lane), held by that lane
+    int zsrc[CEM_TASK_ZONE_AXES] = {};
+    uint32_t zusedm[CEM_TASK_ZONE_AXES] = {}, zonem = 0u, keepm = 0u;   // outputs: zused, zone_on and keep_in as masks in vector registers (cem_task_pick)
     uint32_t kR2 = 0u;
     float zRm2 = 0.f, zpen = 0.f;
     if constexpr (ZONED) {
@@ -113,10 +156,20 @@ __device__ __forceinline__ void cem_task_rows(const TaskParams &p)
         const cem_u4 zr = *reinterpret_cast<const cem_u4 *>(zp + CEM_TASK_ZONE_R2);
         zone_on = l < p.n_zones;
 #pragma unroll
-        for (int d = 0; d < CEM_TASK_ZONE_AXES; ++d) { zused[d] = zone_on && zax[d] < (uint32_t)O; zoff[d] = zused[d] ? (int)zax[d] : 0; }
+        for (int d = 0; d < CEM_TASK_ZONE_AXES; ++d) {
+            const bool feat = zone_on && zax[d] < (uint32_t)O;
+            if constexpr (OUTS) {
+                const bool named = zone_on && !feat && zax[d] - (uint32_t)O < (uint32_t)p.n_outputs;
+                zout[d] = cem_task_mask(named);
+                zsrc[d] = (tid & 48) | (named ? (int)(zax[d] - (uint32_t)O) : 0);
+                zused[d] = feat || named; zusedm[d] = cem_task_mask(zused[d]);
+            } else zused[d] = feat;
+            zoff[d] = feat ? (int)zax[d] : 0;
+        }
         kR2 = cem_f2key(__uint_as_float(zr[0]));
         zRm2 = __uint_as_float(zr[1]); zpen = __uint_as_float(zr[2]);
         keep_in = zr[3] != 0u;
+        if constexpr (OUTS) { zonem = cem_task_mask(zone_on); keepm = cem_task_mask(keep_in); }
     }
 
     const float *const tr = p.traj + (size_t)row * (size_t)(H + 1) * O;
@@ -138,7 +191,7 @@ __device__ __forceinline__ void cem_task_rows(const TaskParams &p)
         // the loads of CEM_TASK_DEPTH states first, with their reference rows and this lane's zone features where the kind has them (a
         // step past the horizon reads the last state again and is not reduced)
         f4 x[CEM_TASK_DEPTH][NT], g[CEM_TASK_DEPTH][NT];
-        float zs[CEM_TASK_DEPTH][CEM_TASK_ZONE_AXES];
+        float zs[CEM_TASK_DEPTH][CEM_TASK_ZONE_AXES], gy[CEM_TASK_DEPTH] = {};
 #pragma unroll
         for (int k = 0; k < CEM_TASK_DEPTH; ++k) {
             const int st = s0 + k <= H ? s0 + k : H;
@@ -157,6 +210,49 @@ __device__ __forceinline__ void cem_task_rows(const TaskParams &p)
             if constexpr (ZONED) {
 #pragma unroll
                 for (int d = 0; d < CEM_TASK_ZONE_AXES; ++d) zs[k][d] = sp[zoff[d]];     // (an unused slot reads feature 0 and drops it)
+            }
+            if constexpr (OUTS) gy[k] = p.out_ref[(size_t)min(k0 + st, last) * gy_stride + l];    // (out_T is T or 1, the launcher's check: inside the table)
+        }
+        // outputs: this lane's sixteen partial dot products of every state in flight (a row of C is read once for all of them; a row from
+        // n_outputs on is skipped, uniformly — on a count the compiler cannot see through, or it would keep the sixteen conditions in
+        // scalar registers across the loop and spill), then the butterfly: at distance dl a lane keeps the outputs whose bit dl is its own and
+        // adds its partner's partials of those, so that lane l ends with y_l, the sixteen partials added pairwise, neighbours first
+        float y[CEM_TASK_DEPTH] = {};
+        if constexpr (OUTS) {
+            float yp[CEM_TASK_DEPTH][CEM_TASK_MAX_OUTPUTS];
+            int n_out = p.n_outputs;
+            asm volatile("" : "+s"(n_out));
+#pragma unroll
+            for (int m = 0; m < CEM_TASK_MAX_OUTPUTS; ++m) {
+                if (m < n_out) {
+                    f4 cq[NT];
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) cq[i] = *reinterpret_cast<const f4 *>(cl + m * CEM_U + 64 * i + 4 * l);
+#pragma unroll
+                    for (int k = 0; k < CEM_TASK_DEPTH; ++k) {
+                        float a = 0.f;
+#pragma unroll
+                        for (int i = 0; i < NT; ++i)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) a = a + cq[i][r] * x[k][i][r];
+                        yp[k][m] = a;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CEM_TASK_DEPTH; ++k) yp[k][m] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CEM_TASK_DEPTH; ++k) {
+                float a8[8], a4[4], a2[2];
+                const uint32_t b0 = 0u - (uint32_t)(l & 1), b1 = 0u - (uint32_t)((l >> 1) & 1), b2 = 0u - (uint32_t)((l >> 2) & 1), b3 = 0u - (uint32_t)((l >> 3) & 1);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a8[j] = cem_task_pick(b0, yp[k][2 * j + 1], yp[k][2 * j]) + __shfl_xor(cem_task_pick(b0, yp[k][2 * j], yp[k][2 * j + 1]), 1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a4[j] = cem_task_pick(b1, a8[2 * j + 1], a8[2 * j]) + __shfl_xor(cem_task_pick(b1, a8[2 * j], a8[2 * j + 1]), 2);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) a2[j] = cem_task_pick(b2, a4[2 * j + 1], a4[2 * j]) + __shfl_xor(cem_task_pick(b2, a4[2 * j], a4[2 * j + 1]), 4);
+                y[k] = cem_task_pick(b3, a2[1], a2[0]) + __shfl_xor(cem_task_pick(b3, a2[0], a2[1]), 8);
             }
         }
 #pragma unroll
@@ -179,23 +275,44 @@ __device__ __forceinline__ void cem_task_rows(const TaskParams &p)
                     const uint32_t ks = cem_f2key(s);
                     out = out || (!cem_task_is_nan(s) && (ks < klo[i][r] || ks > khi[i][r]));
                 }
+            if constexpr (OUTS) {
+                // this lane's output on the same state: its terms behind the lane's feature terms, its bounds with the box's
+                const float yv = y[k];
+                const float e = yv - gy[k];
+                const float ee = e * e;
+                const float w = terminal ? qTy : qy;
+                const float withphi = phi + (w * ee - cy * yv), withn = nsum + my * ee;
+                phi = cem_task_pick(out_on, withphi, phi); nsum = cem_task_pick(out_on, withn, nsum);
+                const uint32_t ky = cem_f2key(yv);
+                out = out || (!cem_task_is_nan(yv) && (ky < kloy || ky > khiy));            // (a lane without an output holds infinite bounds)
+            }
             if constexpr (ZONED) {
                 // this lane's zone on the same state
                 float dist2 = 0.f;
 #pragma unroll
                 for (int d = 0; d < CEM_TASK_ZONE_AXES; ++d) {
+                    if constexpr (OUTS) { const float yz = __shfl(y[k], zsrc[d]); zs[k][d] = cem_task_pick(zout[d], yz, zs[k][d]); }   // (every lane reads: one variable-source lane read)
                     const float e = zs[k][d] - zc[d];
                     const float with = dist2 + zw[d] * (e * e);
-                    dist2 = zused[d] ? with : dist2;
+                    if constexpr (OUTS) dist2 = cem_task_pick(zusedm[d], with, dist2);
+                    else dist2 = zused[d] ? with : dist2;
                 }
                 const bool dnan = cem_task_is_nan(dist2);
                 const uint32_t kd = cem_f2key(dist2);
                 const bool inside = kd <= kR2;
-                const bool hit = zone_on && !dnan && (keep_in ? !inside : inside);
-                const float gap = keep_in ? dist2 - zRm2 : zRm2 - dist2;
+                bool hit;
+                float gap;
+                if constexpr (OUTS) {                                                     // (the same values, selected by the masks)
+                    hit = ((((inside ? 0xffffffffu : 0u) ^ keepm) & zonem) != 0u) && !dnan;
+                    gap = cem_task_pick(keepm, dist2 - zRm2, zRm2 - dist2);
+                } else {
+                    hit = zone_on && !dnan && (keep_in ? !inside : inside);
+                    gap = keep_in ? dist2 - zRm2 : zRm2 - dist2;
+                }
                 // (gap is no NaN behind the bit test, and an exact difference of zero is +0: the larger of gap and +0, by its key)
                 const float hinge = (!dnan && !cem_task_is_nan(gap) && cem_f2key(gap) > cem_f2key(0.0f)) ? gap : 0.0f;
-                pen = zone_on ? zpen * hinge : 0.0f;
+                if constexpr (OUTS) pen = cem_task_pick(zonem, zpen * hinge, 0.0f);
+                else pen = zone_on ? zpen * hinge : 0.0f;
                 out = out || hit;
             }
             // the sixteen partial sums pairwise, neighbours first (an addition commutes: both lanes of a pair hold the same sum)
@@ -253,7 +370,9 @@ hipError_t cem_task_launch(const cem_task_kernel_t (&k)[2][2], const TaskParams 
 {
     if (p.rows < 1 || p.N < 1 || p.H < 1 || p.O < 1 || p.O > CEM_U || p.A < 1 || p.A > CEM_MAX_ACT) return hipErrorInvalidValue;
     if (KIND >= CEM_TASK_KIND_TRACKING && (p.T < 1 || !p.ref || !p.clock)) return hipErrorInvalidValue;
-    if (KIND >= CEM_TASK_KIND_ZONES && (!p.zones || p.n_zones < 1 || p.n_zones > CEM_TASK_MAX_ZONES)) return hipErrorInvalidValue;
+    if (KIND >= CEM_TASK_KIND_ZONES && (!p.zones || p.n_zones < (KIND >= CEM_TASK_KIND_OUTPUTS ? 0 : 1) || p.n_zones > CEM_TASK_MAX_ZONES)) return hipErrorInvalidValue;
+    if (KIND >= CEM_TASK_KIND_OUTPUTS && (!p.out_c || !p.out_tab || !p.out_ref || p.n_outputs < 1 || p.n_outputs > CEM_TASK_MAX_OUTPUTS || (p.out_T != 1 && p.out_T != p.T)))
+        return hipErrorInvalidValue;
     const dim3 grid((unsigned)((p.rows + CEM_TASK_ROWS_PER_BLOCK - 1) / CEM_TASK_ROWS_PER_BLOCK)), block(CEM_TASK_THREADS);
     const bool vec = p.O % 4 == 0 && (reinterpret_cast<uintptr_t>(p.traj) & 15u) == 0;
     hipLaunchKernelGGL(k[p.O > 64][vec], grid, block, 0, st, p);

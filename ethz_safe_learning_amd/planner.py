@@ -122,11 +122,120 @@ class StateZones:
 
 def _zone_tables(task, obs_dim):
     z = getattr(task, 'zones', None)
+    ot = _output_tables(task, obs_dim)                # (an axis may name an output: index obs_dim + m)
     if z is None:
         return None
     if not isinstance(z, StateZones):
         raise ValueError('zones must be a StateZones')
-    return z.tables(obs_dim)
+    return z.tables(int(obs_dim) + (ot['matrix'].shape[0] if ot is not None else 0))
+
+
+@dataclass
+class TaskOutputs:
+    """Linear outputs y = matrix @ s on a task (cem_task_outputs_t; cem_mpc.h "Linear outputs"): up to 16 derived features, each with
+    the vocabulary a state feature has.  Output m pays weights[m] (y_m - target[m])^2 - linear[m] y_m (terminal_weights[m] on the last
+    state of a TrackingTask), counts near[m] (y_m - target[m])^2 towards the goal radius, is a violation outside [lo[m], hi[m]], and a
+    StateZones axis may name it as obs_dim + m.  matrix is [M, obs_dim] (or [obs_dim]: one output); the others are arrays of M or scalars;
+    target may be [T, M] on a TrackingTask with T reference rows (the same clock).  Set as `outputs=` of a QuadraticTask or TrackingTask."""
+    matrix: object = None
+    weights: object = 0.0
+    target: object = 0.0
+    linear: object = 0.0
+    near: object = 0.0
+    lo: object = -np.inf
+    hi: object = np.inf
+    terminal_weights: object = None
+
+    @classmethod
+    def halfspaces(cls, normals, offsets):
+        """The polytope normals @ s <= offsets: one output per row of `normals` [M, obs_dim], bounded above by offsets [M] (or one for all)."""
+        return cls(matrix=normals, hi=offsets)
+
+    @classmethod
+    def quadratic_form(cls, Q, target, terminal=None, tol=1e-10):
+        """The full-matrix cost (s - target)^T Q (s - target) as sum_i (L_i . s - L_i . target)^2: Q [obs_dim, obs_dim] symmetric positive
+        semi-definite is factored in float64, Q = V diag(lam) V^T, and the rows of L are sqrt(lam_i) v_i^T for the eigenvalues above
+        tol * max(lam) (an eigenvalue below -tol * max(lam) is refused; those in between are dropped).  More than 16 rows: ValueError.
+        The weights are 1, the target is L @ target ([obs_dim], or [T, obs_dim] on a TrackingTask); `terminal` are terminal_weights."""
+        Q = np.asarray(Q, np.float64)
+        if Q.ndim != 2 or Q.shape[0] != Q.shape[1] or not np.isfinite(Q).all():
+            raise ValueError('Q must be a finite square matrix')
+        if not np.allclose(Q, Q.T, rtol=1e-12, atol=1e-12 * max(1.0, float(np.abs(Q).max(initial=0.0)))):
+            raise ValueError('Q must be symmetric')
+        lam, V = np.linalg.eigh(0.5 * (Q + Q.T))
+        top = float(lam.max(initial=0.0))
+        if top <= 0.0 or (lam < -float(tol) * top).any():
+            raise ValueError('Q must be positive semi-definite and not zero')
+        keep = lam > float(tol) * top
+        if int(keep.sum()) > _capi.CEM_TASK_MAX_OUTPUTS:
+            raise ValueError('the rank of Q is %d: more than %d outputs' % (int(keep.sum()), _capi.CEM_TASK_MAX_OUTPUTS))
+        L = (np.sqrt(lam[keep])[:, None] * V[:, keep].T)[::-1]            # (largest eigenvalue first)
+        tg = np.asarray(target, np.float64)
+        if tg.ndim not in (1, 2) or tg.shape[-1] != Q.shape[0]:
+            raise ValueError('target must be [%d] or [T, %d]' % (Q.shape[0], Q.shape[0]))
+        return cls(matrix=L.astype(np.float32), weights=1.0, target=(tg @ L.T).astype(np.float32), terminal_weights=terminal)
+
+    @classmethod
+    def stack(cls, a, b):
+        """The outputs of `a` followed by those of `b` (say, a quadratic_form and halfspaces).  A [T, M] target on one side is kept; a
+        [M] target beside it is repeated over its T rows."""
+        if not isinstance(a, TaskOutputs) or not isinstance(b, TaskOutputs):
+            raise ValueError('stack takes two TaskOutputs')
+        ma, mb = np.atleast_2d(np.asarray(a.matrix, np.float32)), np.atleast_2d(np.asarray(b.matrix, np.float32))
+        if ma.shape[1] != mb.shape[1]:
+            raise ValueError('the two matrices must have the same number of columns')
+        ta, tb = a.tables(ma.shape[1]), b.tables(mb.shape[1])
+        R = max(ta['target'].shape[0], tb['target'].shape[0])
+        if {ta['target'].shape[0], tb['target'].shape[0]} - {1, R}:
+            raise ValueError('the two targets have different numbers of rows')
+        tg = np.concatenate([np.broadcast_to(t['target'], (R, t['target'].shape[1])) for t in (ta, tb)], axis=1)
+        cat = {k: np.concatenate([ta[k], tb[k]]) for k in ('weight', 'linear', 'near', 'lo', 'hi')}
+        term = None
+        if ta['terminal'] is not None or tb['terminal'] is not None:
+            term = np.concatenate([t['terminal'] if t['terminal'] is not None else t['weight'] for t in (ta, tb)])
+        return cls(matrix=np.concatenate([ma, mb]), weights=cat['weight'], target=tg if R > 1 else tg[0], linear=cat['linear'], near=cat['near'],
+                   lo=cat['lo'], hi=cat['hi'], terminal_weights=term)
+
+    def tables(self, obs_dim, ref_rows=None):
+        """The tables as the library takes them, validated as it validates them: matrix [M, obs_dim] float32, weight, linear, near, lo, hi
+        [M], target [R, M] (R = 1, or the T rows of a per-step target), terminal [M] or None.  ref_rows: the base task's reference rows
+        (1 for a QuadraticTask), which R must equal unless it is 1; None: not checked."""
+        O, MMAX = int(obs_dim), _capi.CEM_TASK_MAX_OUTPUTS
+        m = np.asarray(self.matrix if self.matrix is not None else (), np.float32)
+        if m.ndim == 1 and m.shape[0] == O:
+            m = m[None]
+        if m.ndim != 2 or m.shape[1] != O or not 1 <= m.shape[0] <= MMAX:
+            raise ValueError('matrix must be [M, %d] with 1 <= M <= %d' % (O, MMAX))
+        M = m.shape[0]
+        out = {'matrix': np.ascontiguousarray(m)}
+        for k, v in (('weight', self.weights), ('linear', self.linear), ('near', self.near), ('lo', self.lo), ('hi', self.hi)):
+            out[k] = _task_table(v, M, k)
+        out['terminal'] = None if self.terminal_weights is None else _task_table(self.terminal_weights, M, 'terminal_weights')
+        tg = np.asarray(self.target, np.float32)
+        if tg.ndim == 2 and tg.shape[1] == M and 1 <= tg.shape[0] <= _capi.CEM_TASK_REF_MAX_STEPS:
+            out['target'] = np.ascontiguousarray(tg)
+        else:
+            out['target'] = _task_table(tg, M, 'target')[None]
+        if ref_rows is not None and out['target'].shape[0] not in (1, int(ref_rows)):
+            raise ValueError('a per-step target must have the %d rows of the task\'s reference' % int(ref_rows))
+        for k in ('matrix', 'weight', 'linear', 'near', 'target', 'terminal'):
+            if out[k] is not None and not np.isfinite(out[k]).all():
+                raise ValueError('%s must be finite' % k)
+        if (out['weight'] < 0).any() or (out['terminal'] is not None and (out['terminal'] < 0).any()):
+            raise ValueError('weights must be >= 0')
+        if np.isnan(out['lo']).any() or np.isnan(out['hi']).any() or (out['lo'] > out['hi']).any():
+            raise ValueError('the bounds must be numbers with lo <= hi')
+        return out
+
+
+def _output_tables(task, obs_dim):
+    o = getattr(task, 'outputs', None)
+    if o is None:
+        return None
+    if not isinstance(o, TaskOutputs):
+        raise ValueError('outputs must be a TaskOutputs')
+    ref = getattr(task, 'reference', None)
+    return o.tables(obs_dim, ref_rows=np.asarray(ref).shape[0] if ref is not None and np.asarray(ref).ndim == 2 else 1)
 
 
 @dataclass
@@ -137,7 +246,8 @@ class QuadraticTask:
         near(s) = goal_radius > 0 and sum_f goal_mask_f (s_f - g_f)^2 <= goal_radius^2             (near ends the episode, as the goal does)
         cost(s) = 1 if any s_f < lo_f or s_f > hi_f                                                  ('safe' / 'cost' handles)
     Every table is an array of the feature count or a scalar broadcast to it.  `zones` (a StateZones) adds round regions the state
-    must stay out of, or inside of: a hit is a cost as leaving the box is, coming near costs reward."""
+    must stay out of, or inside of: a hit is a cost as leaving the box is, coming near costs reward.  `outputs` (a TaskOutputs) adds
+    linear outputs y = C s with the same vocabulary: full-matrix costs, half-spaces, rotated zones."""
     q: object = 0.0
     g: object = 0.0
     c: object = 0.0
@@ -148,15 +258,17 @@ class QuadraticTask:
     goal_radius: float = 0.0
     reward_goal: float = 0.0
     reward_clip: float = 0.0
+    outputs: object = None
     zones: object = None
 
     @classmethod
-    def to_target(cls, target, weights=1.0, action_weights=0.0, lo=-np.inf, hi=np.inf, goal_radius=0.0, reward_goal=0.0, reward_clip=0.0, zones=None):
+    def to_target(cls, target, weights=1.0, action_weights=0.0, lo=-np.inf, hi=np.inf, goal_radius=0.0, reward_goal=0.0, reward_clip=0.0, zones=None,
+                  outputs=None):
         """Stay near `target`: reward = -sum weights (s - target)^2 - sum action_weights a^2; with goal_radius > 0 the episode ends (and
         reward_goal is paid) within that weighted distance of the target, measured on the features whose weight is not zero."""
         w = np.asarray(weights, np.float32)
         return cls(q=w, g=target, goal_mask=(w != 0).astype(np.float32), lo=lo, hi=hi, rho=action_weights, goal_radius=goal_radius,
-                   reward_goal=reward_goal, reward_clip=reward_clip, zones=zones)
+                   reward_goal=reward_goal, reward_clip=reward_clip, zones=zones, outputs=outputs)
 
     def tables(self, obs_dim, act_dim):
         """The float32 tables as the library takes them: dict of q, g, c, goal_mask, lo, hi [obs_dim] and rho [act_dim]."""
@@ -165,8 +277,12 @@ class QuadraticTask:
         return out
 
     def zone_tables(self, obs_dim):
-        """StateZones.tables of `zones`, or None without zones."""
+        """StateZones.tables of `zones` (an axis may name output m as obs_dim + m), or None without zones."""
         return _zone_tables(self, obs_dim)
+
+    def output_tables(self, obs_dim):
+        """TaskOutputs.tables of `outputs`, or None without outputs."""
+        return _output_tables(self, obs_dim)
 
 
 @dataclass
@@ -175,7 +291,7 @@ class TrackingTask:
     `reference` [T, obs_dim] takes g's place for the state that lies j - k0 steps into the plan (the last row is held), the last
     predicted state is weighted by `terminal_weights` (None: q) and every step pays sum_j action_rate_j (a_t[j] - a_{t-1}[j])^2 (None:
     nothing).  k0 and the action before the plan's first are the handle's clock (CemPlanner.set_task_clock; CemMpc keeps it).  The other
-    fields are QuadraticTask's, `zones` among them."""
+    fields are QuadraticTask's, `zones` and `outputs` among them."""
     reference: object = None
     q: object = 0.0
     c: object = 0.0
@@ -188,16 +304,17 @@ class TrackingTask:
     reward_clip: float = 0.0
     terminal_weights: object = None
     action_rate: object = None
+    outputs: object = None
     zones: object = None
 
     @classmethod
     def to_reference(cls, reference, weights=1.0, action_weights=0.0, terminal_weights=None, action_rate=None, lo=-np.inf, hi=np.inf,
-                     goal_radius=0.0, reward_goal=0.0, reward_clip=0.0, zones=None):
+                     goal_radius=0.0, reward_goal=0.0, reward_clip=0.0, zones=None, outputs=None):
         """Follow `reference` [T, obs_dim]: reward = -sum weights (s - reference row)^2 - sum action_weights a^2 - the action-rate term;
         goal_radius as QuadraticTask.to_target's, measured against the row of the moment."""
         w = np.asarray(weights, np.float32)
         return cls(reference=reference, q=w, goal_mask=(w != 0).astype(np.float32), lo=lo, hi=hi, rho=action_weights, goal_radius=goal_radius,
-                   reward_goal=reward_goal, reward_clip=reward_clip, terminal_weights=terminal_weights, action_rate=action_rate, zones=zones)
+                   reward_goal=reward_goal, reward_clip=reward_clip, terminal_weights=terminal_weights, action_rate=action_rate, zones=zones, outputs=outputs)
 
     def tables(self, obs_dim, act_dim):
         """The float32 tables as the library takes them: QuadraticTask.tables' without g, q_terminal [obs_dim], action_rate [act_dim]
@@ -214,8 +331,12 @@ class TrackingTask:
         return out
 
     def zone_tables(self, obs_dim):
-        """StateZones.tables of `zones`, or None without zones."""
+        """StateZones.tables of `zones` (an axis may name output m as obs_dim + m), or None without zones."""
         return _zone_tables(self, obs_dim)
+
+    def output_tables(self, obs_dim):
+        """TaskOutputs.tables of `outputs`, or None without outputs."""
+        return _output_tables(self, obs_dim)
 
 
 @dataclass
@@ -269,7 +390,8 @@ class PlannerConfig:
     task: Optional[object] = None      # None: the Safety-Gym scorer (the reference); a QuadraticTask: rollouts are scored by it
                                        # (cem_planner_set_task) and `scorer` is inert; a TrackingTask: by a reference that
                                        # moves with the handle's clock (cem_planner_set_task_tracking); either with
-                                       # `zones`, a StateZones (cem_planner_set_task_zones); not in cem_config_t: set after create
+                                       # `zones`, a StateZones (cem_planner_set_task_zones) and `outputs`, a TaskOutputs
+                                       # (cem_planner_set_task_outputs); not in cem_config_t: set after create
     action_noise: str = 'white'        # 'white': every step of a sequence drawn independently (the reference) | 'powerlaw' | 'ar1': time-correlated
                                        # noise eps = M xi with M = powerlaw_mixing / ar1_mixing(horizon, action_noise_param)
                                        # (cem_planner_set_action_noise, CEM_NOISE_MIXED); not in cem_config_t: set after create
@@ -967,11 +1089,16 @@ class CemPlanner:
             return
         tb = task.tables(self.cfg.obs_dim, self.cfg.act_dim)      # (kept alive until the call returns: the library copies them)
         zt = task.zone_tables(self.cfg.obs_dim)                   # (refused before anything of the handle changes)
+        ot = task.output_tables(self.cfg.obs_dim)
         self._set_task_base(task, tb)
-        if zt is not None:
-            # zones (cem_planner_set_task_zones): cem_task_zones_kernel in the task kernel's place; the objectives restate it
+        if zt is not None or ot is not None:
+            # outputs (cem_planner_set_task_outputs), then zones (cem_planner_set_task_zones): cem_task_outputs_kernel /
+            # cem_task_zones_kernel in the task kernel's place; the objectives restate them
             try:
-                self._set_task_zones(zt)
+                if ot is not None:
+                    self._set_task_outputs(ot)
+                if zt is not None:
+                    self._set_task_zones(zt)
             except Exception:
                 _capi.check(self.lib.cem_planner_set_task(self.h, None), 'cem_planner_set_task')     # (not half a task: none)
                 self.task, self.task_clock = None, None
@@ -990,9 +1117,43 @@ class CemPlanner:
         else:
             if not isinstance(zones, StateZones):
                 raise ValueError('zones must be a StateZones')
-            self._set_task_zones(zones.tables(self.cfg.obs_dim))
+            ot = self.task.output_tables(self.cfg.obs_dim) if self.task is not None else None
+            self._set_task_zones(zones.tables(self.cfg.obs_dim + (ot['matrix'].shape[0] if ot is not None else 0)))
         if self.task is not None:
             self.task = _dc_replace(self.task, zones=zones)
+
+    @property
+    def task_outputs(self):
+        """The TaskOutputs of the task in force, or None."""
+        return getattr(self.task, 'outputs', None)
+
+    def set_task_outputs(self, outputs=None):
+        """The TaskOutputs of the task in force (cem_planner_set_task_outputs); None clears them.  Either way the zones are cleared:
+        set the outputs, then the zones (which may then name outputs as axes).  Sticky until the next set_task; waits for the stream
+        and re-captures the graph."""
+        if outputs is None:
+            had = self.task_outputs is not None
+            _capi.check(self.lib.cem_planner_set_task_outputs(self.h, None), 'cem_planner_set_task_outputs')
+            if self.task is not None and had:
+                self.task = _dc_replace(self.task, outputs=None, zones=None)
+            return
+        if not isinstance(outputs, TaskOutputs):
+            raise ValueError('outputs must be a TaskOutputs')
+        ref = getattr(self.task, 'reference', None)
+        self._set_task_outputs(outputs.tables(self.cfg.obs_dim, ref_rows=np.asarray(ref).shape[0] if ref is not None else 1))
+        if self.task is not None:
+            self.task = _dc_replace(self.task, outputs=outputs, zones=None)
+
+    def _set_task_outputs(self, ot):
+        fp = C.POINTER(C.c_float)
+        per_step = ot['target'].shape[0] > 1
+        co = _capi.CemTaskOutputs(n_outputs=ot['matrix'].shape[0], matrix=ot['matrix'].ctypes.data_as(fp), weight=ot['weight'].ctypes.data_as(fp),
+                                  target=ot['target'].ctypes.data_as(fp), linear=ot['linear'].ctypes.data_as(fp), near=ot['near'].ctypes.data_as(fp),
+                                  lo=ot['lo'].ctypes.data_as(fp), hi=ot['hi'].ctypes.data_as(fp),
+                                  terminal=ot['terminal'].ctypes.data_as(fp) if ot['terminal'] is not None else None,
+                                  ref_rows=ot['target'].shape[0] if per_step else 0,
+                                  reference=ot['target'].ctypes.data_as(fp) if per_step else None)
+        _capi.check(self.lib.cem_planner_set_task_outputs(self.h, C.byref(co)), 'cem_planner_set_task_outputs')
 
     def _set_task_zones(self, zt):
         fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -1571,10 +1732,37 @@ def zone_terms(traj, zt):
     return hit, acc[..., 0], slots
 
 
-def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, return_done, zt=None):
+def output_terms(traj, ot):
+    """The outputs y = C s of cem_task_outputs_kernel (csrc/cem_task_outputs.h), bit for bit: traj [rows, H + 1, O] float32, ot the tables
+    of TaskOutputs.tables -> y [rows, H + 1, M] float32.  Sixteen partial sums per output, partial l over the features 64 i + 4 l + r (i,
+    then r) from +0, every product and sum a float32 operation of its own; the sixteen added pairwise, neighbours first."""
+    f = np.float32
+    tr = np.asarray(traj, f)
+    rows, H1, O = tr.shape
+    Cm = np.zeros((ot['matrix'].shape[0], 128), f)
+    Cm[:, :O] = ot['matrix']
+    s = np.zeros((rows, H1, 128), f)
+    s[..., :O] = tr
+    s = s.reshape(rows, H1, 2, 16, 4)
+    y = np.zeros((rows, H1, Cm.shape[0]), f)
+    with np.errstate(all='ignore'):
+        for m in range(Cm.shape[0]):
+            cm = Cm[m].reshape(2, 16, 4)
+            acc = np.zeros((rows, H1, 16), f)
+            for i in range(2):
+                for r in range(4):
+                    acc = acc + cm[i, :, r] * s[:, :, i, :, r]
+            for _ in range(4):
+                acc = acc[..., 0::2] + acc[..., 1::2]
+            y[..., m] = acc[..., 0]
+    return y
+
+
+def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, return_done, zt=None, ot=None, gy=None):
     """What task_objective and tracking_objective share, in the kernels' order: tb the [O] / [A] tables, ref [H + 1, O] the row every
     state is compared with (or [O]: one for all), q_terminal [O] the weights of the last state (None: q), rate [N, H] the action-rate
-    term of every step (None: the reward has no such term), zt the zone tables (None: no zones, and the code of a task without)."""
+    term of every step (None: the reward has no such term), zt the zone tables (None: no zones, and the code of a task without), ot the
+    output tables with gy [H + 1, M] the row every state's outputs are compared with (None: no outputs, and the code of a task without)."""
     f = np.float32
     if variant not in VARIANTS:
         raise ValueError("variant must be 'cem', 'safe' or 'cost'")
@@ -1591,26 +1779,40 @@ def _task_objective(traj, actions, tb, ref, q_terminal, rate, task, variant, ret
     s = np.zeros((rows, H1, 128), f)
     s[..., :O] = tr
 
-    def lane_sum(x):                                  # [rows, H + 1, 128] -> [rows, H + 1]
+    def lane_sum(x, extra=None):                      # [rows, H + 1, 128] -> [rows, H + 1]; extra [rows, H + 1, M]: partial m adds it behind its features
         x = x.reshape(rows, H1, 2, 16, 4)
         acc = np.zeros((rows, H1, 16), f)
         for i in range(2):
             for r in range(4):
                 acc = acc + x[:, :, i, :, r]
+        if extra is not None:
+            acc[..., :extra.shape[-1]] = acc[..., :extra.shape[-1]] + extra
         for _ in range(4):
             acc = acc[..., 0::2] + acc[..., 1::2]
         return acc[..., 0]
     with np.errstate(all='ignore'):
         d = s - g
         dd = d * d
-        phi = lane_sum(q * dd - c * s)
-        nsum = lane_sum(m * dd)
+        if ot is None:
+            phi = lane_sum(q * dd - c * s)
+            nsum = lane_sum(m * dd)
+        else:                                         # cem_task_outputs_kernel: output m's terms join partial m of both sums
+            y = output_terms(tr, ot)
+            e = y - gy
+            ee = e * e
+            wy = np.broadcast_to(ot['weight'], (H1, y.shape[-1]))
+            if q_terminal is not None and ot['terminal'] is not None:
+                wy = np.concatenate([wy[:H], ot['terminal'][None]], axis=0)
+            phi = lane_sum(q * dd - c * s, wy * ee - ot['linear'] * y)
+            nsum = lane_sum(m * dd, ot['near'] * ee)
         r2 = f(task.goal_radius) * f(task.goal_radius)
         near = (nsum <= r2) & bool(r2 > 0) & (variant != 'cost')       # (the cost objective's bytes are not masked by done: near is never true)
         viol = ((tr < tb['lo']) | (tr > tb['hi'])).any(axis=2).astype(f)
+        if ot is not None:                            # a bound on an output is a half-space (a NaN compares false)
+            viol = ((viol != 0) | ((y < ot['lo']) | (y > ot['hi'])).any(axis=2)).astype(f)
         pen = None
         if zt is not None:                            # cem_task_zones_kernel: a hit is a violation, pen leaves the reward after v
-            hit, pen, _ = zone_terms(tr, zt)
+            hit, pen, _ = zone_terms(tr if ot is None else np.concatenate([tr, y], axis=2), zt)
             viol = ((viol != 0) | hit).astype(f)
         u = np.zeros((N, H), f)
         for j in range(A):
@@ -1667,7 +1869,9 @@ def task_objective(traj, actions, task, variant='cem', return_done=False):
     A NaN return is stored as 0x7fc00000.  return_done=True appends the first step at which near held, int [rows] (H: never)."""
     tr, act = _task_arrays(traj, actions)
     tb = task.tables(tr.shape[2], act.shape[2])
-    return _task_objective(tr, act, tb, tb['g'], None, None, task, variant, return_done, task.zone_tables(tr.shape[2]))
+    ot = task.output_tables(tr.shape[2])
+    return _task_objective(tr, act, tb, tb['g'], None, None, task, variant, return_done, task.zone_tables(tr.shape[2]), ot,
+                           ot['target'] if ot is not None else None)
 
 
 def tracking_objective(traj, actions, task, variant='cem', k0=0, prev_action=None, return_done=False):
@@ -1691,7 +1895,11 @@ def tracking_objective(traj, actions, task, variant='cem', k0=0, prev_action=Non
         for j in range(A):
             e = act[:, :, j] - before[:, :, j]
             rate = rate + tb['action_rate'][j] * (e * e)
-    return _task_objective(tr, act, tb, ref, tb['q_terminal'], rate, task, variant, return_done, task.zone_tables(tr.shape[2]))
+    ot = task.output_tables(tr.shape[2])
+    gy = None
+    if ot is not None:                                # the outputs' reference runs on the same clock (one row: held)
+        gy = ot['target'][np.minimum(k0 + np.arange(H + 1), T - 1)] if ot['target'].shape[0] > 1 else ot['target']
+    return _task_objective(tr, act, tb, ref, tb['q_terminal'], rate, task, variant, return_done, task.zone_tables(tr.shape[2]), ot, gy)
 
 
 class PlanReadout(NamedTuple):

@@ -77,6 +77,9 @@ handle's clock: before every plan it sets it to (decisions since ``reset()``, th
 Either task may carry ``zones=planner.StateZones(...)``: round regions of the state space the plan must stay out of (or inside of) — a
 state that hits one is a cost exactly as a state outside the box is, so ``SafeCemMpc``'s filter, budget, recovery and ``last_plan``'s
 cost counts see it, and coming within ``margin`` of one costs reward (cem_mpc.h cem_planner_set_task_zones).
+Either task may also carry ``outputs=planner.TaskOutputs(...)``: up to 16 linear outputs y = C s with a feature's vocabulary each — a
+full-matrix cost (``TaskOutputs.quadratic_form``), half-spaces (``TaskOutputs.halfspaces``: a bound that is crossed is a cost as above),
+and zone axes ``obs_dim + m`` for rotated zones (cem_mpc.h cem_planner_set_task_outputs).
 
 With ``replan_every=r``, 1 <= r <= horizon (which implies ``plan_readout``), ``generate_action`` plans at decisions 0, r, 2r, ... of an
 episode and in between returns step j of the kept sequence, plus ``noise_stddev`` times the output noise of that decision's own Philox

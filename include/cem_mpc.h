@@ -908,6 +908,54 @@ typedef struct {
 int cem_planner_set_task_zones(cem_planner_t *h, const cem_task_zones_t *zones /* NULL: none */);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Linear outputs: derived features y = C s on a task.  Beyond the reference, off by default.  A task of either kind
+ * may carry M = n_outputs <= CEM_TASK_MAX_OUTPUTS linear outputs of the state, and each output has the task's whole vocabulary: a
+ * weight, a target (or a per-step reference on a tracking base), a linear term, a near-goal weight, a box bound, a terminal weight,
+ * and a zone may name it as an axis by the index obs_dim + m.  With Q = L^T L the full-matrix cost (x - x_ref)^T Q (x - x_ref) is
+ * matrix = L, weight = 1, target = L x_ref; a bound hi on an output is the half-space C[m] . s <= hi, M of them a polytope; two
+ * outputs under a rotation carry a rotated ellipse.  A plan with outputs launches what its base task plan launches, with the kernel
+ * of csrc/cem_task_outputs.h, cem_task_outputs_kernel, in the place of the task's (or the zones') kernel.  A task without outputs
+ * launches what it launched and returns the bits it returned.
+ *
+ * In fp32, every product, difference and sum rounded on its own, for state s and output m:
+ *   y_m(s): sixteen partial sums; partial l starts at +0 and adds matrix[m][f] * s_f for f = 64 i + 4 l + r, i = 0, 1 and then
+ *           r = 0 .. 3 (features >= obs_dim add nothing); the sixteen are added pairwise, neighbours first, over four levels
+ *   e = y_m - target_m   (a tracking base with ref_rows = T: row min(k0 + st, T - 1) of `reference`, the base task's clock);  ee = e * e
+ *   w = weight_m, on the terminal state of a tracking base terminal_m (NULL: weight)
+ *   phi(s): partial m of its sixteen also adds (w * ee - linear_m * y_m), behind that partial's features;  near's partial m adds near_m * ee
+ *   viol(s) also holds where some y_m < lo_m or y_m > hi_m (a NaN compares false)
+ *   a zone axis obs_dim + m reads y_m where a feature axis reads s[axis]
+ * Everything else is the zones' contract above.  planner.output_terms, task_objective and tracking_objective restate it, bit for bit.
+ * Outputs with weight = linear = near = terminal = 0 and infinite bounds leave every result bit of the task without them.
+ *
+ * cem_planner_set_task_outputs copies the tables (they may be freed on return), allocates before it changes anything, waits for the
+ * stream and drops the captured graph, as cem_planner_set_task_zones does.  outputs NULL clears them (a no-op on a handle without any).
+ * The call clears the zones; cem_planner_set_task and cem_planner_set_task_tracking clear the outputs: set the task, then its
+ * outputs, then its zones.  While outputs are in force cem_planner_set_task_zones accepts axes in [obs_dim, obs_dim + n_outputs).
+ * cem_planner_set_task_clock, cem_planner_task_trajectories and cem_task_score serve a plan with outputs as they serve its base task.
+ *   CEM_ERR_INVALID_ARG  null handle; n_outputs outside 1 .. CEM_TASK_MAX_OUTPUTS; matrix NULL; a NaN or infinite matrix, weight,
+ *                        target, linear, near or terminal entry; a weight or terminal below 0; a NaN bound or lo > hi; ref_rows that
+ *                        is neither 1 nor the base task's ref_steps (a quadratic base: 1; 0 with reference NULL counts as 1)
+ *   CEM_ERR_STATE        no task in force; between the begin and end calls of a stepwise plan
+ *   CEM_ERR_UNSUPPORTED  a library built without cem_task_outputs_kernel
+ * A failed allocation returns CEM_ERR_HIP; the handle keeps its previous setting after any of these. */
+#define CEM_TASK_MAX_OUTPUTS 16
+typedef struct {
+    int32_t n_outputs;            /* 1 .. CEM_TASK_MAX_OUTPUTS */
+    const float *matrix;          /* [n_outputs][obs_dim], host memory */
+    const float *weight;          /* [n_outputs], or NULL: zeros */
+    const float *target;          /* [n_outputs], or NULL: zeros; not read where `reference` is given */
+    const float *linear;          /* [n_outputs], or NULL: zeros */
+    const float *near;            /* [n_outputs], or NULL: zeros */
+    const float *lo;              /* [n_outputs], or NULL: -inf */
+    const float *hi;              /* [n_outputs], or NULL: +inf */
+    const float *terminal;        /* [n_outputs], or NULL: weight */
+    int32_t ref_rows;             /* rows of `reference`: 1 or the base task's ref_steps */
+    const float *reference;       /* [ref_rows][n_outputs], or NULL: `target` on every step */
+} cem_task_outputs_t;
+int cem_planner_set_task_outputs(cem_planner_t *h, const cem_task_outputs_t *outputs /* NULL: none */);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Ensemble training on the device: MlpEnsemble.training_step / validation_step
  * (simba/models/mlp_ensemble.py:134-155), loss negative_log_likelihood (:64-67), optimizer
  * tf.keras.optimizers.Adam(lr, clipvalue=1.0, epsilon=1e-5) (:113-117).  The shuffling / batching / learning-rate
